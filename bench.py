@@ -9,8 +9,11 @@ dropout masks, parameters initialised as weight-init.lua + Torch7 defaults.
         bench.py --gpus 8 --steps 50 --warmup 10
     python bench.py --config 3        # BASELINE configs[2]: G32up, grayscale, batch 256
     python bench.py --config 5        # per-GPU share of configs[4]: G32up-c scaled to 64x64, 64 images per GPU
+    python bench.py --full            # also the kernel rooflines, sustained rate, reference order, dry run, configs 3 / 5, CPU baselines
+    python bench.py --dump-outputs DIR   # the last timed step's outputs as DIR/<name>.npy
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps and prints the line; everything else it measures
+runs only with --full.
 """
 import argparse
 import importlib
@@ -398,6 +401,33 @@ def time_steps(cg, S, data, N, steps, warmup):
     return e0.elapsed_time(e1) / steps
 
 
+DUMP_BYTES = 60 << 20          # --dump-outputs: at most 64 MB on disk, headers included
+
+
+def dump_outputs(cg, S, N, dims, out_dir):
+    """What the timed path hands its caller after its last step, as float32 DIR/<name>.npy: both parameter vectors after the step's D and
+    G updates, the fake images of the D-step's batch, D's output on the G-step's samples and the G-step's loss.  Everything is read where the
+    step left it (no extra launch).  Where the whole set exceeds DUMP_BYTES (config 5), each parameter vector is replaced by a fixed, seeded
+    sample of its entries (sorted indices, the same for every run at the same arguments)."""
+    inputs = cg.adversarial._buffers(S, N, dims)["inputs"]
+    out = {"params_G": S.PARAMETERS_G.numpy().reshape(-1), "params_D": S.PARAMETERS_D.numpy().reshape(-1),
+           "fake_images": inputs.numpy()[N // 2:], "d_output_g_step": S._last["outputs_G"].numpy(),
+           "loss_g_step": np.array([float(S._last["f_G"])])}
+    out = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in out.items()}
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_BYTES:
+        params = out["params_G"].nbytes + out["params_D"].nbytes
+        keep = (DUMP_BYTES - (total - params)) / params
+        for i, k in enumerate(("params_G", "params_D")):
+            v = out[k]
+            idx = np.sort(np.random.RandomState(i).choice(v.size, int(v.size * keep), replace=False))
+            out[k] = v[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return {k: list(v.shape) for k, v in out.items()}
+
+
 def other_config_line(cg, num, steps, warmup):
     """One of the other single-GPU configurations of BASELINE.json, timed in THIS run (VERDICT r05 #6c: the driver's command times configs[1]
     only; builder-run lines of the others are claims): ms per step, images/s, the step's executed MFMA fraction and the configuration's
@@ -438,15 +468,21 @@ def main():
     ap.add_argument("--no-kernel-roofline", action="store_true")
     ap.add_argument("--no-reference-order", action="store_true", help="skip the same-run timing of the reference's order of calls (kernel traces: the "
                     "trace tools analyse the LAST steps of the process)")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the 1500-step sustained-rate leg of the default one-GPU line")
-    ap.add_argument("--no-dp-dry-run", action="store_true", help="skip the data-parallel dry run of the default one-GPU line")
+    ap.add_argument("--no-sustained", action="store_true", help="skip the 1500-step sustained-rate leg of the --full one-GPU line")
+    ap.add_argument("--no-dp-dry-run", action="store_true", help="skip the data-parallel dry run of the --full one-GPU line")
     ap.add_argument("--dp-dry-run", type=int, nargs="?", const=8, default=None, metavar="R",
-                    help="one GPU: also time the per-rank step of an R-rank data-parallel job (sync-BN, gradient buckets, D's all-reduce under the "
+                    help="one GPU, with --full: also time the per-rank step of an R-rank data-parallel job (sync-BN, gradient buckets, D's all-reduce under the "
                          "generator forward) on single-rank RCCL communicators through cg_comm_* -> config.collectives.dry_run_ms_per_step")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the same-run lines of configs 3 and 5 (default run of config 2 on one GPU)")
+    ap.add_argument("--no-other-configs", action="store_true", help="skip the same-run lines of configs 3 and 5 (--full run of config 2 on one GPU)")
     ap.add_argument("--strict-comm", action="store_true",
                     help="N > 1: the engine's transport (cg_comm_*: RCCL through the C ABI) or failure - never the torch.distributed fallback "
                          "(CG_COMM_STRICT=1).  config.collectives.transport names the transport of a run either way.")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other leg of the line: kernel rooflines, the sustained rate, the reference's order of "
+                         "calls, the data-parallel dry run, configs 3 and 5, the CPU baselines (the --no-* switches and --dp-dry-run select among "
+                         "them).  A plain run does none of these")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (parameters, fake images, D's output, loss) as DIR/<name>.npy, float32")
     args = ap.parse_args()
 
     # stdout carries exactly ONE line, the JSON: libraries write banners there from C (RCCL's version block at communicator init,
@@ -515,6 +551,9 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     finite = bool(np.isfinite(S.PARAMETERS_G.numpy()).all() and np.isfinite(S.PARAMETERS_D.numpy()).all())
+    if args.dump_outputs and rank == 0:     # before any leg of --full steps S again
+        shapes = dump_outputs(cg, S, N, dims, args.dump_outputs)
+        print(f"bench: the last timed step's outputs in {args.dump_outputs}: {shapes}", file=sys.stderr)
 
     if rank == 0:
         ms = 1e3 * dt / args.steps
@@ -549,8 +588,8 @@ def main():
         blocks = [pa[1].elapsed_time(pb[1]) / (pb[0] - pa[0]) for pa, pb in zip(pts[:-1], pts[1:])]
         res["spread"] = {"ms_per_step_blocks": [round(v, 4) for v in blocks], "min": min(blocks), "max": max(blocks),
                          "note": f"HIP-event time of consecutive blocks of {blk} steps inside the one timed region of {args.steps} steps"}
-        # The headline numbers above are complete; the two legs below are measured live and must never cost the driver its line.
-        if not args.no_kernel_roofline:
+        # The headline numbers above are complete; the legs below run with --full only, are measured live and must never cost the driver its line.
+        if args.full and not args.no_kernel_roofline:
             try:
                 top = kernel_rooflines(cg, cfg, N)
                 res["roofline"] = dict(top[0])    # the kernel with the largest share of the step
@@ -581,7 +620,7 @@ def main():
                                      "launches, 5.79 ms under the tracer; committed numbers, not measured in this run)"})
         # sustained rate: the same step for ~8 s (the timed region above lasts 0.1-0.3 s: a clock / thermal steady state does not show in it,
         # and a monitor that samples the chip every few seconds never sees it busy)
-        if world == 1 and launch == "eager" and args.config == 2 and not args.no_sustained and not args.batch_per_gpu:
+        if args.full and world == 1 and launch == "eager" and args.config == 2 and not args.no_sustained and not args.batch_per_gpu:
             try:
                 n_sus = 1500
                 blocks = [time_steps(cg, S, data, N, n_sus // 5, 0) for _ in range(5)]
@@ -593,7 +632,7 @@ def main():
         # the reference's ORDER of calls (adversarial.lua:232-233 ... :185: the G-step's generator forward after D's update) in the same run:
         # what an unchanged adversarial.lua gets from the drop-in host; the headline issues the two generator forwards as one
         # cg_net_forward_pair (MODEL_G:forwardPair - six lines of adversarial.lua)
-        if world == 1 and launch == "eager" and S.OPT.get("concurrent_g_both") and not args.no_reference_order:
+        if args.full and world == 1 and launch == "eager" and S.OPT.get("concurrent_g_both") and not args.no_reference_order:
             try:
                 S.OPT["concurrent_g_both"] = False
                 res["config"]["reference_order_ms"] = time_steps(cg, S, data, N, min(args.steps, 30), 3)
@@ -604,9 +643,9 @@ def main():
                 res["config"]["reference_order_note"] = "failed: " + str(e)[:160]
             finally:
                 S.OPT["concurrent_g_both"] = True
-        if args.dp_dry_run is None:     # default: on for the plain one-GPU line of configs[1] (8 ranks = configs[3]'s plan), off otherwise
+        if args.dp_dry_run is None:     # default: on for the --full one-GPU line of configs[1] (8 ranks = configs[3]'s plan), off otherwise
             args.dp_dry_run = 8 if (world == 1 and args.config == 2 and not args.no_dp_dry_run and not args.batch_per_gpu and launch == "eager") else 0
-        if world == 1 and args.dp_dry_run > 1:
+        if args.full and world == 1 and args.dp_dry_run > 1:
             try:
                 cg.parallel.dry_run(args.dp_dry_run)
                 cg.manual_seed(1)
@@ -626,14 +665,14 @@ def main():
                     cg.parallel.shutdown()
                 except Exception:                 # noqa: BLE001
                     pass
-        if world == 1 and args.config == 2 and not args.no_other_configs and not args.batch_per_gpu:
+        if args.full and world == 1 and args.config == 2 and not args.no_other_configs and not args.batch_per_gpu:
             res["other_configs"] = []
             for num in (3, 5):
                 try:
                     res["other_configs"].append(other_config_line(cg, num, 20, 5))
                 except Exception as e:            # noqa: BLE001
                     res["other_configs"].append({"config": num, "error": str(e)[:200]})
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baselines(cfg)
             except Exception as e:                # noqa: BLE001

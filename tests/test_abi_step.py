@@ -117,13 +117,13 @@ def test_reference_host_files_resolve_against_the_lua_providers():
     """The `drop in unchanged` claim, as far as it can be held without a Lua interpreter: every `require`, every namespace call
     (torch.* nn.* cudnn.* image.* paths.* sys.* xlua.* optim.* cutorch.* DISP.*) and every method name that the reference's
     adversarial.lua / models.lua / train.lua / weight-init.lua / utils/nn_utils.lua / dataset.lua use has a provider under lua/ (or
-    is standard Lua, or is defined by those files themselves).  The names come from /root/reference when it is there and from the
-    committed list tests/golden/lua_reference_names.json otherwise; both must agree.  The checker is not vacuous: a name nobody
-    provides is reported."""
+    is standard Lua, or is defined by those files themselves).  The names come from the committed list
+    tests/golden/lua_reference_names.json, or from a checkout of the reference named by CATGAN_REFERENCE, which must then agree with that
+    list.  The checker is not vacuous: a name nobody provides is reported."""
     spec = importlib.util.spec_from_file_location("check_lua_binding", os.path.join(ROOT, "scripts", "check_lua_binding.py"))
     chk = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(chk)
-    errs, names = chk.check_reference(os.environ.get("CATGAN_REFERENCE", "/root/reference"))
+    errs, names = chk.check_reference(os.environ.get("CATGAN_REFERENCE"))
     assert errs == [], errs[:10]
     assert {"pl", "image", "paths", "display", "torch", "nn", "optim", "cutorch"} <= set(names["requires"])
     assert {"torch.load", "torch.save", "xlua.progress", "sys.clock", "image.save", "paths.concat", "nn.BatchNormalization"} <= set(names["calls"])
