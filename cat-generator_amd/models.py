@@ -2,7 +2,7 @@
 
 Only the definitions on the hot path are here: G32up-c (models.lua:196-228, the default
 via create_G :234-240), G32up (:138-160), D32_st3 (:640-711, the only D create_D returns, :276) and the
-spatial-transformer factory (:814-906).  `create_G32up_c_64` is the builder-defined 64x64 extension of
+spatial-transformer factory (:814-906), and the validator V (:716-804) that train_v.py trains.  `create_G32up_c_64` is the builder-defined 64x64 extension of
 BASELINE.json config #5.
 """
 from . import cudnn, nn
@@ -145,6 +145,83 @@ def create_D32_st3(dimensions, cuda=False):
 
     conv = w_init(conv, "heuristic")
     return conv
+
+
+def create_V(dimensions):
+    """models.lua:716-722."""
+    if dimensions[1] == 16:
+        return create_V16(dimensions)
+    return create_V32(dimensions)
+
+
+def _v_head(model, feat):
+    """models.lua:742-754 / :790-802: two Linear -> BatchNormalization -> LeakyReLU -> Dropout blocks and a 2-way SoftMax."""
+    activation = nn.LeakyReLU
+    model.add(nn.View(feat))
+    model.add(nn.Linear(feat, 1024))
+    model.add(nn.BatchNormalization(1024))
+    model.add(activation())
+    model.add(nn.Dropout())
+
+    model.add(nn.Linear(1024, 1024))
+    model.add(nn.BatchNormalization(1024))
+    model.add(activation())
+    model.add(nn.Dropout())
+
+    model.add(nn.Linear(1024, 2))
+    model.add(nn.SoftMax())
+    return w_init(model, "heuristic")
+
+
+def create_V16(dimensions):
+    """models.lua:724-759."""
+    model = nn.Sequential()
+    activation = nn.LeakyReLU
+
+    model.add(nn.SpatialConvolution(dimensions[0], 128, 3, 3, 1, 1, (3 - 1) // 2))
+    model.add(activation())
+    model.add(nn.SpatialConvolution(128, 128, 3, 3, 1, 1, (3 - 1) // 2))
+    model.add(nn.SpatialBatchNormalization(128))
+    model.add(activation())
+    model.add(nn.SpatialMaxPooling(2, 2))
+    model.add(nn.SpatialDropout(0.2))
+
+    model.add(nn.SpatialConvolution(128, 256, 3, 3, 1, 1, (3 - 1) // 2))
+    model.add(activation())
+    model.add(nn.SpatialConvolution(256, 256, 3, 3, 1, 1, (3 - 1) // 2))
+    model.add(nn.SpatialBatchNormalization(256))
+    model.add(activation())
+    model.add(nn.SpatialMaxPooling(2, 2))
+    model.add(nn.SpatialDropout())
+
+    imgSize = dimensions[1] * dimensions[2] // (4 * 4)
+    return _v_head(model, 256 * imgSize)
+
+
+def create_V32(dimensions):
+    """models.lua:761-804 (the nn.Dropout at :776 acts on a 4-D map: an element-wise mask)."""
+    model = nn.Sequential()
+    activation = nn.LeakyReLU
+
+    model.add(nn.SpatialConvolution(dimensions[0], 128, 3, 3, 1, 1, (3 - 1) // 2))
+    model.add(activation())
+    model.add(nn.SpatialMaxPooling(2, 2))
+    model.add(nn.SpatialConvolution(128, 128, 3, 3, 1, 1, (3 - 1) // 2))
+    model.add(nn.SpatialBatchNormalization(128))
+    model.add(activation())
+    model.add(nn.SpatialMaxPooling(2, 2))
+    model.add(nn.Dropout())
+
+    model.add(nn.SpatialConvolution(128, 256, 3, 3, 1, 1, (3 - 1) // 2))
+    model.add(activation())
+    model.add(nn.SpatialConvolution(256, 256, 3, 3, 1, 1, (3 - 1) // 2))
+    model.add(nn.SpatialBatchNormalization(256))
+    model.add(activation())
+    model.add(nn.SpatialMaxPooling(2, 2))
+    model.add(nn.SpatialDropout())
+
+    imgSize = dimensions[1] * dimensions[2] // (8 * 8)
+    return _v_head(model, 256 * imgSize)
 
 
 def createSpatialTransformer(allow_rotation, allow_scaling, allow_translation, input_size, input_channels, cuda=True):

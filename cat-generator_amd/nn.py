@@ -811,11 +811,15 @@ class SpatialBatchNormalization(Module):
         self.save_mean = Tensor.zeros((nFeature,))
         self.save_std = Tensor.zeros((nFeature,))  # holds 1/sqrt(var+eps), as THNN's save_std does
 
-    def updateOutput(self, input):
+    def _rows(self, input):
+        """(x, M, C): the [M][C] view the bn entry points take - NHWC, M = N*H*W."""
         x = as_nhwc(to_device(input))
         N, C, H, W = x.shape
-        M = N * H * W
-        out = self._get("out", x.shape, "nhwc")
+        return x, N * H * W, C
+
+    def updateOutput(self, input):
+        x, M, C = self._rows(input)
+        out = self._get("out", x.shape, x.fmt)
         if not self.train:
             lib().bn_forward_eval(stream(), x.ptr, out.ptr, self.weight.ptr, self.bias.ptr, self.running_mean.ptr,
                                   self.running_var.ptr, M, C, float(self.eps))
@@ -833,9 +837,8 @@ class SpatialBatchNormalization(Module):
 
     def _bwd(self, gradOutput, acc, scale):
         x = self._x
-        dy = as_nhwc(gradOutput)
-        N, C, H, W = x.shape
-        M = N * H * W
+        dy = as_nhwc(gradOutput) if x.fmt == "nhwc" else as_plain(gradOutput)
+        _, M, C = self._rows(x)
         assert self.train, "BN backward in evaluate() mode is not on the path"
         lib().bn_backward_stats(stream(), x.ptr, dy.ptr, self.save_mean.ptr, self.save_std.ptr, M, C, self._bsums.data_ptr())
         gs = self._bsums
@@ -843,7 +846,7 @@ class SpatialBatchNormalization(Module):
             self._bsums_g.copy_(self._bsums)
             parallel.allreduce_sum_(self._bsums_g)
             gs = self._bsums_g
-        gi = self._get("gin", x.shape, "nhwc")
+        gi = self._get("gin", x.shape, x.fmt)
         lib().bn_backward(stream(), x.ptr, dy.ptr, self.weight.ptr, self.save_mean.ptr, self.save_std.ptr,
                           gs.data_ptr(), self._count, self._bsums.data_ptr(), M, C, gi.ptr,
                           self.gradWeight.ptr if acc else None, self.gradBias.ptr if acc else None, float(scale))
@@ -861,6 +864,42 @@ class SpatialBatchNormalization(Module):
 
     def __repr__(self):
         return f"nn.SpatialBatchNormalization({self.nFeature})"
+
+
+class BatchNormalization(SpatialBatchNormalization):
+    """nn.BatchNormalization(n) [upstream] on 2-D input [N][n] (models.lua:745,750,793,798): the same statistics per feature
+    over the batch as the spatial module, so a plain [N][n] tensor is the [M = N][C = n] layout of the same bn entry points.
+    Same defaults, initialisation (gamma ~ U(0,1), beta 0), running statistics and parameter order."""
+    _typename = "nn.BatchNormalization"
+
+    def _rows(self, input):
+        x = as_plain(to_device(input))
+        assert x.dim() == 2 and x.shape[1] == self.nFeature, f"{self}: expected [N, {self.nFeature}], got {x.shape}"
+        return x, x.shape[0], x.shape[1]
+
+    def __repr__(self):
+        return f"nn.BatchNormalization({self.nFeature})"
+
+
+class SoftMax(Module):
+    """nn.SoftMax() [upstream] on 2-D input (models.lua:754,802): per row y = exp(x - max) / sum; dx = y (dy - sum dy y)."""
+    _typename = "nn.SoftMax"
+
+    def updateOutput(self, input):
+        x = as_plain(to_device(input))
+        assert x.dim() == 2, f"nn.SoftMax: expected 2-D input, got {x.shape}"
+        out = self._get("out", x.shape)
+        lib().softmax_forward(stream(), x.ptr, out.ptr, x.shape[0], x.shape[1])
+        self.output = out
+        return out
+
+    def updateGradInput(self, input, gradOutput):
+        y = self.output
+        dy = as_plain(to_device(gradOutput))
+        gi = self._get("gin", y.shape)
+        lib().softmax_backward(stream(), y.ptr, dy.ptr, gi.ptr, y.shape[0], y.shape[1])
+        self.gradInput = gi
+        return gi
 
 
 # ------------------------------------------------------------ shape / data movement

@@ -84,7 +84,7 @@ def to_t7(m, cuda=False):
         base[:, :, 1] = (-1 + np.arange(w, dtype=np.float32) / max(w - 1, 1) * 2)[None, :]
         base[:, :, 2] = 1
         f.update(height=h, width=w, baseGrid=_t(base, cuda), batchGrid=_empty(cuda))
-    elif isinstance(m, (nn.Sigmoid, nn.BilinearSamplerBHWD)):
+    elif isinstance(m, (nn.Sigmoid, nn.SoftMax, nn.BilinearSamplerBHWD)):
         pass
     else:
         raise TypeError(f"no Torch7 form for {type(m).__name__}")
@@ -123,9 +123,12 @@ def from_t7(o):
         m = nn.LeakyReLU(o.get("negative_scale", o.get("negval", 0.333)))
     elif n == "nn.Sigmoid":
         m = nn.Sigmoid()
-    elif n == "nn.SpatialBatchNormalization":
+    elif n == "nn.SoftMax":
+        m = nn.SoftMax()
+    elif n in ("nn.SpatialBatchNormalization", "nn.BatchNormalization"):
         rm = _arr(o["running_mean"])
-        m = nn.SpatialBatchNormalization(rm.size, o.get("eps", 1e-5), o.get("momentum", 0.1))
+        cls = nn.BatchNormalization if n == "nn.BatchNormalization" else nn.SpatialBatchNormalization
+        m = cls(rm.size, o.get("eps", 1e-5), o.get("momentum", 0.1))
         m.weight.copy(_arr(o["weight"])); m.bias.copy(_arr(o["bias"])); m.running_mean.copy(rm)
         if o.get("running_var") is not None:
             m.running_var.copy(_arr(o["running_var"]))

@@ -680,6 +680,35 @@ int cg_adagrad_step(void* stream, float* p, float* g, float* var, long n, float 
 int cg_confusion_update(void* stream, const float* outputs, const float* targets,
                         int32_t* counts, long n);
 
+/* ---- the validator network V and its trainer (csrc/validator.hip; models.lua:716-804, train_v.lua) ------------------------
+ * nn.SoftMax on 2-D input [rows][n] (models.lua:754,802), per row:  y = exp(x - max x) / sum exp(x - max x);
+ * backward: dx = y * (dy - sum_j dy_j y_j).  nn.BatchNormalization (models.lua:745,750,...) has no entry point of its own: a
+ * [N][n] tensor is the [M = N][C = n] layout of cg_bn_stats / cg_bn_forward / cg_bn_backward_stats / cg_bn_backward /
+ * cg_bn_forward_eval. */
+int cg_softmax_forward(void* stream, const float* x, float* y, long rows, int n);
+int cg_softmax_backward(void* stream, const float* y, const float* dy, float* dx, long rows, int n);
+/* Synthetic fakes, V's training input (train_v.lua:294-668), in two launches per batch.
+ * cg_synth_overlays: getGaussianOverlay(blur) (:533-561) for `count` overlays, one workgroup each.  bank: [nbank][H][W] random-walk
+ *   overlays (:573-637, built by the host); desc: int32 [count][5] = {o1, o2, o3, o4, blur} (bank rows; blur 0 = no blur, else the
+ *   side of image.gaussian(blur), <= 16); out: [count][H][W] =
+ *     r = clamp(clamp(2 o1 - o2, 0, 1) + 2 o3 o4, 0, 1);  blur > 0: r = image.convolve(r, image.gaussian(blur), "same"), r /= max r.
+ * cg_synth_images: `count` images, one workgroup each, written NHWC to dst[count][H][W][C] (C <= 4; 2*C*H*W floats of LDS).
+ *   pool: [npool][H][W][C] (NHWC); overlays: [noverlays][H][W] (cg_synth_overlays' output, host-made pixelwise overlays beside it).
+ *   idesc: int32 [count][18]; fdesc: float [count][8].  A "level" is 8 ints {kind, a, b, oa, ob, oc, p0, p1} and 4 floats:
+ *     kind 0 Mix    (:327-382)  o = ov[oa];                        v = o pool[a] + (1 - o) pool[b]
+ *     kind 1 Stamp  (:388-444)  o = ov[oa], q = wrap(y+p0, x+p1);  v = (1 - o) pool[a][y,x] + o pool[a][q]
+ *     kind 2 Warp   (:450-484)  image.warp(pool[a], flow), flow_y = (2 ov[oa] - 1) f0, flow_x = (2 ov[ob] - 1) f0 (f0 = length);
+ *                               bilinear, offset mode, source coordinate clamped to the image
+ *     kind 3 Random (:490-528)  q = wrap(y + (c+1) p0, x + (c+1) p1);  v = f_c + ov[oa][y,x] ov[ob][q] - ov[oc][q],
+ *                               then v += |min v| (the reference's absolute value, also for a positive minimum)
+ *   each level is divided by its maximum over the image (wrap = withinImageCoords, 0-based).  idesc[0..8) / fdesc[0..4) are level 1;
+ *   idesc[8..16) / fdesc[4..8) level 2 (kind -1 = none); with a level 2 the image is mixImages(level 1, level 2, ov[idesc[16]])
+ *   (:309-313,350-365): o l1 + (1 - o) l2, divided by its maximum.  idesc[17] is unused.  Pool and overlay indices are clamped
+ *   into range. */
+int cg_synth_overlays(void* stream, const float* bank, int nbank, const int32_t* desc, float* out, int count, int H, int W);
+int cg_synth_images(void* stream, const float* pool, int npool, const float* overlays, int noverlays, const int32_t* idesc,
+                    const float* fdesc, float* dst, int count, int C, int H, int W);
+
 #ifdef __cplusplus
 }
 #endif

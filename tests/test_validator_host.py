@@ -1,0 +1,251 @@
+"""CPU checks of the validator V and its trainer (models.lua:716-804, train_v.lua): the new C entry points, V's structure, parameter
+counts and weight-init scoping, the Torch7-format round trip, and the numpy twin of the synthetic-fake generator with the recalled
+upstream behaviour it rests on (image.gaussian, image.convolve "same", image.warp)."""
+import ctypes
+import importlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = ("cg_softmax_forward", "cg_softmax_backward", "cg_synth_overlays", "cg_synth_images")
+
+
+@pytest.fixture(scope="module")
+def cg():
+    return importlib.import_module("cat-generator_amd")
+
+
+@pytest.fixture(scope="module")
+def syn(cg):
+    return cg.synthetic
+
+
+def test_new_entry_points_exported_with_plain_c_types(cg):
+    abi = importlib.import_module("cat-generator_amd._abi")
+    protos = abi.parse_header()
+    dll = ctypes.CDLL(abi.LIB_PATH)
+    for name in NEW:
+        assert name in protos and hasattr(dll, name)
+        ret, args = protos[name]
+        assert ret == "int" and all(t in abi._CTYPES for t, _ in args)
+    assert cg.lib().abi_version() == 1
+
+
+def test_new_entry_points_validate_arguments(cg):
+    L = cg.lib()
+    with pytest.raises(cg.CatganError, match="null pointer"):
+        L.softmax_forward(None, None, None, 4, 2)
+    with pytest.raises(cg.CatganError, match="bad geometry"):
+        L.softmax_backward(None, 16, 16, 16, 4, 0)
+    with pytest.raises(cg.CatganError, match="null pointer"):
+        L.synth_overlays(None, None, 10, None, None, 1, 32, 32)
+    with pytest.raises(cg.CatganError, match="bad geometry"):
+        L.synth_overlays(None, 16, 0, 16, 16, 1, 32, 32)
+    with pytest.raises(cg.CatganError, match="bad geometry"):
+        L.synth_images(None, 16, 4, 16, 4, 16, 16, 16, 1, 5, 32, 32)      # C > 4
+    with pytest.raises(cg.CatganError, match="do not fit in LDS"):
+        L.synth_images(None, 16, 4, 16, 4, 16, 16, 16, 1, 3, 256, 256)
+
+
+@pytest.mark.parametrize("dims,count", [((3, 32, 32), 6288258), ((1, 32, 32), 6285954), ((3, 16, 16), 6288258),
+                                        ((3, 64, 64), 18871170)])
+def test_v_parameter_counts(cg, dims, count):
+    V = cg.models.create_V(dims)
+    assert cg.nn_utils.getNumberOfParameters(V) == count
+
+
+def test_v32_structure(cg):
+    V = cg.models.create_V((3, 32, 32))
+    names = [m.typename for m in V.modules]
+    assert names == ["nn.SpatialConvolution", "nn.LeakyReLU", "nn.SpatialMaxPooling", "nn.SpatialConvolution",
+                     "nn.SpatialBatchNormalization", "nn.LeakyReLU", "nn.SpatialMaxPooling", "nn.Dropout",
+                     "nn.SpatialConvolution", "nn.LeakyReLU", "nn.SpatialConvolution", "nn.SpatialBatchNormalization", "nn.LeakyReLU",
+                     "nn.SpatialMaxPooling", "nn.SpatialDropout", "nn.View", "nn.Linear", "nn.BatchNormalization", "nn.LeakyReLU",
+                     "nn.Dropout", "nn.Linear", "nn.BatchNormalization", "nn.LeakyReLU", "nn.Dropout", "nn.Linear", "nn.SoftMax"]
+    assert V.modules[1].negative_scale == 0.333 and V.modules[14].p == 0.5 and V.modules[7].p == 0.5
+    assert V.modules[15].sizes == (4096,)
+    V16 = cg.models.create_V((3, 16, 16))
+    assert V16.modules[6].typename == "nn.SpatialDropout" and V16.modules[6].p == 0.2
+    # the planned executor does not take V: the container walks its modules
+    planned = importlib.import_module("cat-generator_amd.planned")
+    for m in (V.modules[17], V.modules[25]):
+        with pytest.raises(planned.Unsupported):
+            planned.describe(m)
+
+
+def test_v_weight_init_scoping(cg):
+    cg.manual_seed(3)
+    V = cg.models.create_V((3, 32, 32))
+    for m in V.modules:
+        if m.typename in ("nn.SpatialConvolution", "nn.Linear"):
+            fan_in = m.nInputPlane * m.kH * m.kW if m.typename == "nn.SpatialConvolution" else m.weight.shape[1]
+            bound = np.sqrt(1.0 / (3 * fan_in)) * np.sqrt(3.0)
+            w = m.weight.numpy()
+            assert np.abs(w).max() <= bound * (1 + 1e-6) and np.abs(w).max() > 0.9 * bound
+        if getattr(m, "bias", None) is not None:
+            assert np.all(m.bias.numpy() == 0)
+        if "BatchNormalization" in m.typename:
+            w = m.weight.numpy()
+            assert w.min() >= 0 and w.max() < 1 and w.std() > 0.2
+            assert np.all(m.running_mean.numpy() == 0) and np.all(m.running_var.numpy() == 1)
+
+
+def test_v_round_trips_through_t7(cg, tmp_path):
+    t7 = importlib.import_module("cat-generator_amd.t7")
+    t7_nn = importlib.import_module("cat-generator_amd.t7_nn")
+    cg.manual_seed(5)
+    V = cg.models.create_V((1, 32, 32))
+    for m in V.modules:
+        if "BatchNormalization" in m.typename:
+            m.running_mean.copy(np.random.RandomState(1).rand(m.nFeature).astype(np.float32))
+            m.running_var.copy(np.random.RandomState(2).rand(m.nFeature).astype(np.float32) + 0.5)
+    fn = str(tmp_path / "v_1x32x32.net")
+    t7.save(fn, {"V": t7_nn.to_t7(V), "opt": {"scale": 32}, "EPOCH": 3})
+    z = t7.load(fn)
+    W = t7_nn.from_t7(z["V"])
+    assert int(z["EPOCH"]) == 3
+    assert [m.typename for m in W.modules] == [m.typename for m in V.modules]
+    np.testing.assert_array_equal(W.getParameters()[0].numpy(), V.getParameters()[0].numpy())
+    for a, b in zip(V.modules, W.modules):
+        if "BatchNormalization" in a.typename:
+            assert type(a) is type(b)
+            np.testing.assert_array_equal(a.running_mean.numpy(), b.running_mean.numpy())
+            np.testing.assert_array_equal(a.running_var.numpy(), b.running_var.numpy())
+
+
+# ------------------------------------------------------------------------------ the generator's numpy twin
+def test_within_image_coords_wraps(syn):
+    f = syn.within_image_coords
+    assert f(1, 1, 32, 32) == (1, 1)
+    assert f(32, 32, 32, 32) == (32, 32)          # y % 32 == 0 -> 32, not 0
+    assert f(33, 42, 32, 32) == (1, 10)
+    assert f(0, -1, 32, 32) == (32, 31)
+    assert f(-31, -32, 32, 32) == (1, 32)
+    assert f(5 + 2 * 5, 3 - 2 * 4, 16, 16) == (15, 11)
+    for y in range(-70, 70):                       # the kernel's 0-based wrap is the same map
+        assert f(y + 1, 1, 32, 32)[0] - 1 == y % 32
+
+
+def test_gaussian_defaults(syn):
+    g = syn.gaussian(4)
+    c = 0.5 * 4 + 0.5
+    i = np.arange(1, 5)
+    ref = np.exp(-(((i[None, :] - c) / (0.25 * 4)) ** 2 / 2 + ((i[:, None] - c) / (0.25 * 4)) ** 2 / 2))
+    np.testing.assert_allclose(g, ref.astype(np.float32), rtol=0, atol=0)
+    assert g.dtype == np.float32 and abs(g.sum() - 1) > 0.5          # not normalised
+    assert np.allclose(g, g[::-1, ::-1]) and g.max() < 1              # symmetric, centre between taps for even sizes
+    g5 = syn.gaussian(5)
+    assert g5[2, 2] == 1.0                                             # odd size: the centre tap has amplitude 1
+
+
+def test_convolve_same_crop(syn):
+    img = np.zeros((8, 8), np.float32)
+    img[3, 5] = 1
+    for k in (4, 10):
+        ker = np.arange(k * k, dtype=np.float32).reshape(k, k)
+        out = syn.convolve_same(img, ker)
+        s = (k + 1) // 2 - 1
+        for y in range(8):
+            for x in range(8):
+                u, v = y + s - 3, x + s - 5
+                want = ker[u, v] if 0 <= u < k and 0 <= v < k else 0
+                assert out[y, x] == want
+
+
+def test_warp_semantics(syn):
+    """image.warp(img, field): bilinear, offset mode, clamped borders, field[1] = y (the Warp kind at length 1)."""
+    C, H, W = 1, 6, 7
+    img = np.random.RandomState(0).rand(1, C, H, W).astype(np.float32)
+    ov = np.zeros((2, H, W), np.float32)
+    ov[0] = 0.75            # flow_y = (2*0.75 - 1) * 1 = +0.5
+    ov[1] = 0.5             # flow_x = 0
+    I = np.zeros((1, 18), np.int32); F = np.zeros((1, 8), np.float32)
+    I[0, :8] = [syn.WARP, 0, 0, 0, 1, 0, 0, 0]; I[0, 8] = -1; F[0, 0] = 1
+    out = syn.synth_images_np(img, ov, I, F)[0, 0]
+    a = img[0, 0]
+    want = np.empty_like(a)
+    for y in range(H):
+        y0 = min(y, H - 1); y1 = min(y + 1, H - 1)
+        want[y] = 0.5 * a[y0] + 0.5 * a[y1] if y < H - 1 else a[H - 1]   # the last row clamps onto itself
+    np.testing.assert_allclose(out, want / want.max(), rtol=0, atol=1e-6)
+    ov[0], ov[1] = 0.5, 0.0  # flow_x = -1 everywhere: column x reads x - 1, the first column clamps
+    out = syn.synth_images_np(img, ov, I, F)[0, 0]
+    want = np.concatenate([a[:, :1], a[:, :-1]], axis=1)
+    np.testing.assert_allclose(out, want / want.max(), rtol=0, atol=1e-6)
+
+
+def test_overlay_composition_on_handmade_bank(syn):
+    H = W = 8
+    bank = np.zeros((4, H, W), np.float32)
+    bank[0, 2, 2] = 1.0; bank[0, 5, 5] = 0.4         # o1
+    bank[1, 5, 5] = 0.5                              # o2: cancels o1 at (5,5): clamp(0.8-0.5) = 0.3
+    bank[2, 0, 7] = 0.9; bank[3, 0, 7] = 0.5         # o3*o4*2 = 0.9
+    no_blur = syn.compose_overlays_np(bank, np.array([[0, 1, 2, 3, 0]], np.int32))[0]
+    want = np.zeros((H, W), np.float32)
+    want[2, 2] = 1.0; want[5, 5] = np.float32(0.4) * 2 - np.float32(0.5); want[0, 7] = np.float32(0.9) * np.float32(0.5) * 2
+    np.testing.assert_array_equal(no_blur, want)
+    blurred = syn.compose_overlays_np(bank, np.array([[0, 1, 2, 3, 4]], np.int32))[0]
+    ref = syn.convolve_same(want, syn.gaussian(4))
+    np.testing.assert_allclose(blurred, ref / ref.max(), rtol=0, atol=1e-7)
+    assert blurred.max() == 1.0
+
+
+@pytest.fixture(scope="module")
+def small_gen(syn):
+    rs = np.random.RandomState(7)
+    return syn.Generator((3, 16, 16), rs, bank=syn.create_overlay_bank(16, 16, rs, n=40, n_points=2000))
+
+
+@pytest.mark.parametrize("kind", [0, 1, 2, 3])
+@pytest.mark.parametrize("second", [False, True])
+def test_every_kind_is_normalised(syn, small_gen, kind, second):
+    pool = np.random.RandomState(kind).rand(12, 3, 16, 16).astype(np.float32)
+    plan = small_gen.draw(6, 12, kind=kind, second=second)
+    assert plan.idesc.shape == (6, syn.DI) and plan.fdesc.shape == (6, syn.DF) and plan.idesc.dtype == np.int32
+    assert np.all((plan.idesc[:, 8] >= 0) == second) and np.all(plan.idesc[:, 0] == kind)
+    ov = syn.plan_overlays_np(small_gen, plan)
+    assert ov.shape[0] == plan.n_overlays and ov.min() >= 0 and ov.max() <= 1
+    imgs = syn.synth_images_np(pool, ov, plan.idesc, plan.fdesc)
+    assert imgs.shape == (6, 3, 16, 16)
+    for im in imgs:
+        assert im.min() >= 0 and im.max() == 1.0
+
+
+def test_random_kind_adds_absolute_minimum(syn):
+    """img:add(math.abs(torch.min(img))) (train_v.lua:524): a positive minimum is added, not subtracted."""
+    H = W = 4
+    ov = np.zeros((3, H, W), np.float32)          # o1 o2 - o3 = 0: the image is the base value per channel
+    I = np.zeros((1, 18), np.int32); F = np.zeros((1, 8), np.float32)
+    I[0, :8] = [syn.RANDOM, 0, 0, 0, 1, 2, 1, -1]; I[0, 8] = -1
+    F[0, :3] = [0.2, 0.4, 0.6]
+    pool = np.zeros((1, 3, H, W), np.float32)
+    out = syn.synth_images_np(pool, ov, I, F)[0]
+    np.testing.assert_allclose(out[:, 0, 0], (np.float32([0.2, 0.4, 0.6]) + np.float32(0.2)) / np.float32(0.8), rtol=1e-6)
+    assert out.min() > 0.3                        # a true min-max normalisation would give 0
+    F[0, :3] = [-0.2, 0.4, 0.6]
+    out = syn.synth_images_np(pool, ov, I, F)[0]
+    assert out.min() == 0.0 and out.max() == 1.0
+
+
+def test_overlay_bank_is_normalised_random_walks(syn):
+    rs = np.random.RandomState(0)
+    bank = syn.create_overlay_bank(16, 16, rs, n=8, n_points=500)
+    assert bank.shape == (8, 16, 16) and bank.dtype == np.float32
+    assert np.all(bank.reshape(8, -1).max(axis=1) == 1.0) and bank.min() >= 0
+    assert np.all((bank > 0).reshape(8, -1).sum(axis=1) < 256)        # walks cluster: not every pixel visited in 500 steps
+    pw = syn.create_pixelwise_overlay(16, 16, rs)
+    assert pw.shape == (16, 16) and pw.min() >= 0 and pw.max() <= 1
+
+
+def test_train_v_help_parses():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "train_v.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0
+    for flag in ("--V_clamp", "--V_L1", "--V_L2", "--N_epoch", "--saveFreq", "--epochs", "--synthetic", "--dataDir"):
+        assert flag in r.stdout
+    tv = importlib.import_module("train_v")
+    o = tv.parse([])
+    assert (o.batchSize, o.V_clamp, o.V_L2, o.saveFreq, o.scale) == (32, 5.0, 0.01, 10, 32)

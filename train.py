@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """train.lua on the engine: same flags (train.lua:15-49), same set-up order (:115-220: D, G,
 criterion, flat parameters, optimiser state) and the same endless epoch loop (:223-248) around adversarial.train.
-Per epoch (unless --noplot): the image grids of NN_UTILS.visualizeProgress (PNG files; no display server).  The V network
-is not trained here (train_v.lua is out of scope): ratings appear only when a V is attached to the state.
+Per epoch (unless --noplot): the image grids of NN_UTILS.visualizeProgress (PNG files; no display server).  The validator V is
+trained by train_v.py; when <V_dir>/v_CxHxW.net exists (train.lua:19,119-123) it is loaded in evaluate mode and every epoch's
+visualisation prints V's ratings of the random, best and worst samples (nn_utils.lua:177-179,686-711).  Without the file the run
+is what it was before.  The recalled upstream behaviour V relies on is tabulated in train_v.py.
 
     python train.py --batchSize 128 --N_epoch 1000 --epochs 3 --synthetic          # no dataset needed
     python train.py --dataDir dataset/out_aug_64x64 --colorSpace y --saveFreq 30
@@ -36,7 +38,26 @@ def parse():
     a("--epochs", type=int, default=0, help="stop after this many epochs (0 = run forever, as train.lua does)")
     a("--noplot", action="store_true", help="train.lua:33 - skip the per-epoch image grids (logs/images*/<start>_<epoch>.png)")
     a("--blockingLoader", action="store_true", help="decode + upload each epoch's images on the training thread (dataset.loadRandomImages)")
+    a("--V_dir", default="logs", help="train.lua:19 - directory of the validator network v_CxHxW.net that train_v.py writes")
     return ap.parse_args()
+
+
+def load_V(cg, S, V_dir, dims):
+    """train.lua:119-123: V from <V_dir>/v_CxHxW.net, in evaluate mode, as S.MODEL_V (nn_utils.rateWithV reads it)."""
+    fn = os.path.join(V_dir, "v_%dx%dx%d.net" % tuple(dims))
+    if not os.path.exists(fn):
+        print(f"<trainer> no validator network at {fn}: V ratings are off (train_v.py trains one)")
+        return None
+    t7 = importlib.import_module("cat-generator_amd.t7")
+    t7_nn = importlib.import_module("cat-generator_amd.t7_nn")
+    r = cg.tensor.rng()
+    off = r.offset
+    V = t7_nn.from_t7(t7.load(fn)["V"])
+    r.offset = off          # rebuilding V's modules draws initial weights: leave the training streams where they were
+    V.evaluate()
+    S.MODEL_V = V
+    print(f"<trainer> loaded validator network {fn}")
+    return V
 
 
 def main():
@@ -59,6 +80,7 @@ def main():
     if o.network:   # after every generator was seeded: the checkpoint puts each of them back where the run stopped
         print(f"<trainer> reloading previously trained network: {o.network}")
         (cg.checkpoint.load_t7 if o.network.endswith(".net") else cg.checkpoint.load)(o.network, S)
+    load_V(cg, S, o.V_dir, IMG_DIMENSIONS)
     n_pool = o.N_epoch if o.N_epoch > 0 else 10000
     import time
     START_TIME = int(time.time())                                  # train.lua:58

@@ -1,0 +1,215 @@
+#!/usr/bin/env python
+"""train_v.lua on the engine: trains the validator V (models.lua:716-804) to tell real images from synthetic fakes, and saves it
+as <save>/v_CxHxW.net ({V, opt, EPOCH}, train_v.lua:203-210) - the file train.py --V_dir loads to rate G's samples every epoch.
+
+Same flags as train_v.lua:12-28, plus --epochs, --synthetic and --dataDir as in train.py.  Each batch (train_v.lua:119-198) is half
+real rows of the resident pool (cg_gather_rows) and half fakes made on the device (synthetic.py: cg_synth_overlays +
+cg_synth_images, written straight into the batch); fevalV is V forward, BCECriterion over [N, 2] (column 1 = fake), backward, and
+the V_L2 / V_L1 penalty, clamp and optim.adam in the fused update.  The 2-class confusion counts stay on the device; the only host
+synchronisation of an epoch is the reference's own confusion print at its end.  The random choices come from a seeded
+numpy RandomState: Lua's math.random stream is not reproduced.
+
+    python train_v.py --synthetic --N_epoch 1000 --epochs 3
+
+Recalled upstream behaviour the validator and its fakes rely on (the Torch7 rocks are not vendored); each row names the test that
+holds it:
+
+  | behaviour                                                                         | test                                                |
+  |-----------------------------------------------------------------------------------|-----------------------------------------------------|
+  | image.gaussian(size): sigma 0.25, amplitude 1, centre 0.5*size + 0.5, unnormalised | test_validator_host.py::test_gaussian_defaults       |
+  | image.convolve(x, k, "same"): full convolution cropped from row/col ceil(k/2)      | test_validator_host.py::test_convolve_same_crop      |
+  | image.warp(img, field): bilinear, offset mode, clamped borders, field[1] = y       | test_validator_host.py::test_warp_semantics          |
+  | nn.BatchNormalization on 2-D input: per-column batch statistics, unbiased running  | test_gpu_validator.py::test_batchnorm_1d_training,   |
+  |   variance, eval on running statistics                                            |   ::test_batchnorm_1d_evaluate                      |
+  | nn.SoftMax on 2-D input: per row, the row maximum subtracted first                 | test_gpu_validator.py::test_softmax_vs_torch         |
+"""
+import argparse
+import importlib
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+Y_FAKE, Y_REAL = 0, 1   # train_v.lua:36-37: target column Y+1 (1-based), so 0-based column 0 = fake
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser()
+    a = ap.add_argument
+    a("--save", default="logs"); a("--batchSize", type=int, default=32)
+    a("--noplot", action="store_true", help="skip the 'rated real' / 'rated fake' image grids")
+    a("--window", type=int, default=13); a("--seed", type=int, default=1); a("--aws", action="store_true")
+    a("--saveFreq", type=int, default=10); a("--gpu", type=int, default=0); a("--threads", type=int, default=8)
+    a("--colorSpace", default="rgb", choices=["rgb", "y"]); a("--scale", type=int, default=32)
+    a("--V_clamp", type=float, default=5.0); a("--V_L1", type=float, default=0.0); a("--V_L2", type=float, default=0.01)
+    a("--N_epoch", type=int, default=1000)
+    a("--dataDir", default="dataset/out_aug_64x64"); a("--synthetic", action="store_true")
+    a("--epochs", type=int, default=0, help="stop after this many epochs (0 = run forever, as train_v.lua does)")
+    return ap.parse_args(argv)
+
+
+class VTrainer:
+    """The state train_v.lua keeps in globals (V, CRITERION, PARAMETERS_V, CONFUSION, OPTSTATE; :87-99) and its epoch loop."""
+
+    def __init__(self, cg, dims, opt, bank=None):
+        import torch
+        self.cg, self.dims, self.opt = cg, tuple(dims), dict(opt)
+        self.V = cg.models.create_V(self.dims)
+        self.CRITERION = cg.nn.BCECriterion()
+        self.PARAMETERS_V, self.GRAD_PARAMETERS_V = self.V.getParameters()
+        self.CONFUSION = cg.optim.ConfusionMatrix(("0", "1"))
+        self.OPTSTATE = {"adam": {}}
+        self.EPOCH = 1
+        self.random = np.random.RandomState(self.opt.get("seed", 1))          # math.randomseed(OPT.seed), :32
+        self.gen = cg.synthetic.Generator(self.dims, self.random, bank=bank)
+        self._bufs = {}
+        self._torch = torch
+
+    def _buffers(self, N):
+        b = self._bufs.get(N)
+        if b is None:
+            cg, half = self.cg, N // 2
+            t = np.zeros((N, 2), np.float32)
+            t[:half, Y_REAL] = 1                                               # :165-167
+            t[half:, Y_FAKE] = 1                                               # :176-178
+            b = dict(inputs=cg.Tensor.zeros((N,) + self.dims, "nhwc"), targets=cg.Tensor.from_numpy(t),
+                     t_fake=cg.Tensor.from_numpy(np.ascontiguousarray(t[:, Y_FAKE])), p_fake=cg.Tensor.zeros((N,)),
+                     idx=self._torch.zeros(half, dtype=self._torch.int32, device=self.PARAMETERS_V.t.device))
+            self._bufs[N] = b
+        return b
+
+    def batch(self, trainData, N, real_idx=None, plan=None):
+        """Fill the batch (:160-183): N/2 real rows, N/2 device-made fakes.  real_idx / plan inject the random draws (tests)."""
+        cg, b, half = self.cg, self._buffers(N), N // 2
+        rowlen = int(np.prod(self.dims))
+        idx = real_idx if real_idx is not None else self.random.randint(0, trainData.size(), size=half)
+        b["idx"].copy_(self._torch.from_numpy(np.asarray(idx, dtype=np.int32)), non_blocking=True)
+        cg.lib().gather_rows(cg.tensor.stream(), trainData.pool.ptr, b["idx"].data_ptr(), b["inputs"].ptr, half, rowlen)
+        plan = plan if plan is not None else self.gen.draw(half, trainData.size())
+        self.gen.run(plan, trainData.pool, b["inputs"].ptr + half * rowlen * 4)
+        return b
+
+    def step(self, trainData, N, real_idx=None, plan=None):
+        """One iteration of :119-198: the batch, then optim.adam(fevalV, PARAMETERS_V, OPTSTATE.adam)."""
+        cg, o = self.cg, self.opt
+        b = self.batch(trainData, N, real_idx, plan)
+
+        def fevalV(x):                                                         # :124-157
+            if x is not self.PARAMETERS_V:
+                self.PARAMETERS_V.copy(x)
+            self.GRAD_PARAMETERS_V.zero()
+            outputs = self.V.forward(b["inputs"])
+            f = self.CRITERION.forward(outputs, b["targets"])
+            df_do = self.CRITERION.backward(outputs, b["targets"])
+            self.V.backward(b["inputs"], df_do)
+            # confusion (:147-153) on the device: p(fake) > 0.5 against "target is fake"
+            out = cg.nn.as_plain(outputs)
+            cg.lib().copy_channels(cg.tensor.stream(), out.ptr, b["p_fake"].ptr, N, 2, Y_FAKE, 1, 0, 1)
+            self.CONFUSION.batchAdd(b["p_fake"], b["t_fake"])
+            self._last = dict(outputs=outputs, f=f)
+            return f, self.GRAD_PARAMETERS_V                                   # penalty + clamp: in the fused update below
+
+        fused = dict(l1=o.get("V_L1", 0.0), l2=o.get("V_L2", 0.01), clamp=o.get("V_clamp", 5.0))
+        cg.optim.adam(fevalV, self.PARAMETERS_V, self.OPTSTATE["adam"], fused=fused)
+        return self._last
+
+    def epoch(self, trainData, verbose=True):
+        """epoch() (:113-213) without the saving, which main() does."""
+        N_epoch = self.opt["N_epoch"]
+        t0 = time.time()
+        trained = 0
+        while trained < N_epoch:
+            N = min(self.opt["batchSize"], N_epoch - trained)
+            N -= N % 2                                                         # half real, half fake: an even batch
+            if N < 2:
+                break
+            self.step(trainData, N)
+            trained += N
+        self._torch.cuda.synchronize()
+        dt = time.time() - t0
+        c = self.CONFUSION.counts.cpu().numpy()                                # the reference's confusion print (:189-191)
+        if verbose:
+            print("<trainer> time required for this epoch = %d s" % dt)
+            print("<trainer> time to learn 1 sample = %f ms" % (1000 * dt / N_epoch))
+            print("Confusion of V (rows: predicted fake / real, columns: target fake / real):")
+            print("  [[%d %d]\n   [%d %d]]  accuracy %.2f %%" % (c[3], c[2], c[1], c[0], 100.0 * (c[0] + c[3]) / max(1, c.sum())))
+        self.CONFUSION.zero()
+        return c
+
+    def rate(self, images):
+        """V:forward in evaluate mode, p(fake) per image (:235)."""
+        self.V.evaluate()
+        try:
+            p = self.cg.nn.as_plain(self.V.forward(images)).numpy()
+        finally:
+            self.V.training()
+        return p[:, Y_FAKE]
+
+    def save(self, path):
+        from importlib import import_module
+        t7 = import_module("cat-generator_amd.t7")
+        t7_nn = import_module("cat-generator_amd.t7_nn")
+        d = os.path.dirname(path)
+        if d:
+            os.makedirs(d, exist_ok=True)
+        opt = {k: v for k, v in self.opt.items() if isinstance(v, (int, float, str, bool))}
+        return t7.save(path, {"V": t7_nn.to_t7(self.V), "opt": opt, "EPOCH": self.EPOCH + 1})
+
+
+def visualize(T, trainData, save_dir):
+    """visualizeProgress (:218-286) without the display server: 50 real and 50 synthetic images, split by V's p(fake) into the
+    'rated real' and 'rated fake' grids (PNG files under save_dir/v_rated_real, v_rated_fake)."""
+    cg = T.cg
+    n_real = min(50, trainData.size())
+    real = cg.nn.as_nhwc(trainData.pool.rows(1, n_real)).numpy()
+    fake = T.gen.images(50, trainData.pool).numpy()
+    both = np.concatenate([real, fake])
+    p = T.rate(cg.nn.to_device(both))
+    cs = T.opt.get("colorSpace", "rgb")
+    for sub, sel in (("v_rated_real", p < 0.5), ("v_rated_fake", p >= 0.5)):
+        if sel.any():
+            path = os.path.join(save_dir, sub, "%05d.png" % T.EPOCH)
+            cg.nn_utils.saveImagesAsGrid(path, cg.nn_utils.toRgb(both[sel], cs), 10, 10, T.EPOCH)
+
+
+def main(argv=None):
+    o = parse(argv)
+    import torch
+    cg = importlib.import_module("cat-generator_amd")
+    torch.cuda.set_device(o.gpu)
+    cg.manual_seed(o.seed)                                                     # torch.manualSeed(OPT.seed), :33
+    C = 1 if o.colorSpace == "y" else 3
+    dims = (C, o.scale, o.scale)                                               # :44-48
+    T = VTrainer(cg, dims, vars(o))
+    print("network V:")
+    print(T.V)
+    print("Number of free parameters in V: %d" % cg.nn_utils.getNumberOfParameters(T.V))
+    ds = importlib.import_module("cat-generator_amd.dataset")
+    ds.colorSpace = o.colorSpace; ds.setFileExtension("jpg"); ds.setHeight(o.scale); ds.setWidth(o.scale)
+    ds.setDirs([o.dataDir]); ds.seed(o.seed)
+    while True:                                                                # :101-110
+        print("<trainer> Epoch %d" % T.EPOCH)
+        if o.synthetic:
+            pool = np.random.RandomState(T.EPOCH).rand(o.N_epoch, C, o.scale, o.scale).astype(np.float32)
+        else:
+            pool = ds.loadRandomImages(o.N_epoch).scaled                       # TRAIN_DATA = DATASET.loadRandomImages(OPT.N_epoch)
+        trainData = cg.adversarial.TrainData(pool)
+        T.epoch(trainData)
+        if T.EPOCH % o.saveFreq == 0:                                          # :203-210
+            fn = os.path.join(o.save, "v_%dx%dx%d.net" % dims)
+            print("<trainer> saving network to %s" % fn)
+            T.save(fn)
+        if not o.noplot:
+            visualize(T, trainData, o.save)
+        T.EPOCH += 1
+        if o.epochs and T.EPOCH > o.epochs:
+            break
+    return T
+
+
+if __name__ == "__main__":
+    main()
