@@ -195,16 +195,84 @@ using cg::wave_sum;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 
 // ---------------------------------------------------------------- input pipeline
+// NN_UTILS.rgbToColorSpace / toRgb (utils/nn_utils.lua:188-249) for one pixel.  'y' is the reference's own weighting (:253-277); 'yuv' and
+// 'hsl' are image.rgb2yuv / rgb2hsl and back [upstream, recalled: the formulas and constants of lua/image.lua:152-186].  Every operation
+// is a single correctly rounded fp32 one in the order written (no fma, __fdiv_rn for the quotients): dataset.rgb2yuv / rgb2hsl and
+// nn_utils.yuv2rgb / hsl2rgb restate the same sequences in numpy and agree with these bit for bit.
+enum { CS_RGB = 0, CS_Y = 1, CS_YUV = 2, CS_HSL = 3 };
+// one pixel of the loader's output: three planes, one for 'y'
+__device__ __forceinline__ void store_colorspace(float* dst, long i, float r, float g, float b, int cs) {
+#pragma clang fp contract(off)   // no fma: the same products and sums the numpy loader rounds one by one
+    if (cs == CS_RGB) { dst[3 * i] = r; dst[3 * i + 1] = g; dst[3 * i + 2] = b; }
+    else if (cs == CS_Y) {
+        const float t0 = 0.21f * r, t1 = 0.72f * g, t2 = 0.07f * b;   // z = ((0 + .21 r) + .72 g) + .07 b (nn_utils.lua:268-270)
+        dst[i] = (t0 + t1) + t2;
+    } else if (cs == CS_YUV) {
+        const float y0 = 0.299f * r, y1 = 0.587f * g, y2 = 0.114f * b;
+        const float u0 = -0.14713f * r, u1 = 0.28886f * g, u2 = 0.436f * b;
+        const float v0 = 0.615f * r, v1 = 0.51499f * g, v2 = 0.10001f * b;
+        dst[3 * i] = (y0 + y1) + y2; dst[3 * i + 1] = (u0 - u1) + u2; dst[3 * i + 2] = (v0 - v1) - v2;
+    } else {
+        const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b));
+        const float sum = mx + mn, l = __fdiv_rn(sum, 2.f);
+        float h = 0.f, s = 0.f;
+        if (mx != mn) {
+            const float d = mx - mn;
+            s = l > 0.5f ? __fdiv_rn(d, (2.f - mx) - mn) : __fdiv_rn(d, sum);
+            if (mx == r) h = __fdiv_rn(g - b, d) + (g < b ? 6.f : 0.f);
+            else if (mx == g) h = __fdiv_rn(b - r, d) + 2.f;
+            else h = __fdiv_rn(r - g, d) + 4.f;
+            h = __fdiv_rn(h, 6.f);
+        }
+        dst[3 * i] = h; dst[3 * i + 1] = s; dst[3 * i + 2] = l;
+    }
+}
+// image.hsl2rgb's helper (lua/image.lua:171-178); 1/6, 2/3 and 1/3 are the fp32 neighbours of the quotients
+__device__ __forceinline__ float hsl_hue(float p, float q, float t) {
+#pragma clang fp contract(off)
+    const float sixth = (float)(1.0 / 6.0), two_thirds = (float)(2.0 / 3.0);
+    if (t < 0.f) t += 1.f;
+    if (t > 1.f) t -= 1.f;
+    if (t < sixth) { const float a = (q - p) * 6.f, m = a * t; return p + m; }
+    if (t < 0.5f) return q;
+    if (t < two_thirds) { const float a = (q - p) * (two_thirds - t), m = a * 6.f; return p + m; }
+    return p;
+}
+// the way back (NN_UTILS.toRgb, nn_utils.lua:188-220): the three planes of a 'yuv' or 'hsl' pixel -> r, g, b
+__device__ __forceinline__ void colorspace_to_rgb(float a, float b, float c, int cs, float* rgb) {
+#pragma clang fp contract(off)
+    if (cs == CS_YUV) {
+        const float rv = 1.13983f * c, gu = 0.39465f * b, gv = 0.58060f * c, bu = 2.03211f * b;
+        rgb[0] = a + rv; rgb[1] = (a - gu) - gv; rgb[2] = a + bu;
+    } else {
+        const float h = a, s = b, l = c;
+        if (s == 0.f) { rgb[0] = l; rgb[1] = l; rgb[2] = l; return; }
+        const float third = (float)(1.0 / 3.0);
+        const float ls = l * s;
+        const float q = l < 0.5f ? l * (1.f + s) : (l + s) - ls;
+        const float p = 2.f * l - q;
+        rgb[0] = hsl_hue(p, q, h + third); rgb[1] = hsl_hue(p, q, h); rgb[2] = hsl_hue(p, q, h - third);
+    }
+}
+// fp32 NHWC pixels that are on the device already (a pool held as rgb; images on their way to a grid).  One lane per pixel; it reads
+// its three floats before it writes, so src == dst is fine whenever three planes come out
+__global__ void colorspace_convert_k(const float* src, float* dst, long npix, int from, int to) {
+    GRID_STRIDE(i, npix) {
+        const float a = src[3 * i], b = src[3 * i + 1], c = src[3 * i + 2];
+        if (from == CS_RGB) store_colorspace(dst, i, a, b, c, to);
+        else {
+            float rgb[3];
+            colorspace_to_rgb(a, b, c, from, rgb);
+            dst[3 * i] = rgb[0]; dst[3 * i + 1] = rgb[1]; dst[3 * i + 2] = rgb[2];
+        }
+    }
+}
 // one lane per pixel; every operation correctly rounded on its own, like the numpy loader's
 __global__ void images_u8_to_f32_k(const unsigned char* __restrict__ src, float* __restrict__ dst, long npix, int cs) {
 #pragma clang fp contract(off)   // no fma: the same three products and two sums the numpy loader rounds one by one
     GRID_STRIDE(i, npix) {
         const float r = __fdiv_rn((float)src[3 * i], 255.f), g = __fdiv_rn((float)src[3 * i + 1], 255.f), b = __fdiv_rn((float)src[3 * i + 2], 255.f);
-        if (cs == 0) { dst[3 * i] = r; dst[3 * i + 1] = g; dst[3 * i + 2] = b; }
-        else {
-            const float t0 = 0.21f * r, t1 = 0.72f * g, t2 = 0.07f * b;   // plain operators: the pragma above governs them
-            dst[i] = (t0 + t1) + t2;
-        }
+        store_colorspace(dst, i, r, g, b, cs);
     }
 }
 
@@ -284,11 +352,7 @@ __global__ void images_u8_scale_k(const unsigned char* __restrict__ src, float* 
             }
             rgb[c] = scale_axis(col, y0, Hs, Hd, oy);
         }
-        if (cs == 0) { dst[3 * i] = rgb[0]; dst[3 * i + 1] = rgb[1]; dst[3 * i + 2] = rgb[2]; }
-        else {
-            const float t0 = 0.21f * rgb[0], t1 = 0.72f * rgb[1], t2 = 0.07f * rgb[2];   // z = ((0 + .21 r) + .72 g) + .07 b (nn_utils.lua:268-270)
-            dst[i] = (t0 + t1) + t2;
-        }
+        store_colorspace(dst, i, rgb[0], rgb[1], rgb[2], cs);
     }
 }
 
@@ -1449,15 +1513,22 @@ int cg_stream_wait_event(void* stream, void* event) {
     CG_HIP(hipStreamWaitEvent(cg::S(stream), (hipEvent_t)event, 0)); return 0;
 }
 int cg_images_u8_to_f32(void* stream, const unsigned char* src, float* dst, long npixels, int colorspace) {
-    CG_REQUIRE(src && dst && npixels > 0 && (colorspace == 0 || colorspace == 1), "cg_images_u8_to_f32: bad arguments");
+    CG_REQUIRE(src && dst && npixels > 0 && colorspace >= CS_RGB && colorspace <= CS_HSL, "cg_images_u8_to_f32: bad arguments");
     EW_LAUNCH(images_u8_to_f32_k, npixels, src, dst, npixels, colorspace); return 0;
 }
 
 int cg_images_u8_scale_to_f32(void* stream, const unsigned char* src, float* dst, int N, int Hs, int Ws, int Hd, int Wd, int colorspace) {
-    CG_REQUIRE(src && dst && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && (colorspace == 0 || colorspace == 1), "cg_images_u8_scale_to_f32: bad arguments");
+    CG_REQUIRE(src && dst && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && colorspace >= CS_RGB && colorspace <= CS_HSL, "cg_images_u8_scale_to_f32: bad arguments");
     CG_REQUIRE(Hs <= 6 * Hd && Ws <= 6 * Wd, "cg_images_u8_scale_to_f32: down-scaling by more than 6 is not supported");
     const long total = (long)N * Hd * Wd;
     EW_LAUNCH(images_u8_scale_k, total, src, dst, N, Hs, Ws, Hd, Wd, colorspace); return 0;
+}
+int cg_colorspace_convert(void* stream, const float* src, float* dst, long npixels, int from, int to) {
+    CG_REQUIRE(src && dst && npixels > 0, "cg_colorspace_convert: bad arguments");
+    CG_REQUIRE((from == CS_RGB && to >= CS_Y && to <= CS_HSL) || ((from == CS_YUV || from == CS_HSL) && to == CS_RGB),
+               "cg_colorspace_convert: unsupported pair %d -> %d (rgb -> y | yuv | hsl, yuv | hsl -> rgb)", from, to);
+    CG_REQUIRE(to != CS_Y || src != dst, "cg_colorspace_convert: rgb -> y cannot run in place (one plane out of three)");
+    EW_LAUNCH(colorspace_convert_k, npixels, src, dst, npixels, from, to); return 0;
 }
 
 int cg_prelu_forward(void* stream, const float* x, const float* alpha, float* y, long n) {

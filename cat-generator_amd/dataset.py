@@ -1,11 +1,13 @@
 """dataset.lua restated: list + sort the image files of the configured directories
 (dataset.lua:57-83), load `count` random ones (torch.randperm, :158-168), image.load them as floats in [0,1] (:166), scale the
 FLOAT image to width x height (image.scale, :129-131) and convert the colour space (NN_UTILS.rgbToColorSpace,
-nn_utils.lua:223-278: 'rgb' or 'y' with weights 0.21/0.72/0.07).  PIL only decodes; the scaling is `image_scale` below - the `image`
-rock's default separable 'bilinear' [upstream, recalled: box averaging when shrinking, linear interpolation when enlarging] in fp32,
-the arithmetic cg_images_u8_scale_to_f32 performs on the device (oracle/oracle.py holds the independent restatement the tests
-compare both with).  The result is a float array in [0,1] that adversarial.TrainData uploads to HBM once per epoch (the reference
-reloads N_epoch images per epoch, train.lua:225).
+nn_utils.lua:223-278: 'rgb', 'y' with weights 0.21/0.72/0.07, 'yuv' and 'hsl' through image.rgb2yuv / image.rgb2hsl [upstream,
+recalled: the `image` rock's formulas and constants as lua/image.lua:152-186 restates them]).  PIL only decodes; the scaling is
+`image_scale` below - the `image` rock's default separable 'bilinear' [upstream, recalled: box averaging when shrinking, linear
+interpolation when enlarging] in fp32, the arithmetic cg_images_u8_scale_to_f32 performs on the device (oracle/oracle.py holds the
+independent restatement the tests compare both with; for 'yuv' / 'hsl' the yardstick is fp64 and colorsys,
+tests/test_colorspace_host.py).  The result is a float array (in [0,1] except yuv's signed U and V planes) that
+adversarial.TrainData uploads to HBM once per epoch (the reference reloads N_epoch images per epoch, train.lua:225).
 
 AsyncLoader is the production form of the same thing: the NEXT epoch's images are decoded by a worker
 thread straight into a page-locked buffer as 8-bit RGB at their own size (a quarter of the fp32 bytes over PCIe), copied on a copy
@@ -79,18 +81,49 @@ def loadPaths():
     return paths
 
 
+COLOR_SPACES = {"rgb": 0, "y": 1, "yuv": 2, "hsl": 3}      # --colorSpace -> the `colorspace` code of include/catgan.h
+
+
 def rgb2y(im):
     """nn_utils.lua:253-277."""
     return (np.float32(0.21) * im[0] + np.float32(0.72) * im[1] + np.float32(0.07) * im[2])[None].astype(np.float32)
 
 
+def rgb2yuv(im):
+    """image.rgb2yuv [upstream, recalled: the constants and the order of lua/image.lua:152-155] for a float32 [3, H, W] image, every
+    operation a single fp32 one (the device form is store_colorspace in csrc/ops.hip, same sequence).  U and V are signed."""
+    f = np.float32
+    r, g, b = (np.asarray(im[k], dtype=f) for k in range(3))
+    return np.stack([(f(0.299) * r + f(0.587) * g) + f(0.114) * b,
+                     (f(-0.14713) * r - f(0.28886) * g) + f(0.436) * b,
+                     (f(0.615) * r - f(0.51499) * g) - f(0.10001) * b]).astype(f)
+
+
+def rgb2hsl(im):
+    """image.rgb2hsl [upstream, recalled: lua/image.lua:159-170] for a float32 [3, H, W] image -> planes h, s, l with h in [0, 1);
+    fp32 step by step, the quotients correctly rounded (store_colorspace in csrc/ops.hip is the same sequence)."""
+    f = np.float32
+    r, g, b = (np.asarray(im[k], dtype=f) for k in range(3))
+    mx, mn = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))
+    sm = mx + mn
+    l = sm / f(2)
+    d = mx - mn
+    with np.errstate(divide="ignore", invalid="ignore"):      # the grey pixels (d == 0) are replaced below
+        s = np.where(l > f(0.5), d / ((f(2) - mx) - mn), d / sm)
+        h = np.where(mx == r, (g - b) / d + np.where(g < b, f(6), f(0)),
+                     np.where(mx == g, (b - r) / d + f(2), (r - g) / d + f(4))) / f(6)
+    grey = mx == mn
+    return np.stack([np.where(grey, f(0), h), np.where(grey, f(0), s), l]).astype(f)
+
+
 def rgbToColorSpace(images, cs):
-    """nn_utils.lua:223-249 ('hsl'/'yuv' are not reachable from the benchmarked configurations)."""
+    """nn_utils.lua:223-249: 'rgb' as is, 'y' with the reference's own weights, 'yuv' / 'hsl' through image.rgb2yuv / image.rgb2hsl."""
     if cs == "rgb":
         return images
-    if cs == "y":
-        return np.stack([rgb2y(im) for im in images])
-    raise NotImplementedError(f"colour space '{cs}' is outside the hot-path scope (rgb | y)")
+    if cs in ("y", "yuv", "hsl"):
+        convert = {"y": rgb2y, "yuv": rgb2yuv, "hsl": rgb2hsl}[cs]
+        return np.stack([convert(im) for im in images])
+    raise NotImplementedError(f"unknown colour space '{cs}' (rgb | yuv | hsl | y)")
 
 
 class _Data:
@@ -194,6 +227,7 @@ class AsyncLoader:
         from .tensor import Tensor, lib
         self._ct, self._T, self.L = ctypes, Tensor, lib()
         self.count, self.depth = int(count), int(depth)
+        self.cs_code = COLOR_SPACES[colorSpace]
         self.C = 1 if colorSpace == "y" else 3
         if paths is None:
             loadPaths()
@@ -274,7 +308,7 @@ class AsyncLoader:
             L.memcpy_h2d(cs, slot["pool"].ptr, slot["host"], n * self.row)
         else:
             L.memcpy_h2d(cs, slot["dev_u8"], slot["host"], n * self.Hs * self.Ws * 3)
-            L.images_u8_scale_to_f32(cs, slot["dev_u8"], slot["pool"].ptr, n, self.Hs, self.Ws, height, width, 1 if colorSpace == "y" else 0)
+            L.images_u8_scale_to_f32(cs, slot["dev_u8"], slot["pool"].ptr, n, self.Hs, self.Ws, height, width, self.cs_code)
             for i in slot["patches"]:     # images scaled on the host (another source size): over the rows the kernel produced from zeros
                 L.memcpy_h2d(cs, slot["pool"].ptr + i * self.row, slot["side"].value + i * self.row, self.row)
             slot["patches"] = []

@@ -9,6 +9,7 @@ import zlib
 import numpy as np
 
 from . import nn
+from .dataset import COLOR_SPACES
 from .tensor import Tensor, lib, rng, stream
 
 
@@ -129,8 +130,51 @@ def activateCuda(net):
 
 
 # ------------------------------------------------------------------ visual grids
+def yuv2rgb(im):
+    """image.yuv2rgb [upstream, recalled: the constants and the order of lua/image.lua:156-158] for a float32 [3, H, W] image, every
+    operation a single fp32 one (the device form is colorspace_to_rgb in csrc/ops.hip, same sequence).  The two matrices are five-digit
+    constants, no exact inverses: a round trip leaves the unit cube by a few 1e-5, which _png_bytes clamps as image.save does."""
+    f = np.float32
+    y, u, v = (np.asarray(im[k], dtype=f) for k in range(3))
+    return np.stack([y + f(1.13983) * v, (y - f(0.39465) * u) - f(0.58060) * v, y + f(2.03211) * u]).astype(f)
+
+
+def _hue(p, q, t):
+    """image.hsl2rgb's helper (lua/image.lua:171-178); 1/6 and 2/3 rounded to fp32 first."""
+    f = np.float32
+    sixth, two_thirds = f(1 / 6), f(2 / 3)
+    t = np.where(t < f(0), t + f(1), t)
+    t = np.where(t > f(1), t - f(1), t)
+    return np.where(t < sixth, p + ((q - p) * f(6)) * t,
+                    np.where(t < f(0.5), q, np.where(t < two_thirds, p + ((q - p) * (two_thirds - t)) * f(6), p)))
+
+
+def hsl2rgb(im):
+    """image.hsl2rgb [upstream, recalled: lua/image.lua:179-186] for a float32 [3, H, W] image with planes h, s, l; fp32 step by step
+    (colorspace_to_rgb in csrc/ops.hip is the same sequence)."""
+    f = np.float32
+    h, s, l = (np.asarray(im[k], dtype=f) for k in range(3))
+    q = np.where(l < f(0.5), l * (f(1) + s), (l + s) - l * s)
+    p = f(2) * l - q
+    third = f(1 / 3)
+    rgb = np.stack([_hue(p, q, h + third), _hue(p, q, h), _hue(p, q, h - third)])
+    return np.where(s == f(0), l, rgb).astype(f)
+
+
 def toRgb(images, colorSpace):
-    """nn_utils.lua:188-220 for the colour spaces the engine loads ('rgb' as is, 'y' repeated over three channels)."""
+    """nn_utils.lua:188-220: 'rgb' as is, 'y' repeated over three channels, 'yuv' / 'hsl' through image.yuv2rgb / image.hsl2rgb.
+    Returns a host array [n, 3, H, W].  Host arrays (what the grids hold) are converted in numpy; an engine tensor is converted on
+    the device (cg_colorspace_convert, the same arithmetic) before it is copied back."""
+    if colorSpace not in COLOR_SPACES:
+        raise NotImplementedError(f"unknown colour space '{colorSpace}' (rgb | yuv | hsl | y)")
+    if isinstance(images, Tensor):
+        images = nn.as_nhwc(images)
+        if colorSpace in ("yuv", "hsl"):
+            out = Tensor.empty(images.shape, "nhwc")
+            N, _, H, W = images.shape
+            lib().colorspace_convert(stream(), images.ptr, out.ptr, N * H * W, COLOR_SPACES[colorSpace], COLOR_SPACES["rgb"])
+            return out.numpy()
+        images = images.numpy()
     images = np.asarray(images, dtype=np.float32)
     if images.ndim == 3:
         images = images[None]
@@ -138,7 +182,7 @@ def toRgb(images, colorSpace):
         return images
     if colorSpace == "y":
         return np.tile(images, (1, 3, 1, 1))
-    raise NotImplementedError(f"colour space '{colorSpace}' is outside the hot-path scope (rgb | y)")
+    return np.stack([(yuv2rgb if colorSpace == "yuv" else hsl2rgb)(im) for im in images])
 
 
 # the 3 x 5 digit glyphs the reference draws the epoch number with (CHAR_TENSORS, nn_utils.lua:465-515), one 15-bit row-major

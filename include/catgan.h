@@ -93,7 +93,9 @@ int cg_event_sync(void* event);
 int cg_stream_wait_event(void* stream, void* event);
 /* Decoded images as the loader produces them (8-bit RGB, [N][H][W][3]) -> the engine's fp32 NHWC pool in [0,1]:
  * colorspace 0 'rgb' (3 planes, v / 255), 1 'y' (1 plane, 0.21 R + 0.72 G + 0.07 B of the scaled values,
- * nn_utils.lua:253-277).  Every operation is a single correctly rounded fp32 one, in the host loader's order. */
+ * nn_utils.lua:253-277), 2 'yuv' and 3 'hsl' (3 planes each: image.rgb2yuv / image.rgb2hsl as NN_UTILS.rgbToColorSpace applies them,
+ * nn_utils.lua:223-249; formulas under cg_colorspace_convert).  Every operation is a single correctly rounded fp32 one, in the host
+ * loader's order. */
 int cg_images_u8_to_f32(void* stream, const unsigned char* src, float* dst, long npixels, int colorspace);
 /* The loader's whole per-image arithmetic (dataset.lua:123-131,166) on the device: image.load's floats (byte / 255) -> image.scale to
  * Hd x Wd -> colour space, from the decoded 8-bit image at its own size [N][Hs][Ws][3] to the fp32 NHWC pool [N][Hd][Wd][C].
@@ -101,6 +103,19 @@ int cg_images_u8_to_f32(void* stream, const unsigned char* src, float* dst, long
  * shrinking an axis averages the source samples a target sample covers (fractional ends weighted), enlarging interpolates
  * linearly between the two neighbours (corner aligned), equal sizes copy.  Shrink factors up to 6 per axis. */
 int cg_images_u8_scale_to_f32(void* stream, const unsigned char* src, float* dst, int N, int Hs, int Ws, int Hd, int Wd, int colorspace);
+/* NN_UTILS.rgbToColorSpace / NN_UTILS.toRgb (utils/nn_utils.lua:188-249) on fp32 NHWC pixels that are already on the device: three
+ * floats in per pixel, three out (one for to == 1).  from / to are the colorspace codes above; the pairs are rgb -> y | yuv | hsl and
+ * yuv | hsl -> rgb, anything else is an error.  src == dst is allowed when three planes come out.  Per pixel, every operation a single
+ * correctly rounded fp32 one in this order, constants rounded to fp32 first [upstream, recalled: image.rgb2yuv / yuv2rgb / rgb2hsl /
+ * hsl2rgb of the `image` rock, as lua/image.lua:152-186 restates them]:
+ *   rgb -> yuv: y = (0.299 r + 0.587 g) + 0.114 b, u = (-0.14713 r - 0.28886 g) + 0.436 b, v = (0.615 r - 0.51499 g) - 0.10001 b
+ *   yuv -> rgb: r = y + 1.13983 v, g = (y - 0.39465 u) - 0.58060 v, b = y + 2.03211 u
+ *   rgb -> hsl: l = (mx + mn) / 2; mx == mn: h = s = 0; else d = mx - mn, s = l > 0.5 ? d / ((2 - mx) - mn) : d / (mx + mn),
+ *               h = ((g - b) / d + (g < b ? 6 : 0)) / 6 if mx == r, ((b - r) / d + 2) / 6 if mx == g, else ((r - g) / d + 4) / 6
+ *   hsl -> rgb: s == 0: (l, l, l); else q = l < 0.5 ? l (1 + s) : (l + s) - l s, p = 2 l - q, (r, g, b) = hue(p, q, h + 1/3 | h | h - 1/3)
+ *               with hue(p, q, t): t < 0: t += 1; t > 1: t -= 1; t < 1/6: p + ((q - p) 6) t; t < 1/2: q; t < 2/3: p + ((q - p) (2/3 - t)) 6; else p
+ * (planes h, s, l; h in [0, 1)).  The U and V planes are signed (|U| <= 0.436, |V| <= 0.615), as in the reference. */
+int cg_colorspace_convert(void* stream, const float* src, float* dst, long npixels, int from, int to);
 
 /* ---- convolution / linear (implicit GEMM on fp32 MFMA) -------------------
  * Replaces cudnn.SpatialConvolution (models.lua:206,212,218,222),

@@ -33,7 +33,7 @@ def parse():
     a("--D_sgd_lr", type=float, default=0.02); a("--G_sgd_lr", type=float, default=0.02)
     a("--D_sgd_momentum", type=float, default=0.0); a("--G_sgd_momentum", type=float, default=0.0)
     a("--gpu", type=int, default=0); a("--noiseDim", type=int, default=100); a("--scale", type=int, default=32)
-    a("--seed", type=int, default=1); a("--colorSpace", default="rgb", choices=["rgb", "y"])
+    a("--seed", type=int, default=1); a("--colorSpace", default="rgb", choices=["rgb", "yuv", "hsl", "y"])
     a("--dataDir", default="dataset/out_aug_64x64"); a("--synthetic", action="store_true")
     a("--epochs", type=int, default=0, help="stop after this many epochs (0 = run forever, as train.lua does)")
     a("--noplot", action="store_true", help="train.lua:33 - skip the per-epoch image grids (logs/images*/<start>_<epoch>.png)")

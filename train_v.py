@@ -44,7 +44,7 @@ def parse(argv=None):
     a("--noplot", action="store_true", help="skip the 'rated real' / 'rated fake' image grids")
     a("--window", type=int, default=13); a("--seed", type=int, default=1); a("--aws", action="store_true")
     a("--saveFreq", type=int, default=10); a("--gpu", type=int, default=0); a("--threads", type=int, default=8)
-    a("--colorSpace", default="rgb", choices=["rgb", "y"]); a("--scale", type=int, default=32)
+    a("--colorSpace", default="rgb", choices=["rgb", "yuv", "hsl", "y"]); a("--scale", type=int, default=32)
     a("--V_clamp", type=float, default=5.0); a("--V_L1", type=float, default=0.0); a("--V_L2", type=float, default=0.01)
     a("--N_epoch", type=int, default=1000)
     a("--dataDir", default="dataset/out_aug_64x64"); a("--synthetic", action="store_true")
