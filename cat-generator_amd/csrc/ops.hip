@@ -356,6 +356,108 @@ __global__ void images_u8_scale_k(const unsigned char* __restrict__ src, float* 
     }
 }
 
+// The same with the reference's augmentation in front (dataset/dataset.py:284-306 with the matrices of ImageAugmenter.py:160-190;
+// semantics under cg_images_u8_augment_to_f32 in catgan.h, numpy restatement dataset.augment_images).  One workgroup per image.
+// Phase 1 leaves the pixel stage p (flip, brightness, noise, clip) of the whole source image in the LDS as fp32, [Hs][Ws][3], so that a
+// noise value is hashed once and not once per bilinear tap of every box-filter sample that touches it.  Phase 2 is
+// images_u8_scale_k's walk, one lane per output element, whose source samples are the four warp taps out of the LDS.
+// noise value of one source sample: Irwin-Hall sum of the twelve 16-bit fields of three splitmix64 outputs (exact in fp32)
+__device__ __forceinline__ float augment_noise(uint64_t seed, uint64_t ctr) {
+    unsigned S = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        uint64_t z = seed + (ctr + k + 1) * 0x9E3779B97F4A7C15ull;   // common.h u01's generator, all 64 bits of it
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        z = z ^ (z >> 31);
+        S += (unsigned)(z & 0xFFFF) + (unsigned)((z >> 16) & 0xFFFF) + (unsigned)((z >> 32) & 0xFFFF) + (unsigned)(z >> 48);
+    }
+    return (float)((int)S - 393210) * (1.0f / 65536.0f);   // |S - 393210| < 2^24 and a power of two: both steps exact
+}
+// one axis of the warp's source position: clamped to [0, L-1] (NaN -> 0), split into the two taps and the fraction
+__device__ __forceinline__ void warp_taps(float s, int L, int* i0, int* i1, float* f) {
+#pragma clang fp contract(off)
+    const float hi = (float)(L - 1);
+    s = !(s >= 0.f) ? 0.f : (s > hi ? hi : s);
+    *i0 = (int)s;
+    *f = s - (float)*i0;
+    *i1 = min(*i0 + 1, L - 1);
+}
+__global__ void __launch_bounds__(256) images_u8_augment_k(const unsigned char* __restrict__ src, float* __restrict__ dst, int Hs, int Ws,
+                                                            int Hd, int Wd, int cs, const float* __restrict__ desc, float sigma,
+                                                            uint64_t seed, uint64_t offset) {
+#pragma clang fp contract(off)
+    extern __shared__ float aug_p[];   // [Hs][Ws][3]
+    const long n = blockIdx.x;
+    const unsigned char* im = src + n * (long)Hs * Ws * 3;
+    const float* d = desc + n * 8;
+    const float m00 = d[0], m01 = d[1], m02 = d[2], m10 = d[3], m11 = d[4], m12 = d[5], bright = d[6];
+    const bool flip = d[7] != 0.f;
+    const int row3 = Ws * 3, nsrc = Hs * row3;
+    for (int k = threadIdx.x; k < nsrc; k += 256) {
+        const int y = k / row3, r = k - y * row3, x = r / 3, c = r - x * 3;
+        const int xf = flip ? Ws - 1 - x : x;
+        float v = __fdiv_rn((float)im[y * row3 + xf * 3 + c], 255.f) * bright;
+        if (sigma != 0.f) {
+            const float t = sigma * augment_noise(seed, offset + 3ull * (uint64_t)(n * nsrc + k));
+            v += t;
+        }
+        v = v < 0.f ? 0.f : v;
+        aug_p[k] = v > 1.f ? 1.f : v;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < Hd * Wd; e += 256) {
+        const int ox = e % Wd, oy = e / Wd;
+        // the footprints of images_u8_scale_k
+        int y0 = oy, y1 = oy, x0 = ox, x1 = ox;
+        if (Hd < Hs) {
+            const float scale = __fdiv_rn((float)Hs, (float)Hd);
+            y0 = oy == 0 ? 0 : (int)((float)oy * scale);
+            y1 = min(Hs - 1, (int)((float)(oy + 1) * scale));
+        } else if (Hd > Hs) {
+            const float scale = __fdiv_rn((float)(Hs - 1), (float)(Hd - 1));
+            y0 = (oy == Hd - 1 || Hs == 1) ? Hs - 1 : (int)((float)oy * scale);
+            y1 = min(Hs - 1, y0 + 1);
+        }
+        if (Wd < Ws) {
+            const float sc = __fdiv_rn((float)Ws, (float)Wd);
+            x0 = ox == 0 ? 0 : (int)((float)ox * sc);
+            x1 = min(Ws - 1, (int)((float)(ox + 1) * sc));
+        } else if (Wd > Ws) {
+            const float sc = __fdiv_rn((float)(Ws - 1), (float)(Wd - 1));
+            x0 = (ox == Wd - 1 || Ws == 1) ? Ws - 1 : (int)((float)ox * sc);
+            x1 = min(Ws - 1, x0 + 1);
+        }
+        float col[3][8];   // first pass at column ox for the source rows y0..y1, per channel
+        for (int y = y0; y <= y1 && y - y0 < 8; ++y) {
+            float row[3][8];
+            for (int x = x0; x <= x1 && x - x0 < 8; ++x) {
+                const float ax = m00 * (float)x, bx = m01 * (float)y, ay = m10 * (float)x, by = m11 * (float)y;
+                int tx0, tx1, ty0, ty1;
+                float fx, fy;
+                warp_taps((ax + bx) + m02, Ws, &tx0, &tx1, &fx);
+                warp_taps((ay + by) + m12, Hs, &ty0, &ty1, &fy);
+                const float gx = 1.f - fx, gy = 1.f - fy;
+                const float *p00 = aug_p + ty0 * row3 + tx0 * 3, *p01 = aug_p + ty0 * row3 + tx1 * 3;
+                const float *p10 = aug_p + ty1 * row3 + tx0 * 3, *p11 = aug_p + ty1 * row3 + tx1 * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float ta = gx * p00[c], tb = fx * p01[c], ba = gx * p10[c], bb = fx * p11[c];
+                    const float top = ta + tb, bot = ba + bb;
+                    const float wa = gy * top, wb = fy * bot;
+                    row[c][x - x0] = wa + wb;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) col[c][y - y0] = scale_axis(row[c], x0, Ws, Wd, ox);
+        }
+        float rgb[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rgb[c] = scale_axis(col[c], y0, Hs, Hd, oy);
+        store_colorspace(dst, n * (long)Hd * Wd + e, rgb[0], rgb[1], rgb[2], cs);
+    }
+}
+
 // ---------------------------------------------------------------- activations
 // Memory-bound elementwise kernels move 16 B per lane (float4) when the buffers are 16-B aligned; `n4` counts
 // whole float4s, the (<4)-element tail is handled by the last lanes with scalar accesses.
@@ -1522,6 +1624,32 @@ int cg_images_u8_scale_to_f32(void* stream, const unsigned char* src, float* dst
     CG_REQUIRE(Hs <= 6 * Hd && Ws <= 6 * Wd, "cg_images_u8_scale_to_f32: down-scaling by more than 6 is not supported");
     const long total = (long)N * Hd * Wd;
     EW_LAUNCH(images_u8_scale_k, total, src, dst, N, Hs, Ws, Hd, Wd, colorspace); return 0;
+}
+
+int cg_images_u8_augment_to_f32(void* stream, const unsigned char* src, float* dst, int N, int Hs, int Ws, int Hd, int Wd, int colorspace,
+                                const float* desc, float noise_std, uint64_t seed, uint64_t offset) {
+    CG_REQUIRE(src && dst && desc && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && colorspace >= CS_RGB && colorspace <= CS_HSL &&
+               noise_std >= 0.f, "cg_images_u8_augment_to_f32: bad arguments");
+    CG_REQUIRE(Hs <= 6 * Hd && Ws <= 6 * Wd, "cg_images_u8_augment_to_f32: down-scaling by more than 6 is not supported");
+    // the pixel stage of one image in the LDS: 64 x 64 sources take 48 KB (three workgroups per CU); above 64 KB a kernel has to ask
+    static thread_local int lds_dev = -1, lds_max = 0, lds_asked = 0;
+    int dev = 0;
+    CG_HIP(hipGetDevice(&dev));
+    if (dev != lds_dev) {
+        CG_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+        lds_dev = dev; lds_asked = 0;
+    }
+    const long lds = (long)Hs * Ws * 3 * sizeof(float);
+    CG_REQUIRE(lds <= lds_max, "cg_images_u8_augment_to_f32: a %d x %d source needs %ld bytes of LDS, the device has %d per workgroup", Ws, Hs,
+               lds, lds_max);
+    if (lds > 65536 && lds > lds_asked) {
+        CG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(images_u8_augment_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        lds_asked = lds_max;
+    }
+    hipLaunchKernelGGL(images_u8_augment_k, dim3(N), dim3(256), (size_t)lds, cg::S(stream), src, dst, Hs, Ws, Hd, Wd, colorspace, desc, noise_std,
+                       seed, offset);
+    CG_LAUNCH_CHECK();
+    return 0;
 }
 int cg_colorspace_convert(void* stream, const float* src, float* dst, long npixels, int from, int to) {
     CG_REQUIRE(src && dst && npixels > 0, "cg_colorspace_convert: bad arguments");

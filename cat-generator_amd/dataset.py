@@ -13,7 +13,10 @@ AsyncLoader is the production form of the same thing: the NEX
 thread straight into a page-locked buffer as 8-bit RGB at their own size (a quarter of the fp32 bytes over PCIe), copied on a copy
 stream while the current epoch trains, scaled and converted on the device (cg_images_u8_scale_to_f32: /255, image.scale, colour
 space) into the second of two HBM pools, and handed to the compute stream through an event - no host synchronisation on the
-training path."""
+training path.
+
+setAugmentation turns on the augmentation the reference only has as an offline tool (dataset/generate_dataset.py): both loaders then
+draw fresh variants for every epoch pool (augment_images on the host, cg_images_u8_augment_to_f32 on the device, bit-equal)."""
 import os
 import threading
 
@@ -27,6 +30,10 @@ colorSpace = "rgb"
 paths = None
 _rs = np.random.RandomState(1)
 _prefetch_state = None   # AsyncLoader: the generator's state BEFORE the pick of the prefetch that has not been consumed yet
+# On-the-fly augmentation (setAugmentation below): off unless asked for; the ranges are generate_dataset.py:68-73's
+AUG_DEFAULTS = dict(hflip=True, scale=(0.93, 1.08), rotation=8, translation=4, brightness=0.15, noise_std=0.02)
+augmentation = None      # None = off, else a dict with AUG_DEFAULTS' keys
+AUG_LDS_BYTES = 160 * 1024   # gfx950's LDS per workgroup: cg_images_u8_augment_to_f32 keeps one source image there as fp32
 
 
 def setDirs(d):
@@ -206,13 +213,164 @@ def image_scale(img, w, h):
     return np.ascontiguousarray(_scale_axis(np.ascontiguousarray(t.transpose(0, 2, 1)), h).transpose(0, 2, 1))
 
 
+# ---------------------------------------------------------------- augmentation
+def setAugmentation(on=True, **ranges):
+    """On-the-fly augmentation for both loaders: what the reference ships as an offline tool (dataset/generate_dataset.py:68-73 ->
+    Image.augment, dataset/dataset.py:284-306, with the matrices of dataset/ImageAugmenter.py:160-190) that writes nine fixed variants of
+    every face to disk, drawn afresh for every epoch pool instead - so --dataDir points at the UN-augmented faces.  Per image: a
+    left-right flip with probability 1/2 (`hflip`), a brightness factor ~ U(1-B, 1+B) (`brightness`), noise of deviation `noise_std`,
+    clipping to [0, 1], then an affine warp about the image centre (bilinear, edges replicated): zoom ~ U(`scale`) equal on both
+    axes, a whole number of degrees in [-`rotation`, `rotation`], whole pixels in [-`translation`, `translation`] on each axis.
+    Ranges not named keep AUG_DEFAULTS' values; setAugmentation(False) turns it off again (the default: the loaders then consume the
+    generator and compute exactly what they always did).  augment_images holds the arithmetic, cg_images_u8_augment_to_f32 is its
+    device form.
+
+    Deliberate differences from the offline tool: no re-quantisation to 8 bits between the stages; the warp acts on the dataset's
+    64 x 64 files, which have none of the tool's 30 px padding left, so rotated / shifted borders show replicated edge pixels;
+    numpy's seeded generator (dataset.seed) instead of Python's `random`; the noise is a bit-reproducible Irwin-Hall normal
+    (augment_noise), not numpy's."""
+    global augmentation
+    if not on:
+        augmentation = None
+        return
+    unknown = set(ranges) - set(AUG_DEFAULTS)
+    if unknown:
+        raise TypeError(f"setAugmentation: unknown range(s) {sorted(unknown)} ({' | '.join(AUG_DEFAULTS)})")
+    a = dict(AUG_DEFAULTS)
+    a.update({k: v for k, v in ranges.items() if v is not None})
+    a["scale"] = (float(a["scale"][0]), float(a["scale"][1]))
+    a["rotation"], a["translation"] = int(a["rotation"]), int(a["translation"])
+    if not (0 < a["scale"][0] <= a["scale"][1] and a["rotation"] >= 0 and a["translation"] >= 0 and 0 <= a["brightness"] < 1 and a["noise_std"] >= 0):
+        raise ValueError(f"setAugmentation: bad ranges {a}")
+    augmentation = a
+
+
+def augment_draw(n):
+    """The random choices of one pool of n images (create_aug_matrices' and Image.augment's draws, ImageAugmenter.py:160-172,
+    dataset.py:284-293) from the loader's own generator: flip [n] 0/1, scale [n], rotation [n] whole degrees, tx / ty [n] whole pixels,
+    brightness [n], one 63-bit seed for the pool's noise, and the noise deviation in force (no draw)."""
+    a = augmentation if augmentation is not None else AUG_DEFAULTS
+    R, T, B = a["rotation"], a["translation"], a["brightness"]
+    return dict(flip=_rs.randint(0, 2, size=n) if a["hflip"] else np.zeros(n, np.int64),
+                scale=_rs.uniform(a["scale"][0], a["scale"][1], size=n),
+                rotation=_rs.randint(-R, R + 1, size=n), tx=_rs.randint(-T, T + 1, size=n), ty=_rs.randint(-T, T + 1, size=n),
+                brightness=_rs.uniform(1.0 - B, 1.0 + B, size=n),
+                seed=int(_rs.randint(0, 2 ** 63 - 1, dtype=np.int64)), noise_std=float(a["noise_std"]))
+
+
+def augment_matrix(scale, rotation_deg, tx, ty, Hs, Ws):
+    """The 3 x 3 forward matrix of ImageAugmenter.py:174-187 in fp64: to_center . A . to_topleft with the shift int(W/2), int(H/2) and
+    A = [[s cos r, -s sin r, tx], [s sin r, s cos r, ty], [0, 0, 1]] (skimage's AffineTransform without shear).  The warp reads the
+    source at the INVERSE of it (:190)."""
+    r = np.deg2rad(float(rotation_deg))
+    sx, sy = int(Ws / 2.0), int(Hs / 2.0)
+    A = np.array([[scale * np.cos(r), -scale * np.sin(r), tx], [scale * np.sin(r), scale * np.cos(r), ty], [0, 0, 1]], np.float64)
+    to_topleft = np.array([[1, 0, -sx], [0, 1, -sy], [0, 0, 1]], np.float64)
+    to_center = np.array([[1, 0, sx], [0, 1, sy], [0, 0, 1]], np.float64)
+    return to_center @ A @ to_topleft
+
+
+def augment_descriptors(n, Hs=64, Ws=64, draw=None):
+    """float32 [n, 8], per image (m00 m01 m02 m10 m11 m12 brightness flip): the first two rows of the inverse of augment_matrix (fp64,
+    rounded once), the brightness factor and the flip - what cg_images_u8_augment_to_f32 and augment_images read.  draw = an
+    augment_draw(n) made earlier (the loaders draw when they pick the files and build the matrix once an image's size is known);
+    None draws now."""
+    d = augment_draw(n) if draw is None else draw
+    desc = np.empty((n, 8), np.float32)
+    for i in range(n):
+        desc[i] = augment_descriptor(d, i, Hs, Ws)
+    return desc
+
+
+def augment_descriptor(draw, i, Hs, Ws):
+    """Row i of augment_descriptors for an image of Hs x Ws pixels."""
+    inv = np.linalg.inv(augment_matrix(draw["scale"][i], draw["rotation"][i], draw["tx"][i], draw["ty"][i], Hs, Ws))
+    return np.array([inv[0, 0], inv[0, 1], inv[0, 2], inv[1, 0], inv[1, 1], inv[1, 2], draw["brightness"][i], draw["flip"][i]], np.float32)
+
+
+def augment_noise(seed, offset, j):
+    """z for the sample indices j (any integer array): the engine's counter generator (splitmix64 of (seed, counter), tensor.SplitMix)
+    at the counters offset + 3 j + {0, 1, 2}; S = the sum of the twelve 16-bit fields of the three outputs; z = (S - 393210) / 65536 as
+    fp32.  Irwin-Hall of twelve: the sum of twelve uniform integers on 0..65535 has mean 393210 and deviation 65536 sqrt(1 - 2^-32),
+    support +-6; S - 393210 and the division by 2^16 are exact in fp32, so host and device agree bit for bit (a Box-Muller normal would
+    need logf / cosf, which are not correctly rounded on the device)."""
+    u = np.uint64
+    with np.errstate(over="ignore"):
+        ctr = u(int(offset) & (2 ** 64 - 1)) + u(3) * np.asarray(j).astype(np.uint64)
+        S = np.zeros(ctr.shape, np.int64)
+        for k in (1, 2, 3):      # counter + 1: the generator's own convention (SplitMix.u01)
+            z = u(int(seed) & (2 ** 64 - 1)) + (ctr + u(k)) * u(0x9E3779B97F4A7C15)
+            z = (z ^ (z >> u(30))) * u(0xBF58476D1CE4E5B9)
+            z = (z ^ (z >> u(27))) * u(0x94D049BB133111EB)
+            z = z ^ (z >> u(31))
+            for sh in (0, 16, 32, 48):
+                S += ((z >> u(sh)) & u(0xFFFF)).astype(np.int64)
+    return (S - 393210).astype(np.float32) / np.float32(65536.0)
+
+
+def _warp_taps(s, L):
+    """One axis of the warp's source positions: clamped to [0, L-1] (NaN -> 0) -> lower tap, upper tap, fraction."""
+    f32 = np.float32
+    with np.errstate(invalid="ignore"):
+        s = np.where(~(s >= f32(0)), f32(0), np.where(s > f32(L - 1), f32(L - 1), s)).astype(f32)
+    i0 = s.astype(np.int64)
+    return i0, np.minimum(i0 + 1, L - 1), (s - i0.astype(f32)).astype(f32)
+
+
+def augment_images(u8_batch, desc, noise_std, seed, offset, index0=0):
+    """The pixel stage and the warp for 8-bit RGB images [N, Hs, Ws, 3] with their descriptors [N, 8] -> float32 [N, 3, Hs, Ws], still
+    on the source grid, ready for image_scale / rgbToColorSpace.  Every step is one fp32 operation in this order (the device kernel
+    images_u8_augment_k performs the same sequence, so the two agree bit for bit):
+      p[y][x][c] = min(max((u8[y][flip ? Ws-1-x : x][c] / 255) * brightness + noise_std * z, 0), 1), z = augment_noise at
+                   j = (((index0 + n) Hs + y) Ws + x) 3 + c - index0 + n is the image's index in its pool;
+      sx = (m00 x + m01 y) + m02, sy = (m10 x + m11 y) + m12, clamped to the image (edge replication); x0 = floor(sx), fx = sx - x0,
+      x1 = min(x0 + 1, Ws-1), likewise y; top = (1-fx) p[y0][x0] + fx p[y0][x1], bot likewise on y1; w[y][x] = (1-fy) top + fy bot.
+    An image of another size than its pool's (the loaders' host path) is passed on its own with index0 = its pool index and so
+    evaluates j with its OWN Hs, Ws: its counters may overlap a neighbour's, which is accepted - the pool is what either loader gives."""
+    f32 = np.float32
+    u8_batch, desc = np.asarray(u8_batch), np.asarray(desc, dtype=f32)
+    N, Hs, Ws, _ = u8_batch.shape
+    sigma = f32(noise_std)
+    out = np.empty((N, 3, Hs, Ws), f32)
+    xs, ys = np.arange(Ws, dtype=f32)[None, :], np.arange(Hs, dtype=f32)[:, None]
+    per = Hs * Ws * 3
+    for n in range(N):
+        m00, m01, m02, m10, m11, m12, bright, flip = desc[n]
+        im = u8_batch[n, :, ::-1] if flip != 0 else u8_batch[n]
+        p = (im.astype(f32) / f32(255.0)) * bright
+        if sigma != 0:
+            j = np.arange(per, dtype=np.uint64).reshape(Hs, Ws, 3) + np.uint64((int(index0) + n) * per)
+            p = p + sigma * augment_noise(seed, offset, j)
+        p = np.where(p < f32(0), f32(0), p)
+        p = np.where(p > f32(1), f32(1), p).astype(f32)
+        x0, x1, fx = _warp_taps((m00 * xs + m01 * ys) + m02, Ws)
+        y0, y1, fy = _warp_taps((m10 * xs + m11 * ys) + m12, Hs)
+        fx, fy = fx[..., None], fy[..., None]
+        gx, gy = f32(1) - fx, f32(1) - fy
+        top = gx * p[y0, x0] + fx * p[y0, x1]
+        bot = gx * p[y1, x0] + fx * p[y1, x1]
+        out[n] = (gy * top + fy * bot).transpose(2, 0, 1)
+    return out
+
+
+def _load_scaled(u8, draw=None, i=0):
+    """One decoded image -> float32 [3, height, width] in rgb: image.load's floats (or, with a draw, image i of the pool augmented),
+    image.scale."""
+    if draw is None:
+        img = u8.astype(np.float32).transpose(2, 0, 1) / np.float32(255.0)      # image.load(path, 3, 'float')
+    else:
+        desc = augment_descriptor(draw, i, u8.shape[0], u8.shape[1])
+        img = augment_images(u8[None], desc[None], draw["noise_std"], draw["seed"], 0, index0=i)[0]
+    return image_scale(img, width, height)
+
+
 def loadRandomImages(count):
-    """dataset.lua:123-170."""
+    """dataset.lua:123-170; with setAugmentation on, every image goes through augment_images first."""
     files = _pick(count)
+    draw = augment_draw(len(files)) if augmentation is not None else None
     data = np.empty((len(files), 3, height, width), np.float32)
     for i, f in enumerate(files):
-        img = _decode(f).astype(np.float32).transpose(2, 0, 1) / np.float32(255.0)      # image.load(path, 3, 'float')
-        data[i] = image_scale(img, width, height)
+        data[i] = _load_scaled(_decode(f), draw, i)
     return _Data(rgbToColorSpace(data, colorSpace))
 
 
@@ -220,7 +378,9 @@ class AsyncLoader:
     """Double-buffered epoch pools in HBM.  next() returns the pool (an engine tensor [n,C,H,W], NHWC memory) whose upload
     was started one call earlier and immediately starts on the following one: decode (worker thread) -> pinned u8 buffer ->
     cg_memcpy_h2d on the copy stream -> cg_images_u8_to_f32 -> event.  The image choice and the pixel values are exactly
-    loadRandomImages' (same generator, same decode, same fp32 operations), so switching loaders does not change a run."""
+    loadRandomImages' (same generator, same decode, same fp32 operations), so switching loaders does not change a run.  With
+    setAugmentation on (read when the loader is built) the pool's draws follow its pick on the caller's thread, the descriptors travel
+    with the 8-bit images and cg_images_u8_augment_to_f32 takes the place of the scaling kernel."""
 
     def __init__(self, count, depth=2):
         import ctypes
@@ -241,6 +401,11 @@ class AsyncLoader:
         if self.host_all:
             import warnings
             warnings.warn(f"AsyncLoader: {self.Ws}x{self.Hs} sources are more than 6x the {width}x{height} target: scaling on the host")
+        self.aug = augmentation is not None
+        if self.aug and not self.host_all and self.Hs * self.Ws * 12 > AUG_LDS_BYTES:      # the kernel keeps one source image in the LDS
+            import warnings
+            warnings.warn(f"AsyncLoader: {self.Ws}x{self.Hs} sources do not fit the augmentation kernel's LDS: augmenting on the host")
+            self.host_all = True
         # host_all: nothing is scaled on the device, so no 8-bit staging / device buffer of the (large) SOURCE size exists at all - the
         # worker writes the finished fp32 NHWC rows into a pinned buffer of the POOL's size and one asynchronous copy moves them
         # (the u8 path would pin count x Hs x Ws x 3 bytes per slot for images it never uploads).  Otherwise: the u8
@@ -253,6 +418,7 @@ class AsyncLoader:
         f32p = ctypes.POINTER(ctypes.c_float)
         for _ in range(self.depth):
             host, dev_u8, ev_ready, ev_free, side = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+            host_desc, dev_desc, desc = ctypes.c_void_p(), ctypes.c_void_p(), None
             self.L.host_alloc(ctypes.byref(host), self.nbytes)
             self.L.event_create(ctypes.byref(ev_ready)); self.L.event_create(ctypes.byref(ev_free))
             pool = Tensor.empty((self.count, self.C, height, width), "nhwc")
@@ -264,8 +430,12 @@ class AsyncLoader:
                 staging = np.ctypeslib.as_array(ctypes.cast(host, ctypes.POINTER(ctypes.c_uint8)), shape=(self.count, self.Hs, self.Ws, 3))
                 self.L.host_alloc(ctypes.byref(side), self.count * self.row)
                 patch = np.ctypeslib.as_array(ctypes.cast(side, f32p), shape=(self.count, height, width, self.C))
+                if self.aug:      # the descriptors ride with the 8-bit batch: pinned on the host, eight floats per image on the device
+                    self.L.host_alloc(ctypes.byref(host_desc), self.count * 32)
+                    self.L.malloc(ctypes.byref(dev_desc), self.count * 32)
+                    desc = np.ctypeslib.as_array(ctypes.cast(host_desc, f32p), shape=(self.count, 8))
             self.slots.append(dict(host=host, staging=staging, dev_u8=dev_u8, side=side, patch=patch, ready=ev_ready, free=ev_free, pool=pool,
-                                   n=0, used=False))
+                                   host_desc=host_desc, dev_desc=dev_desc, desc=desc, n=0, used=False))
         self.k = 0
         self._thread = None
         self._err = None
@@ -274,6 +444,7 @@ class AsyncLoader:
     def _start(self, slot):
         files = _prefetch_pick(self.count)   # on the caller's thread: the generator's draws stay in program order
         slot["n"] = len(files)
+        draw = slot["draw"] = augment_draw(len(files)) if self.aug else None      # likewise, right after the pick (as loadRandomImages)
         if slot["used"]:
             self.L.event_sync(slot["ready"])   # its previous upload has left the pinned buffers (long ago; costs nothing)
 
@@ -284,17 +455,21 @@ class AsyncLoader:
                 for i, f in enumerate(files):
                     im = _decode(f)
                     if self.host_all or im.shape[:2] != (self.Hs, self.Ws):
-                        # loadRandomImages' arithmetic for this one image: /255 -> image.scale -> colour space, as NHWC rows
-                        img = image_scale(im.astype(np.float32).transpose(2, 0, 1) / np.float32(255.0), width, height)
-                        img = rgbToColorSpace(img[None], colorSpace)[0].transpose(1, 2, 0)
+                        # loadRandomImages' arithmetic for this one image: /255 (or its augmentation, with the matrix of its own
+                        # size) -> image.scale -> colour space, as NHWC rows
+                        img = rgbToColorSpace(_load_scaled(im, draw, i)[None], colorSpace)[0].transpose(1, 2, 0)
                         if self.host_all:
                             slot["staging"][i] = img
                         else:
                             slot["patch"][i] = img         # pinned: the copy below needs no synchronisation
                             slot["patches"].append(i)
                             slot["staging"][i] = 0
+                            if draw is not None:
+                                slot["desc"][i] = (1, 0, 0, 0, 1, 0, 1, 0)      # the kernel's output for this row is overwritten
                     else:
                         slot["staging"][i] = im
+                        if draw is not None:
+                            slot["desc"][i] = augment_descriptor(draw, i, self.Hs, self.Ws)
             except Exception as e:   # surfaced by next()
                 self._err = e
         self._thread = threading.Thread(target=work, daemon=True)
@@ -308,7 +483,12 @@ class AsyncLoader:
             L.memcpy_h2d(cs, slot["pool"].ptr, slot["host"], n * self.row)
         else:
             L.memcpy_h2d(cs, slot["dev_u8"], slot["host"], n * self.Hs * self.Ws * 3)
-            L.images_u8_scale_to_f32(cs, slot["dev_u8"], slot["pool"].ptr, n, self.Hs, self.Ws, height, width, self.cs_code)
+            if self.aug:
+                L.memcpy_h2d(cs, slot["dev_desc"], slot["host_desc"], n * 32)
+                L.images_u8_augment_to_f32(cs, slot["dev_u8"], slot["pool"].ptr, n, self.Hs, self.Ws, height, width, self.cs_code,
+                                           slot["dev_desc"], slot["draw"]["noise_std"], slot["draw"]["seed"], 0)
+            else:
+                L.images_u8_scale_to_f32(cs, slot["dev_u8"], slot["pool"].ptr, n, self.Hs, self.Ws, height, width, self.cs_code)
             for i in slot["patches"]:     # images scaled on the host (another source size): over the rows the kernel produced from zeros
                 L.memcpy_h2d(cs, slot["pool"].ptr + i * self.row, slot["side"].value + i * self.row, self.row)
             slot["patches"] = []
@@ -343,6 +523,8 @@ class AsyncLoader:
                 self.L.free(s_["dev_u8"])
             if s_["side"]:
                 self.L.host_free(s_["side"])
+            if s_["host_desc"]:
+                self.L.host_free(s_["host_desc"]); self.L.free(s_["dev_desc"])
             self.L.event_destroy(s_["ready"]); self.L.event_destroy(s_["free"])
         self.L.stream_destroy(self.copy_stream)
         self.slots = []

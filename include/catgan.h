@@ -103,6 +103,26 @@ int cg_images_u8_to_f32(void* stream, const unsigned char* src, float* dst, long
  * shrinking an axis averages the source samples a target sample covers (fractional ends weighted), enlarging interpolates
  * linearly between the two neighbours (corner aligned), equal sizes copy.  Shrink factors up to 6 per axis. */
 int cg_images_u8_scale_to_f32(void* stream, const unsigned char* src, float* dst, int N, int Hs, int Ws, int Hd, int Wd, int colorspace);
+/* cg_images_u8_scale_to_f32 with the reference's augmentation in front of the scaling: what its offline tool writes to disk as nine
+ * fixed variants per face (dataset/generate_dataset.py:68-73, dataset/ImageAugmenter.py:160-190, Image.augment in
+ * dataset/dataset.py:284-306), drawn afresh for every epoch pool.  desc (device memory) holds eight floats per image,
+ * (m00 m01 m02 m10 m11 m12 brightness flip): the first two rows of the INVERSE affine matrix (output -> source position; no
+ * trigonometry runs on the device), the brightness factor, flip != 0 = mirrored left-right.  Per image, on the SOURCE grid:
+ *   pixel stage (dataset.py:284-304: flip, brightness, noise, clip)
+ *     p[y][x][c] = min(max((u8[y][flip ? Ws-1-x : x][c] / 255) * brightness + noise_std * z, 0), 1)
+ *     z = (float)(S - 393210) / 65536, S = the sum of the twelve 16-bit fields of the engine's counter generator (splitmix64 of
+ *     (seed, counter), as cg_rng_*) at the counters offset + 3 j + {0, 1, 2}, j = ((n Hs + y) Ws + x) 3 + c: an Irwin-Hall sum of
+ *     twelve, mean 0, deviation 1, support +-6, exact in fp32 - no transcendental, so that a host restatement agrees bit for bit;
+ *   warp (tf.warp(..., mode="nearest"), order 1, dataset.py:306)
+ *     sx = (m00 x + m01 y) + m02, sy = (m10 x + m11 y) + m12, clamped to [0, Ws-1] x [0, Hs-1] (edge replication, NaN -> 0);
+ *     x0 = floor(sx), fx = sx - x0, x1 = min(x0 + 1, Ws-1), likewise y; top = (1-fx) p[y0][x0] + fx p[y0][x1], bot likewise on y1,
+ *     w[y][x] = (1-fy) top + fy bot;
+ * then w goes through image.scale and the colour space exactly as above.  Every operation is a single correctly rounded fp32 one in
+ * the order written (dataset.augment_images is the numpy restatement); with desc = (1 0 0 0 1 0 1 0) and noise_std = 0 the result is
+ * cg_images_u8_scale_to_f32's bit for bit.  The pixel stage of one image lives in the LDS (Hs Ws 12 bytes): a source too large for
+ * the device's LDS per workgroup is an error, as are shrink factors above 6 and noise_std < 0. */
+int cg_images_u8_augment_to_f32(void* stream, const unsigned char* src, float* dst, int N, int Hs, int Ws, int Hd, int Wd,
+                                int colorspace, const float* desc, float noise_std, uint64_t seed, uint64_t offset);
 /* NN_UTILS.rgbToColorSpace / NN_UTILS.toRgb (utils/nn_utils.lua:188-249) on fp32 NHWC pixels that are already on the device: three
  * floats in per pixel, three out (one for to == 1).  from / to are the colorspace codes above; the pairs are rgb -> y | yuv | hsl and
  * yuv | hsl -> rgb, anything else is an error.  src == dst is allowed when three planes come out.  Per pixel, every operation a single

@@ -36,6 +36,14 @@ def parse():
     a("--seed", type=int, default=1); a("--colorSpace", default="rgb", choices=["rgb", "yuv", "hsl", "y"])
     a("--dataDir", default="dataset/out_aug_64x64"); a("--synthetic", action="store_true")
     a("--epochs", type=int, default=0, help="stop after this many epochs (0 = run forever, as train.lua does)")
+    a("--augment", action="store_true", help="augment every epoch's images on the fly (dataset.setAugmentation: flip, brightness, noise, "
+      "affine warp; on the device with the asynchronous loader) - point --dataDir at the UN-augmented faces, e.g. dataset/out_unaug_64x64")
+    a("--augNoFlip", action="store_true", help="--augment without the left-right flips")
+    a("--augScale", type=float, nargs=2, default=[0.93, 1.08], metavar=("LO", "HI"), help="--augment: zoom range")
+    a("--augRotation", type=int, default=8, help="--augment: rotation of up to this many whole degrees either way")
+    a("--augTranslation", type=int, default=4, help="--augment: shift of up to this many pixels on each axis")
+    a("--augBrightness", type=float, default=0.15, help="--augment: brightness factor in [1 - this, 1 + this]")
+    a("--augNoise", type=float, default=0.02, help="--augment: standard deviation of the noise added to the [0, 1] pixels")
     a("--noplot", action="store_true", help="train.lua:33 - skip the per-epoch image grids (logs/images*/<start>_<epoch>.png)")
     a("--blockingLoader", action="store_true", help="decode + upload each epoch's images on the training thread (dataset.loadRandomImages)")
     a("--V_dir", default="logs", help="train.lua:19 - directory of the validator network v_CxHxW.net that train_v.py writes")
@@ -77,6 +85,9 @@ def main():
     ds = importlib.import_module("cat-generator_amd.dataset")
     ds.colorSpace = o.colorSpace; ds.setFileExtension("jpg"); ds.setHeight(o.scale); ds.setWidth(o.scale)
     ds.setDirs([o.dataDir]); ds.seed(o.seed)
+    if o.augment:
+        ds.setAugmentation(True, hflip=not o.augNoFlip, scale=tuple(o.augScale), rotation=o.augRotation, translation=o.augTranslation,
+                           brightness=o.augBrightness, noise_std=o.augNoise)
     if o.network:   # after every generator was seeded: the checkpoint puts each of them back where the run stopped
         print(f"<trainer> reloading previously trained network: {o.network}")
         (cg.checkpoint.load_t7 if o.network.endswith(".net") else cg.checkpoint.load)(o.network, S)

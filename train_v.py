@@ -49,6 +49,14 @@ def parse(argv=None):
     a("--N_epoch", type=int, default=1000)
     a("--dataDir", default="dataset/out_aug_64x64"); a("--synthetic", action="store_true")
     a("--epochs", type=int, default=0, help="stop after this many epochs (0 = run forever, as train_v.lua does)")
+    a("--augment", action="store_true", help="augment every epoch's images on the fly (dataset.setAugmentation: flip, brightness, noise, "
+      "affine warp; on the device with the asynchronous loader) - point --dataDir at the UN-augmented faces, e.g. dataset/out_unaug_64x64")
+    a("--augNoFlip", action="store_true", help="--augment without the left-right flips")
+    a("--augScale", type=float, nargs=2, default=[0.93, 1.08], metavar=("LO", "HI"), help="--augment: zoom range")
+    a("--augRotation", type=int, default=8, help="--augment: rotation of up to this many whole degrees either way")
+    a("--augTranslation", type=int, default=4, help="--augment: shift of up to this many pixels on each axis")
+    a("--augBrightness", type=float, default=0.15, help="--augment: brightness factor in [1 - this, 1 + this]")
+    a("--augNoise", type=float, default=0.02, help="--augment: standard deviation of the noise added to the [0, 1] pixels")
     return ap.parse_args(argv)
 
 
@@ -191,6 +199,9 @@ def main(argv=None):
     ds = importlib.import_module("cat-generator_amd.dataset")
     ds.colorSpace = o.colorSpace; ds.setFileExtension("jpg"); ds.setHeight(o.scale); ds.setWidth(o.scale)
     ds.setDirs([o.dataDir]); ds.seed(o.seed)
+    if o.augment:
+        ds.setAugmentation(True, hflip=not o.augNoFlip, scale=tuple(o.augScale), rotation=o.augRotation, translation=o.augTranslation,
+                           brightness=o.augBrightness, noise_std=o.augNoise)
     while True:                                                                # :101-110
         print("<trainer> Epoch %d" % T.EPOCH)
         if o.synthetic:
