@@ -15,6 +15,9 @@ stream while the current epoch trains, scaled and converted on the device (cg_im
 space) into the second of two HBM pools, and handed to the compute stream through an event - no host synchronisation on the
 training path.
 
+SequentialLoader is the same pipeline over a given file list, in order, in chunks: one pass over the whole set for the nearest-neighbour
+search of sample.py --neighbours (nn_utils.findClosestNeighboursOnDevice), which never holds the set.
+
 setAugmentation turns on the augmentation the reference only has as an offline tool (dataset/generate_dataset.py): both loaders then
 draw fresh variants for every epoch pool (augment_images on the host, cg_images_u8_augment_to_f32 on the device, bit-equal)."""
 import os
@@ -155,6 +158,12 @@ def _pick(count):
         raise FileNotFoundError(f"no *.{fileExtension} images under {dirs}")
     shuffle = _rs.permutation(len(paths))
     return [paths[shuffle[i]] for i in range(min(len(paths), count))]
+
+
+def pickFiles(count):
+    """The files loadRandomImages(count) would load, in its order, consuming the same single draw of the generator: for callers that
+    walk the files themselves (sample.py --neighbours streams them through a SequentialLoader)."""
+    return _pick(count)
 
 
 def _prefetch_pick(count):
@@ -364,6 +373,12 @@ def _load_scaled(u8, draw=None, i=0):
     return image_scale(img, width, height)
 
 
+def loadImageFile(path):
+    """One file through the blocking loader's per-image path (decode, image.load's floats, image.scale, colour space), never augmented:
+    float32 [C, height, width], the bits loadRandomImages gives for it."""
+    return rgbToColorSpace(_load_scaled(_decode(path))[None], colorSpace)[0]
+
+
 def loadRandomImages(count):
     """dataset.lua:123-170; with setAugmentation on, every image goes through augment_images first."""
     files = _pick(count)
@@ -383,28 +398,35 @@ class AsyncLoader:
     with the 8-bit images and cg_images_u8_augment_to_f32 takes the place of the scaling kernel."""
 
     def __init__(self, count, depth=2):
+        if paths is None:
+            loadPaths()
+        if not paths:
+            raise FileNotFoundError(f"no *.{fileExtension} images under {dirs}")
+        self._setup(count, depth, paths[0], augmentation is not None)
+
+    def _next_files(self, slot):
+        """The files of the pool after the last one started; on the caller's thread: the generator's draws stay in program order."""
+        return _prefetch_pick(self.count)
+
+    def _setup(self, count, depth, probe, aug):
         import ctypes
         from .tensor import Tensor, lib
         self._ct, self._T, self.L = ctypes, Tensor, lib()
         self.count, self.depth = int(count), int(depth)
         self.cs_code = COLOR_SPACES[colorSpace]
         self.C = 1 if colorSpace == "y" else 3
-        if paths is None:
-            loadPaths()
-        if not paths:
-            raise FileNotFoundError(f"no *.{fileExtension} images under {dirs}")
-        self.Hs, self.Ws = _decode(paths[0]).shape[:2]      # the dataset is written at one size (generate_dataset.py: 64 x 64)
+        self.Hs, self.Ws = _decode(probe).shape[:2]      # the dataset is written at one size (generate_dataset.py: 64 x 64)
         # The device kernel scales a batch of ONE source size, and at most 6x down (images_u8_scale_k's box loop).  The reference
         # (dataset.lua:129-131) scales every image on its own: an image of another size - or all of them, if the source is more than
         # 6x the target - takes the blocking loader's host path (image_scale, same arithmetic) and is patched into the pool.
         self.host_all = self.Hs > 6 * height or self.Ws > 6 * width
         if self.host_all:
             import warnings
-            warnings.warn(f"AsyncLoader: {self.Ws}x{self.Hs} sources are more than 6x the {width}x{height} target: scaling on the host")
-        self.aug = augmentation is not None
+            warnings.warn(f"{type(self).__name__}: {self.Ws}x{self.Hs} sources are more than 6x the {width}x{height} target: scaling on the host")
+        self.aug = aug
         if self.aug and not self.host_all and self.Hs * self.Ws * 12 > AUG_LDS_BYTES:      # the kernel keeps one source image in the LDS
             import warnings
-            warnings.warn(f"AsyncLoader: {self.Ws}x{self.Hs} sources do not fit the augmentation kernel's LDS: augmenting on the host")
+            warnings.warn(f"{type(self).__name__}: {self.Ws}x{self.Hs} sources do not fit the augmentation kernel's LDS: augmenting on the host")
             self.host_all = True
         # host_all: nothing is scaled on the device, so no 8-bit staging / device buffer of the (large) SOURCE size exists at all - the
         # worker writes the finished fp32 NHWC rows into a pinned buffer of the POOL's size and one asynchronous copy moves them
@@ -442,7 +464,7 @@ class AsyncLoader:
         self._start(self.slots[0])
 
     def _start(self, slot):
-        files = _prefetch_pick(self.count)   # on the caller's thread: the generator's draws stay in program order
+        files = self._next_files(slot)
         slot["n"] = len(files)
         draw = slot["draw"] = augment_draw(len(files)) if self.aug else None      # likewise, right after the pick (as loadRandomImages)
         if slot["used"]:
@@ -514,6 +536,9 @@ class AsyncLoader:
     def close(self):
         global _prefetch_state
         _prefetch_state = None             # the pending pick dies with the loader
+        self._release()
+
+    def _release(self):
         if self._thread is not None:
             self._thread.join()
         self.L.stream_sync(self.copy_stream)
@@ -528,3 +553,47 @@ class AsyncLoader:
             self.L.event_destroy(s_["ready"]); self.L.event_destroy(s_["free"])
         self.L.stream_destroy(self.copy_stream)
         self.slots = []
+
+
+class SequentialLoader(AsyncLoader):
+    """AsyncLoader's pipeline (worker decode -> pinned 8-bit buffer -> copy stream -> cg_images_u8_scale_to_f32 -> event, two pools) over
+    a GIVEN file list, in that order, `chunk` files at a time: what a pass over the whole training set needs (sample.py --neighbours,
+    nn_utils.findClosestNeighboursOnDevice) without ever holding the set.  next() returns (pool, index0, n) - the engine tensor
+    [n,C,H,W] (NHWC memory) of files[index0 : index0 + n] - and None once the list is exhausted; iterating the loader does the same.  A
+    pool stays valid until the next-but-one next().  The generator is never touched and augmentation never applied: the search is over
+    the set as it is on disk, pixel for pixel what loadRandomImages gives for the same files (odd-sized sources and the more-than-6x
+    shrink case take AsyncLoader's host path)."""
+
+    def __init__(self, files, chunk, depth=2):
+        self.files = list(files)
+        if not self.files:
+            raise FileNotFoundError("SequentialLoader: an empty file list")
+        if int(chunk) < 1:
+            raise ValueError(f"SequentialLoader: chunk = {chunk}")
+        self._pos = 0
+        self._setup(min(int(chunk), len(self.files)), depth, self.files[0], False)
+
+    def _next_files(self, slot):
+        slot["index0"] = self._pos
+        files = self.files[self._pos:self._pos + self.count]
+        self._pos += len(files)
+        return files
+
+    def next(self):
+        slot = self.slots[self.k]
+        if slot["n"] == 0:      # the list is exhausted (its worker had nothing to do)
+            return None
+        index0, n = slot["index0"], slot["n"]
+        return AsyncLoader.next(self), index0, n
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        item = self.next()
+        if item is None:
+            raise StopIteration
+        return item
+
+    def close(self):
+        self._release()

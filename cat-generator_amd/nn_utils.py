@@ -1,7 +1,9 @@
 """utils/nn_utils.lua — what the training step uses: createNoiseInputs :35-39,
 createImagesFromNoise :45-69, createImages :75-77, getNumberOfParameters :453-462, activateCuda :620-680 — and the
 consumer side of the trained nets: sortImagesByPrediction :89-117, visualizeProgress :130-186 (without
-the display server), toRgb :188-220, imagesToGridTensor / saveImagesAsGrid :526-583, rateWithV :686-711."""
+the display server), toRgb :188-220, imagesToGridTensor / saveImagesAsGrid :526-583, rateWithV :686-711; and sample.lua's
+nearest-neighbour check (:131-151) both as the reference's host loop (findClosestNeighboursOf) and on the device
+(findClosestNeighboursOnDevice: cg_nearest_update over the pools of a dataset.SequentialLoader)."""
 import os
 import struct
 import zlib
@@ -329,3 +331,127 @@ def findClosestNeighboursOf(images, trainingSet):
         j = int(np.argmin(d))
         out.append((img, train[j].copy(), float(d[j])))
     return out
+
+
+# ------------------------------------------------------------------ the same search on the device (cg_nearest_update)
+NEAREST_LANES = 64       # partial sums per tile
+NEAREST_PER_LANE = 8     # elements each partial adds up, one after the other
+NEAREST_TILE = NEAREST_LANES * NEAREST_PER_LANE      # 512 elements of D per tile
+NEAREST_TREE = 6         # levels of the binary tree over a tile's 64 partials
+NEAREST_MAX_Q = 64
+
+
+def nearest_chain_length(D):
+    """The longest chain of dependent additions in cg_nearest_update's summation order for rows of D elements: the eight of a partial,
+    the six levels of the tree, one per tile."""
+    return NEAREST_PER_LANE + NEAREST_TREE + -(-int(D) // NEAREST_TILE)
+
+
+def nearest_d2_np(pool, queries):
+    """cg_nearest_update's arithmetic in numpy, bit for bit (include/catgan.h states the order): pool [N][D], queries [Q][D] ->
+    float32 [Q][N] of sum_e (pool[n][e] - q[e])^2, every subtraction, multiplication and addition a single fp32 operation.  D is cut into
+    tiles of 512 (the last one filled up with zeros on both sides, which contribute +0); partial l of a tile adds the squares of its
+    elements l, 64 + l, ... 448 + l in that order; the 64 partials go through a binary tree over adjacent pairs; the tile sums are added
+    in tile order."""
+    f32 = np.float32
+    pool, queries = np.asarray(pool, dtype=f32), np.asarray(queries, dtype=f32)
+    pool, queries = pool.reshape(pool.shape[0], -1), queries.reshape(queries.shape[0], -1)
+    (N, D), Q = pool.shape, queries.shape[0]
+    assert queries.shape[1] == D and D >= 1
+    T = -(-D // NEAREST_TILE)
+    pad = T * NEAREST_TILE - D
+    if pad:
+        pool, queries = np.pad(pool, ((0, 0), (0, pad))), np.pad(queries, ((0, 0), (0, pad)))
+    out = np.zeros((Q, N), f32)
+    for t in range(T):
+        sl = slice(t * NEAREST_TILE, (t + 1) * NEAREST_TILE)
+        x = pool[:, sl].reshape(N, NEAREST_PER_LANE, NEAREST_LANES)
+        for q in range(Q):
+            d = x - queries[q, sl].reshape(1, NEAREST_PER_LANE, NEAREST_LANES)
+            sq = d * d
+            s = np.zeros((N, NEAREST_LANES), f32)
+            for j in range(NEAREST_PER_LANE):
+                s = s + sq[:, j]
+            for _ in range(NEAREST_TREE):
+                s = s[:, 0::2] + s[:, 1::2]
+            out[q] = out[q] + s[:, 0]
+    return out
+
+
+def nearest_merge_np(best_d2, best_idx, d2, index0):
+    """cg_nearest_update's merge rule for one chunk: d2 [Q][N] are the distances to rows index0 .. index0 + N - 1; a candidate replaces
+    (best_d2[q], best_idx[q]) if its d2 is smaller, or equal with a smaller index.  Returns the new (best_d2 float32 [Q], best_idx int32
+    [Q]); start from nearest_reset_np(Q)."""
+    best_d2, best_idx = np.array(best_d2, dtype=np.float32), np.array(best_idx, dtype=np.int32)
+    d2 = np.asarray(d2, dtype=np.float32)
+    if d2.shape[1] == 0:
+        return best_d2, best_idx
+    for q in range(d2.shape[0]):
+        j = int(np.argmin(d2[q]))      # the first of equal minima = the smallest index of the chunk
+        d, i = d2[q, j], int(index0) + j
+        if d < best_d2[q] or (d == best_d2[q] and i < best_idx[q]):
+            best_d2[q], best_idx[q] = d, i
+    return best_d2, best_idx
+
+
+def nearest_reset_np(Q):
+    return np.full(Q, np.inf, np.float32), np.full(Q, -1, np.int32)
+
+
+class NearestSearch:
+    """The running nearest-neighbour search of up to 64 queries on the device.  queries: a host array [Q,C,H,W] (uploaded permuted to
+    the pools' NHWC element order) or [Q,D] (taken as it is).  update(pool, index0) merges a chunk of the training set - an engine tensor
+    [n,C,H,W] in NHWC memory or a plain [n,D] one, whose first row has the index index0 - on the engine stream without any host
+    synchronisation; result() returns (indices int32 [Q], distances float32 [Q] = the fp32 square roots of the best d2)."""
+
+    def __init__(self, queries):
+        import torch
+        from .tensor import device
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim not in (2, 4) or not 1 <= q.shape[0] <= NEAREST_MAX_Q:
+            raise ValueError(f"NearestSearch: queries of shape {q.shape} (1..{NEAREST_MAX_Q} rows, [Q,C,H,W] or [Q,D])")
+        self.Q, self.D = q.shape[0], int(np.prod(q.shape[1:]))
+        self.queries = Tensor.from_numpy(q)      # 4-D: NHWC memory, as the pools
+        self.best_d2 = torch.empty(self.Q, dtype=torch.float32, device=device())
+        self.best_idx = torch.empty(self.Q, dtype=torch.int32, device=device())
+        self.workspace = None
+        self.fresh = True
+
+    def update(self, pool, index0, n=None):
+        import torch
+        from .tensor import device
+        n = pool.shape[0] if n is None else int(n)
+        if n > pool.shape[0] or (pool.shape[0] and pool.nElement() // pool.shape[0] != self.D) or pool.ups or \
+                (pool.dim() == 4) != (self.queries.dim() == 4) or pool.fmt != self.queries.fmt:
+            raise ValueError(f"NearestSearch.update: {n} rows of {pool} against queries {self.queries}")
+        need = lib().nearest_workspace_bytes(n, self.Q, self.D)
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=device())
+        lib().nearest_update(stream(), pool.ptr, n, self.D, self.queries.ptr, self.Q, int(index0), 1 if self.fresh else 0,
+                             self.best_d2.data_ptr(), self.best_idx.data_ptr(), self.workspace.data_ptr())
+        self.fresh = False
+        return self
+
+    def reset(self):
+        self.fresh = True
+        return self
+
+    def result(self):
+        if self.fresh:      # nothing searched: (+inf, -1)
+            self.update(Tensor.empty((0,) + self.queries.shape[1:], self.queries.fmt), 0)
+        return self.best_idx.cpu().numpy(), np.sqrt(self.best_d2.cpu().numpy())
+
+
+def findClosestNeighboursOnDevice(images, loader):
+    """findClosestNeighboursOf over a training set that is never held: the pools of a dataset.SequentialLoader pass through
+    cg_nearest_update while the next one is decoded and uploaded.  Returns ([(image, neighbour, distance)], indices into loader.files);
+    the <= Q winning files are decoded once more on the host (dataset.loadImageFile) instead of keeping pools alive."""
+    from . import dataset
+    images = np.asarray(images, dtype=np.float32)
+    search = NearestSearch(images)
+    for pool, index0, n in loader:
+        search.update(pool, index0, n)
+    idx, dist = search.result()
+    if (idx < 0).any():
+        raise ValueError("findClosestNeighboursOnDevice: no training row is at a finite distance")
+    return [(img, dataset.loadImageFile(loader.files[j]), float(d)) for img, j, d in zip(images, idx, dist)], idx

@@ -136,6 +136,28 @@ int cg_images_u8_augment_to_f32(void* stream, const unsigned char* src, float* d
  *               with hue(p, q, t): t < 0: t += 1; t > 1: t -= 1; t < 1/6: p + ((q - p) 6) t; t < 1/2: q; t < 2/3: p + ((q - p) (2/3 - t)) 6; else p
  * (planes h, s, l; h in [0, 1)).  The U and V planes are signed (|U| <= 0.436, |V| <= 0.615), as in the reference. */
 int cg_colorspace_convert(void* stream, const float* src, float* dst, long npixels, int from, int to);
+/* sample.lua:131-151 (--neighbours, the memorisation check) on the device: for each of Q queries the nearest row of a training set that
+ * arrives in chunks, the running best kept in device memory.  pool [N][D] is a chunk as the loaders leave it (NHWC rows, D = H W C),
+ * queries [Q][D] in the same element order, 1 <= Q <= 64; best_d2 [Q] / best_idx [Q] are updated in place, reset != 0 first sets them
+ * to (+inf, -1).  N == 0 is a valid no-op (after the reset).  workspace: cg_nearest_workspace_bytes(N, Q, D) bytes of device memory.
+ * Arithmetic, per query q and row n: d2 = sum_e (pool[n][e] - q[e])^2, the DIFFERENCE form - ||t||^2 + ||q||^2 - 2 t.q cancels exactly
+ * where the answer matters, at a near-duplicate - with every subtraction, multiplication and addition a single correctly rounded fp32
+ * operation (no fma) and the additions in this order, a function of D alone (never of N, Q, index0, the chunking or the launch):
+ *   D is cut into tiles of 512 elements, the last one filled up with elements that contribute +0;
+ *   in tile t, partial l (0..63) = ((((0 + s[l]) + s[64 + l]) + s[128 + l]) ... + s[448 + l]), s[i] = the square of element 512 t + i;
+ *   the 64 partials go through a binary tree over ADJACENT pairs (0+1, 2+3, ...; then those sums pairwise; six levels) to the tile's sum;
+ *   d2 = (((0 + tile 0) + tile 1) + ...).  The longest chain of additions is 8 + 6 + ceil(D / 512).
+ * nn_utils.nearest_d2_np restates this bit for bit.  Merge rule: a candidate (d2, index0 + n) replaces (best_d2, best_idx) if its d2 is
+ * smaller, or equal with a smaller index - the reference's "first one wins" (dist < closestDist, sample.lua:142) made independent of
+ * chunk order and size; (d2, index) is a total order, the workgroups' candidates go through the workspace and a finishing launch, no
+ * floating-point atomics.  A row whose d2 is not smaller than +inf (overflow, NaN) is never a candidate.
+ * Declared deviation: the reference compares the square-rooted values torch.dist returns, and TH's dist accumulates in double for
+ * float tensors [upstream, recalled, not verified here] - the yardstick is therefore the fp64 distance, from which d2 differs by at
+ * most (8 + 6 + ceil(D / 512) + 3) 2^-24 relative; two rows closer to each other than that may swap.
+ * Errors: a null pointer, Q outside 1..64, N < 0, D < 1, index0 < 0 or index0 + N beyond int32. */
+size_t cg_nearest_workspace_bytes(int N, int Q, long D);
+int cg_nearest_update(void* stream, const float* pool, int N, long D, const float* queries, int Q, int index0, int reset, float* best_d2,
+                      int32_t* best_idx, void* workspace);
 
 /* ---- convolution / linear (implicit GEMM on fp32 MFMA) -------------------
  * Replaces cudnn.SpatialConvolution (models.lua:206,212,218,222),
