@@ -2,7 +2,8 @@
 
 Only the definitions on the hot path are here: G32up-c (models.lua:196-228, the default
 via create_G :234-240), G32up (:138-160), D32_st3 (:640-711, the only D create_D returns, :276) and the
-spatial-transformer factory (:814-906), and the validator V (:716-804) that train_v.py trains.  `create_G32up_c_64` is the builder-defined 64x64 extension of
+spatial-transformer factory (:814-906), the validator V (:716-804) that train_v.py trains, and G's encoder / auto-encoder form
+(:50-83, :246-262) that pretrain_g.py trains.  `create_G32up_c_64` is the builder-defined 64x64 extension of
 BASELINE.json config #5.
 """
 from . import cudnn, nn
@@ -79,6 +80,54 @@ def create_G(dimensions, noiseDim):
     if dimensions[1] == 64:
         return create_G32up_c_64(dimensions, noiseDim)
     return create_G_decoder_upsampling32c(dimensions, noiseDim)
+
+
+def create_G_encoder32(dimensions, noiseDim):
+    """models.lua:50-83: the encoder half of G in auto-encoder form (pretrain_g.lua).  Three 2x2 poolings: the flattened map has
+    32 * H/8 * W/8 features (32 * 0.25^3 * H * W, :73-74), which is what makes the same definition serve 64x64."""
+    model = nn.Sequential()
+    activation = nn.LeakyReLU
+
+    model.add(nn.SpatialConvolution(dimensions[0], 16, 3, 3, 1, 1, (3 - 1) // 2))
+    model.add(nn.SpatialBatchNormalization(16))
+    model.add(activation())
+    model.add(nn.SpatialMaxPooling(2, 2))
+
+    model.add(nn.SpatialConvolution(16, 16, 3, 3, 1, 1, (3 - 1) // 2))
+    model.add(nn.SpatialBatchNormalization(16))
+    model.add(activation())
+    model.add(nn.SpatialMaxPooling(2, 2))
+
+    model.add(nn.SpatialConvolution(16, 32, 3, 3, 1, 1, (3 - 1) // 2))
+    model.add(nn.SpatialBatchNormalization(32))
+    model.add(activation())
+    model.add(nn.SpatialMaxPooling(2, 2))
+
+    model.add(nn.SpatialConvolution(32, 32, 3, 3, 1, 1, (3 - 1) // 2))
+    model.add(nn.SpatialBatchNormalization(32))
+    model.add(activation())
+
+    feat = 32 * dimensions[1] * dimensions[2] // (4 * 4 * 4)
+    model.add(nn.View(feat))
+    model.add(nn.Linear(feat, 1024))
+    model.add(nn.BatchNormalization(1024))
+    model.add(activation())
+    model.add(nn.Linear(1024, noiseDim))
+
+    model = w_init(model, "heuristic")
+    return model
+
+
+def create_G_autoencoder(dimensions, noiseDim):
+    """models.lua:246-262: nn.Sequential{encoder, decoder}.  The decoder is what create_G returns for these dimensions (G32up-c, its
+    64x64 extension when dimensions[1] == 64), so the half pretrain_g.py saves is the net train.py trains.  The tree holds modules
+    the planned executor has no entry for (nn.BatchNormalization): it runs on the per-module walk, encoder and decoder alike."""
+    model = nn.Sequential()
+    if dimensions[1] == 16:
+        raise NotImplementedError("create_G_encoder16 / create_G_decoder_upsampling16 are not on the hot path (SURVEY.md §2.1 row 2)")
+    model.add(create_G_encoder32(dimensions, noiseDim))
+    model.add(create_G(dimensions, noiseDim))
+    return model
 
 
 def create_D(dimensions, cuda=False):

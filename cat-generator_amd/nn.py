@@ -1248,3 +1248,47 @@ class BCECriterion:
         lib().bce_backward(stream(), x.ptr, t.ptr, self._g.ptr, x.nElement())
         self.gradInput = Tensor(self._g.t, x.shape)
         return self.gradInput
+
+
+class MSECriterion:
+    """nn.MSECriterion() (pretrain_g.lua:101): sizeAverage [upstream].  The loss is a lazily-read device scalar, as BCECriterion's;
+    input and gradInput stay in the input's own storage format (G's output is NHWC: the mean over all elements does not care about
+    their order), the target is brought to that format when it comes in another.
+    Contract, as Torch's: :backward(input, target) follows a :forward on the same input and target.  A target in another format is
+    converted once, in :forward; :backward reuses that copy when it is handed the same target object, so a target buffer overwritten
+    in place after :forward needs a new :forward before :backward sees the new contents (a target already in the input's format, as
+    pretrain_g.py's, is read in place by both calls)."""
+
+    def __init__(self):
+        self.output = None
+        self.gradInput = None
+        self._loss = None
+        self._g = None
+        self._t = None      # (the target as given to :forward, the same in the input's format)
+
+    def _prep(self, input, target, fresh):
+        x = materialise(to_device(input))
+        t = to_device(target)
+        assert x.nElement() == t.nElement(), f"nn.MSECriterion: input {x.shape} against target {t.shape}"
+        if t.fmt != x.fmt or t.ups:
+            c = self._t
+            if fresh or c is None or c[0] is not target or c[1].fmt != x.fmt:   # converted once: :backward reuses :forward's copy
+                self._t = c = (target, as_nhwc(t) if x.fmt == "nhwc" else as_plain(t))
+            t = c[1]
+        return x, t
+
+    def forward(self, input, target):
+        x, t = self._prep(input, target, True)
+        if self._loss is None:
+            self._loss = torch.zeros(1, dtype=torch.float32, device=x.t.device)
+        lib().mse_forward(stream(), x.ptr, t.ptr, self._loss.data_ptr(), x.nElement())
+        self.output = LazyScalar(self._loss)
+        return self.output
+
+    def backward(self, input, target):
+        x, t = self._prep(input, target, False)
+        if self._g is None or self._g.t.numel() != x.nElement():
+            self._g = Tensor.empty(x.shape, x.fmt)
+        lib().mse_backward(stream(), x.ptr, t.ptr, self._g.ptr, x.nElement())
+        self.gradInput = Tensor(self._g.t, x.shape, x.fmt)
+        return self.gradInput

@@ -120,6 +120,25 @@ def getNumberOfParameters(net):
     return n
 
 
+MSE_CHUNK = 4096           # elements of one chunk of cg_mse_forward's summation order (csrc/criterion.hip)
+MSE_MAX_PARTIALS = 1024    # workgroup partials of one launch: beyond MSE_CHUNK * MSE_MAX_PARTIALS elements a workgroup walks several chunks
+
+
+def mse_np(x, t):
+    """nn.MSECriterion (cg_mse_forward / cg_mse_backward, include/catgan.h) stated in numpy: (loss float32, gradient float32 of x's
+    shape).  The difference is taken in fp32, as Torch7 does; the squares are summed in fp64 (the device adds the same fp64 squares in
+    another, fixed order: the two sums agree to n 2^-53 relative, so the rounded results are equal or neighbours) and the mean is
+    rounded to fp32 once.  The gradient is norm * (x - t) with norm = float32(2) / float32(n): two fp32 operations, bit for bit."""
+    f32 = np.float32
+    x, t = np.asarray(x, dtype=f32), np.asarray(t, dtype=f32)
+    assert x.shape == t.shape and x.size > 0
+    n = x.size
+    d = (x - t).astype(f32)
+    loss = f32(np.sum(d.astype(np.float64) ** 2) / n)
+    norm = f32(2.0) / f32(n)
+    return loss, (norm * d).astype(f32)
+
+
 def activateCuda(net):
     """nn_utils.lua:620-680: wrap the net in Copy layers unless it already contains some."""
     if any(isinstance(m, nn.Copy) for m in net.listModules()):

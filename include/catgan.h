@@ -366,6 +366,16 @@ int cg_sigmoid_backward(void* stream, const float* y, const float* dy, float* dx
 int cg_bce_forward(void* stream, const float* p, const float* t, float* loss, long n);
 int cg_bce_backward(void* stream, const float* p, const float* t, float* dp, long n);
 
+/* nn.MSECriterion (pretrain_g.lua:101,168-172), sizeAverage, over n elements in any layout x and t share:
+ * *loss = (1/n) sum (x-t)^2 ; dx = (2/n) (x-t).
+ * x - t is one fp32 subtraction; the squares and every sum are fp64, added in an order that depends on n only (chunks of 4096
+ * elements, at most 1024 workgroup partials, merged by the last workgroup to arrive: csrc/criterion.hip) - the same bits on
+ * every run, for any pointer alignment, within one fp32 ulp of the exact mean.  No floating-point atomics; the partials live in
+ * the stream's reduction scratch, so there is no workspace argument.  dx = norm * (x - t) with norm = 2.f / (float)n: one fp32
+ * subtraction and one fp32 multiplication per element.  16-byte accesses when n % 4 == 0 and the pointers are 16-byte aligned. */
+int cg_mse_forward(void* stream, const float* x, const float* t, float* loss, long n);
+int cg_mse_backward(void* stream, const float* x, const float* t, float* dx, long n);
+
 /* ---- nn.SpatialBatchNormalization, training mode (models.lua:207,213,219) --
  * x,y: [M][C] (M = N*H*W).  Statistics are exchanged as fp64 sums so that a
  * data-parallel host can all-reduce them between the two calls (sync-BN).

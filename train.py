@@ -4,7 +4,9 @@ criterion, flat parameters, optimiser state) and the same endless epoch loop (:2
 Per epoch (unless --noplot): the image grids of NN_UTILS.visualizeProgress (PNG files; no display server).  The validator V is
 trained by train_v.py; when <V_dir>/v_CxHxW.net exists (train.lua:19,119-123) it is loaded in evaluate mode and every epoch's
 visualisation prints V's ratings of the random, best and worst samples (nn_utils.lua:177-179,686-711).  Without the file the run
-is what it was before.  The recalled upstream behaviour V relies on is tabulated in train_v.py.
+is what it was before.  The recalled upstream behaviour V relies on is tabulated in train_v.py.  Likewise G: when --network is empty
+and <G_pretrained_dir>/g_pretrained_CxHxW_ndN.net exists (train.lua:20,152-158; pretrain_g.py writes it) G starts from that decoder
+instead of create_G; without the file nothing changes.
 
     python train.py --batchSize 128 --N_epoch 1000 --epochs 3 --synthetic          # no dataset needed
     python train.py --dataDir dataset/out_aug_64x64 --colorSpace y --saveFreq 30
@@ -20,7 +22,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     a = ap.add_argument
     a("--save", default="logs"); a("--saveFreq", type=int, default=30); a("--network", default="")
@@ -47,7 +49,26 @@ def parse():
     a("--noplot", action="store_true", help="train.lua:33 - skip the per-epoch image grids (logs/images*/<start>_<epoch>.png)")
     a("--blockingLoader", action="store_true", help="decode + upload each epoch's images on the training thread (dataset.loadRandomImages)")
     a("--V_dir", default="logs", help="train.lua:19 - directory of the validator network v_CxHxW.net that train_v.py writes")
-    return ap.parse_args()
+    a("--G_pretrained_dir", default="logs", help="train.lua:20 - directory of the pre-trained generator g_pretrained_CxHxW_ndN.net that "
+      "pretrain_g.py writes")
+    return ap.parse_args(argv)
+
+
+def load_pretrained_G(cg, G_pretrained_dir, dims, noiseDim):
+    """train.lua:152-158: G from <G_pretrained_dir>/g_pretrained_CxHxW_ndN.net (the decoder pretrain_g.py saved) when the file exists,
+    else None - the caller then builds a fresh one (:160-161), and the run is what it is without the flag."""
+    fn = os.path.join(G_pretrained_dir, "g_pretrained_%dx%dx%d_nd%d.net" % (tuple(dims) + (noiseDim,)))
+    if not os.path.isfile(fn):
+        return None
+    print("<trainer> loading pretrained G...")
+    t7 = importlib.import_module("cat-generator_amd.t7")
+    t7_nn = importlib.import_module("cat-generator_amd.t7_nn")
+    r = cg.tensor.rng()
+    off = r.offset
+    G = t7_nn.from_t7(t7.load(fn)["G"])
+    r.offset = off          # rebuilding G's modules draws initial weights, torch.load does not: the streams stay where D left them
+    G.training()
+    return G
 
 
 def load_V(cg, S, V_dir, dims):
@@ -68,8 +89,8 @@ def load_V(cg, S, V_dir, dims):
     return V
 
 
-def main():
-    o = parse()
+def main(argv=None):
+    o = parse(argv)
     import torch
     cg = importlib.import_module("cat-generator_amd")
     torch.cuda.set_device(o.gpu)                                   # cutorch.setDevice(OPT.gpu + 1), train.lua:109
@@ -77,7 +98,9 @@ def main():
     C = 1 if o.colorSpace == "y" else 3
     IMG_DIMENSIONS = (C, o.scale, o.scale)                         # train.lua:74-78
     MODEL_D = cg.models.create_D(IMG_DIMENSIONS)                   # train.lua:147
-    MODEL_G = cg.models.create_G(IMG_DIMENSIONS, o.noiseDim)       # train.lua:161
+    MODEL_G = None if o.network else load_pretrained_G(cg, o.G_pretrained_dir, IMG_DIMENSIONS, o.noiseDim)   # train.lua:152-158
+    if MODEL_G is None:
+        MODEL_G = cg.models.create_G(IMG_DIMENSIONS, o.noiseDim)   # train.lua:161
     print(MODEL_G); print(MODEL_D)
     print("Number of free parameters in D: %d" % cg.nn_utils.getNumberOfParameters(MODEL_D))
     print("Number of free parameters in G: %d" % cg.nn_utils.getNumberOfParameters(MODEL_G))
