@@ -36,56 +36,38 @@ import argparse
 import importlib
 import os
 import sys
-import time
-
-import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+fe = importlib.import_module("cat-generator_amd.frontend")
 
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     a = ap.add_argument
-    a("--save", default="logs"); a("--batchSize", type=int, default=16)
-    a("--noplot", action="store_true", help="skip the per-epoch grids of originals / reconstructions and the loss log")
-    a("--window", type=int, default=23); a("--seed", type=int, default=1); a("--aws", action="store_true")
-    a("--saveFreq", type=int, default=1); a("--gpu", type=int, default=0); a("--threads", type=int, default=8)
-    a("--colorSpace", default="rgb", choices=["rgb", "yuv", "hsl", "y"]); a("--scale", type=int, default=32)
+    fe.run_flags(ap, batchSize=16, noplot_help="skip the per-epoch grids of originals / reconstructions and the loss log", window=23, saveFreq=1)
     a("--G_clamp", type=float, default=5.0); a("--G_L1", type=float, default=0.0); a("--G_L2", type=float, default=0.0)
     a("--N_epoch", type=int, default=10000); a("--noiseDim", type=int, default=100)
-    a("--dataDir", default="dataset/out_aug_64x64"); a("--synthetic", action="store_true")
-    a("--epochs", type=int, default=0, help="stop after this many epochs (0 = run forever, as pretrain_g.lua does)")
-    a("--augment", action="store_true", help="augment every epoch's images on the fly (dataset.setAugmentation: flip, brightness, noise, "
-      "affine warp; on the device with the asynchronous loader) - point --dataDir at the UN-augmented faces, e.g. dataset/out_unaug_64x64")
-    a("--augNoFlip", action="store_true", help="--augment without the left-right flips")
-    a("--augScale", type=float, nargs=2, default=[0.93, 1.08], metavar=("LO", "HI"), help="--augment: zoom range")
-    a("--augRotation", type=int, default=8, help="--augment: rotation of up to this many whole degrees either way")
-    a("--augTranslation", type=int, default=4, help="--augment: shift of up to this many pixels on each axis")
-    a("--augBrightness", type=float, default=0.15, help="--augment: brightness factor in [1 - this, 1 + this]")
-    a("--augNoise", type=float, default=0.02, help="--augment: standard deviation of the noise added to the [0, 1] pixels")
+    fe.data_flags(ap, "pretrain_g.lua")
+    fe.augment_flags(ap)
     return ap.parse_args(argv)
 
 
 def pretrained_filename(save_dir, dims, noiseDim):
     """pretrain_g.lua:203 / train.lua:152: g_pretrained_CHANNELSxHEIGHTxWIDTH_ndNOISEDIM.net."""
-    return os.path.join(save_dir, "g_pretrained_%dx%dx%d_nd%d.net" % (tuple(dims) + (noiseDim,)))
+    return fe.net_path("g_pretrained", save_dir, dims, noiseDim)
 
 
-class GPretrainer:
+class GPretrainer(fe.AdamFitter):
     """The state pretrain_g.lua keeps in globals (G_AUTOENCODER, CRITERION, PARAMETERS_G_AUTOENCODER, OPTSTATE, EPOCH; :88-111) and
     its epoch loop."""
+    KEY, L2 = "G", 0.0
 
     def __init__(self, cg, dims, opt):
-        import torch
-        self.cg, self.dims, self.opt = cg, tuple(dims), dict(opt)
-        self.noiseDim = int(self.opt.get("noiseDim", 100))
-        self.G_AUTOENCODER = cg.models.create_G_autoencoder(self.dims, self.noiseDim)
-        self.CRITERION = cg.nn.MSECriterion()
-        self.PARAMETERS_G_AUTOENCODER, self.GRAD_PARAMETERS_G_AUTOENCODER = self.G_AUTOENCODER.getParameters()
-        self.OPTSTATE = {"adam": {}}
-        self.EPOCH = 1
-        self._torch = torch
+        self.noiseDim = int(opt.get("noiseDim", 100))
+        super().__init__(cg, dims, opt, cg.models.create_G_autoencoder(tuple(dims), self.noiseDim), cg.nn.MSECriterion())
+        self.G_AUTOENCODER, self.PARAMETERS_G_AUTOENCODER, self.GRAD_PARAMETERS_G_AUTOENCODER = self.net, self.params, self.grads
+        self.saved = self.decoder                        # :199-214: {G = the decoder only, opt, EPOCH = EPOCH + 1} in torch.save's format
 
     @property
     def encoder(self):
@@ -96,63 +78,33 @@ class GPretrainer:
         return self.G_AUTOENCODER.get(2)
 
     def step(self, inputs):
-        """One iteration of :131-190 on a batch [N,C,H,W] (inputs == targets): optim.adam(fevalG, PARAMETERS_G_AUTOENCODER, OPTSTATE.adam)."""
-        cg, o, AE = self.cg, self.opt, self.G_AUTOENCODER
-        inputs = cg.nn.as_nhwc(cg.nn.to_device(inputs))
+        """One iteration of :131-190 on a batch [N,C,H,W] (inputs == targets): optim.adam(fevalG, PARAMETERS_G_AUTOENCODER, OPTSTATE.adam);
+        fevalG (:148-181) is the shared closure, which here keeps df_do as well."""
+        inputs = self.cg.nn.as_nhwc(self.cg.nn.to_device(inputs))
         targets = inputs                                                       # :142-145: both the same image(s)
 
-        def fevalG(x):                                                         # :148-181
-            if x is not self.PARAMETERS_G_AUTOENCODER:
-                self.PARAMETERS_G_AUTOENCODER.copy(x)
-            self.GRAD_PARAMETERS_G_AUTOENCODER.zero()
-            outputs = AE.forward(inputs)
+        def walked():
             # the encoder trains on the gradInput the decoder's first nn.Linear hands back: the module-by-module walk computes it
-            assert not AE._planned_last, "the auto-encoder runs on the per-module walk"
-            f = self.CRITERION.forward(outputs, targets)
-            df_do = self.CRITERION.backward(outputs, targets)
-            AE.backward(inputs, df_do)
-            self._last = dict(outputs=outputs, f=f, df_do=df_do)
-            return f, self.GRAD_PARAMETERS_G_AUTOENCODER                       # penalty + clamp: in the fused update below
+            assert not self.G_AUTOENCODER._planned_last, "the auto-encoder runs on the per-module walk"
 
-        fused = dict(l1=o.get("G_L1", 0.0), l2=o.get("G_L2", 0.0), clamp=o.get("G_clamp", 5.0))
-        cg.optim.adam(fevalG, self.PARAMETERS_G_AUTOENCODER, self.OPTSTATE["adam"], fused=fused)
-        return self._last
+        return self.adam_step(inputs, targets, forwarded=walked, after=lambda outputs, df_do: self._last.update(df_do=df_do))
 
     def epoch(self, trainData, verbose=True):
-        """epoch() (:120-216) without the saving, which main() does.  Returns the last batch's loss."""
-        N_epoch = min(self.opt["N_epoch"], trainData.size())
-        t0 = time.time()
-        trained = 0
-        while trained < N_epoch:
-            N = min(self.opt["batchSize"], N_epoch - trained)
+        """epoch() (:120-216) without the saving, which run() does.  Returns the last batch's loss."""
+        def train(trained, left):
+            N = min(self.opt["batchSize"], left)
             self.step(trainData.pool.rows(trained + 1, trained + N))
-            trained += N
-        self._torch.cuda.synchronize()
-        dt = time.time() - t0
+            return N
+        self.run_epoch(min(self.opt["N_epoch"], trainData.size()), train, verbose)
         loss = float(self.CRITERION.output)
         if verbose:
-            print("<trainer> time required for this epoch = %d s" % dt)
-            print("<trainer> time to learn 1 sample = %f ms" % (1000 * dt / N_epoch))
             print("<trainer> last batch loss: %.4f" % loss)
         return loss
 
     def reconstruct(self, images):
         """G_AUTOENCODER:forward in evaluate mode (:221,241,255)."""
-        self.G_AUTOENCODER.evaluate()
-        try:
-            return self.cg.nn.as_plain(self.G_AUTOENCODER.forward(self.cg.nn.as_nhwc(self.cg.nn.to_device(images)))).numpy()
-        finally:
-            self.G_AUTOENCODER.training()
-
-    def save(self, path):
-        """:199-214: {G = the decoder only, opt, EPOCH = EPOCH + 1} in torch.save's format."""
-        t7 = importlib.import_module("cat-generator_amd.t7")
-        t7_nn = importlib.import_module("cat-generator_amd.t7_nn")
-        d = os.path.dirname(path)
-        if d:
-            os.makedirs(d, exist_ok=True)
-        opt = {k: v for k, v in self.opt.items() if isinstance(v, (int, float, str, bool))}
-        return t7.save(path, {"G": t7_nn.to_t7(self.decoder), "opt": opt, "EPOCH": self.EPOCH + 1})
+        with self.evaluating() as AE:
+            return self.cg.nn.as_plain(AE.forward(self.cg.nn.as_nhwc(self.cg.nn.to_device(images)))).numpy()
 
 
 def visualize(T, images, loss, save_dir):
@@ -175,39 +127,20 @@ def main(argv=None):
     cg = importlib.import_module("cat-generator_amd")
     torch.cuda.set_device(o.gpu)
     cg.manual_seed(o.seed)                                                     # torch.manualSeed(OPT.seed), :39
-    C = 1 if o.colorSpace == "y" else 3
-    dims = (C, o.scale, o.scale)                                               # :42-46
+    dims = fe.img_dimensions(o)                                                # :42-46
     T = GPretrainer(cg, dims, vars(o))
     print("G autoencoder:")
     print(T.G_AUTOENCODER)
     print("Number of free parameters in G (total): %d" % cg.nn_utils.getNumberOfParameters(T.G_AUTOENCODER))
     print("... encoder: %d" % cg.nn_utils.getNumberOfParameters(T.encoder))
     print("... decoder: %d" % cg.nn_utils.getNumberOfParameters(T.decoder))
-    ds = importlib.import_module("cat-generator_amd.dataset")
-    ds.colorSpace = o.colorSpace; ds.setFileExtension("jpg"); ds.setHeight(o.scale); ds.setWidth(o.scale)
-    ds.setDirs([o.dataDir]); ds.seed(o.seed)
-    if o.augment:
-        ds.setAugmentation(True, hflip=not o.augNoFlip, scale=tuple(o.augScale), rotation=o.augRotation, translation=o.augTranslation,
-                           brightness=o.augBrightness, noise_std=o.augNoise)
-    while True:                                                                # :113-127
-        print("<trainer> Epoch %d" % T.EPOCH)
-        if o.synthetic:
-            pool = np.random.RandomState(T.EPOCH).rand(o.N_epoch, C, o.scale, o.scale).astype(np.float32)
-        else:
-            pool = ds.loadRandomImages(o.N_epoch).scaled                       # TRAIN_DATA = DATASET.loadRandomImages(OPT.N_epoch)
-        trainData = cg.adversarial.TrainData(pool)
-        loss = T.epoch(trainData)
-        if T.EPOCH % o.saveFreq == 0:                                          # :199-214
-            fn = pretrained_filename(o.save, dims, o.noiseDim)
-            print("<trainer> saving network to %s" % fn)
-            T.save(fn)
-        if not o.noplot:
-            images = trainData.pool.rows(1, min(100, trainData.size())) if o.synthetic else ds.loadRandomImages(100).scaled   # :229
-            visualize(T, images, loss, o.save)
-        T.EPOCH += 1
-        if o.epochs and T.EPOCH > o.epochs:
-            break
-    return T
+    ds = fe.configure_dataset(o)
+
+    def plot(trainData, loss):
+        images = trainData.pool.rows(1, min(100, trainData.size())) if o.synthetic else ds.loadRandomImages(100).scaled   # :229
+        visualize(T, images, loss, o.save)
+
+    return T.run(o, ds, pretrained_filename(o.save, dims, o.noiseDim), plot)   # :113-127
 
 
 if __name__ == "__main__":

@@ -10,12 +10,12 @@ copy's destination) stays in the 256 MB Infinity Cache over the repetitions: its
 
 --end-to-end DIR: a directory of *.jpg images and a checkpoint DIR/logs/adversarial.net (train.py --save DIR/logs); times
 sample.py --neighbours against --neighboursHost on it, one child process each, and adds both wall times."""
-import argparse
-import json
 import os
 import subprocess
 import sys
 import time
+
+import devbench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 D = 3072
@@ -32,32 +32,20 @@ def child(reps, warmup):
     rs = np.random.RandomState(0)
     rows = []
 
-    def timed(fn):
-        for _ in range(warmup):
-            fn()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1e3 / reps      # us per call
-
     for N in sorted({n for n, _ in SHAPES}):
         pool = cg.Tensor.from_numpy(rs.rand(N, D).astype(np.float32))
         other = cg.Tensor.empty((N, D))
         nbytes = N * D * 4
-        us = timed(lambda: L.memcpy_d2d(cg.tensor.stream(), other.ptr, pool.ptr, nbytes))
+        us = devbench.timed(lambda: L.memcpy_d2d(cg.tensor.stream(), other.ptr, pool.ptr, nbytes), reps, warmup)
         rows.append(dict(what="memcpy_d2d", N=N, D=D, us=us, pool_bytes_per_s=nbytes / us * 1e6))
         for Q in sorted({q for n, q in SHAPES if n == N}):
             s = U.NearestSearch(rs.rand(Q, D).astype(np.float32))
-            us = timed(lambda: s.update(pool, 0))
+            us = devbench.timed(lambda: s.update(pool, 0), reps, warmup)
             idx, _ = s.result()
             assert (idx >= 0).all()
             rows.append(dict(what="cg_nearest_update", N=N, D=D, Q=Q, us=us, pool_bytes_per_s=nbytes / us * 1e6,
                              gflops=3.0 * N * D * Q / us * 1e-3))
-    print("NEAREST_BENCH " + json.dumps(dict(device=torch.cuda.get_device_name(0), reps=reps, warmup=warmup, rows=rows)))
+    return dict(device=torch.cuda.get_device_name(0), reps=reps, warmup=warmup, rows=rows)
 
 
 def derive(res):
@@ -71,17 +59,7 @@ def derive(res):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out"); ap.add_argument("--timeout", type=int, default=300); ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5); ap.add_argument("--end-to-end"); ap.add_argument("--child", action="store_true")
-    o = ap.parse_args()
-    if o.child:
-        return child(o.reps, o.warmup)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--reps", str(o.reps), "--warmup", str(o.warmup)],
-                       capture_output=True, text=True, timeout=o.timeout)
-    if r.returncode != 0:
-        sys.exit(f"the measuring process failed ({r.returncode}):\n{r.stderr[-3000:]}")
-    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("NEAREST_BENCH ")][-1][len("NEAREST_BENCH "):])
+    o, res = devbench.run(__file__, "NEAREST_BENCH", child, dict(reps=50, warmup=5), extra=["--end-to-end"])
     for x in derive(res)["rows"]:
         print("%-18s N=%6d Q=%2s %9.1f us  %7.1f GB/s of memory traffic  %5.2f of the copy's traffic rate" % (
             x["what"], x["N"], x.get("Q", "-"), x["us"], x["traffic_bytes_per_s"] * 1e-9, x["share_of_copy_traffic"]))
@@ -97,9 +75,7 @@ def main():
                 sys.exit(f"sample.py ({name}) failed:\n{e.stderr[-3000:]}")
             res["end_to_end"][name + "_wall_s"] = time.perf_counter() - t0
             print(f"sample.py [{name}]: {res['end_to_end'][name + '_wall_s']:.2f} s wall")
-    if o.out:
-        os.makedirs(os.path.dirname(os.path.abspath(o.out)), exist_ok=True)
-        json.dump(res, open(o.out, "w"), indent=1)
+    devbench.write(o.out, res)
 
 
 if __name__ == "__main__":

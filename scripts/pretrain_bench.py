@@ -9,11 +9,10 @@ figures, not HBM ones.  Then ms per GPretrainer.step at batch 16 and batch 128 (
 under a time limit; the parent never touches the GPU.
 
     python scripts/pretrain_bench.py [--out FILE.json] [--timeout 300]"""
-import argparse
-import json
 import os
-import subprocess
 import sys
+
+import devbench
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = [16 * 3 * 32 * 32, 128 * 3 * 64 * 64]
@@ -31,18 +30,6 @@ def child(reps, warmup, iters):
     rs = np.random.RandomState(0)
     rows = []
 
-    def timed(fn, reps=reps, warmup=warmup):
-        for _ in range(warmup):
-            fn()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        torch.cuda.synchronize()
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) * 1e3 / reps      # us per call
-
     for n in SIZES:
         x, t = cg.Tensor.from_numpy(rs.rand(n).astype(np.float32)), cg.Tensor.from_numpy(rs.rand(n).astype(np.float32))
         dx, loss = cg.Tensor.empty((n,)), cg.Tensor.zeros((1,))
@@ -50,7 +37,7 @@ def child(reps, warmup, iters):
         for what, floats, fn in (("memcpy_d2d", 2, lambda: L.memcpy_d2d(s, dx.ptr, x.ptr, 4 * n)),
                                  ("cg_mse_forward", 2, lambda: L.mse_forward(s, x.ptr, t.ptr, loss.ptr, n)),
                                  ("cg_mse_backward", 3, lambda: L.mse_backward(s, x.ptr, t.ptr, dx.ptr, n))):
-            us = timed(fn)
+            us = devbench.timed(fn, reps, warmup)
             rows.append(dict(what=what, n=n, us=us, traffic_bytes_per_s=4.0 * floats * n / us * 1e6))
         ref_loss, _ = cg.nn_utils.mse_np(x.numpy(), t.numpy())
         assert abs(float(loss.numpy()[0]) - float(ref_loss)) <= np.spacing(ref_loss)
@@ -58,9 +45,9 @@ def child(reps, warmup, iters):
         cg.manual_seed(1)
         T = pg.GPretrainer(cg, (3, 32, 32), dict(batchSize=N, N_epoch=N, noiseDim=100))
         batch = cg.nn.as_nhwc(cg.nn.to_device(rs.rand(N, 3, 32, 32).astype(np.float32)))
-        us = timed(lambda: T.step(batch), reps=iters, warmup=5)
+        us = devbench.timed(lambda: T.step(batch), iters, 5)
         rows.append(dict(what="autoencoder_step", batch=N, ms=us * 1e-3, ms_per_sample=us * 1e-3 / N))
-    print("PRETRAIN_BENCH " + json.dumps(dict(device=torch.cuda.get_device_name(0), reps=reps, warmup=warmup, iters=iters, rows=rows)))
+    return dict(device=torch.cuda.get_device_name(0), reps=reps, warmup=warmup, iters=iters, rows=rows)
 
 
 def derive(res):
@@ -72,26 +59,14 @@ def derive(res):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--out"); ap.add_argument("--timeout", type=int, default=300); ap.add_argument("--reps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=10); ap.add_argument("--iters", type=int, default=30); ap.add_argument("--child", action="store_true")
-    o = ap.parse_args()
-    if o.child:
-        return child(o.reps, o.warmup, o.iters)
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--reps", str(o.reps), "--warmup", str(o.warmup), "--iters",
-                        str(o.iters)], capture_output=True, text=True, timeout=o.timeout)
-    if r.returncode != 0:
-        sys.exit(f"the measuring process failed ({r.returncode}):\n{r.stderr[-3000:]}")
-    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("PRETRAIN_BENCH ")][-1][len("PRETRAIN_BENCH "):])
+    o, res = devbench.run(__file__, "PRETRAIN_BENCH", child, dict(reps=200, warmup=10, iters=30))
     for x in derive(res)["rows"]:
         if "n" in x:
             print("%-16s n=%8d %8.2f us  %7.1f GB/s of memory traffic  %5.2f of the copy's traffic rate" % (
                 x["what"], x["n"], x["us"], x["traffic_bytes_per_s"] * 1e-9, x["share_of_copy_traffic"]))
         else:
             print("%-16s batch %3d  %8.3f ms per iteration  %7.4f ms per sample" % (x["what"], x["batch"], x["ms"], x["ms_per_sample"]))
-    if o.out:
-        os.makedirs(os.path.dirname(os.path.abspath(o.out)), exist_ok=True)
-        json.dump(res, open(o.out, "w"), indent=1)
+    devbench.write(o.out, res)
 
 
 if __name__ == "__main__":

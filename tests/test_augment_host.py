@@ -11,6 +11,8 @@ import sys
 import numpy as np
 import pytest
 
+from helpers import make_jpgs
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 IDENTITY = np.array([1, 0, 0, 0, 1, 0, 1, 0], np.float32)
 GEOMETRIES = [(64, 64, 32, 32), (64, 64, 64, 64), (32, 32, 64, 64), (96, 60, 32, 24)]      # Hs, Ws, h, w
@@ -24,13 +26,6 @@ def ds():
     d.colorSpace = "rgb"
     d.setHeight(32); d.setWidth(32)
     d.seed(1)
-
-
-def _make_jpgs(d, n=6, size=64):
-    from PIL import Image
-    rs = np.random.RandomState(0)
-    for i in range(n):
-        Image.fromarray((rs.rand(size, size, 3) * 255).astype(np.uint8)).save(os.path.join(d, f"cat_{i:03d}.jpg"), quality=95)
 
 
 # ---------------------------------------------------------------- 1. identity
@@ -182,7 +177,7 @@ def test_descriptor_draws(ds, tmp_path):
 
 
 def test_generator_consumption_and_checkpoint(ds, tmp_path):
-    _make_jpgs(str(tmp_path), n=9)
+    make_jpgs(str(tmp_path), n=9)
     ds.setDirs([str(tmp_path)]); ds.setFileExtension("jpg")
     # off: nothing beyond the permutations is consumed
     assert ds.augmentation is None

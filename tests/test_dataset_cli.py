@@ -1,6 +1,7 @@
 """Host-side neighbours of the hot path: the dataset loader (dataset.lua) on CPU, the train.py
 CLI on the GPU."""
 import importlib
+import json
 import os
 import subprocess
 import sys
@@ -8,19 +9,14 @@ import sys
 import numpy as np
 import pytest
 
+from helpers import make_jpgs
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _make_jpgs(d, n=6, size=64):
-    from PIL import Image
-    rs = np.random.RandomState(0)
-    for i in range(n):
-        Image.fromarray((rs.rand(size, size, 3) * 255).astype(np.uint8)).save(os.path.join(d, f"cat_{i:03d}.jpg"), quality=95)
 
 
 def test_dataset_loader(tmp_path):
     ds = importlib.import_module("cat-generator_amd.dataset")
-    _make_jpgs(str(tmp_path))
+    make_jpgs(str(tmp_path))
     (tmp_path / "notes.txt").write_text("ignored")
     ds.setDirs([str(tmp_path)]); ds.setFileExtension("jpg"); ds.setHeight(32); ds.setWidth(32); ds.seed(1)
     ds.colorSpace = "rgb"
@@ -63,7 +59,7 @@ def test_checkpoint_during_a_pending_prefetch_resumes_on_the_same_pools(tmp_path
     pick - so the resumed run trains E+1, E+2 ... on exactly the pools the uninterrupted (or blocking-loader) run uses."""
     ds = importlib.import_module("cat-generator_amd.dataset")
     ck = importlib.import_module("cat-generator_amd.checkpoint")
-    _make_jpgs(str(tmp_path), n=9)
+    make_jpgs(str(tmp_path), n=9)
     ds.setDirs([str(tmp_path)]); ds.setFileExtension("jpg"); ds.seed(3)
     blocking = [ds._pick(5) for _ in range(4)]                     # epochs 1..4 with --blockingLoader
     ds.seed(3)
@@ -126,7 +122,7 @@ def test_async_loader_pools_equal_the_blocking_loader(tmp_path, cs):
     cg = importlib.import_module("cat-generator_amd")
     ds = importlib.import_module("cat-generator_amd.dataset")
     from oracle import oracle as O
-    _make_jpgs(str(tmp_path), n=9)
+    make_jpgs(str(tmp_path), n=9)
     ds.setDirs([str(tmp_path)]); ds.setFileExtension("jpg"); ds.setHeight(32); ds.setWidth(32)
     ds.colorSpace = cs
     try:
@@ -199,7 +195,7 @@ def test_async_loader_pools_equal_the_blocking_loader(tmp_path, cs):
 
 @pytest.mark.gpu
 def test_train_cli_runs_epochs_and_resumes(tmp_path):
-    _make_jpgs(str(tmp_path), n=40)
+    make_jpgs(str(tmp_path), n=40)
     cmd = [sys.executable, os.path.join(ROOT, "train.py"), "--batchSize", "16", "--N_epoch", "32", "--epochs", "2",
            "--dataDir", str(tmp_path), "--save", str(tmp_path / "logs"), "--saveFreq", "1", "--colorSpace", "y"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -236,7 +232,7 @@ def test_sample_cli_writes_the_grids_from_a_torch7_checkpoint(tmp_path):
     """train.py (one epoch, saves adversarial.net in torch.save's format) -> sample.py: the seven grids of sample.lua:77-121 with
     their sizes (1024 samples in 32 x 32 cells, 64 in 8 x 8, 16 neighbour pairs in two rows)."""
     from PIL import Image
-    _make_jpgs(str(tmp_path), n=40)
+    make_jpgs(str(tmp_path), n=40)
     logs = tmp_path / "logs"
     cmd = [sys.executable, os.path.join(ROOT, "train.py"), "--batchSize", "16", "--N_epoch", "32", "--epochs", "1", "--noplot",
            "--dataDir", str(tmp_path), "--save", str(logs), "--saveFreq", "1"]
@@ -255,3 +251,32 @@ def test_sample_cli_writes_the_grids_from_a_torch7_checkpoint(tmp_path):
     for name, (h, w) in sizes.items():
         im = np.asarray(Image.open(str(dst / name)))
         assert im.shape == (h, w, 3), (name, im.shape)
+
+
+def _cli_record(monkeypatch, capsys):
+    """What tests/golden/cli_flags.json holds per front-end script: vars(parse([])) and the --help text at COLUMNS=100."""
+    monkeypatch.setenv("COLUMNS", "100")
+    monkeypatch.syspath_prepend(ROOT)
+    rec = {}
+    for name in ("train", "train_v", "pretrain_g", "sample"):
+        parse = importlib.import_module(name).parse
+        run = (lambda argv: parse()) if name == "sample" else parse          # sample.parse() reads sys.argv
+        monkeypatch.setattr(sys, "argv", [name + ".py"])
+        defaults = vars(run([]))
+        monkeypatch.setattr(sys, "argv", [name + ".py", "--help"])
+        with pytest.raises(SystemExit):
+            run(["--help"])
+        rec[name] = dict(defaults=defaults, help=capsys.readouterr().out)
+    return json.loads(json.dumps(rec))
+
+
+def test_front_end_command_lines_are_the_recorded_ones(monkeypatch, capsys):
+    """Every flag, default and help text of train.py, train_v.py, pretrain_g.py and sample.py against the record taken before their
+    flag groups moved into frontend.py: sharing the groups changes no command line."""
+    with open(os.path.join(ROOT, "tests", "golden", "cli_flags.json")) as f:
+        want = json.load(f)
+    got = _cli_record(monkeypatch, capsys)
+    assert got.keys() == want.keys()
+    for name in want:
+        assert got[name]["defaults"] == want[name]["defaults"], name
+        assert got[name]["help"] == want[name]["help"], name

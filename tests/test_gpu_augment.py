@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import make_jpgs
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CODE = {"rgb": 0, "y": 1, "yuv": 2, "hsl": 3}
@@ -32,13 +34,6 @@ def ds():
     d.colorSpace = "rgb"
     d.setHeight(32); d.setWidth(32)
     d.seed(1)
-
-
-def _make_jpgs(d, n=6, size=64):
-    from PIL import Image
-    rs = np.random.RandomState(0)
-    for i in range(n):
-        Image.fromarray((rs.rand(size, size, 3) * 255).astype(np.uint8)).save(os.path.join(d, f"cat_{i:03d}.jpg"), quality=95)
 
 
 def _device(cg, u8, desc, h, w, cs, sigma, seed, offset):
@@ -122,7 +117,7 @@ def test_bad_arguments_are_refused_before_any_launch(cg):
 @pytest.mark.parametrize("cs", ["rgb", "hsl"])
 def test_async_loader_augmented_pools_equal_the_blocking_loader(cg, ds, tmp_path, cs):
     from PIL import Image
-    _make_jpgs(str(tmp_path), n=9)
+    make_jpgs(str(tmp_path), n=9)
     Image.fromarray(np.random.RandomState(11).randint(0, 256, size=(48, 80, 3)).astype(np.uint8)).save(str(tmp_path / "odd.jpg"), quality=95)
     ds.setDirs([str(tmp_path)]); ds.setFileExtension("jpg"); ds.setHeight(32); ds.setWidth(32)
     ds.colorSpace = cs
@@ -155,7 +150,7 @@ def test_train_cli_with_augment_is_reproducible(tmp_path):
     from PIL import Image
     data = tmp_path / "data"
     os.makedirs(str(data))
-    _make_jpgs(str(data), n=40)
+    make_jpgs(str(data), n=40)
     Image.fromarray(np.random.RandomState(12).randint(0, 256, size=(64, 40, 3)).astype(np.uint8)).save(str(data / "odd.jpg"), quality=95)
     saved = []
     for run in ("a", "b"):

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import make_jpgs
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CODE = {"rgb": 0, "y": 1, "yuv": 2, "hsl": 3}
@@ -24,13 +26,6 @@ def cg():
 @pytest.fixture(scope="module")
 def ds():
     return importlib.import_module("cat-generator_amd.dataset")
-
-
-def _make_jpgs(d, n=6, size=64):
-    from PIL import Image
-    rs = np.random.RandomState(0)
-    for i in range(n):
-        Image.fromarray((rs.rand(size, size, 3) * 255).astype(np.uint8)).save(os.path.join(d, f"cat_{i:03d}.jpg"), quality=95)
 
 
 # ---------------------------------------------------------------- 6. the loader kernels
@@ -133,7 +128,7 @@ def test_async_loader_pools_equal_the_blocking_loader(cg, ds, tmp_path, cs):
     """The shape of test_dataset_cli.py's test of the same name for the two new spaces: four epochs over both pools, fewer files than
     asked for, and files of another source size that take the host path inside the loader."""
     from PIL import Image
-    _make_jpgs(str(tmp_path), n=9)
+    make_jpgs(str(tmp_path), n=9)
     ds.setDirs([str(tmp_path)]); ds.setFileExtension("jpg"); ds.setHeight(32); ds.setWidth(32)
     ds.colorSpace = cs
     try:
@@ -197,7 +192,7 @@ def test_train_and_sample_clis_run_in_the_colour_space(tmp_path, cs):
     assert (logs / "adversarial.net").exists()
     data = tmp_path / "data"
     os.makedirs(str(data))
-    _make_jpgs(str(data), n=12)
+    make_jpgs(str(data), n=12)
     dst = tmp_path / "samples"
     cmd = [sys.executable, os.path.join(ROOT, "sample.py"), "--save", str(logs), "--colorSpace", cs, "--nSamples", "64",
            "--dataDir", str(data), "--writeto", str(dst)]

@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import make_jpgs
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U24 = 2.0 ** -24
@@ -176,17 +178,9 @@ def test_queries_are_permuted_to_the_pool_layout(cg, U):
     assert (dist == 0).all()
 
 
-def _make_jpgs(d, n, odd=None):
-    from PIL import Image
-    rs = np.random.RandomState(0)
-    for i in range(n):
-        size = (48, 80, 3) if i == odd else (64, 64, 3)
-        Image.fromarray((rs.rand(*size) * 255).astype(np.uint8)).save(os.path.join(d, f"cat_{i:03d}.jpg"), quality=95)
-
-
 @pytest.mark.parametrize("cs", ["rgb", "y"])
 def test_sequential_loader_and_the_device_search_over_it(cg, U, ds, tmp_path, cs):
-    _make_jpgs(str(tmp_path), 23, odd=13)
+    make_jpgs(str(tmp_path), 23, odd=13)
     ds.setDirs([str(tmp_path)]); ds.setFileExtension("jpg"); ds.setHeight(32); ds.setWidth(32)
     ds.colorSpace = cs
     ds.seed(5)
@@ -223,7 +217,7 @@ def test_sample_cli_neighbours_on_the_device_write_the_host_path_files(tmp_path)
     """train.py for one epoch, then sample.py --neighbours --runs 2 on the device and on the host: every file of both runs byte for byte
     the same (the generator draws of later runs are preserved), and --neighboursOf 64 writes 64 pairs."""
     from PIL import Image
-    _make_jpgs(str(tmp_path), 40)
+    make_jpgs(str(tmp_path), 40)
     logs = tmp_path / "logs"
     cmd = [sys.executable, os.path.join(ROOT, "train.py"), "--batchSize", "16", "--N_epoch", "32", "--epochs", "1", "--noplot",
            "--dataDir", str(tmp_path), "--save", str(logs), "--saveFreq", "1"]

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import bulk_close, close
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -27,23 +28,6 @@ def cg():
     mod.lib()  # fails loudly if the HIP extension is missing
     mod.nn.SpatialConvolution.winograd_min_tiles = 0  # small test shapes must exercise the Winograd kernels too
     return mod
-
-
-def close(a, b, K=1024, tol=2e-5, what=""):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    assert a.shape == b.shape, f"{what}: shape {a.shape} vs {b.shape}"
-    s = max(1.0, np.sqrt(K / 1024.0)) * max(1.0, float(np.abs(b).max()))
-    err = float(np.abs(a - b).max())
-    assert err <= tol * s, f"{what}: max|d|={err:.3e} > {tol * s:.3e} (K={K})"
-
-
-def bulk_close(a, b, max_rel=3e-2, mean_rel=2e-3, what=""):
-    a, b = np.asarray(a, dtype=np.float64).ravel(), np.asarray(b, dtype=np.float64).ravel()
-    scale = max(float(np.abs(b).max()), 1e-12)
-    d = np.abs(a - b)
-    assert d.max() <= max_rel * scale, f"{what}: max|d|={d.max():.3e} vs scale {scale:.3e}"
-    if a.size > 1:
-        assert d.mean() <= mean_rel * scale, f"{what}: mean|d|={d.mean():.3e} vs scale {scale:.3e}"
 
 
 # ------------------------------------------------------------------------------ convolution

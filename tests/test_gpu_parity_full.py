@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 import torch
 
+from helpers import close
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -30,16 +31,6 @@ def cg():
     assert torch.cuda.is_available(), "these tests need the MI355X"
     mod.lib()
     return mod
-
-
-def close(a, b, K=1024, tol=2e-5, what=""):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    assert a.shape == b.shape, f"{what}: shape {a.shape} vs {b.shape}"
-    s = max(1.0, np.sqrt(K / 1024.0)) * max(1.0, float(np.abs(b).max()))
-    err = float(np.abs(a - b).max())
-    assert np.isfinite(a).all(), f"{what}: non-finite values"
-    assert err <= tol * s, f"{what}: max|d|={err:.3e} > {tol * s:.3e} (K={K})"
-    return err
 
 
 class options:

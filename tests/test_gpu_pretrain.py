@@ -10,15 +10,13 @@ import sys
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
-import test_gpu_validator as TV       # its measures and numbers: close(tol=1e-4), bulk_close, the per-tensor 3e-2 * scale rule
+from helpers import KINK, bulk_close, check_grads, close, snapshot, torch_twin
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
-close, bulk_close = TV.close, TV.bulk_close
 
 
 @pytest.fixture(scope="module")
@@ -146,85 +144,6 @@ def test_mse_criterion_formats(cg):
 
 
 # ------------------------------------------------------------------------------ the auto-encoder against torch
-def _snapshot(net):
-    """Parameters and running statistics of every module, as host arrays taken now (depth first, as getParameters orders them)."""
-    snap = {}
-    for m in net.listModules():
-        d = {k: getattr(m, k).numpy().copy() for k in ("weight", "bias", "running_mean", "running_var") if getattr(m, k, None) is not None}
-        if d:
-            snap[id(m)] = d
-    return snap
-
-
-KINK = 1e-4        # relative to max|h|: inside it the side of PReLU's kink is the last bit's, not the net's (test_autoencoder_vs_torch)
-
-
-def _torch_net(net, snap, h, params, taps, sides=None):
-    """nn.Sequential `net` restated in torch fp64 on the snapshot's values.  params collects the leaves in getParameters' order; taps
-    records every child container's output (retain_grad), the torch running statistics per batch-norm module and the output per
-    nn.Linear.  sides: {id(an nn.PReLU): the device's input to it} - where the twin's own input lies within KINK max|h| of zero the
-    twin takes the device's side of the kink (teacher-forced, as _torch_V forces the dropout masks); taps counts those elements."""
-    for m in net.modules:
-        t = m.typename
-        s = snap.get(id(m), {})
-        leaf = lambda k: torch.tensor(s[k], dtype=torch.float64, requires_grad=True)
-        if t == "nn.Sequential":
-            h = _torch_net(m, snap, h, params, taps, sides)
-            h.retain_grad()
-            taps[id(m)] = h
-        elif t in ("nn.SpatialConvolution", "cudnn.SpatialConvolution", "nn.Linear"):
-            w, b = leaf("weight"), leaf("bias")
-            params += [w, b]
-            h = F.conv2d(h, w, b, padding=m.padH) if "Convolution" in t else F.linear(h, w, b)
-            if t == "nn.Linear":
-                taps[id(m)] = h
-        elif t in ("nn.SpatialBatchNormalization", "nn.BatchNormalization"):
-            w, b = leaf("weight"), leaf("bias")
-            params += [w, b]
-            rm, rv = torch.tensor(s["running_mean"], dtype=torch.float64), torch.tensor(s["running_var"], dtype=torch.float64)
-            taps[id(m)] = (rm, rv)
-            h = F.batch_norm(h, rm, rv, w, b, training=True, momentum=0.1, eps=1e-5)
-        elif t == "nn.LeakyReLU":
-            h = torch.where(h >= 0, h, h * m.negative_scale)
-        elif t == "nn.PReLU":
-            w = leaf("weight")
-            params.append(w)
-            pos = h > 0
-            if sides and id(m) in sides:
-                a = h.detach().abs()
-                near = a <= KINK * a.max()
-                pos = torch.where(near, torch.from_numpy(sides[id(m)].reshape(tuple(h.shape)) > 0), pos)
-                taps["forced", id(m)] = (int(near.sum()), int((pos != (h > 0)).sum()))
-            h = torch.where(pos, h, h * w)
-        elif t == "nn.SpatialMaxPooling":
-            h = F.max_pool2d(h, 2)
-        elif t == "nn.SpatialUpSamplingNearest":
-            h = F.interpolate(h, scale_factor=2, mode="nearest")
-        elif t == "nn.View":
-            h = h.reshape(h.shape[0], *m.sizes)
-        elif t == "nn.Sigmoid":
-            h = torch.sigmoid(h)
-        else:
-            raise AssertionError(t)
-    return h
-
-
-def _check_grads(g, params):
-    gref = torch.cat([p.grad.reshape(-1) for p in params]).numpy()
-    bulk_close(g, gref, what="gradParameters")
-    off = 0
-    for p in params:     # per tensor, with a floor: a convolution bias in front of a batch norm has an exactly-zero gradient
-        k = p.numel()
-        a, b = g[off:off + k].astype(np.float64), p.grad.numpy().ravel()
-        scale = max(float(np.abs(b).max()), 1e-4 * float(np.abs(gref).max()))
-        d = np.abs(a - b)
-        print(f"gradParameters [{off}:{off + k}]: max|d| {d.max():.3e} against {3e-2 * scale:.3e}")
-        assert d.max() <= 3e-2 * scale, f"gradParameters [{off}:{off + k}]"
-        off += k
-    assert off == g.size
-    return gref
-
-
 @pytest.mark.parametrize("dims,N", [((3, 32, 32), 4), ((1, 32, 32), 4), ((3, 64, 64), 2)])
 def test_autoencoder_vs_torch(cg, dims, N):
     cg.manual_seed(13)
@@ -232,7 +151,7 @@ def test_autoencoder_vs_torch(cg, dims, N):
     _, G = AE.getParameters()
     enc, dec = AE.get(1), AE.get(2)
     x = np.random.RandomState(5).rand(N, *dims).astype(np.float32)
-    snap = _snapshot(AE)
+    snap = snapshot(AE)
     crit = cg.nn.MSECriterion()
     G.zero()
     xi = cg.nn.to_device(x)
@@ -250,7 +169,7 @@ def test_autoencoder_vs_torch(cg, dims, N):
     h_dev = lin.output.numpy().copy()
     xt = torch.tensor(x, dtype=torch.float64, requires_grad=True)
     params, taps = [], {}
-    yt = _torch_net(AE, snap, xt, params, taps, sides={id(prelu): h_dev})
+    yt = torch_twin(AE, snap, xt, params, taps, sides={id(prelu): h_dev})
     loss = ((yt - xt.detach()) ** 2).mean()
     loss.backward()
     h_ref = taps[id(lin)].detach().numpy()
@@ -271,7 +190,7 @@ def test_autoencoder_vs_torch(cg, dims, N):
     assert gz.shape == (N, 100) and np.abs(gz).max() > 0 and np.abs(gz_ref).max() > 0
     bulk_close(gz, gz_ref, what="encoder output gradient")
     close(enc.output.numpy(), taps[id(enc)].detach().numpy(), tol=1e-4, what="code z")
-    _check_grads(G.numpy(), params)
+    check_grads(G.numpy(), params)
     n_enc = cg.nn_utils.getNumberOfParameters(enc)
     assert np.abs(G.numpy()[:n_enc]).max() > 0, "the encoder received no gradient"
     nbn = 0
@@ -290,13 +209,13 @@ def test_fevalG_adam_step_vs_torch(cg):
     cg.manual_seed(2)
     T = pg.GPretrainer(cg, (3, 32, 32), dict(seed=2, batchSize=4, G_L1=0.0, G_L2=L2, G_clamp=CLAMP, N_epoch=4, noiseDim=100))
     x = np.random.RandomState(9).rand(4, 3, 32, 32).astype(np.float32)
-    snap = _snapshot(T.G_AUTOENCODER)
+    snap = snapshot(T.G_AUTOENCODER)
     p0 = T.PARAMETERS_G_AUTOENCODER.numpy().copy()
     last = T.step(x)
     torch.cuda.synchronize()
     xt = torch.tensor(x, dtype=torch.float64)
     params, taps = [], {}
-    yt = _torch_net(T.G_AUTOENCODER, snap, xt, params, taps)
+    yt = torch_twin(T.G_AUTOENCODER, snap, xt, params, taps)
     loss = ((yt - xt) ** 2).mean()
     loss.backward()
     gref = torch.cat([p.grad.reshape(-1) for p in params]).numpy()

@@ -11,25 +11,10 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from helpers import bulk_close, check_grads, close, snapshot, torch_twin
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def close(a, b, K=1024, tol=2e-5, what=""):        # the bounds of tests/test_gpu_parity.py
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    assert a.shape == b.shape, f"{what}: shape {a.shape} vs {b.shape}"
-    s = max(1.0, np.sqrt(K / 1024.0)) * max(1.0, float(np.abs(b).max()))
-    err = float(np.abs(a - b).max())
-    assert err <= tol * s, f"{what}: max|d|={err:.3e} > {tol * s:.3e} (K={K})"
-
-
-def bulk_close(a, b, max_rel=3e-2, mean_rel=2e-3, what=""):
-    a, b = np.asarray(a, dtype=np.float64).ravel(), np.asarray(b, dtype=np.float64).ravel()
-    scale = max(float(np.abs(b).max()), 1e-12)
-    d = np.abs(a - b)
-    assert d.max() <= max_rel * scale, f"{what}: max|d|={d.max():.3e} vs scale {scale:.3e}"
-    if a.size > 1:
-        assert d.mean() <= mean_rel * scale, f"{what}: mean|d|={d.mean():.3e} vs scale {scale:.3e}"
 
 
 @pytest.fixture(scope="module")
@@ -96,7 +81,7 @@ def test_batchnorm_1d_evaluate(cg):
 
 # ------------------------------------------------------------------------------ V against torch
 def _fix_masks(V, N, rs, dims):
-    """Explicit dropout masks (the fixed_noise test hook) for every dropout of V; returned in the logical layout for torch."""
+    """Explicit dropout masks (the fixed_noise test hook) for every dropout of V; returned by id(module) in the logical layout for torch."""
     masks = {}
     shape = None
     x_shapes = _shapes(V, N, dims)
@@ -105,11 +90,11 @@ def _fix_masks(V, N, rs, dims):
         if m.typename == "nn.SpatialDropout":
             k = (rs.rand(N, shape[1]) >= m.p).astype(np.float32)
             m.fixed_noise = k
-            masks[i] = torch.tensor(k, dtype=torch.float64)[:, :, None, None]
+            masks[id(m)] = torch.tensor(k, dtype=torch.float64)[:, :, None, None]
         elif m.typename == "nn.Dropout":
             k = ((rs.rand(*shape) >= m.p) / (1 - m.p)).astype(np.float32)
             m.fixed_noise = k          # logical layout: a 4-D host array is stored NHWC like the map it masks
-            masks[i] = torch.tensor(k, dtype=torch.float64)
+            masks[id(m)] = torch.tensor(k, dtype=torch.float64)
     return masks
 
 
@@ -130,38 +115,6 @@ def _shapes(V, N, dims):
     return out
 
 
-def _torch_V(V, x, masks):
-    h = x
-    params = []
-    for i, m in enumerate(V.modules):
-        t = m.typename
-        if t in ("nn.SpatialConvolution", "nn.Linear"):
-            w = torch.tensor(m.weight.numpy(), dtype=torch.float64, requires_grad=True)
-            b = torch.tensor(m.bias.numpy(), dtype=torch.float64, requires_grad=True)
-            params += [w, b]
-            h = F.conv2d(h, w, b, padding=m.padH) if t == "nn.SpatialConvolution" else F.linear(h, w, b)
-        elif t in ("nn.SpatialBatchNormalization", "nn.BatchNormalization"):
-            w = torch.tensor(m.weight.numpy(), dtype=torch.float64, requires_grad=True)
-            b = torch.tensor(m.bias.numpy(), dtype=torch.float64, requires_grad=True)
-            params += [w, b]
-            m._ref_rm = torch.tensor(m.running_mean.numpy(), dtype=torch.float64)
-            m._ref_rv = torch.tensor(m.running_var.numpy(), dtype=torch.float64)
-            h = F.batch_norm(h, m._ref_rm, m._ref_rv, w, b, training=True, momentum=0.1, eps=1e-5)
-        elif t == "nn.LeakyReLU":
-            h = torch.where(h >= 0, h, h * m.negative_scale)
-        elif t == "nn.SpatialMaxPooling":
-            h = F.max_pool2d(h, 2)
-        elif t in ("nn.Dropout", "nn.SpatialDropout"):
-            h = h * masks[i]
-        elif t == "nn.View":
-            h = h.reshape(h.shape[0], -1)
-        elif t == "nn.SoftMax":
-            h = torch.softmax(h, 1)
-        else:
-            raise AssertionError(t)
-    return h, params
-
-
 def _bce(p, t):
     eps = 1e-12
     return -(t * torch.log(p + eps) + (1 - t) * torch.log(1 - p + eps)).mean()
@@ -179,7 +132,8 @@ def test_v_forward_backward_vs_torch(cg, dims, N):
     t[N // 2:, 0] = 1
     masks = _fix_masks(V, N, rs, dims)
     xt = torch.tensor(x, dtype=torch.float64, requires_grad=True)
-    yt, params = _torch_V(V, xt, masks)
+    params, taps = [], {}
+    yt = torch_twin(V, snapshot(V), xt, params, taps, masks=masks)
     loss = _bce(yt, torch.tensor(t, dtype=torch.float64))
     loss.backward()
     crit = cg.nn.BCECriterion()
@@ -190,21 +144,12 @@ def test_v_forward_backward_vs_torch(cg, dims, N):
     close(cg.nn.as_plain(y).numpy(), yt.detach().numpy(), tol=1e-4, what="V output")
     close(float(f), float(loss.detach()), tol=1e-4, what="loss")
     bulk_close(cg.nn.as_plain(gi).numpy(), xt.grad.numpy(), what="V gradInput")
-    g = G.numpy()
-    gref = torch.cat([p.grad.reshape(-1) for p in params]).numpy()
-    bulk_close(g, gref, what="gradParameters")
-    off = 0
-    for p in params:     # per tensor, with a floor: a convolution bias in front of a batch norm has an exactly-zero gradient
-        k = p.numel()
-        a, b = g[off:off + k].astype(np.float64), p.grad.numpy().ravel()
-        scale = max(float(np.abs(b).max()), 1e-4 * float(np.abs(gref).max()))
-        assert np.abs(a - b).max() <= 3e-2 * scale, f"gradParameters [{off}:{off + k}]"
-        off += k
-    assert off == g.size
+    check_grads(G.numpy(), params)
     for m in V.modules:
         if "BatchNormalization" in m.typename:
-            close(m.running_mean.numpy(), m._ref_rm.numpy(), tol=1e-4, what="running mean")
-            close(m.running_var.numpy(), m._ref_rv.numpy(), tol=1e-4, what="running var")
+            rm, rv = taps[id(m)]
+            close(m.running_mean.numpy(), rm.numpy(), tol=1e-4, what="running mean")
+            close(m.running_var.numpy(), rv.numpy(), tol=1e-4, what="running var")
 
 
 def _bank():
@@ -221,6 +166,7 @@ def test_fevalV_adam_step_vs_torch(cg):
     rs = np.random.RandomState(4)
     masks = _fix_masks(T.V, N, rs, (3, 32, 32))
     p0 = T.PARAMETERS_V.numpy().copy()
+    snap = snapshot(T.V)                                       # the values before the step, for the torch restatement
     b = T.batch(pool, N)
     x = cg.nn.as_plain(b["inputs"]).numpy()
     t = b["targets"].numpy()
@@ -230,7 +176,8 @@ def test_fevalV_adam_step_vs_torch(cg):
     last = T.step(pool, N)
     torch.cuda.synchronize()
     xt = torch.tensor(x, dtype=torch.float64)
-    yt, params = _torch_V(_with_params(T.V, p0), xt, masks)
+    params = []
+    yt = torch_twin(T.V, snap, xt, params, {}, masks=masks)
     loss = _bce(yt, torch.tensor(t, dtype=torch.float64))
     loss.backward()
     gref = torch.cat([p.grad.reshape(-1) for p in params]).numpy()
@@ -243,39 +190,6 @@ def test_fevalV_adam_step_vs_torch(cg):
     np.testing.assert_allclose(v, 0.001 * g * g, rtol=1e-4, atol=1e-20)     # (1 - beta2) g^2 rounded in fp32
     step = 1e-3 * np.sqrt(1 - 0.999) / (1 - 0.9) * m / (np.sqrt(v) + 1e-8)   # Torch7 adam: eps outside the bias correction
     np.testing.assert_allclose(T.PARAMETERS_V.numpy(), p0 - step, rtol=0, atol=2e-7)
-
-
-def _with_params(V, flat):
-    """V's modules with their parameters read from `flat` (the values before the step) for the torch restatement."""
-    class _M:
-        pass
-    out = _M()
-    out.modules = []
-    off = 0
-    for m in V.modules:
-        c = _M()
-        c.__dict__.update({k: getattr(m, k) for k in ("typename", "padH", "negative_scale", "p") if hasattr(m, k)})
-        c.typename = m.typename
-        for name in ("weight", "bias"):
-            w = getattr(m, name, None)
-            if w is not None and m.typename not in ("nn.LeakyReLU",):
-                k = w.nElement()
-                arr = flat[off:off + k].reshape(w.shape)
-                setattr(c, name, _Arr(arr))
-                off += k
-        for name in ("running_mean", "running_var"):
-            if hasattr(m, name):
-                setattr(c, name, _Arr(np.zeros(m.nFeature, np.float32) if name == "running_mean" else np.ones(m.nFeature, np.float32)))
-        out.modules.append(c)
-    return out
-
-
-class _Arr:
-    def __init__(self, a):
-        self.a = a
-
-    def numpy(self):
-        return self.a
 
 
 # ------------------------------------------------------------------------------ the device generator

@@ -20,6 +20,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+fe = importlib.import_module("cat-generator_amd.frontend")
 
 
 def parse(argv=None):
@@ -35,17 +36,9 @@ def parse(argv=None):
     a("--D_sgd_lr", type=float, default=0.02); a("--G_sgd_lr", type=float, default=0.02)
     a("--D_sgd_momentum", type=float, default=0.0); a("--G_sgd_momentum", type=float, default=0.0)
     a("--gpu", type=int, default=0); a("--noiseDim", type=int, default=100); a("--scale", type=int, default=32)
-    a("--seed", type=int, default=1); a("--colorSpace", default="rgb", choices=["rgb", "yuv", "hsl", "y"])
-    a("--dataDir", default="dataset/out_aug_64x64"); a("--synthetic", action="store_true")
-    a("--epochs", type=int, default=0, help="stop after this many epochs (0 = run forever, as train.lua does)")
-    a("--augment", action="store_true", help="augment every epoch's images on the fly (dataset.setAugmentation: flip, brightness, noise, "
-      "affine warp; on the device with the asynchronous loader) - point --dataDir at the UN-augmented faces, e.g. dataset/out_unaug_64x64")
-    a("--augNoFlip", action="store_true", help="--augment without the left-right flips")
-    a("--augScale", type=float, nargs=2, default=[0.93, 1.08], metavar=("LO", "HI"), help="--augment: zoom range")
-    a("--augRotation", type=int, default=8, help="--augment: rotation of up to this many whole degrees either way")
-    a("--augTranslation", type=int, default=4, help="--augment: shift of up to this many pixels on each axis")
-    a("--augBrightness", type=float, default=0.15, help="--augment: brightness factor in [1 - this, 1 + this]")
-    a("--augNoise", type=float, default=0.02, help="--augment: standard deviation of the noise added to the [0, 1] pixels")
+    a("--seed", type=int, default=1); a("--colorSpace", default="rgb", choices=fe.COLOR_SPACES)
+    fe.data_flags(ap, "train.lua")
+    fe.augment_flags(ap)
     a("--noplot", action="store_true", help="train.lua:33 - skip the per-epoch image grids (logs/images*/<start>_<epoch>.png)")
     a("--blockingLoader", action="store_true", help="decode + upload each epoch's images on the training thread (dataset.loadRandomImages)")
     a("--V_dir", default="logs", help="train.lua:19 - directory of the validator network v_CxHxW.net that train_v.py writes")
@@ -57,32 +50,20 @@ def parse(argv=None):
 def load_pretrained_G(cg, G_pretrained_dir, dims, noiseDim):
     """train.lua:152-158: G from <G_pretrained_dir>/g_pretrained_CxHxW_ndN.net (the decoder pretrain_g.py saved) when the file exists,
     else None - the caller then builds a fresh one (:160-161), and the run is what it is without the flag."""
-    fn = os.path.join(G_pretrained_dir, "g_pretrained_%dx%dx%d_nd%d.net" % (tuple(dims) + (noiseDim,)))
-    if not os.path.isfile(fn):
-        return None
-    print("<trainer> loading pretrained G...")
-    t7 = importlib.import_module("cat-generator_amd.t7")
-    t7_nn = importlib.import_module("cat-generator_amd.t7_nn")
-    r = cg.tensor.rng()
-    off = r.offset
-    G = t7_nn.from_t7(t7.load(fn)["G"])
-    r.offset = off          # rebuilding G's modules draws initial weights, torch.load does not: the streams stay where D left them
-    G.training()
+    G = fe.load_net(fe.net_path("g_pretrained", G_pretrained_dir, dims, noiseDim), "G")   # the streams stay where D left them
+    if G is not None:
+        print("<trainer> loading pretrained G...")
+        G.training()
     return G
 
 
 def load_V(cg, S, V_dir, dims):
     """train.lua:119-123: V from <V_dir>/v_CxHxW.net, in evaluate mode, as S.MODEL_V (nn_utils.rateWithV reads it)."""
-    fn = os.path.join(V_dir, "v_%dx%dx%d.net" % tuple(dims))
-    if not os.path.exists(fn):
+    fn = fe.net_path("v", V_dir, dims)
+    V = fe.load_net(fn, "V")                                       # leaves the training streams where they were
+    if V is None:
         print(f"<trainer> no validator network at {fn}: V ratings are off (train_v.py trains one)")
         return None
-    t7 = importlib.import_module("cat-generator_amd.t7")
-    t7_nn = importlib.import_module("cat-generator_amd.t7_nn")
-    r = cg.tensor.rng()
-    off = r.offset
-    V = t7_nn.from_t7(t7.load(fn)["V"])
-    r.offset = off          # rebuilding V's modules draws initial weights: leave the training streams where they were
     V.evaluate()
     S.MODEL_V = V
     print(f"<trainer> loaded validator network {fn}")
@@ -95,8 +76,7 @@ def main(argv=None):
     cg = importlib.import_module("cat-generator_amd")
     torch.cuda.set_device(o.gpu)                                   # cutorch.setDevice(OPT.gpu + 1), train.lua:109
     cg.manual_seed(o.seed)                                         # train.lua:61-62,110
-    C = 1 if o.colorSpace == "y" else 3
-    IMG_DIMENSIONS = (C, o.scale, o.scale)                         # train.lua:74-78
+    IMG_DIMENSIONS = fe.img_dimensions(o)                          # train.lua:74-78
     MODEL_D = cg.models.create_D(IMG_DIMENSIONS)                   # train.lua:147
     MODEL_G = None if o.network else load_pretrained_G(cg, o.G_pretrained_dir, IMG_DIMENSIONS, o.noiseDim)   # train.lua:152-158
     if MODEL_G is None:
@@ -105,12 +85,7 @@ def main(argv=None):
     print("Number of free parameters in D: %d" % cg.nn_utils.getNumberOfParameters(MODEL_D))
     print("Number of free parameters in G: %d" % cg.nn_utils.getNumberOfParameters(MODEL_G))
     S = cg.adversarial.State(vars(o), MODEL_G, MODEL_D)            # criterion, getParameters, OPTSTATE: :181-207
-    ds = importlib.import_module("cat-generator_amd.dataset")
-    ds.colorSpace = o.colorSpace; ds.setFileExtension("jpg"); ds.setHeight(o.scale); ds.setWidth(o.scale)
-    ds.setDirs([o.dataDir]); ds.seed(o.seed)
-    if o.augment:
-        ds.setAugmentation(True, hflip=not o.augNoFlip, scale=tuple(o.augScale), rotation=o.augRotation, translation=o.augTranslation,
-                           brightness=o.augBrightness, noise_std=o.augNoise)
+    ds = fe.configure_dataset(o)
     if o.network:   # after every generator was seeded: the checkpoint puts each of them back where the run stopped
         print(f"<trainer> reloading previously trained network: {o.network}")
         (cg.checkpoint.load_t7 if o.network.endswith(".net") else cg.checkpoint.load)(o.network, S)
@@ -125,7 +100,7 @@ def main(argv=None):
     while True:                                                    # train.lua:223
         print("Loading new training data...")
         if o.synthetic:
-            pool = np.random.RandomState(S.EPOCH).rand(n_pool, C, o.scale, o.scale).astype(np.float32)
+            pool = fe.synthetic_pool(S.EPOCH, n_pool, IMG_DIMENSIONS)
         elif loader is not None:
             pool = loader.next()
         else:

@@ -27,12 +27,12 @@ import argparse
 import importlib
 import os
 import sys
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+fe = importlib.import_module("cat-generator_amd.frontend")
 
 Y_FAKE, Y_REAL = 0, 1   # train_v.lua:36-37: target column Y+1 (1-based), so 0-based column 0 = fake
 
@@ -40,42 +40,25 @@ Y_FAKE, Y_REAL = 0, 1   # train_v.lua:36-37: target column Y+1 (1-based), so 0-b
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     a = ap.add_argument
-    a("--save", default="logs"); a("--batchSize", type=int, default=32)
-    a("--noplot", action="store_true", help="skip the 'rated real' / 'rated fake' image grids")
-    a("--window", type=int, default=13); a("--seed", type=int, default=1); a("--aws", action="store_true")
-    a("--saveFreq", type=int, default=10); a("--gpu", type=int, default=0); a("--threads", type=int, default=8)
-    a("--colorSpace", default="rgb", choices=["rgb", "yuv", "hsl", "y"]); a("--scale", type=int, default=32)
+    fe.run_flags(ap, batchSize=32, noplot_help="skip the 'rated real' / 'rated fake' image grids", window=13, saveFreq=10)
     a("--V_clamp", type=float, default=5.0); a("--V_L1", type=float, default=0.0); a("--V_L2", type=float, default=0.01)
     a("--N_epoch", type=int, default=1000)
-    a("--dataDir", default="dataset/out_aug_64x64"); a("--synthetic", action="store_true")
-    a("--epochs", type=int, default=0, help="stop after this many epochs (0 = run forever, as train_v.lua does)")
-    a("--augment", action="store_true", help="augment every epoch's images on the fly (dataset.setAugmentation: flip, brightness, noise, "
-      "affine warp; on the device with the asynchronous loader) - point --dataDir at the UN-augmented faces, e.g. dataset/out_unaug_64x64")
-    a("--augNoFlip", action="store_true", help="--augment without the left-right flips")
-    a("--augScale", type=float, nargs=2, default=[0.93, 1.08], metavar=("LO", "HI"), help="--augment: zoom range")
-    a("--augRotation", type=int, default=8, help="--augment: rotation of up to this many whole degrees either way")
-    a("--augTranslation", type=int, default=4, help="--augment: shift of up to this many pixels on each axis")
-    a("--augBrightness", type=float, default=0.15, help="--augment: brightness factor in [1 - this, 1 + this]")
-    a("--augNoise", type=float, default=0.02, help="--augment: standard deviation of the noise added to the [0, 1] pixels")
+    fe.data_flags(ap, "train_v.lua")
+    fe.augment_flags(ap)
     return ap.parse_args(argv)
 
 
-class VTrainer:
+class VTrainer(fe.AdamFitter):
     """The state train_v.lua keeps in globals (V, CRITERION, PARAMETERS_V, CONFUSION, OPTSTATE; :87-99) and its epoch loop."""
+    KEY, L2 = "V", 0.01
 
     def __init__(self, cg, dims, opt, bank=None):
-        import torch
-        self.cg, self.dims, self.opt = cg, tuple(dims), dict(opt)
-        self.V = cg.models.create_V(self.dims)
-        self.CRITERION = cg.nn.BCECriterion()
-        self.PARAMETERS_V, self.GRAD_PARAMETERS_V = self.V.getParameters()
+        super().__init__(cg, dims, opt, cg.models.create_V(tuple(dims)), cg.nn.BCECriterion())
+        self.V, self.PARAMETERS_V, self.GRAD_PARAMETERS_V = self.net, self.params, self.grads
         self.CONFUSION = cg.optim.ConfusionMatrix(("0", "1"))
-        self.OPTSTATE = {"adam": {}}
-        self.EPOCH = 1
         self.random = np.random.RandomState(self.opt.get("seed", 1))          # math.randomseed(OPT.seed), :32
         self.gen = cg.synthetic.Generator(self.dims, self.random, bank=bank)
         self._bufs = {}
-        self._torch = torch
 
     def _buffers(self, N):
         b = self._bufs.get(N)
@@ -102,47 +85,28 @@ class VTrainer:
         return b
 
     def step(self, trainData, N, real_idx=None, plan=None):
-        """One iteration of :119-198: the batch, then optim.adam(fevalV, PARAMETERS_V, OPTSTATE.adam)."""
-        cg, o = self.cg, self.opt
-        b = self.batch(trainData, N, real_idx, plan)
+        """One iteration of :119-198: the batch, then optim.adam(fevalV, PARAMETERS_V, OPTSTATE.adam); fevalV (:124-157) is the shared
+        closure with the confusion update at its end."""
+        cg, b = self.cg, self.batch(trainData, N, real_idx, plan)
 
-        def fevalV(x):                                                         # :124-157
-            if x is not self.PARAMETERS_V:
-                self.PARAMETERS_V.copy(x)
-            self.GRAD_PARAMETERS_V.zero()
-            outputs = self.V.forward(b["inputs"])
-            f = self.CRITERION.forward(outputs, b["targets"])
-            df_do = self.CRITERION.backward(outputs, b["targets"])
-            self.V.backward(b["inputs"], df_do)
-            # confusion (:147-153) on the device: p(fake) > 0.5 against "target is fake"
+        def confusion(outputs, df_do):                                         # :147-153 on the device: p(fake) > 0.5 against "target is fake"
             out = cg.nn.as_plain(outputs)
             cg.lib().copy_channels(cg.tensor.stream(), out.ptr, b["p_fake"].ptr, N, 2, Y_FAKE, 1, 0, 1)
             self.CONFUSION.batchAdd(b["p_fake"], b["t_fake"])
-            self._last = dict(outputs=outputs, f=f)
-            return f, self.GRAD_PARAMETERS_V                                   # penalty + clamp: in the fused update below
 
-        fused = dict(l1=o.get("V_L1", 0.0), l2=o.get("V_L2", 0.01), clamp=o.get("V_clamp", 5.0))
-        cg.optim.adam(fevalV, self.PARAMETERS_V, self.OPTSTATE["adam"], fused=fused)
-        return self._last
+        return self.adam_step(b["inputs"], b["targets"], after=confusion)
 
     def epoch(self, trainData, verbose=True):
-        """epoch() (:113-213) without the saving, which main() does."""
-        N_epoch = self.opt["N_epoch"]
-        t0 = time.time()
-        trained = 0
-        while trained < N_epoch:
-            N = min(self.opt["batchSize"], N_epoch - trained)
+        """epoch() (:113-213) without the saving, which run() does."""
+        def train(trained, left):
+            N = min(self.opt["batchSize"], left)
             N -= N % 2                                                         # half real, half fake: an even batch
-            if N < 2:
-                break
-            self.step(trainData, N)
-            trained += N
-        self._torch.cuda.synchronize()
-        dt = time.time() - t0
+            if N >= 2:
+                self.step(trainData, N)
+            return N
+        self.run_epoch(self.opt["N_epoch"], train, verbose)
         c = self.CONFUSION.counts.cpu().numpy()                                # the reference's confusion print (:189-191)
         if verbose:
-            print("<trainer> time required for this epoch = %d s" % dt)
-            print("<trainer> time to learn 1 sample = %f ms" % (1000 * dt / N_epoch))
             print("Confusion of V (rows: predicted fake / real, columns: target fake / real):")
             print("  [[%d %d]\n   [%d %d]]  accuracy %.2f %%" % (c[3], c[2], c[1], c[0], 100.0 * (c[0] + c[3]) / max(1, c.sum())))
         self.CONFUSION.zero()
@@ -150,22 +114,8 @@ class VTrainer:
 
     def rate(self, images):
         """V:forward in evaluate mode, p(fake) per image (:235)."""
-        self.V.evaluate()
-        try:
-            p = self.cg.nn.as_plain(self.V.forward(images)).numpy()
-        finally:
-            self.V.training()
-        return p[:, Y_FAKE]
-
-    def save(self, path):
-        from importlib import import_module
-        t7 = import_module("cat-generator_amd.t7")
-        t7_nn = import_module("cat-generator_amd.t7_nn")
-        d = os.path.dirname(path)
-        if d:
-            os.makedirs(d, exist_ok=True)
-        opt = {k: v for k, v in self.opt.items() if isinstance(v, (int, float, str, bool))}
-        return t7.save(path, {"V": t7_nn.to_t7(self.V), "opt": opt, "EPOCH": self.EPOCH + 1})
+        with self.evaluating() as V:
+            return self.cg.nn.as_plain(V.forward(images)).numpy()[:, Y_FAKE]
 
 
 def visualize(T, trainData, save_dir):
@@ -190,36 +140,13 @@ def main(argv=None):
     cg = importlib.import_module("cat-generator_amd")
     torch.cuda.set_device(o.gpu)
     cg.manual_seed(o.seed)                                                     # torch.manualSeed(OPT.seed), :33
-    C = 1 if o.colorSpace == "y" else 3
-    dims = (C, o.scale, o.scale)                                               # :44-48
+    dims = fe.img_dimensions(o)                                                # :44-48
     T = VTrainer(cg, dims, vars(o))
     print("network V:")
     print(T.V)
     print("Number of free parameters in V: %d" % cg.nn_utils.getNumberOfParameters(T.V))
-    ds = importlib.import_module("cat-generator_amd.dataset")
-    ds.colorSpace = o.colorSpace; ds.setFileExtension("jpg"); ds.setHeight(o.scale); ds.setWidth(o.scale)
-    ds.setDirs([o.dataDir]); ds.seed(o.seed)
-    if o.augment:
-        ds.setAugmentation(True, hflip=not o.augNoFlip, scale=tuple(o.augScale), rotation=o.augRotation, translation=o.augTranslation,
-                           brightness=o.augBrightness, noise_std=o.augNoise)
-    while True:                                                                # :101-110
-        print("<trainer> Epoch %d" % T.EPOCH)
-        if o.synthetic:
-            pool = np.random.RandomState(T.EPOCH).rand(o.N_epoch, C, o.scale, o.scale).astype(np.float32)
-        else:
-            pool = ds.loadRandomImages(o.N_epoch).scaled                       # TRAIN_DATA = DATASET.loadRandomImages(OPT.N_epoch)
-        trainData = cg.adversarial.TrainData(pool)
-        T.epoch(trainData)
-        if T.EPOCH % o.saveFreq == 0:                                          # :203-210
-            fn = os.path.join(o.save, "v_%dx%dx%d.net" % dims)
-            print("<trainer> saving network to %s" % fn)
-            T.save(fn)
-        if not o.noplot:
-            visualize(T, trainData, o.save)
-        T.EPOCH += 1
-        if o.epochs and T.EPOCH > o.epochs:
-            break
-    return T
+    plot = lambda trainData, confusion: visualize(T, trainData, o.save)
+    return T.run(o, fe.configure_dataset(o), fe.net_path("v", o.save, dims), plot)   # :101-110
 
 
 if __name__ == "__main__":
