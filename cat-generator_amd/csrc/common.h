@@ -87,8 +87,14 @@ int queue_class(hipStream_t ref, hipStream_t s);                // class of a po
 void wgrad_discard_all();
 
 // 3x3 convolutions with <= 3 output planes as a scatter-form GEMM on the MFMA, input read once (csrc/skinny.hip, round 6): widths that
-// are a multiple of 32 up to 128, 64 or 128 input planes.  CG_SKINNY: 1 = these where they apply (else round 1's VALU kernels of
-// gemm.hip), 2 = the VALU kernels always, 0 = the generic implicit GEMM.
+// are a multiple of 32 up to 128, 64 or 128 input planes.  CG_SKINNY: 1 = these where they apply (else round 1's VALU kernels in the
+// same file), 2 = the VALU kernels always, 0 = the generic implicit GEMM.  gemm.hip decides which family runs.
+constexpr int kSkinnyWgradBlocks = 512;   // partial planes of a skinny weight gradient, at most
+bool skinny_ok(int ngroups, int Cin, int Cout, int kH, int kW, int padH, int padW, int ups);   // a skinny layer at all (either family)
+size_t skinny_wgrad_ws_bytes(int Cin, int Cout);
+void skinny_valu_forward(hipStream_t st, const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout);
+void skinny_valu_wgrad(hipStream_t st, const float* x, const float* dy, float* part, float* bias_part, int N, int H, int W, int Cin, int Cout,
+                       int blocks, long ppb);
 bool skinny_mfma_ok(int Cin, int Cout, int H, int W);
 int skinny_mfma_forward(hipStream_t st, const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout);
 int skinny_mfma_wgrad(hipStream_t st, const float* x, const float* dy, float* part, float* bias_part, int N, int H, int W, int Cin, int Cout,

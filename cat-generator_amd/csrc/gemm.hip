@@ -29,6 +29,10 @@
 //     quad weight-gradient kernel of rounds 2-4 lost every A/B they were in and were removed in round 5: profiles/NOTES_r01_r02.md.)
 //   * igemm_nng_kernel / igemm_tng_kernel (LDS-direct loads, buffer_load_dwordx4 ... lds): the default where the
 //     geometry allows (round 2: the ablation builds below located the loop's loss in the register -> LDS staging).
+// What the two staging families of a GEMM have in common is written once: the blockIdx.z decode and operand selection (nn_tile / tn_tile),
+// the NN epilogue (nn_epilogue: bias, activation, statistics, the lean and the generic stores), the TN partial store (tn_store_partials) and
+// the host's packing of the four-pointer argument fields (set4).  The skinny 3x3 layers (<= 3 output planes) have their kernels, MFMA and
+// VALU, in skinny.hip; this file only decides which of them runs (cg::skinny_ok, CG_SKINNY).
 #include "common.h"
 #include <stdlib.h>
 #include <algorithm>
@@ -137,6 +141,26 @@ struct TNArgs {
 template <typename T>
 __device__ __forceinline__ T sel4(int i, T a, T b, T c, T d) { return i == 0 ? a : (i == 1 ? b : (i == 2 ? c : d)); }
 
+// blockIdx.z = group * nphase + phase of every GEMM launch, phase bits (pa, pb); with the operands of that group (w: this phase's kernel)
+struct ZTile { int group, phase, pa, pb; };
+struct NNTile : ZTile { const float* x; const float* bias; float* y; const float* w; };
+struct TNTile : ZTile { const float* x; const float* dy; };
+__device__ __forceinline__ ZTile z_decode(const Geom& g, int zz) {
+    const int group = g.nphase == 1 ? zz : (g.nphase == 4 ? zz >> 2 : zz / g.nphase);
+    const int phase = zz - group * g.nphase;
+    return {group, phase, phase >> 1, phase & 1};
+}
+__device__ __forceinline__ NNTile nn_tile(const NNArgs& a, int zz) {
+    const ZTile z = z_decode(a.g, zz);
+    return {z, sel4(z.group, a.x0, a.x1, a.x2, a.x3), sel4(z.group, a.b0, a.b1, a.b2, a.b3), sel4(z.group, a.y0, a.y1, a.y2, a.y3),
+            sel4(z.group, a.w0, a.w1, a.w2, a.w3) + (long)z.phase * a.g.Ktot * a.g.Cout};
+}
+__device__ __forceinline__ TNTile tn_tile(const TNArgs& a, int zz) {
+    const ZTile z = z_decode(a.g, zz);
+    return {z, a.xgs ? a.x0 + (long)z.group * a.xgs : sel4(z.group, a.x0, a.x1, a.x2, a.x3),
+            a.dgs ? a.d0 + (long)z.group * a.dgs : sel4(z.group, a.d0, a.d1, a.d2, a.d3)};
+}
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float f4c(const float4& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
 
@@ -236,6 +260,129 @@ __device__ __forceinline__ void nn_store_lean(const f32x16 (&acc)[MI][NI], const
     }
 }
 
+// batch-norm statistics of a wave's columns -> a.stats[srow][2][Cout]; the two half-waves hold the two row halves of the same columns.
+// GUARD: the tile may reach past Cout.
+template <int BM, int WM, int WN, int NI, bool GUARD>
+__device__ __forceinline__ void nn_store_stats(const NNArgs& a, const float (&s1)[NI], const float (&s2)[NI], int zz, int tm, int wave, int ncol, int h) {
+    const Geom& g = a.g;
+    const int srow = (zz * (int)((g.M + BM - 1) / BM) + tm) * WM + wave / WN;
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+        const float t1 = s1[j] + __shfl_xor(s1[j], 32, 64), t2 = s2[j] + __shfl_xor(s2[j], 32, 64);
+        const int n = ncol + j * 32;
+        if (h == 0 && (!GUARD || n < g.Cout)) {
+            a.stats[((long)srow * 2 + 0) * g.Cout + n] = t1;
+            a.stats[((long)srow * 2 + 1) * g.Cout + n] = t2;
+        }
+    }
+}
+
+// Epilogue of both NN kernels: D[i][j], i = (r&3) + 8*(r>>2) + 4*h (pixel), j = l31 (channel).  Bias, fused activation (second output),
+// batch-norm statistics; split launches store their partials.  The stores, cheapest first: position-major lean (PM kernels only) ->
+// consecutive lean -> strided lean (STRIDED: the LDS-direct kernel only) -> the generic bounds-checked loop.
+// The arguments come BY VALUE, as the kernel holds them: through a reference the compiler merges the two loads of the slope into one load
+// through a pointer that may point into the argument copy, and that copy then stays in scratch (8 bytes per lane in every NN kernel).
+template <int BM, int BN, int WM, int WN, bool STRIDED, bool PM>
+__device__ __forceinline__ void nn_epilogue(const f32x16 (&acc)[BM / WM / 32][BN / WN / 32], const NNArgs a, const NNTile z, int m0, int n0, int wm0,
+                                            int wn0, int l31, int h, int wave, int tm, int zz, int split, int pos_u) {
+    // Floating-point contraction is off in the epilogue, and the statistics' sum of squares states its own rounding: s2 = fma(v, v, s2) in
+    // the strided loop and in the generic loop of the 32-column wave tiles (NI == 1), s2 + v * v (two roundings) in the generic loop of
+    // the 64-column ones (NI == 2).  The bits of a batch-norm layer are part of what the parity tests pin (tests/test_gpu_gemm_bits.py).
+#pragma clang fp contract(off)
+    constexpr int MI = BM / WM / 32, NI = BN / WN / 32;
+    const Geom& g = a.g;
+    const int group = z.group, pa = z.pa, pb = z.pb;
+    const float* gbias = z.bias;
+    const bool partial = a.nsplit > 1;
+    const bool add_bias = (gbias != nullptr) && !partial;
+    float* yout = partial ? a.part : z.y;
+    const int act = partial ? 0 : a.act;
+    float* zout = act ? sel4(group, a.z0, a.z1, a.z2, a.z3) : nullptr;
+    float aslope = a.slope;
+    if (act == 1) aslope = *sel4(group, a.al0, a.al1, a.al2, a.al3);
+    const bool stats = a.stats != nullptr && !partial;
+    float bj[NI], s1[NI], s2[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+        const int n = n0 + wn0 + j * 32 + l31;
+        bj[j] = (add_bias && n < g.Cout) ? gbias[n] : 0.f;
+        s1[j] = 0.f; s2[j] = 0.f;
+    }
+    {
+        // lean path: full tile, consecutive output rows, byte offsets inside the 2 GB a buffer descriptor spans
+        if (PM && !partial) {
+            // position-major tile: 64 images at one pixel - the accumulator rows are an image apart (host: full tiles, < 2 GB)
+            const int hwc = g.Hg * g.Wg * g.Cout;
+            const unsigned vo = ((unsigned)((m0 & (g.pmn - 1)) + wm0 + 4 * h) * (unsigned)hwc + (unsigned)(pos_u * g.Cout + n0 + wn0 + l31)) * 4u;
+            if (act) nn_store_lean<MI, NI, true>(acc, bj, yout, zout, vo, hwc * 4, act, aslope);
+            else nn_store_lean<MI, NI, false>(acc, bj, yout, nullptr, vo, hwc * 4, 0, 0.f);
+            CG_STAMP(3);
+            return;
+        }
+        const bool lin = partial || (g.so == 1 && g.nphase == 1);
+        const long rows_total = partial ? (long)a.nsplit * a.ngroups * g.nphase * g.M : (long)g.M;
+        if (lin && !stats && m0 + BM <= g.M && n0 + BN <= g.Cout && rows_total * g.Cout < 0x1fffffffL) {
+            const long rowbase = partial ? (long)(split * (a.ngroups * g.nphase) + zz) * g.M : 0L;
+            const unsigned vo = ((unsigned)(rowbase + m0 + wm0 + 4 * h) * (unsigned)g.Cout + (unsigned)(n0 + wn0 + l31)) * 4u;
+            if (act) nn_store_lean<MI, NI, true>(acc, bj, yout, zout, vo, g.Cout * 4, act, aslope);
+            else nn_store_lean<MI, NI, false>(acc, bj, yout, nullptr, vo, g.Cout * 4, 0, 0.f);
+            CG_STAMP(3);
+            return;
+        }
+        // lean STRIDED path (round 5): the phase-folded forward of a layer behind an upsampling (output pixel (2 oy + a, 2 ox + b), so == 2)
+        // with or without the batch-norm statistics of the layer behind it - power-of-two grids, full tiles, no fused activation, an
+        // output below 2 GB: the pixel decode is shifts and masks, the byte offset of an accumulator row one 32-bit value, a row past
+        // the end stores to the out-of-range offset.  (The generic loop below decodes, bounds-checks and builds a 64-bit address per
+        // VALUE.)  Same values, same order of the statistics' sums.
+        if constexpr (STRIDED) {
+        if (!partial && !act && g.lgW >= 0 && m0 + BM <= g.M && n0 + BN <= g.Cout && !lin &&
+            (long)(g.M >> g.lgHW) * g.Hout * g.Wout * g.Cout * 4L < 0x7fffffffL) {
+            const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)yout, 0, 0x7fffffff, 0x00020000);
+            const int colb = (n0 + wn0 + l31) * 4;
+#pragma unroll
+            for (int i = 0; i < MI; ++i) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int n = m >> g.lgHW, oy = (m >> g.lgW) & (g.Hg - 1), ox = m & (g.Wg - 1);
+                    const int vo = ((n * g.Hout + oy * g.so + pa) * g.Wout + ox * g.so + pb) * g.Cout * 4 + colb;
+#pragma unroll
+                    for (int j = 0; j < NI; ++j) {
+                        const float v = acc[i][j][r] + bj[j];
+                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ry, vo, j * 128, 0);
+                        if (stats) { s1[j] += v; s2[j] = __builtin_fmaf(v, v, s2[j]); }
+                    }
+                }
+            }
+            if (stats) nn_store_stats<BM, WM, WN, NI, false>(a, s1, s2, zz, tm, wave, n0 + wn0 + l31, h);
+            CG_STAMP(3);
+            return;
+        }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (m >= g.M) continue;
+            const long ro = partial ? ((long)(split * (a.ngroups * g.nphase) + zz) * g.M + m) * g.Cout : out_row(g, m, pa, pb);
+#pragma unroll
+            for (int j = 0; j < NI; ++j) {
+                const int n = n0 + wn0 + j * 32 + l31;
+                if (n < g.Cout) {
+                    const float v = acc[i][j][r] + bj[j];
+                    yout[ro + n] = v;
+                    if (act) zout[ro + n] = apply_act(act, v, aslope);
+                    if (stats) { s1[j] += v; s2[j] = NI == 1 ? __builtin_fmaf(v, v, s2[j]) : s2[j] + v * v; }
+                }
+            }
+        }
+    }
+    if (stats) nn_store_stats<BM, WM, WN, NI, true>(a, s1, s2, zz, tm, wave, n0 + wn0 + l31, h);
+    CG_STAMP(3);
+}
+
 // ---------------------------------------------------------------------------
 // NN: Y[m][n] = sum_k A(m,k) * W[k][n]
 // ---------------------------------------------------------------------------
@@ -280,15 +427,13 @@ __global__ __launch_bounds__(256, BK == 16 ? 4 : 2) void igemm_nn_kernel(NNArgs 
     const int m0 = tm * BM, n0 = tn * BN;
     const int split = blockIdx.y;
     const int zz = blockIdx.z;
-    const int group = g.nphase == 1 ? zz : (g.nphase == 4 ? zz >> 2 : zz / g.nphase);
-    const int phase = zz - group * g.nphase, pa = phase >> 1, pb = phase & 1;
-    const float* gx = sel4(group, a.x0, a.x1, a.x2, a.x3);
-    const float* gbias = sel4(group, a.b0, a.b1, a.b2, a.b3);
-    float* gy = sel4(group, a.y0, a.y1, a.y2, a.y3);
+    const NNTile z = nn_tile(a, zz);
+    const int phase = z.phase, pa = z.pa, pb = z.pb;
+    const float* gx = z.x;
+    const float* wph = z.w;
     const int ks = split * a.kchunk;
     const int kend = min(g.Ktot, ks + a.kchunk);
     const int T = CG_PROBE_HALF(1, (kend - ks + BK - 1) / BK);
-    const float* wph = sel4(group, a.w0, a.w1, a.w2, a.w3) + (long)phase * g.Ktot * g.Cout;
 
     // ---- A staging: thread owns k-vector a_kv (4 consecutive k) of rows a_r + 64p
     const int a_kv = tid % KV, a_r = tid / KV;
@@ -491,67 +636,7 @@ __global__ __launch_bounds__(256, BK == 16 ? 4 : 2) void igemm_nn_kernel(NNArgs 
     }
 
     CG_STAMP(2);
-    // ---- epilogue: D[i][j], i = (r&3) + 8*(r>>2) + 4*h (pixel), j = l31 (channel)
-    const bool partial = a.nsplit > 1;
-    const bool add_bias = (gbias != nullptr) && !partial;
-    float* yout = partial ? a.part : gy;
-    const int act = partial ? 0 : a.act;
-    float* zout = act ? sel4(group, a.z0, a.z1, a.z2, a.z3) : nullptr;
-    float aslope = a.slope;
-    if (act == 1) aslope = *sel4(group, a.al0, a.al1, a.al2, a.al3);
-    const bool stats = a.stats != nullptr && !partial;
-    float bj[NI], s1[NI], s2[NI];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        const int n = n0 + wn0 + j * 32 + l31;
-        bj[j] = (add_bias && n < g.Cout) ? gbias[n] : 0.f;
-        s1[j] = 0.f; s2[j] = 0.f;
-    }
-    {
-        // lean path: full tile, consecutive output rows, byte offsets inside the 2 GB a buffer descriptor spans
-        const bool lin = partial || (g.so == 1 && g.nphase == 1);
-        const long rows_total = partial ? (long)a.nsplit * a.ngroups * g.nphase * g.M : (long)g.M;
-        if (lin && !stats && m0 + BM <= g.M && n0 + BN <= g.Cout && rows_total * g.Cout < 0x1fffffffL) {
-            const long rowbase = partial ? (long)(split * (a.ngroups * g.nphase) + zz) * g.M : 0L;
-            const unsigned vo = ((unsigned)(rowbase + m0 + wm0 + 4 * h) * (unsigned)g.Cout + (unsigned)(n0 + wn0 + l31)) * 4u;
-            if (act) nn_store_lean<MI, NI, true>(acc, bj, yout, zout, vo, g.Cout * 4, act, aslope);
-            else nn_store_lean<MI, NI, false>(acc, bj, yout, nullptr, vo, g.Cout * 4, 0, 0.f);
-            CG_STAMP(3);
-            return;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (m >= g.M) continue;
-            const long ro = partial ? ((long)(split * (a.ngroups * g.nphase) + zz) * g.M + m) * g.Cout : out_row(g, m, pa, pb);
-#pragma unroll
-            for (int j = 0; j < NI; ++j) {
-                const int n = n0 + wn0 + j * 32 + l31;
-                if (n < g.Cout) {
-                    const float v = acc[i][j][r] + bj[j];
-                    yout[ro + n] = v;
-                    if (act) zout[ro + n] = apply_act(act, v, aslope);
-                    if (stats) { s1[j] += v; s2[j] += v * v; }
-                }
-            }
-        }
-    }
-    if (stats) {   // the two half-waves hold the two row halves of the same columns
-        const int srow = (zz * (int)((g.M + BM - 1) / BM) + tm) * WM + wave / WN;
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            const float t1 = s1[j] + __shfl_xor(s1[j], 32, 64), t2 = s2[j] + __shfl_xor(s2[j], 32, 64);
-            const int n = n0 + wn0 + j * 32 + l31;
-            if (h == 0 && n < g.Cout) {
-                a.stats[((long)srow * 2 + 0) * g.Cout + n] = t1;
-                a.stats[((long)srow * 2 + 1) * g.Cout + n] = t2;
-            }
-        }
-    }
-    CG_STAMP(3);
+    nn_epilogue<BM, BN, WM, WN, false, false>(acc, a, z, m0, n0, wm0, wn0, l31, h, wave, tm, zz, split, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -621,16 +706,14 @@ __global__ __launch_bounds__(256, 2) void igemm_nng_kernel(NNArgs a) {
     const int m0 = tm * BM, n0 = tn * BN;
     const int split = blockIdx.y;
     const int zz = blockIdx.z;
-    const int group = g.nphase == 1 ? zz : (g.nphase == 4 ? zz >> 2 : zz / g.nphase);
-    const int phase = zz - group * g.nphase, pa = phase >> 1, pb = phase & 1;
-    const float* gx = sel4(group, a.x0, a.x1, a.x2, a.x3);
-    const float* gbias = sel4(group, a.b0, a.b1, a.b2, a.b3);
-    float* gy = sel4(group, a.y0, a.y1, a.y2, a.y3);
+    const NNTile z = nn_tile(a, zz);
+    const int phase = z.phase, pa = z.pa, pb = z.pb;
+    const float* gx = z.x;
+    const float* wph = z.w;
     int ks = split * a.kchunk;
     const int kend = min(g.Ktot, ks + a.kchunk);
     int T = (kend - ks + BK - 1) / BK;
     const int pos_u = PM ? (m0 >> g.pm_lg) : 0;      // PM: the tile's pixel position (wave-uniform; N is a multiple of BM)
-    const float* wph = sel4(group, a.w0, a.w1, a.w2, a.w3) + (long)phase * g.Ktot * g.Cout;
 
     // ---- A: lane -> (row a_r + ARPP p, LDS quad position a_kv); the quad it loads is a_kv ^ swz(row)
     const int a_kv = tid % KV, a_r = tid / KV;
@@ -806,114 +889,7 @@ __global__ __launch_bounds__(256, 2) void igemm_nng_kernel(NNArgs a) {
     }
 
     CG_STAMP(2);
-    // ---- epilogue (as igemm_nn_kernel): D[i][j], i = (r&3) + 8*(r>>2) + 4*h (pixel), j = l31 (channel)
-    const bool partial = a.nsplit > 1;
-    const bool add_bias = (gbias != nullptr) && !partial;
-    float* yout = partial ? a.part : gy;
-    const int act = partial ? 0 : a.act;
-    float* zout = act ? sel4(group, a.z0, a.z1, a.z2, a.z3) : nullptr;
-    float aslope = a.slope;
-    if (act == 1) aslope = *sel4(group, a.al0, a.al1, a.al2, a.al3);
-    const bool stats = a.stats != nullptr && !partial;
-    float bj[NI], s1[NI], s2[NI];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        const int n = n0 + wn0 + j * 32 + l31;
-        bj[j] = (add_bias && n < g.Cout) ? gbias[n] : 0.f;
-        s1[j] = 0.f; s2[j] = 0.f;
-    }
-    {
-        // lean path: full tile, consecutive output rows, byte offsets inside the 2 GB a buffer descriptor spans
-        if (PM && !partial) {
-            // position-major tile: 64 images at one pixel - the accumulator rows are an image apart (host: full tiles, < 2 GB)
-            const int hwc = g.Hg * g.Wg * g.Cout;
-            const unsigned vo = ((unsigned)((m0 & (g.pmn - 1)) + wm0 + 4 * h) * (unsigned)hwc + (unsigned)(pos_u * g.Cout + n0 + wn0 + l31)) * 4u;
-            if (act) nn_store_lean<MI, NI, true>(acc, bj, yout, zout, vo, hwc * 4, act, aslope);
-            else nn_store_lean<MI, NI, false>(acc, bj, yout, nullptr, vo, hwc * 4, 0, 0.f);
-            CG_STAMP(3);
-            return;
-        }
-        const bool lin = partial || (g.so == 1 && g.nphase == 1);
-        const long rows_total = partial ? (long)a.nsplit * a.ngroups * g.nphase * g.M : (long)g.M;
-        if (lin && !stats && m0 + BM <= g.M && n0 + BN <= g.Cout && rows_total * g.Cout < 0x1fffffffL) {
-            const long rowbase = partial ? (long)(split * (a.ngroups * g.nphase) + zz) * g.M : 0L;
-            const unsigned vo = ((unsigned)(rowbase + m0 + wm0 + 4 * h) * (unsigned)g.Cout + (unsigned)(n0 + wn0 + l31)) * 4u;
-            if (act) nn_store_lean<MI, NI, true>(acc, bj, yout, zout, vo, g.Cout * 4, act, aslope);
-            else nn_store_lean<MI, NI, false>(acc, bj, yout, nullptr, vo, g.Cout * 4, 0, 0.f);
-            CG_STAMP(3);
-            return;
-        }
-        // lean STRIDED path (round 5): the phase-folded forward of a layer behind an upsampling (output pixel (2 oy + a, 2 ox + b), so == 2)
-        // with or without the batch-norm statistics of the layer behind it - power-of-two grids, full tiles, no fused activation, an
-        // output below 2 GB: the pixel decode is shifts and masks, the byte offset of an accumulator row one 32-bit value, a row past
-        // the end stores to the out-of-range offset.  (The generic loop below decodes, bounds-checks and builds a 64-bit address per
-        // VALUE.)  Same values, same order of the statistics' sums.
-        if (!partial && !act && g.lgW >= 0 && m0 + BM <= g.M && n0 + BN <= g.Cout && !lin &&
-            (long)(g.M >> g.lgHW) * g.Hout * g.Wout * g.Cout * 4L < 0x7fffffffL) {
-            const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)yout, 0, 0x7fffffff, 0x00020000);
-            const int colb = (n0 + wn0 + l31) * 4;
-#pragma unroll
-            for (int i = 0; i < MI; ++i) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    const int n = m >> g.lgHW, oy = (m >> g.lgW) & (g.Hg - 1), ox = m & (g.Wg - 1);
-                    const int vo = ((n * g.Hout + oy * g.so + pa) * g.Wout + ox * g.so + pb) * g.Cout * 4 + colb;
-#pragma unroll
-                    for (int j = 0; j < NI; ++j) {
-                        const float v = acc[i][j][r] + bj[j];
-                        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ry, vo, j * 128, 0);
-                        if (stats) { s1[j] += v; s2[j] += v * v; }
-                    }
-                }
-            }
-            if (stats) {
-                const int srow = (zz * (int)((g.M + BM - 1) / BM) + tm) * WM + wave / WN;
-#pragma unroll
-                for (int j = 0; j < NI; ++j) {
-                    const float t1 = s1[j] + __shfl_xor(s1[j], 32, 64), t2 = s2[j] + __shfl_xor(s2[j], 32, 64);
-                    if (h == 0) {
-                        a.stats[((long)srow * 2 + 0) * g.Cout + n0 + wn0 + j * 32 + l31] = t1;
-                        a.stats[((long)srow * 2 + 1) * g.Cout + n0 + wn0 + j * 32 + l31] = t2;
-                    }
-                }
-            }
-            CG_STAMP(3);
-            return;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < MI; ++i) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (m >= g.M) continue;
-            const long ro = partial ? ((long)(split * (a.ngroups * g.nphase) + zz) * g.M + m) * g.Cout : out_row(g, m, pa, pb);
-#pragma unroll
-            for (int j = 0; j < NI; ++j) {
-                const int n = n0 + wn0 + j * 32 + l31;
-                if (n < g.Cout) {
-                    const float v = acc[i][j][r] + bj[j];
-                    yout[ro + n] = v;
-                    if (act) zout[ro + n] = apply_act(act, v, aslope);
-                    if (stats) { s1[j] += v; s2[j] += v * v; }
-                }
-            }
-        }
-    }
-    if (stats) {   // the two half-waves hold the two row halves of the same columns
-        const int srow = (zz * (int)((g.M + BM - 1) / BM) + tm) * WM + wave / WN;
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            const float t1 = s1[j] + __shfl_xor(s1[j], 32, 64), t2 = s2[j] + __shfl_xor(s2[j], 32, 64);
-            const int n = n0 + wn0 + j * 32 + l31;
-            if (h == 0 && n < g.Cout) {
-                a.stats[((long)srow * 2 + 0) * g.Cout + n] = t1;
-                a.stats[((long)srow * 2 + 1) * g.Cout + n] = t2;
-            }
-        }
-    }
-    CG_STAMP(3);
+    nn_epilogue<BM, BN, WM, WN, true, PM>(acc, a, z, m0, n0, wm0, wn0, l31, h, wave, tm, zz, split, pos_u);
 }
 
 // split-K reduce for NN: y_group[out_row(m)][n] = bias_group[n] + sum_s part[s][group*nphase+phase][m][n]
@@ -1003,6 +979,29 @@ __global__ __launch_bounds__(256) void nn_splitk_reduce_kernel(NNArgs a, int S) 
     }
 }
 
+// the (split, group, phase) plane of a weight-gradient launch's partials: part[plane][Ktot][Cout] (tn_part), bias_part[plane][Cout]
+__device__ __forceinline__ long tn_plane(const TNArgs& a, int split, int zz) { return (long)(split * (a.ngroups * a.g.nphase) + zz); }
+__device__ __forceinline__ float* tn_part(const TNArgs& a, int split, int zz) { return a.part + tn_plane(a, split, zz) * a.g.Ktot * a.g.Cout; }
+
+// generic tail of both TN kernels: the bounds-checked store of a wave's accumulators into its plane of the partials
+template <int MI, int NI>
+__device__ __forceinline__ void tn_store_partials(const f32x16 (&acc)[MI][NI], float* pout, const Geom& g, int m0, int n0, int wm0, int wn0, int l31,
+                                                  int h) {
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+        const int n = n0 + wn0 + j * 32 + l31;
+        if (n >= g.Cout) continue;
+#pragma unroll
+        for (int i = 0; i < MI; ++i) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                if (m < g.Ktot) pout[(long)m * g.Cout + n] = acc[i][j][r];
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------
 // TN: dW[k][n] = sum_m A(m,k) * dY[m][n]   (k = (tap,ci) rows, m = grid pixels reduced)
 // ---------------------------------------------------------------------------
@@ -1043,10 +1042,10 @@ __global__ __launch_bounds__(256, 4) void igemm_tn_kernel(TNArgs a) {
     const int tn = ntn == 1 ? 0 : bid % ntn, tm = ntn == 1 ? bid : bid / ntn;
     const int m0 = tm * BM, n0 = tn * BN;  // m0: row of dW (tap,ci)
     const int zz = blockIdx.z;
-    const int group = g.nphase == 1 ? zz : (g.nphase == 4 ? zz >> 2 : zz / g.nphase);
-    const int phase = zz - group * g.nphase, pa = phase >> 1, pb = phase & 1;
-    const float* gx = a.xgs ? a.x0 + (long)group * a.xgs : sel4(group, a.x0, a.x1, a.x2, a.x3);
-    const float* gdy = a.dgs ? a.d0 + (long)group * a.dgs : sel4(group, a.d0, a.d1, a.d2, a.d3);
+    const TNTile z = tn_tile(a, zz);
+    const int phase = z.phase, pa = z.pa, pb = z.pb;
+    const float* gx = z.x;
+    const float* gdy = z.dy;
     const int ps = split * a.pchunk;
     const int pend = min(g.M, ps + a.pchunk);
     const int T = CG_PROBE_HALF(2, (pend - ps + BK - 1) / BK);
@@ -1263,23 +1262,10 @@ __global__ __launch_bounds__(256, 4) void igemm_tn_kernel(TNArgs a) {
             float t = 0.f;
 #pragma unroll
             for (int r = 0; r < 256 / BVEC; ++r) t += red[r * BN + tid];
-            a.bias_part[(long)(split * (a.ngroups * g.nphase) + zz) * g.Cout + n0 + tid] = t;
+            a.bias_part[tn_plane(a, split, zz) * g.Cout + n0 + tid] = t;
         }
     }
-    float* pout = a.part + (long)(split * (a.ngroups * g.nphase) + zz) * g.Ktot * g.Cout;
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        const int n = n0 + wn0 + j * 32 + l31;
-        if (n >= g.Cout) continue;
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (m < g.Ktot) pout[(long)m * g.Cout + n] = acc[i][j][r];
-            }
-        }
-    }
+    tn_store_partials<MI, NI>(acc, tn_part(a, split, zz), g, m0, n0, wm0, wn0, l31, h);
 }
 
 // ---------------------------------------------------------------------------
@@ -1337,10 +1323,10 @@ __global__ __launch_bounds__(256, 2) void igemm_tng_kernel(TNArgs a, int mode) {
     const int tn = ntn == 1 ? 0 : bid % ntn, tm = ntn == 1 ? bid : bid / ntn;
     const int m0 = tm * BM, n0 = tn * BN;
     const int zz = blockIdx.z;
-    const int group = g.nphase == 1 ? zz : (g.nphase == 4 ? zz >> 2 : zz / g.nphase);
-    const int phase = zz - group * g.nphase, pa = phase >> 1, pb = phase & 1;
-    const float* gx = a.xgs ? a.x0 + (long)group * a.xgs : sel4(group, a.x0, a.x1, a.x2, a.x3);
-    const float* gdy = a.dgs ? a.d0 + (long)group * a.dgs : sel4(group, a.d0, a.d1, a.d2, a.d3);
+    const TNTile z = tn_tile(a, zz);
+    const int phase = z.phase, pa = z.pa, pb = z.pb;
+    const float* gx = z.x;
+    const float* gdy = z.dy;
     const int ps = split * a.pchunk;
     const int pend = min(g.M, ps + a.pchunk);
     int T = CG_PROBE_HALF(2, (pend - ps) / BK);
@@ -1491,8 +1477,8 @@ __global__ __launch_bounds__(256, 2) void igemm_tng_kernel(TNArgs a, int mode) {
     }
 
     if (do_bias && tid < BN && n0 + tid < g.Cout)
-        a.bias_part[(long)(split * (a.ngroups * g.nphase) + zz) * g.Cout + n0 + tid] = bsum;
-    float* pout = a.part + (long)(split * (a.ngroups * g.nphase) + zz) * g.Ktot * g.Cout;
+        a.bias_part[tn_plane(a, split, zz) * g.Cout + n0 + tid] = bsum;
+    float* pout = tn_part(a, split, zz);
     // lean path (round 5, as nn_store_lean): a FULL tile stores through a buffer descriptor at (per-lane byte offset) + (row offset in an
     // SGPR) - no bounds test, no 64-bit address per value (the generic loop below is ~2000 instructions per wave, 1 VALU per MFMA of the
     // whole launch; the partial sums of one (split, phase) plane always fit the 2 GB a descriptor spans)
@@ -1511,19 +1497,7 @@ __global__ __launch_bounds__(256, 2) void igemm_tng_kernel(TNArgs a, int mode) {
             }
         return;
     }
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        const int n = n0 + wn0 + j * 32 + l31;
-        if (n >= g.Cout) continue;
-#pragma unroll
-        for (int i = 0; i < MI; ++i) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (m < g.Ktot) pout[(long)m * g.Cout + n] = acc[i][j][r];
-            }
-        }
-    }
+    tn_store_partials<MI, NI>(acc, pout, g, m0, n0, wm0, wn0, l31, h);
 }
 
 // canonical tap d of a k-tap kernel (pad p) seen from output phase a -> index of the low-res tap it folds into
@@ -2006,151 +1980,6 @@ __global__ __launch_bounds__(256) void pack_weight_ups2_kernel(const float* w, f
     }
 }
 
-// ---------------------------------------------------------------------------
-// Skinny 3x3 convolution, Cout <= 4 (G's last layer 128 -> 3, and D's first layer seen from its data gradient
-// 64 -> 3): 2.3 kFLOP per 512-byte pixel, i.e. HBM-bound; an MFMA tile would spend >= 90 % of its columns on
-// padding.  LP lanes share a pixel, each lane owns one channel quad (Cin = 4*LP) whose 9 x 4 x CO weights
-// (weight-gradient: accumulators) live in registers; pixel loads are coalesced float4 rows.
-// ---------------------------------------------------------------------------
-template <int CO, int LP>
-__global__ __launch_bounds__(256) void skinny_conv3x3_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                             const float* __restrict__ bias, float* __restrict__ y, int N,
-                                                             int H, int W) {
-    constexpr int Cin = 4 * LP;
-    const int sub = threadIdx.x & (LP - 1);
-    float wr[9][4][CO];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int co = 0; co < CO; ++co) wr[t][j][co] = w[((long)t * Cin + sub * 4 + j) * CO + co];
-    const long npix = (long)N * H * W;
-    const long grp0 = (blockIdx.x * 256L + threadIdx.x) / LP;
-    const long ngrp = gridDim.x * 256L / LP;
-    const long iters = (npix + ngrp - 1) / ngrp;   // uniform trip count: the shuffles below need every lane
-    for (long it = 0; it < iters; ++it) {
-        const long pix = grp0 + it * ngrp;
-        const bool live = pix < npix;
-        const unsigned pc = live ? (unsigned)pix : 0u;   // npix < 2^31 (checked by the host): 32-bit divisions
-        const unsigned row = pc / (unsigned)W;
-        const int ox = (int)(pc - row * (unsigned)W), oy = (int)(row % (unsigned)H);
-        const long n = row / (unsigned)H;
-        float acc[CO];
-#pragma unroll
-        for (int co = 0; co < CO; ++co) acc[co] = 0.f;
-        float4 v[9];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int iy = oy + t / 3 - 1, ix = ox + t % 3 - 1;
-            const bool ok = live && iy >= 0 && iy < H && ix >= 0 && ix < W;
-            const int cy = min(max(iy, 0), H - 1), cx = min(max(ix, 0), W - 1);
-            const float4 q = ld4(x + ((n * H + cy) * (long)W + cx) * Cin + sub * 4);
-            v[t] = ok ? q : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-            for (int co = 0; co < CO; ++co)
-                acc[co] += v[t].x * wr[t][0][co] + v[t].y * wr[t][1][co] + v[t].z * wr[t][2][co] + v[t].w * wr[t][3][co];
-#pragma unroll
-        for (int off = LP >> 1; off > 0; off >>= 1)
-#pragma unroll
-            for (int co = 0; co < CO; ++co) acc[co] += __shfl_down(acc[co], off, LP);
-        if (live && sub == 0) {
-#pragma unroll
-            for (int co = 0; co < CO; ++co) y[pix * CO + co] = acc[co] + (bias ? bias[co] : 0.f);
-        }
-    }
-}
-
-// weight/bias gradient partials of the same layer: part[block][(t*Cin+ci)][co], bias_part[block][co]
-template <int CO, int LP>
-__global__ __launch_bounds__(256) void skinny_wgrad3x3_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                              float* __restrict__ part, float* __restrict__ bias_part, int N,
-                                                              int H, int W, long pix_per_block) {
-    constexpr int Cin = 4 * LP, NGL = 256 / LP, PER = 36 * CO;
-    extern __shared__ float sk_sh[];   // [4 waves][LP][PER + 1]
-    const int sub = threadIdx.x & (LP - 1), gl = threadIdx.x / LP;
-    const long npix = (long)N * H * W;
-    const long p0 = blockIdx.x * pix_per_block, p1 = min(npix, p0 + pix_per_block);
-    float acc[9][4][CO];
-    float bacc[CO];
-#pragma unroll
-    for (int co = 0; co < CO; ++co) {
-        bacc[co] = 0.f;
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[t][j][co] = 0.f;
-    }
-    for (long pix = p0 + gl; pix < p1; pix += NGL) {
-        const unsigned row = (unsigned)pix / (unsigned)W;
-        const int ox = (int)((unsigned)pix - row * (unsigned)W), oy = (int)(row % (unsigned)H);
-        const long n = row / (unsigned)H;
-        float d[CO];
-#pragma unroll
-        for (int co = 0; co < CO; ++co) { d[co] = dy[pix * CO + co]; bacc[co] += d[co]; }
-        float4 v[9];
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int iy = oy + t / 3 - 1, ix = ox + t % 3 - 1;
-            const bool ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
-            const int cy = min(max(iy, 0), H - 1), cx = min(max(ix, 0), W - 1);
-            const float4 q = ld4(x + ((n * H + cy) * (long)W + cx) * Cin + sub * 4);
-            v[t] = ok ? q : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-            for (int co = 0; co < CO; ++co) {
-                acc[t][0][co] += v[t].x * d[co]; acc[t][1][co] += v[t].y * d[co];
-                acc[t][2][co] += v[t].z * d[co]; acc[t][3][co] += v[t].w * d[co];
-            }
-    }
-    // fold the pixel groups of a wave (lanes with equal sub), then the four waves through LDS
-#pragma unroll
-    for (int off = LP; off < 64; off <<= 1) {
-#pragma unroll
-        for (int co = 0; co < CO; ++co) {
-            bacc[co] += __shfl_xor(bacc[co], off, 64);
-#pragma unroll
-            for (int t = 0; t < 9; ++t)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[t][j][co] += __shfl_xor(acc[t][j][co], off, 64);
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane < LP) {
-        float* dst = sk_sh + ((long)wave * LP + sub) * (PER + CO + 1);
-#pragma unroll
-        for (int t = 0; t < 9; ++t)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int co = 0; co < CO; ++co) dst[(t * 4 + j) * CO + co] = acc[t][j][co];
-#pragma unroll
-        for (int co = 0; co < CO; ++co) dst[PER + co] = bacc[co];
-    }
-    __syncthreads();
-    float* pout = part + (long)blockIdx.x * 9 * Cin * CO;
-    for (int idx = threadIdx.x; idx < LP * PER; idx += 256) {
-        const int sb = idx / PER, r = idx % PER;           // r = (t*4+j)*CO+co
-        const int co = r % CO, tj = r / CO, t = tj >> 2, j = tj & 3;
-        float s = 0.f;
-#pragma unroll
-        for (int wv = 0; wv < 4; ++wv) s += sk_sh[((long)wv * LP + sb) * (PER + CO + 1) + r];
-        pout[((long)t * Cin + sb * 4 + j) * CO + co] = s;
-    }
-    if (bias_part && threadIdx.x < CO) {
-        float s = 0.f;
-        // every lane group saw the same dy values of its own pixels; sub == 0 of each wave holds the wave total
-#pragma unroll
-        for (int wv = 0; wv < 4; ++wv) s += sk_sh[((long)wv * LP + 0) * (PER + CO + 1) + PER + threadIdx.x];
-        bias_part[(long)blockIdx.x * CO + threadIdx.x] = s;
-    }
-}
-
 // ---- host-side dispatch -----------------------------------------------------
 struct TileCfg { int bm, bn; };
 // swept in rounds 2-5 (profiles/r0N_sweeps.txt: flat or worse around these), constants since round 6
@@ -2439,35 +2268,6 @@ static size_t tn_ws_bytes(const Geom& g, const TNPlan& p, int ngroups) {
     return (size_t)splits * ngroups * g.nphase * ((size_t)g.Ktot + 1) * g.Cout * sizeof(float);
 }
 
-// ---- skinny 3x3 path (see skinny_conv3x3_kernel) ----
-constexpr int kSkinnyWgradBlocks = 512;
-static bool skinny_ok(int ngroups, int Cin, int Cout, int kH, int kW, int padH, int padW, int ups) {
-    const bool on = cg::opt(cg::OPT_SKINNY) != 0;
-    return on && ngroups == 1 && ups == 0 && kH == 3 && kW == 3 && padH == 1 && padW == 1 && (Cout == 3 || Cout == 1) &&
-           (Cin == 64 || Cin == 128);
-}
-static size_t skinny_wgrad_ws_bytes(int Cin, int Cout) {
-    return (size_t)kSkinnyWgradBlocks * (9 * (size_t)Cin + 1) * Cout * sizeof(float);
-}
-template <int CO>
-static void skinny_forward_launch(hipStream_t st, const float* x, const float* w, const float* bias, float* y, int N, int H,
-                                  int W, int Cin) {
-    const long npix = (long)N * H * W;
-    const int lp = Cin / 4;
-    long blocks = (npix * lp + 255) / 256;
-    if (blocks > cg::kNumCU * 2) blocks = cg::kNumCU * 2;
-    if (lp == 32) hipLaunchKernelGGL((skinny_conv3x3_kernel<CO, 32>), dim3((unsigned)blocks), dim3(256), 0, st, x, w, bias, y, N, H, W);
-    else hipLaunchKernelGGL((skinny_conv3x3_kernel<CO, 16>), dim3((unsigned)blocks), dim3(256), 0, st, x, w, bias, y, N, H, W);
-}
-template <int CO>
-static void skinny_wgrad_launch(hipStream_t st, const float* x, const float* dy, float* part, float* bias_part, int N, int H,
-                                int W, int Cin, int blocks, long ppb) {
-    const int lp = Cin / 4;
-    const size_t shb = (size_t)4 * lp * (36 * CO + CO + 1) * sizeof(float);
-    if (lp == 32) hipLaunchKernelGGL((skinny_wgrad3x3_kernel<CO, 32>), dim3(blocks), dim3(256), shb, st, x, dy, part, bias_part, N, H, W, ppb);
-    else hipLaunchKernelGGL((skinny_wgrad3x3_kernel<CO, 16>), dim3(blocks), dim3(256), shb, st, x, dy, part, bias_part, N, H, W, ppb);
-}
-
 struct Epi { int act; float slope; const float* const* alpha; float* const* y_act; float* stats; };
 
 // Position-major rows with the zero-padding taps skipped (Geom::pmn): a plain stride-1 convolution whose padding is a real share of
@@ -2490,6 +2290,14 @@ static long pad_skip_valid(const Geom& g, const TileCfg& tc) {
     return (long)hw * g.ntaps * (100 - thr) >= valid * 100 ? valid : 0;
 }
 
+// the four-pointer fields of the kernel arguments (x0 .. x3 and their like: scalars, see TapDesc) from an array of n <= MAXG group pointers
+// (or none at all); the fields past n stay null
+template <typename T>
+static void set4(T& p0, T& p1, T& p2, T& p3, const T* src, int n) {
+    T* const dst[MAXG] = {&p0, &p1, &p2, &p3};
+    for (int i = 0; i < MAXG; ++i) *dst[i] = (src && i < n) ? src[i] : nullptr;
+}
+
 static int run_nn(hipStream_t st, const Geom& g, int ngroups, const float* const* x, const float* const* w,
                   const float* const* bias, float* const* y, void* ws, size_t ws_bytes, const char* who,
                   const Epi* ep = nullptr) {
@@ -2504,40 +2312,29 @@ static int run_nn(hipStream_t st, const Geom& g, int ngroups, const float* const
     CG_REQUIRE(need == 0 || (ws && ws_bytes >= need), "%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
     NNArgs a;
     memset(&a, 0, sizeof(a));
-    const float* xs[MAXG] = {nullptr, nullptr, nullptr, nullptr};
-    const float* wsv[MAXG] = {nullptr, nullptr, nullptr, nullptr};
-    const float* bs[MAXG] = {nullptr, nullptr, nullptr, nullptr};
-    float* ys[MAXG] = {nullptr, nullptr, nullptr, nullptr};
     bool al = true, alw = true;
     for (int i = 0; i < ngroups; ++i) {
         CG_REQUIRE(x[i] && w[i] && y[i], "%s: null pointer (group %d)", who, i);
-        xs[i] = x[i]; wsv[i] = w[i]; bs[i] = bias ? bias[i] : nullptr; ys[i] = y[i];
         al = al && ((uintptr_t)x[i] % 16 == 0);
         alw = alw && ((uintptr_t)w[i] % 16 == 0);
     }
-    a.x0 = xs[0]; a.x1 = xs[1]; a.x2 = xs[2]; a.x3 = xs[3];
-    a.w0 = wsv[0]; a.w1 = wsv[1]; a.w2 = wsv[2]; a.w3 = wsv[3];
-    a.b0 = bs[0]; a.b1 = bs[1]; a.b2 = bs[2]; a.b3 = bs[3];
-    a.y0 = ys[0]; a.y1 = ys[1]; a.y2 = ys[2]; a.y3 = ys[3];
+    set4(a.x0, a.x1, a.x2, a.x3, x, ngroups);
+    set4(a.w0, a.w1, a.w2, a.w3, w, ngroups);
+    set4(a.b0, a.b1, a.b2, a.b3, bias, ngroups);
+    set4(a.y0, a.y1, a.y2, a.y3, y, ngroups);
     a.part = (float*)ws; a.ngroups = ngroups; a.g = g;
     a.kchunk = p.kchunk; a.nsplit = p.splits;
     a.xcd_swizzle = (int)cg::opt(cg::OPT_XCD_SWIZZLE);
     if (ep && ep->act) {
         CG_REQUIRE(ep->act == 1 || ep->act == 2, "%s: unknown activation %d", who, ep->act);
         CG_REQUIRE(ep->y_act, "%s: fused activation needs y_act", who);
-        const float* als[MAXG] = {nullptr, nullptr, nullptr, nullptr};
-        float* zs[MAXG] = {nullptr, nullptr, nullptr, nullptr};
         for (int i = 0; i < ngroups; ++i) {
             CG_REQUIRE(ep->y_act[i], "%s: null y_act (group %d)", who, i);
-            zs[i] = ep->y_act[i];
-            if (ep->act == 1) {
-                CG_REQUIRE(ep->alpha && ep->alpha[i], "%s: PReLU epilogue needs the slope pointer (group %d)", who, i);
-                als[i] = ep->alpha[i];
-            }
+            CG_REQUIRE(ep->act != 1 || (ep->alpha && ep->alpha[i]), "%s: PReLU epilogue needs the slope pointer (group %d)", who, i);
         }
         a.act = ep->act; a.slope = ep->slope;
-        a.al0 = als[0]; a.al1 = als[1]; a.al2 = als[2]; a.al3 = als[3];
-        a.z0 = zs[0]; a.z1 = zs[1]; a.z2 = zs[2]; a.z3 = zs[3];
+        set4(a.al0, a.al1, a.al2, a.al3, ep->act == 1 ? ep->alpha : nullptr, ngroups);
+        set4(a.z0, a.z1, a.z2, a.z3, ep->y_act, ngroups);
     }
     if (ep && ep->stats) {
         CG_REQUIRE(ngroups == 1 && p.splits == 1, "%s: epilogue statistics need a single-group, unsplit launch", who);
@@ -2569,7 +2366,7 @@ static int run_nn(hipStream_t st, const Geom& g, int ngroups, const float* const
         const long PMN = (long)ngroups * g.nphase * g.M * g.Cout;
         bool v4 = g.Cout % 4 == 0 && (uintptr_t)ws % 16 == 0;
         for (int i = 0; i < ngroups; ++i)
-            v4 = v4 && (uintptr_t)ys[i] % 16 == 0 && (!bs[i] || (uintptr_t)bs[i] % 16 == 0) && (!a.act || (uintptr_t)ep->y_act[i] % 16 == 0);
+            v4 = v4 && (uintptr_t)y[i] % 16 == 0 && (!bias || (uintptr_t)bias[i] % 16 == 0) && (!a.act || (uintptr_t)ep->y_act[i] % 16 == 0);
         if ((PMN >= 256L * 1024 || p.splits < 8) && v4)
             hipLaunchKernelGGL((nn_splitk_reduce_kernel<1, true>), dim3(cg::ew_grid(PMN / 4)), dim3(256), 0, st, a, p.splits);
         else if (PMN >= 256L * 1024 || p.splits < 8)
@@ -2612,7 +2409,7 @@ size_t cg_conv2d_workspace_bytes(int N, int Hp, int Wp, int Cin, int Cout, int k
 size_t cg_conv2d_stats_rows(int N, int Hp, int Wp, int Cin, int Cout, int kH, int kW, int padH, int padW, int ups) {
     Geom g;
     if (conv_geom(g, N, Hp, Wp, Cin, Cout, kH, kW, padH, padW, ups)) return 0;
-    if (skinny_ok(1, Cin, Cout, kH, kW, padH, padW, ups)) return 0;
+    if (cg::skinny_ok(1, Cin, Cout, kH, kW, padH, padW, ups)) return 0;
     const NNPlan p = plan_nn(g, 1, false);   // run_nn launches the image-major plan whenever statistics are asked for: query THAT plan
     if (p.splits != 1) return 0;
     const int wm = p.tc.bn == 32 ? 4 : 2;
@@ -2626,7 +2423,7 @@ int cg_conv2d_forward_ex(void* stream, int ngroups, const float* const* x, const
     CG_REQUIRE(x && wpk && y, "cg_conv2d_forward_ex: null pointer");
     Geom g;
     if (conv_geom(g, N, Hp, Wp, Cin, Cout, kH, kW, padH, padW, ups)) return 1;
-    CG_REQUIRE(!skinny_ok(ngroups, Cin, Cout, kH, kW, padH, padW, ups) || (act == 0 && !stats),
+    CG_REQUIRE(!cg::skinny_ok(ngroups, Cin, Cout, kH, kW, padH, padW, ups) || (act == 0 && !stats),
                "cg_conv2d_forward_ex: no fused epilogue on the skinny (<= 4 output planes) path");
     if (act == 0 && !stats)
         return cg_conv2d_forward_grouped(stream, ngroups, x, wpk, bias, y, N, Hp, Wp, Cin, Cout, kH, kW, padH, padW, ups, ws,
@@ -2641,14 +2438,13 @@ int cg_conv2d_forward_grouped(void* stream, int ngroups, const float* const* x, 
     CG_REQUIRE(x && wpk && y, "cg_conv2d_forward_grouped: null pointer");
     Geom g;
     if (conv_geom(g, N, Hp, Wp, Cin, Cout, kH, kW, padH, padW, ups)) return 1;
-    if (skinny_ok(ngroups, Cin, Cout, kH, kW, padH, padW, ups) && x[0] && wpk[0] && y[0] && (uintptr_t)x[0] % 16 == 0 &&
+    if (cg::skinny_ok(ngroups, Cin, Cout, kH, kW, padH, padW, ups) && x[0] && wpk[0] && y[0] && (uintptr_t)x[0] % 16 == 0 &&
         (long)N * Hp * Wp < 0x7fffffffL) {
         const float* b0 = bias ? bias[0] : nullptr;
         if (cg::opt(cg::OPT_SKINNY) == 1 && cg::skinny_mfma_ok(Cin, Cout, Hp, Wp)) {
             if (cg::skinny_mfma_forward(cg::S(stream), x[0], wpk[0], b0, y[0], N, Hp, Wp, Cin, Cout)) return 1;
         }
-        else if (Cout == 3) skinny_forward_launch<3>(cg::S(stream), x[0], wpk[0], b0, y[0], N, Hp, Wp, Cin);
-        else skinny_forward_launch<1>(cg::S(stream), x[0], wpk[0], b0, y[0], N, Hp, Wp, Cin);
+        else cg::skinny_valu_forward(cg::S(stream), x[0], wpk[0], b0, y[0], N, Hp, Wp, Cin, Cout);
         CG_LAUNCH_CHECK();
         return 0;
     }
@@ -2685,7 +2481,7 @@ static size_t wgrad_ws_bytes_groups(int ngroups, int maxg, int N, int Hp, int Wp
     Geom g;
     if (ngroups < 1 || ngroups > maxg || conv_geom(g, N, Hp, Wp, Cin, Cout, kH, kW, padH, padW, ups)) return 0;
     const size_t reg = tn_ws_bytes(g, plan_tn(g, ngroups), ngroups);
-    return skinny_ok(ngroups, Cin, Cout, kH, kW, padH, padW, ups) ? std::max(reg, skinny_wgrad_ws_bytes(Cin, Cout)) : reg;
+    return cg::skinny_ok(ngroups, Cin, Cout, kH, kW, padH, padW, ups) ? std::max(reg, cg::skinny_wgrad_ws_bytes(Cin, Cout)) : reg;
 }
 // The size query doubles as the capability check of the entry point it belongs to (0 = this launch does not exist): <= MAXG groups of
 // separate tensors for cg_conv2d_wgrad_grouped / _deferred, <= kMaxStridedGroups equally spaced ones for cg_conv2d_wgrad_strided.
@@ -2768,7 +2564,7 @@ int cg_conv2d_wgrad_strided(void* stream, int ngroups, const float* x, long x_st
 int cg_conv2d_wgrad_gemm(void* stream, const float* x, const float* dy, int N, int Hp, int Wp, int Cin, int Cout, int kH, int kW, int padH,
                          int padW, int ups, void* ws, size_t ws_bytes) {
     CG_REQUIRE(x && dy && ws, "cg_conv2d_wgrad_gemm: null pointer");
-    CG_REQUIRE(!skinny_ok(1, Cin, Cout, kH, kW, padH, padW, ups), "cg_conv2d_wgrad_gemm: this geometry runs the skinny kernel, not the GEMM");
+    CG_REQUIRE(!cg::skinny_ok(1, Cin, Cout, kH, kW, padH, padW, ups), "cg_conv2d_wgrad_gemm: this geometry runs the skinny kernel, not the GEMM");
     float* gw = (float*)ws;   // never written: the reduction is skipped
     return wgrad_impl(stream, 1, &x, &dy, &gw, nullptr, N, Hp, Wp, Cin, Cout, kH, kW, padH, padW, ups, 1.f, ws, ws_bytes, false, 0, 0, 0, true);
 }
@@ -2820,22 +2616,21 @@ int wgrad_impl(void* stream, int ngroups, const float* const* x, const float* co
     memset(&a, 0, sizeof(a));
     if (conv_geom(a.g, N, Hp, Wp, Cin, Cout, kH, kW, padH, padW, ups)) return 1;
     const Geom& g = a.g;
-    if (!strided && skinny_ok(ngroups, Cin, Cout, kH, kW, padH, padW, ups) && x[0] && dy[0] && gw[0] && (uintptr_t)x[0] % 16 == 0 && ws &&
-        ws_bytes >= skinny_wgrad_ws_bytes(Cin, Cout) && (long)N * Hp * Wp < 0x7fffffffL) {
+    if (!strided && cg::skinny_ok(ngroups, Cin, Cout, kH, kW, padH, padW, ups) && x[0] && dy[0] && gw[0] && (uintptr_t)x[0] % 16 == 0 && ws &&
+        ws_bytes >= cg::skinny_wgrad_ws_bytes(Cin, Cout) && (long)N * Hp * Wp < 0x7fffffffL) {
         hipStream_t st = cg::S(stream);
         const long npix = (long)N * Hp * Wp;
-        const long ppb = (npix + kSkinnyWgradBlocks - 1) / kSkinnyWgradBlocks;
+        const long ppb = (npix + cg::kSkinnyWgradBlocks - 1) / cg::kSkinnyWgradBlocks;
         int blocks = (int)((npix + ppb - 1) / ppb);
         float* part = (float*)ws;
-        float* bpart = part + (size_t)kSkinnyWgradBlocks * 9 * Cin * Cout;
+        float* bpart = part + (size_t)cg::kSkinnyWgradBlocks * 9 * Cin * Cout;
         float* gb0 = gb ? gb[0] : nullptr;
         if (cg::opt(cg::OPT_SKINNY) == 1 && cg::skinny_mfma_ok(Cin, Cout, Hp, Wp)) {
             // 256 partial planes: the kernel itself measures the same with 512 (18.0 / 18.8 us at batch 128), the reduction behind it 18 -> 12.6 us
-            blocks = cg::skinny_mfma_wgrad(st, x[0], dy[0], part, gb0 ? bpart : nullptr, N, Hp, Wp, Cin, Cout, kSkinnyWgradBlocks / 2);
+            blocks = cg::skinny_mfma_wgrad(st, x[0], dy[0], part, gb0 ? bpart : nullptr, N, Hp, Wp, Cin, Cout, cg::kSkinnyWgradBlocks / 2);
             if (blocks < 0) return 1;
         }
-        else if (Cout == 3) skinny_wgrad_launch<3>(st, x[0], dy[0], part, gb0 ? bpart : nullptr, N, Hp, Wp, Cin, blocks, ppb);
-        else skinny_wgrad_launch<1>(st, x[0], dy[0], part, gb0 ? bpart : nullptr, N, Hp, Wp, Cin, blocks, ppb);
+        else cg::skinny_valu_wgrad(st, x[0], dy[0], part, gb0 ? bpart : nullptr, N, Hp, Wp, Cin, Cout, blocks, ppb);
         CG_LAUNCH_CHECK();
         RedJob job;
         memset(&job, 0, sizeof(job));
@@ -2854,12 +2649,10 @@ int wgrad_impl(void* stream, int ngroups, const float* const* x, const float* co
     TNPlan p = plan_tn(g, ngroups);
     const size_t need = tn_ws_bytes(g, p, ngroups);
     CG_REQUIRE(ws && ws_bytes >= need, "cg_conv2d_wgrad: workspace too small (%zu < %zu)", ws_bytes, need);
-    const float* xs[MAXG] = {nullptr, nullptr, nullptr, nullptr};
-    const float* ds[MAXG] = {nullptr, nullptr, nullptr, nullptr};
+    const int nptr = strided ? 1 : ngroups;
     bool veca = Cin % 4 == 0, vecb = Cout % 4 == 0, any_gb = false;
-    for (int i = 0; i < (strided ? 1 : ngroups); ++i) {
+    for (int i = 0; i < nptr; ++i) {
         CG_REQUIRE(x[i] && dy[i] && gw[i], "cg_conv2d_wgrad: null pointer (group %d)", i);
-        xs[i] = x[i]; ds[i] = dy[i];
         veca = veca && ((uintptr_t)x[i] % 16 == 0);
         vecb = vecb && ((uintptr_t)dy[i] % 16 == 0);
         any_gb = any_gb || (gb && gb[i]);
@@ -2867,8 +2660,8 @@ int wgrad_impl(void* stream, int ngroups, const float* const* x, const float* co
     if (strided) { veca = veca && xgs % 4 == 0; vecb = vecb && dgs % 4 == 0; }
     if (p.pm && !(veca && vecb)) p = plan_tn(g, ngroups, false);   // unaligned operands: the image-major plan (the workspace holds either)
     a.xgs = xgs; a.dgs = dgs;
-    a.x0 = xs[0]; a.x1 = xs[1]; a.x2 = xs[2]; a.x3 = xs[3];
-    a.d0 = ds[0]; a.d1 = ds[1]; a.d2 = ds[2]; a.d3 = ds[3];
+    set4(a.x0, a.x1, a.x2, a.x3, x, nptr);
+    set4(a.d0, a.d1, a.d2, a.d3, dy, nptr);
     a.ngroups = ngroups; a.part = (float*)ws; a.pchunk = p.pchunk;
     a.xcd_swizzle = (int)cg::opt(cg::OPT_XCD_SWIZZLE);
     const int ZP = ngroups * g.nphase;
@@ -2908,12 +2701,9 @@ int wgrad_impl(void* stream, int ngroups, const float* const* x, const float* co
     if ((long)rgrid.x * rgrid.y < cg::kNumCU) {
         RedJob job;
         memset(&job, 0, sizeof(job));
-        float* gws[MAXG] = {nullptr, nullptr, nullptr, nullptr};
-        float* gbs[MAXG] = {nullptr, nullptr, nullptr, nullptr};
-        for (int gi = 0; gi < (strided ? 1 : ngroups); ++gi) { gws[gi] = gw[gi]; gbs[gi] = gb ? gb[gi] : nullptr; }
         job.rp.gws = strided ? gws_ : 0;
-        job.rp.gw0 = gws[0]; job.rp.gw1 = gws[1]; job.rp.gw2 = gws[2]; job.rp.gw3 = gws[3];
-        job.rp.gb0 = gbs[0]; job.rp.gb1 = gbs[1]; job.rp.gb2 = gbs[2]; job.rp.gb3 = gbs[3];
+        set4(job.rp.gw0, job.rp.gw1, job.rp.gw2, job.rp.gw3, gw, nptr);
+        set4(job.rp.gb0, job.rp.gb1, job.rp.gb2, job.rp.gb3, gb, nptr);
         job.part = (const float*)ws; job.bias_part = a.bias_part;
         job.Cin = Cin; job.Cout = Cout; job.k = kH; job.KK = KK; job.pad = padH; job.kp = ups ? kp : 0; job.S = p.splits; job.P = g.nphase;
         job.ups = ups ? 1 : 0; job.scale = scale;

@@ -3,7 +3,7 @@
 // Stands in for cudnn.SpatialConvolution(128, C, 3, 3, 1, 1, 1, 1) (G's last layer, models.lua:222 / :154), for the data gradient of
 // nn.SpatialConvolution(C, 64, 3, 3, 1, 1, 1) (D's first layer seen from its output, models.lua:646) and for the weight gradient of the
 // former.  These layers move 512 (256) bytes per pixel for 2.3 kFLOP: HBM-bound, 67 MB per launch at batch 128.  Round 1's kernels
-// (skinny_conv3x3_kernel / skinny_wgrad3x3_kernel, gemm.hip: still the fallback for widths that are not a multiple of 32) fetched the
+// (skinny_conv3x3_kernel / skinny_wgrad3x3_kernel, at the end of this file: still the fallback for widths that are not a multiple of 32) fetched the
 // nine taps of every pixel from L2 - 9x read amplification, 0.03-0.17 of the HBM roofline.
 //
 // Scatter form: y[p][co] = sum_t Z[p + d_t][t, co]  with  Z[q][(t, co)] = sum_c x[q][c] w[t][c][co].
@@ -20,7 +20,7 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ float4 ld4g(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
 __device__ __forceinline__ void glds16(__amdgpu_buffer_rsrc_t r, float* lds, unsigned voff, int soff) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256, 2) void skinny_mfma_fwd_k(const float* __restr
 #pragma unroll
         for (int c = 0; c < NCH; ++c)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) st[c][i] = ld4g(src + (long)i * 8 * CIN + c * 32);
+            for (int i = 0; i < 4; ++i) st[c][i] = ld4(src + (long)i * 8 * CIN + c * 32);
     };
 
     float4 sa[NCH][4], sb[NCH][4];
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256, 2) void skinny_mfma_fwd_k(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// weight + bias gradient partials, the layout skinny_wgrad3x3_kernel wrote: part[block][(t * CIN + c) * CO + co], bias_part[block][co].
+// weight + bias gradient partials, the layout skinny_wgrad3x3_kernel (below) writes: part[block][(t * CIN + c) * CO + co], bias_part[block][co].
 // One workgroup walks strips of R rows of one image: dy strip (with halo, zero outside the image) -> LDS, then the strip's x rows as
 // 32-pixel stages (32 CIN consecutive floats each) by LDS-direct loads, two buffers.  Wave = (32-channel slice, K part of the stage).
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -282,9 +282,192 @@ int fwd_rows(int N, int H, int W, int Cin, int CO) {
     return std::max(want, std::min(cap, 2));
 }
 
+// ---------------------------------------------------------------------------
+// Round 1's VALU kernels (moved here from gemm.hip unchanged; cg::skinny_valu_forward / _wgrad below; gemm.hip picks the family).
+// Skinny 3x3 convolution, Cout <= 4 (G's last layer 128 -> 3, and D's first layer seen from its data gradient
+// 64 -> 3): 2.3 kFLOP per 512-byte pixel, i.e. HBM-bound; an MFMA tile would spend >= 90 % of its columns on
+// padding.  LP lanes share a pixel, each lane owns one channel quad (Cin = 4*LP) whose 9 x 4 x CO weights
+// (weight-gradient: accumulators) live in registers; pixel loads are coalesced float4 rows.
+// ---------------------------------------------------------------------------
+template <int CO, int LP>
+__global__ __launch_bounds__(256) void skinny_conv3x3_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                             const float* __restrict__ bias, float* __restrict__ y, int N,
+                                                             int H, int W) {
+    constexpr int Cin = 4 * LP;
+    const int sub = threadIdx.x & (LP - 1);
+    float wr[9][4][CO];
+#pragma unroll
+    for (int t = 0; t < 9; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int co = 0; co < CO; ++co) wr[t][j][co] = w[((long)t * Cin + sub * 4 + j) * CO + co];
+    const long npix = (long)N * H * W;
+    const long grp0 = (blockIdx.x * 256L + threadIdx.x) / LP;
+    const long ngrp = gridDim.x * 256L / LP;
+    const long iters = (npix + ngrp - 1) / ngrp;   // uniform trip count: the shuffles below need every lane
+    for (long it = 0; it < iters; ++it) {
+        const long pix = grp0 + it * ngrp;
+        const bool live = pix < npix;
+        const unsigned pc = live ? (unsigned)pix : 0u;   // npix < 2^31 (checked by the host): 32-bit divisions
+        const unsigned row = pc / (unsigned)W;
+        const int ox = (int)(pc - row * (unsigned)W), oy = (int)(row % (unsigned)H);
+        const long n = row / (unsigned)H;
+        float acc[CO];
+#pragma unroll
+        for (int co = 0; co < CO; ++co) acc[co] = 0.f;
+        float4 v[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int iy = oy + t / 3 - 1, ix = ox + t % 3 - 1;
+            const bool ok = live && iy >= 0 && iy < H && ix >= 0 && ix < W;
+            const int cy = min(max(iy, 0), H - 1), cx = min(max(ix, 0), W - 1);
+            const float4 q = ld4(x + ((n * H + cy) * (long)W + cx) * Cin + sub * 4);
+            v[t] = ok ? q : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int co = 0; co < CO; ++co)
+                acc[co] += v[t].x * wr[t][0][co] + v[t].y * wr[t][1][co] + v[t].z * wr[t][2][co] + v[t].w * wr[t][3][co];
+#pragma unroll
+        for (int off = LP >> 1; off > 0; off >>= 1)
+#pragma unroll
+            for (int co = 0; co < CO; ++co) acc[co] += __shfl_down(acc[co], off, LP);
+        if (live && sub == 0) {
+#pragma unroll
+            for (int co = 0; co < CO; ++co) y[pix * CO + co] = acc[co] + (bias ? bias[co] : 0.f);
+        }
+    }
+}
+
+// weight/bias gradient partials of the same layer: part[block][(t*Cin+ci)][co], bias_part[block][co]
+template <int CO, int LP>
+__global__ __launch_bounds__(256) void skinny_wgrad3x3_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                              float* __restrict__ part, float* __restrict__ bias_part, int N,
+                                                              int H, int W, long pix_per_block) {
+    constexpr int Cin = 4 * LP, NGL = 256 / LP, PER = 36 * CO;
+    extern __shared__ float sk_sh[];   // [4 waves][LP][PER + 1]
+    const int sub = threadIdx.x & (LP - 1), gl = threadIdx.x / LP;
+    const long npix = (long)N * H * W;
+    const long p0 = blockIdx.x * pix_per_block, p1 = min(npix, p0 + pix_per_block);
+    float acc[9][4][CO];
+    float bacc[CO];
+#pragma unroll
+    for (int co = 0; co < CO; ++co) {
+        bacc[co] = 0.f;
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[t][j][co] = 0.f;
+    }
+    for (long pix = p0 + gl; pix < p1; pix += NGL) {
+        const unsigned row = (unsigned)pix / (unsigned)W;
+        const int ox = (int)((unsigned)pix - row * (unsigned)W), oy = (int)(row % (unsigned)H);
+        const long n = row / (unsigned)H;
+        float d[CO];
+#pragma unroll
+        for (int co = 0; co < CO; ++co) { d[co] = dy[pix * CO + co]; bacc[co] += d[co]; }
+        float4 v[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) {
+            const int iy = oy + t / 3 - 1, ix = ox + t % 3 - 1;
+            const bool ok = iy >= 0 && iy < H && ix >= 0 && ix < W;
+            const int cy = min(max(iy, 0), H - 1), cx = min(max(ix, 0), W - 1);
+            const float4 q = ld4(x + ((n * H + cy) * (long)W + cx) * Cin + sub * 4);
+            v[t] = ok ? q : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int co = 0; co < CO; ++co) {
+                acc[t][0][co] += v[t].x * d[co]; acc[t][1][co] += v[t].y * d[co];
+                acc[t][2][co] += v[t].z * d[co]; acc[t][3][co] += v[t].w * d[co];
+            }
+    }
+    // fold the pixel groups of a wave (lanes with equal sub), then the four waves through LDS
+#pragma unroll
+    for (int off = LP; off < 64; off <<= 1) {
+#pragma unroll
+        for (int co = 0; co < CO; ++co) {
+            bacc[co] += __shfl_xor(bacc[co], off, 64);
+#pragma unroll
+            for (int t = 0; t < 9; ++t)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[t][j][co] += __shfl_xor(acc[t][j][co], off, 64);
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane < LP) {
+        float* dst = sk_sh + ((long)wave * LP + sub) * (PER + CO + 1);
+#pragma unroll
+        for (int t = 0; t < 9; ++t)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int co = 0; co < CO; ++co) dst[(t * 4 + j) * CO + co] = acc[t][j][co];
+#pragma unroll
+        for (int co = 0; co < CO; ++co) dst[PER + co] = bacc[co];
+    }
+    __syncthreads();
+    float* pout = part + (long)blockIdx.x * 9 * Cin * CO;
+    for (int idx = threadIdx.x; idx < LP * PER; idx += 256) {
+        const int sb = idx / PER, r = idx % PER;           // r = (t*4+j)*CO+co
+        const int co = r % CO, tj = r / CO, t = tj >> 2, j = tj & 3;
+        float s = 0.f;
+#pragma unroll
+        for (int wv = 0; wv < 4; ++wv) s += sk_sh[((long)wv * LP + sb) * (PER + CO + 1) + r];
+        pout[((long)t * Cin + sb * 4 + j) * CO + co] = s;
+    }
+    if (bias_part && threadIdx.x < CO) {
+        float s = 0.f;
+        // every lane group saw the same dy values of its own pixels; sub == 0 of each wave holds the wave total
+#pragma unroll
+        for (int wv = 0; wv < 4; ++wv) s += sk_sh[((long)wv * LP + 0) * (PER + CO + 1) + PER + threadIdx.x];
+        bias_part[(long)blockIdx.x * CO + threadIdx.x] = s;
+    }
+}
+
+template <int CO>
+static void skinny_forward_launch(hipStream_t st, const float* x, const float* w, const float* bias, float* y, int N, int H,
+                                  int W, int Cin) {
+    const long npix = (long)N * H * W;
+    const int lp = Cin / 4;
+    long blocks = (npix * lp + 255) / 256;
+    if (blocks > cg::kNumCU * 2) blocks = cg::kNumCU * 2;
+    if (lp == 32) hipLaunchKernelGGL((skinny_conv3x3_kernel<CO, 32>), dim3((unsigned)blocks), dim3(256), 0, st, x, w, bias, y, N, H, W);
+    else hipLaunchKernelGGL((skinny_conv3x3_kernel<CO, 16>), dim3((unsigned)blocks), dim3(256), 0, st, x, w, bias, y, N, H, W);
+}
+template <int CO>
+static void skinny_wgrad_launch(hipStream_t st, const float* x, const float* dy, float* part, float* bias_part, int N, int H,
+                                int W, int Cin, int blocks, long ppb) {
+    const int lp = Cin / 4;
+    const size_t shb = (size_t)4 * lp * (36 * CO + CO + 1) * sizeof(float);
+    if (lp == 32) hipLaunchKernelGGL((skinny_wgrad3x3_kernel<CO, 32>), dim3(blocks), dim3(256), shb, st, x, dy, part, bias_part, N, H, W, ppb);
+    else hipLaunchKernelGGL((skinny_wgrad3x3_kernel<CO, 16>), dim3(blocks), dim3(256), shb, st, x, dy, part, bias_part, N, H, W, ppb);
+}
+
 }  // namespace
 
 namespace cg {
+
+bool skinny_ok(int ngroups, int Cin, int Cout, int kH, int kW, int padH, int padW, int ups) {
+    const bool on = cg::opt(cg::OPT_SKINNY) != 0;
+    return on && ngroups == 1 && ups == 0 && kH == 3 && kW == 3 && padH == 1 && padW == 1 && (Cout == 3 || Cout == 1) &&
+           (Cin == 64 || Cin == 128);
+}
+size_t skinny_wgrad_ws_bytes(int Cin, int Cout) {
+    return (size_t)kSkinnyWgradBlocks * (9 * (size_t)Cin + 1) * Cout * sizeof(float);
+}
+void skinny_valu_forward(hipStream_t st, const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cin, int Cout) {
+    if (Cout == 3) skinny_forward_launch<3>(st, x, w, bias, y, N, H, W, Cin);
+    else skinny_forward_launch<1>(st, x, w, bias, y, N, H, W, Cin);
+}
+void skinny_valu_wgrad(hipStream_t st, const float* x, const float* dy, float* part, float* bias_part, int N, int H, int W, int Cin, int Cout,
+                       int blocks, long ppb) {
+    if (Cout == 3) skinny_wgrad_launch<3>(st, x, dy, part, bias_part, N, H, W, Cin, blocks, ppb);
+    else skinny_wgrad_launch<1>(st, x, dy, part, bias_part, N, H, W, Cin, blocks, ppb);
+}
 
 bool skinny_mfma_ok(int Cin, int Cout, int H, int W) {
     if (!((Cin == 64 || Cin == 128) && (Cout == 1 || Cout == 3) && W % 32 == 0 && W <= 128 && H >= 1)) return false;

@@ -1,5 +1,6 @@
 """What several test modules share (a plain module, imported as tests/plan_trace.py is): the two measures of the parity tests, the
-per-tensor gradient rule, the JPEG directory of the loader tests, and the torch fp64 twin of an engine nn.Sequential."""
+`options` context that forces dispatch tunables, the per-tensor gradient rule, the JPEG directory of the loader tests, and the torch fp64
+twin of an engine nn.Sequential."""
 import os
 
 import numpy as np
@@ -15,6 +16,21 @@ def close(a, b, K=1024, tol=2e-5, what=""):
     assert np.isfinite(a).all(), f"{what}: non-finite values"
     assert err <= tol * s, f"{what}: max|d|={err:.3e} > {tol * s:.3e} (K={K})"
     return err
+
+
+class options:
+    """with options(cg, CG_NN_TILE=128064, ...): force dispatch tunables through the C ABI, restore afterwards."""
+
+    def __init__(self, cg, **kv):
+        self.cg, self.kv = cg, kv
+
+    def __enter__(self):
+        for k, v in self.kv.items():
+            self.cg.lib().set_option(k.encode(), int(v))
+
+    def __exit__(self, *exc):
+        for k in self.kv:
+            self.cg.lib().set_option(k.encode(), -1)
 
 
 def bulk_close(a, b, max_rel=3e-2, mean_rel=2e-3, what=""):

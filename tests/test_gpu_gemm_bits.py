@@ -1,0 +1,212 @@
+"""Bit-for-bit pins of the implicit-GEMM kernels of csrc/gemm.hip and of the VALU skinny kernels of csrc/skinny.hip.
+
+The four GEMM kernels (igemm_nn / igemm_nng / igemm_tn / igemm_tng) share their epilogues, their tile decode and their host-side
+argument packing; a restructuring of those must not move a single bit.  Every case below forces ONE branch of the shared code through
+`cg_set_option` (reset afterwards), runs a small layer forward and backward on fixed inputs and takes one sha256 over the raw bytes of
+output, gradInput, gradWeight and gradBias.  tests/golden/gemm_bits.json holds the digests, RECORDED ON A BUILD OF THE COMMIT BEFORE THE
+RESTRUCTURING by this same file:
+
+    CG_GEMM_BITS_RECORD=<file.json> pytest tests/test_gpu_gemm_bits.py      # writes the digests instead of comparing them
+
+Nothing here compares with a reference implementation - the oracle-compared parity of the same shapes is tests/test_gpu_parity_full.py.
+"""
+import hashlib
+import importlib
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from helpers import options
+
+pytestmark = pytest.mark.gpu
+f32 = np.float32
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemm_bits.json")
+RECORD = os.environ.get("CG_GEMM_BITS_RECORD")
+_recorded = {}
+
+
+@pytest.fixture(scope="module")
+def cg():
+    mod = importlib.import_module("cat-generator_amd")
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    mod.lib()
+    yield mod
+    if RECORD:
+        with open(RECORD, "w") as f:
+            json.dump(_recorded, f, indent=1, sort_keys=True)
+            f.write("\n")
+
+
+@pytest.fixture(scope="module")
+def golden():
+    if RECORD:
+        return {}
+    with open(GOLDEN) as f:
+        return json.load(f)
+
+
+def check(golden, case, *arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        a = np.ascontiguousarray(a, dtype=f32)
+        assert np.isfinite(a).all() and np.abs(a).max() > 0, f"{case}: an all-zero or non-finite tensor pins nothing"
+        h.update(a.tobytes())
+    digest = h.hexdigest()
+    print(f"{case}: sha256 {digest}")
+    if RECORD:
+        _recorded[case] = digest
+        return
+    assert case in golden, f"{case}: no digest in {GOLDEN}"
+    assert digest == golden[case], f"{case}: output / gradInput / gradWeight / gradBias differ from the recorded bits"
+
+
+# the two staging families (register staging / LDS-direct loads) of the NN and TN kernels
+FAMILIES = {"regs": dict(CG_NN_GLDS=0, CG_TN_GLDS=0), "glds": dict(CG_NN_GLDS=3, CG_TN_GLDS=1)}
+NO_OTHER = dict(CG_SKINNY=0, CG_WINO3=0)      # keep the skinny and the fused-Winograd kernels out of the way
+
+
+def conv_bits(cg, N, Cin, H, W, Cout, k, ups, seed):
+    """One SpatialConvolution (optionally behind the lazy 2x upsampling), forward and backward on fixed inputs."""
+    rs = np.random.RandomState(seed)
+    pad = (k - 1) // 2
+    cg.nn.SpatialConvolution.winograd = False
+    try:
+        m = cg.nn.SpatialConvolution(Cin, Cout, k, k, 1, 1, pad)
+        m.weight.copy((rs.randn(Cout, Cin, k, k) / np.sqrt(Cin * k * k)).astype(f32))
+        m.bias.copy(rs.randn(Cout).astype(f32))
+        xin = cg.Tensor.from_numpy(rs.randn(N, Cin, H, W).astype(f32))
+        if ups:
+            up = cg.nn.SpatialUpSamplingNearest(2)
+            xin = up.forward(xin)
+        y = m.forward(xin).numpy().copy()
+        dy = rs.randn(*y.shape).astype(f32)
+        m.gradWeight.zero(); m.gradBias.zero()
+        gi = m.backward(xin, cg.Tensor.from_numpy(dy))
+        if ups:
+            gi = up.updateGradInput(None, gi)
+        return y, gi.numpy().copy(), m.gradWeight.numpy().copy(), m.gradBias.numpy().copy()
+    finally:
+        cg.nn.SpatialConvolution.winograd = True
+
+
+# (N, Cin, H, W, Cout, k, ups): H, W are the convolution's input dims before the folded upsampling
+TAILS = {
+    "ragged generic tail": (3, 64, 10, 6, 72, 3, 0),            # M = 180, Cout = 72: no full tile anywhere
+    "lean consecutive tail": (4, 64, 16, 16, 128, 3, 0),        # M = 1024, Cout = 128: full tiles, consecutive rows
+    "strided tail, four phases": (2, 32, 8, 8, 128, 3, 1),      # lean strided stores in the LDS-direct family, generic in the other
+    "strided tail, 3x5 grid": (3, 16, 3, 5, 8, 3, 1),           # no power-of-two grid: the pixel decode by division
+}
+
+
+@pytest.mark.parametrize("splits", [1, 3])
+@pytest.mark.parametrize("family", list(FAMILIES))
+@pytest.mark.parametrize("tail", list(TAILS))
+def test_store_tails(cg, golden, tail, family, splits):
+    """Unsplit (one forced split: the value 0 would leave the count to the plan, which splits the first two shapes four ways) the NN
+    epilogue adds the bias and stores the output itself; with three forced splits it stores partials and the reduce kernels finish."""
+    with options(cg, CG_NN_SPLITS=splits, CG_TN_SPLITS=splits, **FAMILIES[family], **NO_OTHER):
+        check(golden, f"{tail} / {family} / splits {splits}", *conv_bits(cg, *TAILS[tail], seed=len(tail)))
+
+
+def planned_bits(cg, build, x, fusion, seed):
+    """A small nn.Sequential through the planned executor: output, gradInput and the flat gradient (weights and biases)."""
+    cg.manual_seed(seed)
+    net = build()
+    p, g = net.getParameters()
+    rs = np.random.RandomState(seed)
+    p.copy(p.numpy() + (rs.randn(p.nElement()) * 0.01).astype(f32))
+    xin = cg.nn.as_nhwc(cg.Tensor.from_numpy(x))
+    pn = net._planned_net()
+    assert pn is not None
+    cg.lib().net_set_option(pn.h, b"fusion", int(fusion))
+    y = cg.nn.as_plain(net.forward(xin)).numpy().copy()
+    assert net._planned_last
+    dy = cg.Tensor.from_numpy(rs.randn(*y.shape).astype(f32))
+    g.zero()
+    gi = cg.nn.as_plain(net.backward(xin, dy)).numpy().copy()
+    return (y, gi, g.numpy().copy()), pn.stats()["launches_forward"]
+
+
+def _act_net(cg):
+    net = cg.nn.Sequential()
+    net.add(cg.nn.SpatialConvolution(64, 64, 3, 3, 1, 1, 1)); net.add(cg.nn.PReLU(None, None, True))
+    net.add(cg.nn.SpatialConvolution(64, 128, 3, 3, 1, 1, 1)); net.add(cg.nn.LeakyReLU(0.2))
+    return net
+
+
+def _stats_net(cg, planes=128):
+    net = cg.nn.Sequential()
+    net.add(cg.nn.SpatialUpSamplingNearest(2)); net.add(cg.nn.SpatialConvolution(64, planes, 3, 3, 1, 1, 1))
+    net.add(cg.nn.SpatialBatchNormalization(planes)); net.add(cg.nn.PReLU(None, None, True))
+    return net
+
+
+EPILOGUE_NETS = {"activation": (_act_net, 16), "statistics": (_stats_net, 8), "statistics, 64 planes": (lambda cg: _stats_net(cg, 64), 8)}
+
+
+@pytest.mark.parametrize("fusion", [1, 0], ids=["fused", "unfused"])
+@pytest.mark.parametrize("family", list(FAMILIES))
+@pytest.mark.parametrize("which", list(EPILOGUE_NETS))
+def test_epilogue_with_activation_and_with_statistics(cg, golden, which, family, fusion):
+    """conv -> PReLU, conv -> LeakyReLU (the activation in the GEMM's epilogue, two outputs) and upsample -> conv -> batch norm -> PReLU (the
+    batch-norm column sums in the epilogue of the four phase GEMMs; 128 planes = 64-column wave tiles, 64 planes = 32-column ones, whose
+    sums of squares are formed differently) at N = 4, unsplit: a split launch leaves both to its reduce kernel.  The fused leg must really
+    have folded the modules into the GEMM launches: its forward plan is shorter than the unfused one, whose bits it shares."""
+    build, hw = EPILOGUE_NETS[which]
+    x = np.random.RandomState(5).randn(4, 64, hw, hw).astype(f32)
+    with options(cg, CG_NN_SPLITS=1, **FAMILIES[family], **NO_OTHER):
+        bits, launches = planned_bits(cg, lambda: build(cg), x, fusion, seed=3)
+        if fusion:
+            _, unfused = planned_bits(cg, lambda: build(cg), x, 0, seed=3)
+            print(f"epilogue {which} / {family}: {launches} forward launches fused, {unfused} unfused")
+            assert launches < unfused, f"{which}: nothing was folded into the GEMM's epilogue ({launches} launches against {unfused})"
+        check(golden, f"epilogue {which} / {family} / fusion {fusion}", *bits)
+
+
+@pytest.mark.parametrize("splits", [1, 3])
+@pytest.mark.parametrize("shape", [(64, 128, 8, 128, 7), (64, 32, 4, 64, 5)])
+def test_position_major_rows_and_k_tiles(cg, golden, shape, splits):
+    """igemm_nng_kernel<..., PM> (forward, data gradient) and igemm_tng_kernel mode 2 (weight gradient): unsplit the NN kernel stores
+    through its position-major lean path, split its partials take the consecutive one."""
+    N, Cin, H, Cout, k = shape
+    with options(cg, CG_PAD_SKIP=1, CG_NN_TILE=64000 + (128 if Cout >= 128 else 64), CG_NN_SPLITS=splits, CG_TN_SPLITS=splits, **NO_OTHER):
+        check(golden, f"position-major {shape} / splits {splits}", *conv_bits(cg, N, Cin, H, H, Cout, k, 0, seed=5 + k))
+
+
+@pytest.mark.parametrize("N,i,o", [(64, 1024, 64), (5, 64, 4)])
+def test_flat_tn_mode(cg, golden, N, i, o):
+    """nn.Linear: the weight gradient is igemm_tng_kernel's flat mode at N = 64 and the register-staged kernel on the ragged N = 5."""
+    rs = np.random.RandomState(N + i + o)
+    m = cg.nn.Linear(i, o)
+    m.weight.copy((rs.randn(o, i) / np.sqrt(i)).astype(f32)); m.bias.copy(rs.randn(o).astype(f32))
+    x = cg.Tensor.from_numpy(rs.randn(N, i).astype(f32))
+    y = m.forward(x).numpy().copy()
+    m.gradWeight.zero(); m.gradBias.zero()
+    gi = m.backward(x, cg.Tensor.from_numpy(rs.randn(N, o).astype(f32))).numpy().copy()
+    check(golden, f"linear {N} x {i} -> {o}", y, gi, m.gradWeight.numpy(), m.gradBias.numpy())
+
+
+@pytest.mark.parametrize("splits", [0, 1])
+def test_grouped_launch(cg, golden, splits):
+    """Three structurally identical conv 64 -> 64 -> PReLU branches under nn.Concat run as ONE grouped launch (blockIdx.z = branch):
+    the four-pointer fields of the kernel arguments, with the plan's own split and unsplit (activation in the epilogue)."""
+    def build():
+        net = cg.nn.Sequential()
+        cat = cg.nn.Concat(2)
+        for _ in range(3):
+            cat.add(cg.nn.Sequential().add(cg.nn.SpatialConvolution(64, 64, 3, 3, 1, 1, 1)).add(cg.nn.PReLU()))
+        return net.add(cat)
+    x = np.random.RandomState(12).randn(2, 64, 16, 16).astype(f32)
+    with options(cg, CG_NN_SPLITS=splits, **NO_OTHER):
+        check(golden, f"grouped branches / splits {splits}", *planned_bits(cg, build, x, 1, seed=12)[0])
+
+
+@pytest.mark.parametrize("shape", [(2, 128, 32, 32, 3), (2, 64, 8, 8, 1)])
+def test_valu_skinny_kernels(cg, golden, shape):
+    """skinny_conv3x3_kernel / skinny_wgrad3x3_kernel (CG_SKINNY = 2: the VALU family wherever a skinny layer runs)."""
+    N, Cin, H, W, Cout = shape
+    with options(cg, CG_SKINNY=2):
+        check(golden, f"skinny valu {shape}", *conv_bits(cg, N, Cin, H, W, Cout, 3, 0, seed=N + Cin + H + W + Cout))

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import close
+from helpers import close, options
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -31,21 +31,6 @@ def cg():
     assert torch.cuda.is_available(), "these tests need the MI355X"
     mod.lib()
     return mod
-
-
-class options:
-    """with options(cg, CG_NN_TILE=128064, ...): force dispatch tunables through the C ABI, restore afterwards."""
-
-    def __init__(self, cg, **kv):
-        self.cg, self.kv = cg, kv
-
-    def __enter__(self):
-        for k, v in self.kv.items():
-            self.cg.lib().set_option(k.encode(), int(v))
-
-    def __exit__(self, *exc):
-        for k in self.kv:
-            self.cg.lib().set_option(k.encode(), -1)
 
 
 def run_conv(cg, N, Cin, H, W, Cout, k, ups, seed=0, wino=True, check_dgrad=True):
@@ -144,7 +129,7 @@ def test_conv_layer_at_benchmarked_batch(cg, name, N, Cin, H, W, Cout, k, ups):
 
 
 # (N, Cin, H, W, Cout): 3x3 layers with <= 3 planes on ONE side.  Cout <= 3: forward + weight gradient run the skinny kernels
-# (csrc/skinny.hip on the MFMA for widths % 32 == 0, gemm.hip's VALU kernels otherwise / with CG_SKINNY=2); Cin <= 3: the DATA gradient
+# (csrc/skinny.hip on the MFMA for widths % 32 == 0, the same file's VALU kernels otherwise / with CG_SKINNY=2); Cin <= 3: the DATA gradient
 # does (D's first layer seen from its output, models.lua:646).  Batches that are not a multiple of 8 (block -> image map), heights that
 # are not a multiple of the strip, every compiled (planes, width) combination, a width the MFMA path refuses (8, 40).
 SKINNY_CASES = [(3, 128, 32, 32, 3), (9, 64, 40, 32, 3), (2, 128, 64, 64, 3), (16, 128, 32, 32, 1), (2, 64, 24, 96, 1), (5, 128, 6, 128, 3),
