@@ -58,9 +58,13 @@ constexpr int kEwWgsPerCU = 4, kColReduceWgsPerCU = 1;
 // else the built-in value; cg_set_option overrides both at run time (tests force every kernel variant this way).
 enum Opt {
     OPT_SKINNY, OPT_GEMM_BK32, OPT_WINO_BK, OPT_NN_TILE, OPT_TN_TILE, OPT_NN_SPLITS, OPT_TN_SPLITS,
-    OPT_XCD_SWIZZLE, OPT_NN_GLDS, OPT_TN_GLDS, OPT_WINO_GLDS, OPT_PAD_SKIP, OPT_WINO3, OPT_COUNT
+    OPT_XCD_SWIZZLE, OPT_NN_GLDS, OPT_TN_GLDS, OPT_WINO_GLDS, OPT_PAD_SKIP, OPT_WINO3, OPT_WINO_DGRAD_FUSE, OPT_WINO_DGRAD_FUSE_LAUNCHES,
+    OPT_COUNT
 };
 long opt(Opt o);
+// CG_WINO_DGRAD_FUSE_LAUNCHES is not a tunable but a counter kept in the same table (cg_get_option reads it, cg_set_option resets it):
+// the launches of wino_dgrad_fused_kernel (winograd.hip), so that a test can tell that the fused path ran and not its fallback.
+void opt_count(Opt o);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
@@ -123,6 +127,19 @@ static inline int ew_grid(long n, int per_block = 256) {
 }
 
 // ---- device-side helpers -------------------------------------------------
+// The fused-transform Winograd kernels (wino3.hip, wino_dgrad_fused_kernel in winograd.hip) read their A operand from an LDS patch with
+// ds_read_b128, which the LDS serves in 16-lane groups {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} (+32).  Row i of an MFMA tile (= lane & 31
+// of the A operand) -> output tile (ty, tx) of a 4 x 8 block, ty = result >> 3, tx = result & 7: the first group takes tile rows 0, 1, the
+// second 2, 3, so that a group covers two whole tile rows.
+constexpr int tile_of_row_c(int l) {
+    return ((l < 4 || (l >= 12 && l < 16) || (l >= 20 && l < 28)) ? 0 : 16) +
+           ((l < 4 || (l >= 12 && l < 16) || (l >= 20 && l < 28)) ? (l < 4 ? l : (l < 16 ? l - 8 : l - 12)) : (l < 12 ? l - 4 : (l < 20 ? l - 8 : l - 16)));
+}
+__device__ __forceinline__ int tile_of_row(int l) {
+    const bool ga = l < 4 || (l >= 12 && l < 16) || (l >= 20 && l < 28);
+    const int rank = ga ? (l < 4 ? l : (l < 16 ? l - 8 : l - 12)) : (l < 12 ? l - 4 : (l < 20 ? l - 8 : l - 16));
+    return (ga ? 0 : 16) + rank;
+}
 // the engine's counter-based generator: splitmix64 of (seed, counter), 24-bit mantissa uniform in [0,1)
 // (host twin tensor.SplitMix, oracle twin orc_rng_u01)
 __device__ __forceinline__ float u01(uint64_t seed, uint64_t ctr) {

@@ -62,17 +62,8 @@ __global__ void wino3_pack_k(PackJobs jobs) {
     }
 }
 
-// row i of an MFMA tile (= lane & 31 of the A operand) -> output tile (ty, tx) of the 4 x 8 block: ty = result >> 3, tx = result & 7.
-// The 16-lane groups of ds_read_b128 are lanes {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} (+32): the first takes tile rows 0, 1, the second 2, 3
-constexpr int tile_of_row_c(int l) {
-    return ((l < 4 || (l >= 12 && l < 16) || (l >= 20 && l < 28)) ? 0 : 16) +
-           ((l < 4 || (l >= 12 && l < 16) || (l >= 20 && l < 28)) ? (l < 4 ? l : (l < 16 ? l - 8 : l - 12)) : (l < 12 ? l - 4 : (l < 20 ? l - 8 : l - 16)));
-}
-__device__ __forceinline__ int tile_of_row(int l) {
-    const bool ga = l < 4 || (l >= 12 && l < 16) || (l >= 20 && l < 28);
-    const int rank = ga ? (l < 4 ? l : (l < 16 ? l - 8 : l - 12)) : (l < 12 ? l - 4 : (l < 20 ? l - 8 : l - 16));
-    return (ga ? 0 : 16) + rank;
-}
+using cg::tile_of_row;     // lane -> tile permutation of the ds_read_b128 lane groups (common.h)
+using cg::tile_of_row_c;
 
 template <int XI>
 __device__ __forceinline__ void wino_row(const float* P, int tyl, int txl, int h, __amdgpu_buffer_rsrc_t rsU, unsigned uvoff, f32x16 (&T)[2]) {

@@ -656,6 +656,254 @@ __global__ __launch_bounds__(512, 4) void wino_gemm_g_kernel(WinoArgs a) {
 }
 
 // ---------------------------------------------------------------------------
+// The data gradient's 16 GEMMs with the input transform fused in: V is never written.  The unfused pair writes V = 16 T 4Cout floats (268 MB
+// on G's 256 -> 128 layer at batch 128) and reads it straight back; nothing else ever reads it.  Here the A operand is formed from dy:
+//   workgroup = an 8 x 8 block of tiles of one image (64 GEMM rows) x 64 columns of dx_lo.  K = 4 Cout walks the four phase sub-lattices of
+//               dy side by side in steps of 32 planes: the block's 18 x 18 pixel patch of the phase lattice (zero outside the image, the
+//               border rule of wino_input_transform_kernel<1>) x 32 planes = one full 128-byte line per pixel goes to LDS by LDS-direct
+//               loads, double buffered (2 x 41 KB), and U [16 positions][8 k][64 columns] in sub-steps of 8 k (2 x 32 KB).
+//   wave      = ONE row xy of the 4 x 4 positions x one half (32 tiles) of the block, all 64 columns (the structure of wino3.hip): per 8 k
+//               eight ds_read_b128 bring rows I1, I2 of B^T's row xy, e = d[I1] -+ d[I2] is shared by the row's four positions,
+//               v[nu] = e[J1] -+ e[J2] in wino_input_transform_kernel's operation order (a V element has the bits it has there), and
+//               32 v_mfma_f32_32x32x2_f32 (4 positions x 2 column tiles x 4 k pairs) follow on eight accumulators that live through all of
+//               K: 32 VALU per 32 MFMAs.  Every product is added in wino_gemm_g_kernel's order, in the K loop and in the output
+//               transform (the four rows' waves hand the running sums on through LDS): dx_lo has the unfused pair's bits.
+//   LDS image : a patch row holds its even pixel columns first, then the odd ones, 8 plane quads per pixel XORed with
+//               ((px >> 2) & 3) * 2 + ((py >> 1) & 1); with the lanes -> tiles permutation of tile_of_row a 16-lane group of
+//               ds_read_b128 (two tile rows x eight tile columns, one plane quad) touches 16 distinct 16-byte slots.  The swizzle is
+//               applied to the SOURCE address of the LDS-direct loads, the LDS side of one wave instruction is 1 KB of consecutive slots.
+// grid = N * ceil(tH/8) * ceil(tW/8) * Nc/64 workgroups of 512 threads, one per CU (150 KB of LDS, 2 waves per SIMD).
+// ---------------------------------------------------------------------------
+struct WinoFusedArgs {
+    const float* dy;     // [N][2 Hl][2 Wl][Cs], Hl = 2 tH, Wl = 2 tW
+    const float* U;      // [16][K][Nc], K = 4 Cs
+    float* y;            // dx_lo [N][Hl][Wl][Nc]
+    int N, tH, tW, Cs, K, Nc;
+    int bH, bW;          // 8 x 8 tile blocks per image
+    int xcd;             // the column blocks of one tile block on ONE XCD (they share the patch), see wino_gemm_kernel
+};
+constexpr int kFusedPatchSlots = 18 * 18 * 8;                       // 16-byte slots of a patch: pixels x plane quads
+constexpr int kFusedPatchInstr = (kFusedPatchSlots + 63) / 64;      // wave instructions of 64 slots (the last one half empty: zeros)
+constexpr int kFusedPatchFloats = kFusedPatchInstr * 64 * 4;
+constexpr int kFusedUFloats = 16 * 8 * 64;
+
+__device__ __forceinline__ int fused_pidx(int px) { return (px >> 1) + 9 * (px & 1); }
+__device__ __forceinline__ int fused_swz(int py, int px) { return (((px >> 2) & 3) << 1) | ((py >> 1) & 1); }
+
+__global__ __launch_bounds__(512, 2) void wino_dgrad_fused_kernel(WinoFusedArgs a) {
+    // four arrays, not one: the compiler must see that an LDS-direct load into one buffer does not feed the reads of the other
+    __shared__ __attribute__((aligned(16))) float P0[kFusedPatchFloats];
+    __shared__ __attribute__((aligned(16))) float P1[kFusedPatchFloats];
+    __shared__ __attribute__((aligned(16))) float U0[kFusedUFloats];
+    __shared__ __attribute__((aligned(16))) float U1[kFusedUFloats];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 31, h = lane >> 5;
+    const int xy = wave & 3, mh = wave >> 2;
+    const int Hl = 2 * a.tH, Wl = 2 * a.tW;
+    const int ncb = a.Nc >> 6, nblk = a.N * a.bH * a.bW;
+    int cb = blockIdx.x % ncb, blk = blockIdx.x / ncb;
+    if (a.xcd && (nblk & 7) == 0) {
+        const int slot = blockIdx.x >> 3;
+        cb = slot % ncb;
+        blk = (slot / ncb) * 8 + (blockIdx.x & 7);
+    }
+    const int bx = blk % a.bW, by = (blk / a.bW) % a.bH, n = blk / (a.bW * a.bH);
+    const int ty0 = by * 8, tx0 = bx * 8, n0 = cb * 64;
+
+    // ---- staging.  dy: one buffer per image (host: below 2 GB); the phase and the plane offset of a K step are the SGPR offset, a lane's
+    // pixel and plane quad its VGPR offset, fixed for the whole launch; a pixel outside the image is an out-of-range offset (-> 0)
+    const unsigned img_bytes = (unsigned)(4 * Hl * Wl * a.Cs) * 4u;
+    const __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc((void*)(a.dy + (long)n * 4 * Hl * Wl * a.Cs), 0, img_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsu = __builtin_amdgcn_make_buffer_rsrc((void*)a.U, 0, 0x7fffffff, 0x00020000);
+    constexpr int PJ = (kFusedPatchInstr + 7) / 8;     // patch instructions per wave: instruction wave + 8 jj
+    unsigned pvoff[PJ];
+#pragma unroll
+    for (int jj = 0; jj < PJ; ++jj) {
+        const int slot = (wave + 8 * jj) * 64 + lane;
+        const int pi = slot >> 3, py = pi / 18, pxi = pi - py * 18;
+        const int px = pxi < 9 ? 2 * pxi : 2 * (pxi - 9) + 1;
+        const int q = (slot & 7) ^ fused_swz(py, px);
+        const int iy = 2 * ty0 - 1 + py, ix = 2 * tx0 - 1 + px;
+        const bool in = slot < kFusedPatchSlots && iy >= 0 && iy < Hl && ix >= 0 && ix < Wl;
+        pvoff[jj] = in ? (unsigned)(((2 * iy * 2 * Wl + 2 * ix) * a.Cs + 4 * q) * 4) : 0x80000000u;
+    }
+    unsigned uvoff[4];      // U: wave instruction wave * 4 + i = (position, k half), lanes = 4 k rows x 16 column quads
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int idx = wave * 4 + i, pos = idx >> 1, kh = idx & 1;
+        uvoff[i] = (unsigned)(((pos * a.K + kh * 4 + (lane >> 4)) * a.Nc + n0 + 4 * (lane & 15)) * 4);
+    }
+    // part PART (0..3) of the patch of K step kp into buffer PB: instructions jj = 0, 1 | 2, 3 | 4 | 5 of this wave
+    auto dma_patch = [&](auto pbc, auto partc, int kp) {
+        constexpr int PB = decltype(pbc)::value, PART = decltype(partc)::value;
+        constexpr int J0 = PART == 0 ? 0 : (PART == 1 ? 2 : (PART == 2 ? 4 : 5)), J1 = PART == 0 ? 2 : (PART == 1 ? 4 : (PART == 2 ? 5 : 6));
+        const int k0 = kp * 32, p = k0 / a.Cs, cs0 = k0 - p * a.Cs;
+        const int soff = (((p >> 1) * 2 * Wl + (p & 1)) * a.Cs + cs0) * 4;
+#pragma unroll
+        for (int jj = J0; jj < J1 && jj < PJ; ++jj)
+            if (wave + 8 * jj < kFusedPatchInstr) wino_glds16(rsd, (PB ? P1 : P0) + (wave + 8 * jj) * 256, pvoff[jj], soff);
+    };
+    auto dma_u = [&](auto ubc, int k) {       // the 8 K rows from k on, all 16 positions
+        constexpr int UB = decltype(ubc)::value;
+        const int soff = k * a.Nc * 4;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) wino_glds16(rsu, (UB ? U1 : U0) + (wave * 4 + i) * 256, uvoff[i], soff);
+    };
+
+    // ---- fragments: the wave's row xy of B^T takes patch rows I1 -+ I2 (0: d0 - d2, 1: d1 + d2, 2: d2 - d1, 3: d1 - d3)
+    const int I1 = xy == 0 ? 0 : (xy == 2 ? 2 : 1), I2 = xy == 0 ? 2 : (xy == 1 ? 2 : (xy == 2 ? 1 : 3));
+    const int tl = cg::tile_of_row(j), tyl = (tl >> 3) + 4 * mh, txl = tl & 7;
+    int pa_rd[2][4];        // byte address in a patch buffer of (row I1 / I2, column c), plane quad h; K sub-step s: ^ (s << 5)
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int py = 2 * tyl + (rr ? I2 : I1), px = 2 * txl + c;
+            pa_rd[rr][c] = ((py * 18 + fused_pidx(px)) * 8 + (h ^ fused_swz(py, px))) * 16;
+        }
+    const float sgn = xy == 1 ? 1.f : -1.f;      // e = d[I1] + sgn * d[I2]: the product is exact, the sum has the bits of the plain + / -
+    const int ub_rd = xy * 4 * 512 + h * 4 * 64 + j;     // U fragment: + nu * 512 + comp * 64 + ni * 32
+
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int nu = 0; nu < 4; ++nu)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[nu][ni][r] = 0.f;
+
+    using I0c = std::integral_constant<int, 0>;
+    using I1c = std::integral_constant<int, 1>;
+    using I2c = std::integral_constant<int, 2>;
+    using I3c = std::integral_constant<int, 3>;
+    const int KP = CG_PROBE_HALF(4, a.K / 32);      // K steps of 32 planes, even (host: K % 512 == 0)
+    dma_patch(I0c{}, I0c{}, 0); dma_patch(I0c{}, I1c{}, 0); dma_patch(I0c{}, I2c{}, 0); dma_patch(I0c{}, I3c{}, 0);
+    dma_u(I0c{}, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    // K sub-step S (8 planes) of K step kp from patch buffer PB and U buffer S & 1; requests the next sub-step's U and a part of the next patch
+    auto sub_step = [&](auto pbc, auto sc, int kp) {
+        constexpr int PB = decltype(pbc)::value, S = decltype(sc)::value;
+        const bool more_p = kp + 1 < KP;
+        if (more_p) dma_patch(std::integral_constant<int, PB ^ 1>{}, sc, kp + 1);
+        if (S < 3 || more_p) dma_u(std::integral_constant<int, (S & 1) ^ 1>{}, kp * 32 + 8 * S + 8);
+        const char* P = reinterpret_cast<const char*>(PB ? P1 : P0);
+        const float* B = ((S & 1) ? U1 : U0) + ub_rd;
+        // MFMA (S, comp) contracts planes 8 S + comp (lane half 0) and 8 S + 4 + comp (lane half 1) and rotates over the eight accumulators.
+        // Software-pipelined by hand: the U fragments and the A values of k pair comp + 1 are requested / formed before the MFMAs of k pair
+        // comp are issued (left to itself the compiler reads every U pair right in front of its two MFMAs: same time alone, but the step
+        // gained nothing - profiles/wino_dgrad_fused.txt)
+        float4 d1[4], d2[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            d1[c] = *reinterpret_cast<const float4*>(P + (pa_rd[0][c] ^ (S << 5)));
+            d2[c] = *reinterpret_cast<const float4*>(P + (pa_rd[1][c] ^ (S << 5)));
+        }
+        auto frag = [&](int comp, float (&o)[4]) {     // e = d[I1] -+ d[I2] per patch column, then B's columns: e0 - e2, e1 + e2, e2 - e1, e1 - e3
+            float e[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) e[c] = __builtin_fmaf(sgn, wf4c(d2[c], comp), wf4c(d1[c], comp));
+            o[0] = e[0] - e[2]; o[1] = e[1] + e[2]; o[2] = e[2] - e[1]; o[3] = e[1] - e[3];
+        };
+        float b[2][8], v[2][4];      // [k pair & 1][position nu * 2 + column tile ni], [k pair & 1][nu]
+#pragma unroll
+        for (int i = 0; i < 8; ++i) b[0][i] = B[(i >> 1) * 512 + (i & 1) * 32];
+        frag(0, v[0]);
+#pragma unroll
+        for (int comp = 0; comp < 4; ++comp) {
+            if (comp < 3) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) b[(comp + 1) & 1][i] = B[(i >> 1) * 512 + (comp + 1) * 64 + (i & 1) * 32];
+                frag(comp + 1, v[(comp + 1) & 1]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                acc[i >> 1][i & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(v[comp & 1][i >> 1], b[comp & 1][i], acc[i >> 1][i & 1], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    };
+    for (int kp = 0; kp < KP; kp += 2) {
+        sub_step(I0c{}, I0c{}, kp); sub_step(I0c{}, I1c{}, kp); sub_step(I0c{}, I2c{}, kp); sub_step(I0c{}, I3c{}, kp);
+        sub_step(I1c{}, I0c{}, kp + 1); sub_step(I1c{}, I1c{}, kp + 1); sub_step(I1c{}, I2c{}, kp + 1); sub_step(I1c{}, I3c{}, kp + 1);
+    }
+
+    // ---- output transform, with the bits of wino_gemm_g_kernel: there one wave walks xi = 0..15 and adds every finished M_xi to the outputs
+    // it feeds, one after the other (Y_o = ((0 + c M_0) + c M_1) + ...; A^T = [1 1 1 0; 0 1 -1 -1] on both axes).  Here the rows of the positions
+    // sit in four waves, so the running sums pass from the wave of row 0 to that of row 3 through LDS (the patch buffer of the wave's tile
+    // half, dead after the loop's last barrier): [output o][column tile ni][1024 floats].  Row xy adds its positions in the order xx = 0..3;
+    // outputs 0, 1 (first row of A^T) are complete after row 2, outputs 2, 3 after row 3.  The K loop adds every product in
+    // wino_gemm_g_kernel's order as well, so dx_lo is the transform + GEMM pair's bit for bit.
+    static_assert(kFusedPatchFloats >= 8 * 1024, "the epilogue's exchange fits in a patch buffer");
+    const __amdgpu_buffer_rsrc_t rsy = __builtin_amdgcn_make_buffer_rsrc((void*)(a.y + (long)n * Hl * Wl * a.Nc), 0, (unsigned)(Hl * Wl * a.Nc) * 4u, 0x00020000);
+    const int rowb = 2 * Wl * a.Nc * 4, colb = 2 * a.Nc * 4;       // bytes per tile row / tile column of dx_lo
+    float* const X = mh ? P1 : P0;
+    // accumulator row r of lane half h is MFMA row (r & 3) + 8 (r >> 2) + 4 h -> tile_of_row(): a compile-time tile per (r, h)
+    auto store_out = [&](int o, int ni, const f32x16& Y) {
+        const int lane_base = (((2 * ty0 + (o >> 1)) * Wl + 2 * tx0 + (o & 1)) * a.Nc + n0 + ni * 32 + j) * 4;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row0 = (r & 3) + 8 * (r >> 2);
+            const int t = h ? cg::tile_of_row_c(row0 + 4) : cg::tile_of_row_c(row0);
+            const int ty = (t >> 3) + 4 * mh, tx = t & 7;
+            const bool in = ty0 + ty < a.tH && tx0 + tx < a.tW;     // a partly filled block: tiles past the image's grid are not stored
+            const unsigned vo = in ? (unsigned)(lane_base + ty * rowb + tx * colb) : 0x80000000u;
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(Y[r] + 0.f), rsy, (int)vo, 0, 0);     // + 0.f: the pair's "+ bias" without one
+        }
+    };
+    const float cyr[2] = {xy < 3 ? 1.f : 0.f, xy == 0 ? 0.f : (xy == 1 ? 1.f : -1.f)};     // column xy of A^T
+    // this wave's row added to output o of column tile ni: the running sum comes from LDS unless the row is the output's first
+    auto add_row = [&](int o, int ni, f32x16& Y) {
+        const bool first = (o >> 1) == 0 ? xy == 0 : xy == 1;
+        float* Xo = X + (o * 2 + ni) * 1024;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) Y[r] = first ? 0.f : Xo[r * 64 + lane];
+#pragma unroll
+        for (int xx = 0; xx < 4; ++xx) {
+            const float cx = (o & 1) == 0 ? (xx < 3 ? 1.f : 0.f) : (xx == 0 ? 0.f : (xx == 1 ? 1.f : -1.f));
+            const float c = cyr[o >> 1] * cx;
+            if (c != 0.f) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) Y[r] += c * acc[xx][ni][r];
+            }
+        }
+    };
+#pragma unroll
+    for (int row = 0; row < 4; ++row) {
+        if (xy == row) {
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                if (cyr[o >> 1] == 0.f) continue;
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) {
+                    f32x16 Y;
+                    add_row(o, ni, Y);
+                    if (row == 3) store_out(o, ni, Y);      // outputs 2, 3 are complete
+                    else {
+                        float* Xo = X + (o * 2 + ni) * 1024;
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) Xo[r * 64 + lane] = Y[r];
+                    }
+                }
+            }
+        } else if (row == 3 && xy < 2) {     // meanwhile the waves of rows 0 and 1 store the complete outputs 0 and 1
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) {
+                f32x16 Y;
+                const float* Xo = X + (xy * 2 + ni) * 1024;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) Y[r] = Xo[r * 64 + lane];
+                if (xy == 0) store_out(0, ni, Y); else store_out(1, ni, Y);
+            }
+        }
+        if (row < 3) __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------------------
 // Weight gradient, Winograd domain.  dM = A dY_p A^T per tile and phase (A = [1 0; 1 1; 1 -1; 0 -1]):
 //   Mdy[xi][tile][p*Cout+co]; then dU_xi = V_xi^T Mdy_xi (plain TN GEMMs), and G^T dU G maps back to the 3x3 phase
 //   kernels, whose taps are scattered onto the canonical 5x5 taps exactly like the direct path's reduce.
@@ -995,11 +1243,37 @@ int cg_conv2d_ups2_wino22_dgrad(void* stream, const float* dy, const float* u_bw
 
 // dx_lo[N][Hp][Wp][Cin] = gradient w.r.t. the low-res input (the upsampling's 2x2 block sum folded in);
 // v_dy: scratch of cg_conv2d_ups2_wino_v_floats(..., 4*Cout) floats.
+// With CG_WINO_DGRAD_FUSE != 0 the input transform is fused into the GEMMs (wino_dgrad_fused_kernel) and v_dy is left untouched:
+// 1 (default) where the fused kernel supports the shape and wins - whole 8 x 8 tile blocks and at least one workgroup per CU -, 2 wherever
+// it supports the shape (tests), 0 = the transform + wino_gemm_g_kernel pair everywhere.  Returns 1 = takes the fused path.
+static bool wino_dgrad_fused_takes(const float* dy, const float* u_bwd, const float* dx_lo, int N, int Hp, int Wp, int Cin, int Cout) {
+    const long mode = cg::opt(cg::OPT_WINO_DGRAD_FUSE);
+    if (mode == 0) return false;
+    const int tH = Hp / 2, tW = Wp / 2, bH = cg::cdiv(tH, 8), bW = cg::cdiv(tW, 8);
+    const long wgs = (long)N * bH * bW * (Cin / 64);
+    // one image of dy / of dx_lo and all of U within a buffer descriptor's 2 GB; K = 4 Cout in an even number of 32-plane steps
+    const bool fits = 4L * Hp * Wp * Cout * 4L < 0x7fffffffL && (long)Hp * Wp * Cin * 4L < 0x7fffffffL && 16L * 4L * Cout * Cin * 4L < 0x7fffffffL &&
+                      Cout % 32 == 0 && Cin % 64 == 0 && wgs <= 0x7fffffffL &&
+                      ((uintptr_t)dy % 16) == 0 && ((uintptr_t)u_bwd % 16) == 0 && ((uintptr_t)dx_lo % 4) == 0;
+    if (!fits) return false;
+    return mode == 2 || (tH % 8 == 0 && tW % 8 == 0 && wgs >= cg::kNumCU);
+}
+
 int cg_conv2d_ups2_wino_dgrad(void* stream, const float* dy, const float* u_bwd, float* dx_lo, float* v_dy, int N, int Hp,
                               int Wp, int Cin, int Cout) {
     CG_REQUIRE(dy && u_bwd && dx_lo && v_dy, "cg_conv2d_ups2_wino_dgrad: null pointer");
     CG_REQUIRE(wino_dims_ok(N, Hp, Wp, Cin, Cout), "cg_conv2d_ups2_wino_dgrad: unsupported dimensions");
     hipStream_t st = cg::S(stream);
+    if (wino_dgrad_fused_takes(dy, u_bwd, dx_lo, N, Hp, Wp, Cin, Cout)) {
+        WinoFusedArgs f;
+        f.dy = dy; f.U = u_bwd; f.y = dx_lo; f.N = N; f.tH = Hp / 2; f.tW = Wp / 2; f.Cs = Cout; f.K = 4 * Cout; f.Nc = Cin;
+        f.bH = cg::cdiv(f.tH, 8); f.bW = cg::cdiv(f.tW, 8);
+        f.xcd = (int)cg::opt(cg::OPT_XCD_SWIZZLE);
+        hipLaunchKernelGGL(wino_dgrad_fused_kernel, dim3((unsigned)(N * f.bH * f.bW * (Cin / 64))), dim3(512), 0, st, f);
+        CG_LAUNCH_CHECK();
+        cg::opt_count(cg::OPT_WINO_DGRAD_FUSE_LAUNCHES);
+        return 0;
+    }
     const int T = N * (Hp / 2) * (Wp / 2);
     hipLaunchKernelGGL(wino_input_transform_kernel<1>, dim3(cg::ew_grid((long)T * Cout)), dim3(256), 0, st, dy, v_dy, N, Hp, Wp,
                        4 * Cout, Cout);

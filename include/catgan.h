@@ -44,7 +44,7 @@ extern "C" {
  * utils/nn_utils.lua:638-643). */
 int         cg_abi_version(void);
 const char* cg_last_error(void);
-/* Tunables of the kernel dispatch, named like the environment variables that set their defaults (13 names; value == -1 restores the
+/* Tunables of the kernel dispatch, named like the environment variables that set their defaults (14 names and one counter; value == -1 restores the
  * default).  Results never depend on them beyond fp32 re-association; the parity tests use them to run every compiled kernel variant
  * against the oracle.
  *   CG_NN_TILE / CG_TN_TILE (bm*1000+bn), CG_NN_SPLITS / CG_TN_SPLITS : block tile and split count of the forward (data-gradient) /
@@ -56,6 +56,11 @@ const char* cg_last_error(void);
  *       kernels, 0 = the generic GEMM;
  *   CG_WINO3 : 1 = fused-transform Winograd F(2x2,3x3) for plain 64 -> 64 plane 3x3 layers with >= 2 workgroups per CU, 2 = wherever the
  *       geometry fits, 0 = never;
+ *   CG_WINO_DGRAD_FUSE : 1 = cg_conv2d_ups2_wino_dgrad forms the transformed dy inside its GEMM kernel (wino_dgrad_fused_kernel: v_dy is
+ *       neither written nor read) where the low-res grid divides into whole 8x8 blocks of 2x2 tiles and the launch has >= 1 workgroup per
+ *       CU, 2 = wherever the kernel supports the shape, 0 = never (the input transform + the 16 GEMMs through v_dy);
+ *       CG_WINO_DGRAD_FUSE_LAUNCHES is not a tunable but the count of that kernel's launches (read it with cg_get_option, any
+ *       cg_set_option value restarts it from there): how a test tells the fused path from its fallback;
  *   CG_PAD_SKIP : least share (per cent) of zero-padding MACs from which a plain convolution's forward / data gradient runs on
  *       POSITION-MAJOR row tiles and does not issue them (default 20: D32_st3's 7x7 layer at 8x8 with 38 %, models.lua:685, not its 5x5
  *       layer at 16x16 with 14 %).  The weight gradient (round 6: position-major K tiles, igemm_tng_kernel mode 2) takes HALF that share
