@@ -77,7 +77,7 @@ class Lib:
                 setattr(self, name[3:], fn)
         v = self.abi_version()
         self.timing_probe = v == -1 and os.environ.get("CG_ALLOW_TIMING_PROBE") == "1"
-        if v != 1 and not self.timing_probe:
+        if v != 2 and not self.timing_probe:
             raise CatganError("ABI version mismatch" + (" (a -DCG_TIMING_PROBE build: wrong results by construction; CG_ALLOW_TIMING_PROBE=1 "
                                                         "lets bench.py time it)" if v == -1 else ""))
 

@@ -59,11 +59,12 @@ constexpr int kEwWgsPerCU = 4, kColReduceWgsPerCU = 1;
 enum Opt {
     OPT_SKINNY, OPT_GEMM_BK32, OPT_WINO_BK, OPT_NN_TILE, OPT_TN_TILE, OPT_NN_SPLITS, OPT_TN_SPLITS,
     OPT_XCD_SWIZZLE, OPT_NN_GLDS, OPT_TN_GLDS, OPT_WINO_GLDS, OPT_PAD_SKIP, OPT_WINO3, OPT_WINO_DGRAD_FUSE, OPT_WINO_DGRAD_FUSE_LAUNCHES,
-    OPT_COUNT
+    OPT_WINO3_LAUNCHES, OPT_COUNT
 };
 long opt(Opt o);
-// CG_WINO_DGRAD_FUSE_LAUNCHES is not a tunable but a counter kept in the same table (cg_get_option reads it, cg_set_option resets it):
-// the launches of wino_dgrad_fused_kernel (winograd.hip), so that a test can tell that the fused path ran and not its fallback.
+// CG_WINO_DGRAD_FUSE_LAUNCHES and CG_WINO3_LAUNCHES are not tunables but counters kept in the same table (cg_get_option reads them,
+// cg_set_option resets them): the launches of wino_dgrad_fused_kernel (winograd.hip) and of wino3_fused_k (wino3.hip), so that a test can
+// tell that the fused path ran and not its fallback.
 void opt_count(Opt o);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
@@ -109,6 +110,10 @@ int skinny_mfma_wgrad(hipStream_t st, const float* x, const float* dy, float* pa
 // headwg.hip: weight gradient of nn.View -> nn.Linear on an NHWC map (T = H*W taps of C planes) straight into the canonical gradWeight
 bool head_wgrad_ok(int N, int T, int C, int Co);
 int head_wgrad(hipStream_t st, const float* x, const float* dy, float* gw, float* gb, int N, int T, int C, int Co, float scale);
+// The transformed filters U (kWino3UFloats floats) ride behind the packed taps of such a layer's operands, at wf / wb + kWino3UOffset:
+// cg_pack_conv_weight_floats() counts them, wino3_note_pack (called by cg_pack_conv_weight / _batch) writes them, wino3_forward reads them.
+constexpr int kWino3UOffset = 9 * 64 * 64, kWino3UFloats = 16 * 64 * 64;
+static inline bool wino3_layer(int Cout, int Cin, int kH, int kW) { return Cout == 64 && Cin == 64 && kH == 3 && kW == 3; }
 bool wino3_geom_ok(int ngroups, int N, int H, int W, int Cin, int Cout, int kH, int kW, int padH, int padW, int ups);
 int wino3_note_pack(hipStream_t st, int n, const float* const* w, float* const* wf, float* const* wb, const int* Cout, const int* Cin,
                     const int* kH, const int* kW, const int* wb_map);

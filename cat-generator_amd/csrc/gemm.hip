@@ -2803,6 +2803,11 @@ int cg_pack_conv_weight_batch(void* stream, int n, const float* const* w_canonic
     return cg::wino3_note_pack(cg::S(stream), n, w_canonical, wf, wb, Cout, Cin, kH, kW, wb_map);
 }
 
+size_t cg_pack_conv_weight_floats(int Cout, int Cin, int kH, int kW) {
+    if (Cout <= 0 || Cin <= 0 || kH <= 0 || kW <= 0) return 0;
+    return (size_t)kH * kW * Cin * Cout + (cg::wino3_layer(Cout, Cin, kH, kW) ? cg::kWino3UFloats : 0);
+}
+
 size_t cg_pack_conv_weight_ups2_floats(int Cout, int Cin, int k, int pad) {
     if (Cout <= 0 || Cin <= 0 || k <= 0 || (k & 1) == 0 || pad != (k - 1) / 2) return 0;
     const int kp = phase_kp(k, pad);

@@ -499,12 +499,12 @@ struct Compiler {
     // launch for the plain layers, cg_pack_conv_weight_ups2 (+ Winograd) for layers behind a folded upsampling).
     void need_plain(Mod& m, bool map, long C = 0, long H = 0, long W = 0) {
         if (dry) return;
-        const long n = m.kind == K_LINEAR ? m.ia[0] * m.ia[1] : m.ia[0] * m.ia[1] * m.ia[2] * m.ia[3];
+        const size_t n = cg_pack_conv_weight_floats((int)m.ia[1], (int)m.ia[0], (int)m.kH(), (int)m.kW());   // nn.Linear: kH = kW = 1
         const long taps = map ? H * W : m.kH() * m.kW();
         const int want = map ? 1 : 0;
         if (m.pk_map == want && (!map || (m.map_c == C && m.map_h == H && m.map_w == W))) return;
-        if (!m.wf) m.wf = (float*)alloc((size_t)n * 4);
-        if (taps > 1 && !m.wb) m.wb = (float*)alloc((size_t)n * 4);
+        if (!m.wf) m.wf = (float*)alloc(n * 4);
+        if (taps > 1 && !m.wb) m.wb = (float*)alloc(n * 4);
         if (taps <= 1) m.wb = nullptr;     // 1x1 / linear: the canonical [out][in] matrix already is the backward operand
         m.pk_map = want; m.map_c = C; m.map_h = H; m.map_w = W;
         m.dirty_plain = true;

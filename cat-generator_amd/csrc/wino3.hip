@@ -14,13 +14,11 @@
 // Executed MFMA work = 16 / 36 of the direct count; results differ from the direct kernel by fp32 re-association only (the transforms'
 // coefficients are 0, +-1, +-1/2).  Measured alone at batch 128 (profiles/r06_wino_lab.txt): 32 x 32: 61 us against 96 us direct.
 //
-// The transformed filters live in a library-owned cache keyed by the PACKED operand's address: cg_pack_conv_weight* (gemm.hip) call
-// wino3_note_pack for every 64 -> 64 3x3 layer they pack, which (re)computes U for the forward operand wf and the flipped, transposed U
-// for the data-gradient operand wb from the canonical weights in the same stream; cg_conv2d_forward_grouped looks its operands up and
-// takes this path when every group's operand is known.  No new entry point, nothing for a host to manage.
+// The transformed filters ride behind the packed operand: cg_pack_conv_weight* (gemm.hip) call wino3_note_pack for every 64 -> 64 3x3
+// layer they pack, which writes U for the forward operand at wf + 9 * 64 * 64 and the flipped, transposed U for the data-gradient operand
+// at wb + 9 * 64 * 64 from the canonical weights in the same stream, whatever CG_WINO3 says (cg_pack_conv_weight_floats() sizes the
+// buffers).  The host owns that memory like any other operand; nothing is allocated, cached or looked up here.
 #include "common.h"
-#include <mutex>
-#include <unordered_map>
 
 namespace {
 
@@ -30,7 +28,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int C = 64;          // input planes = output planes
 constexpr int PLD = 68;        // floats per patch pixel
 constexpr int PW = 18, PH = 10;
-constexpr int kUFloats = 16 * C * C;
+constexpr int kUFloats = cg::kWino3UFloats;
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 bufld4(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
@@ -195,21 +193,6 @@ __global__ __launch_bounds__(512, 2) void wino3_fused_k(W3Args a) {
     }
 }
 
-struct Entry { float* u; };
-std::mutex g_mu;
-std::unordered_map<const float*, Entry> g_cache;     // packed operand (wf or wb) -> its transformed filters
-
-float* slot_for(const float* packed, bool create) {
-    auto it = g_cache.find(packed);
-    if (it != g_cache.end()) return it->second.u;
-    if (!create) return nullptr;
-    float* u = nullptr;
-    // the first pack of a layer: outside any graph capture by construction (plans are compiled and packed in the eager warm-up passes)
-    if (hipMalloc((void**)&u, (size_t)kUFloats * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    g_cache[packed] = Entry{u};
-    return u;
-}
-
 }  // namespace
 
 namespace cg {
@@ -224,12 +207,10 @@ bool wino3_geom_ok(int ngroups, int N, int H, int W, int Cin, int Cout, int kH, 
     return v == 2 || (v == 1 && full);
 }
 
-// called by cg_pack_conv_weight / _batch for every layer they pack: 64 -> 64 3x3 layers get their transformed filters (re)computed,
-// anything else packed into a known address drops that address from the cache
+// called by cg_pack_conv_weight / _batch with every layer they pack: the 64 -> 64 3x3 ones (not the View -> Linear map layout, whose
+// pad-0 geometry never gets here) have their transformed filters written behind the packed taps
 int wino3_note_pack(hipStream_t st, int n, const float* const* w, float* const* wf, float* const* wb, const int* Cout, const int* Cin,
                     const int* kH, const int* kW, const int* wb_map) {
-    if (opt(OPT_WINO3) == 0) return 0;
-    std::lock_guard<std::mutex> lk(g_mu);
     PackJobs jobs;
     jobs.n = 0;
     auto flush = [&]() {
@@ -237,16 +218,10 @@ int wino3_note_pack(hipStream_t st, int n, const float* const* w, float* const* 
         jobs.n = 0;
     };
     for (int i = 0; i < n; ++i) {
-        const bool fits = Cout[i] == C && Cin[i] == C && kH[i] == 3 && kW[i] == 3 && !(wb_map && wb_map[i]);
-        if (!fits) {
-            if (wf[i]) g_cache.erase(wf[i]);     // (the buffers stay allocated: a handful of 256 KB blocks per process)
-            if (wb[i]) g_cache.erase(wb[i]);
-            continue;
-        }
-        float* uf = wf[i] ? slot_for(wf[i], true) : nullptr;
-        float* ub = wb[i] ? slot_for(wb[i], true) : nullptr;
-        if ((wf[i] && !uf) || (wb[i] && !ub)) return cg::fail("wino3: cannot allocate the transformed filters");
-        jobs.w[jobs.n] = w[i]; jobs.uf[jobs.n] = uf; jobs.ub[jobs.n] = ub;
+        if (!wino3_layer(Cout[i], Cin[i], kH[i], kW[i]) || (wb_map && wb_map[i])) continue;
+        jobs.w[jobs.n] = w[i];
+        jobs.uf[jobs.n] = wf[i] ? wf[i] + kWino3UOffset : nullptr;
+        jobs.ub[jobs.n] = wb[i] ? wb[i] + kWino3UOffset : nullptr;
         if (++jobs.n == 8) flush();
     }
     flush();
@@ -254,22 +229,19 @@ int wino3_note_pack(hipStream_t st, int n, const float* const* w, float* const* 
     return 0;
 }
 
-// 1 = launched, 0 = not this path (an operand without transformed filters), -1 = error
+// 1 = launched, 0 = not this path (a null or misaligned tensor), -1 = error
 int wino3_forward(hipStream_t st, int ngroups, const float* const* x, const float* const* wpk, const float* const* bias, float* const* y,
                   int N, int H, int W) {
     W3Args a;
     memset(&a, 0, sizeof(a));
-    {
-        std::lock_guard<std::mutex> lk(g_mu);
-        for (int g = 0; g < ngroups; ++g) {
-            const float* u = slot_for(wpk[g], false);
-            if (!u || !x[g] || !y[g] || (uintptr_t)x[g] % 16) return 0;
-            a.x[g] = x[g]; a.u[g] = u; a.bias[g] = bias ? bias[g] : nullptr; a.y[g] = y[g];
-        }
+    for (int g = 0; g < ngroups; ++g) {
+        if (!wpk[g] || !x[g] || !y[g] || (uintptr_t)x[g] % 16 || (uintptr_t)wpk[g] % 16) return 0;
+        a.x[g] = x[g]; a.u[g] = wpk[g] + kWino3UOffset; a.bias[g] = bias ? bias[g] : nullptr; a.y[g] = y[g];
     }
     a.N = N; a.H = H; a.W = W;
     hipLaunchKernelGGL(wino3_fused_k, dim3((unsigned)(N * (H / 8) * (W / 16)), ngroups), dim3(512), 0, st, a);
     if (hipGetLastError() != hipSuccess) { cg::fail("wino3_forward: launch failed"); return -1; }
+    opt_count(OPT_WINO3_LAUNCHES);
     return 1;
 }
 

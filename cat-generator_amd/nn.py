@@ -433,7 +433,7 @@ class _GemmLayer(Module):
         if getattr(self, "_packed_epoch", None) == ep and getattr(self, "_packed_ptr", None) == self.weight.ptr:
             return
         Cout, Cin, kH, kW = self._wdims()
-        n = Cout * Cin * kH * kW
+        n = lib().pack_conv_weight_floats(Cout, Cin, kH, kW)   # 64 -> 64 3x3: the transformed filters ride behind the taps
         if getattr(self, "_wf", None) is None or self._wf.numel() != n or (self._wb is None) != (kH * kW == 1):
             self._wf = torch.empty(n, dtype=torch.float32, device=self.weight.t.device)
             self._wb = torch.empty(n, dtype=torch.float32, device=self.weight.t.device) if kH * kW > 1 else None

@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define CG_ABI_VERSION 1
+#define CG_ABI_VERSION 2
 
 /* ---- runtime: device memory / streams for hosts without their own (LuaJIT).
  * Replaces cutorch.setDevice (train.lua:109), CudaTensor storage, and the
@@ -44,7 +44,7 @@ extern "C" {
  * utils/nn_utils.lua:638-643). */
 int         cg_abi_version(void);
 const char* cg_last_error(void);
-/* Tunables of the kernel dispatch, named like the environment variables that set their defaults (14 names and one counter; value == -1 restores the
+/* Tunables of the kernel dispatch, named like the environment variables that set their defaults (14 names and two counters; value == -1 restores the
  * default).  Results never depend on them beyond fp32 re-association; the parity tests use them to run every compiled kernel variant
  * against the oracle.
  *   CG_NN_TILE / CG_TN_TILE (bm*1000+bn), CG_NN_SPLITS / CG_TN_SPLITS : block tile and split count of the forward (data-gradient) /
@@ -55,7 +55,9 @@ const char* cg_last_error(void);
  *   CG_SKINNY : 1 = the MFMA scatter-form kernels of csrc/skinny.hip for 3x3 layers with <= 3 planes on one side, 2 = round 1's VALU
  *       kernels, 0 = the generic GEMM;
  *   CG_WINO3 : 1 = fused-transform Winograd F(2x2,3x3) for plain 64 -> 64 plane 3x3 layers with >= 2 workgroups per CU, 2 = wherever the
- *       geometry fits, 0 = never;
+ *       geometry fits, 0 = never.  The kernel reads the transformed filters that cg_pack_conv_weight(_batch) writes behind the packed
+ *       taps whatever this option says, so changing it never needs a re-pack.  CG_WINO3_LAUNCHES counts the kernel's launches like
+ *       CG_WINO_DGRAD_FUSE_LAUNCHES below;
  *   CG_WINO_DGRAD_FUSE : 1 = cg_conv2d_ups2_wino_dgrad forms the transformed dy inside its GEMM kernel (wino_dgrad_fused_kernel: v_dy is
  *       neither written nor read) where the low-res grid divides into whole 8x8 blocks of 2x2 tiles and the launch has >= 1 workgroup per
  *       CU, 2 = wherever the kernel supports the shape, 0 = never (the input transform + the 16 GEMMs through v_dy);
@@ -267,7 +269,12 @@ int cg_bias_grad(void* stream, const float* dy, float* gb, long M, int C, float 
 
 /* canonical [Cout][Cin][kH][kW] -> wf[(ky*kW+kx)*Cin+ci][Cout] (forward) and
  * wb[((kH-1-ky)*kW+(kW-1-kx))*Cout+co][Cin] (updateGradInput; flipped taps).
- * Either output may be NULL. */
+ * Either output may be NULL.  wf and wb hold cg_pack_conv_weight_floats(Cout, Cin, kH, kW) floats each: kH*kW*Cin*Cout, and for a
+ * 64 -> 64 plane 3x3 layer 16*64*64 more - the pack writes the Winograd-transformed filters of csrc/wino3.hip at offset 9*64*64 of wf
+ * and the flipped, transposed ones at the same offset of wb, in the same stream, whatever CG_WINO3 says.  A packed operand is plain
+ * memory of that size: it may be copied or moved, and must be 16-byte aligned to reach the fused kernel.  0 for non-positive dimensions.
+ * (ABI version 2: version 1 took kH*kW*Cin*Cout floats for every layer.) */
+size_t cg_pack_conv_weight_floats(int Cout, int Cin, int kH, int kW);
 int cg_pack_conv_weight(void* stream, const float* w_canonical, float* wf, float* wb,
                         int Cout, int Cin, int kH, int kW);
 /* The same for n layers in one launch (host arrays of n entries; wb[i] may be NULL for 1x1 / linear layers): every
@@ -279,7 +286,8 @@ int cg_pack_conv_weight_batch(void* stream, int n, const float* const* w_canonic
  * wf as cg_pack_conv_weight (forward: cg_conv2d_forward(x_nhwc, wf, ..., N, H, W, C, Cout, H, W, 0, 0, 0); weight gradient:
  * cg_conv2d_wgrad with the same geometry, canonical gw); wbT[co][(h*W+w)*C + c] is the data-gradient operand of the linear
  * form: cg_conv2d_forward(dy, wbT, NULL, dx_nhwc, N, 1, 1, Cout, H*W*C, 1, 1, 0, 0, 0).  wb_map[i] != 0 in the batch form
- * selects this layout for layer i (wb_map may be NULL). */
+ * selects this layout for layer i (wb_map may be NULL).  No transformed filters are written in this layout (a 3x3 map has pad 0 and
+ * never reaches the fused Winograd kernel): cg_pack_conv_weight_floats is an upper bound here, Cout*Cin*kH*kW floats are used. */
 int cg_pack_conv_weight_map(void* stream, const float* w_canonical, float* wf, float* wbT, int Cout, int Cin, int kH, int kW);
 /* phase-summed weights for upsample2 -> conv k x k (pad (k-1)/2), k' = (k+1)/2 rounded up (2 for 3, 3 for 5):
  * wf_ph[p][(t'*Cin+ci)][Cout], wb_ph[((p*k'*k' + t')*Cout+co)][Cin]; each holds

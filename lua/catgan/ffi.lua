@@ -13,7 +13,7 @@ local function load_header(path)
 end
 load_header(os.getenv('CATGAN_HEADER') or 'include/catgan.h')
 local C = ffi.load(os.getenv('CATGAN_LIB') or 'cat-generator_amd/lib/libcatgan_hip.so')
-assert(C.cg_abi_version() == 1, 'libcatgan_hip.so: ABI version mismatch')
+assert(C.cg_abi_version() == 2, 'libcatgan_hip.so: ABI version mismatch')
 
 local function check(rc)
    if rc ~= 0 then error(ffi.string(C.cg_last_error()), 2) end

@@ -362,7 +362,7 @@ function Gemm:_ensure_packed()
    local v = self.weight.store.version
    if self._packed_version == v and self._packed_ptr == self.weight.ptr then return end
    local Cout, Cin, kH, kW = self:_wdims()
-   local n = Cout * Cin * kH * kW
+   local n = tonumber(C.cg_pack_conv_weight_floats(Cout, Cin, kH, kW))   -- 64 -> 64 3x3: the transformed filters ride behind the taps
    self._wf = self._wf or Device.new(n)
    if kH * kW > 1 then self._wb = self._wb or Device.new(n) end
    check(C.cg_pack_conv_weight(S(), self.weight.ptr, self._wf.ptr, self._wb and self._wb.ptr or nil, Cout, Cin, kH, kW))

@@ -1,6 +1,7 @@
 """What several test modules share (a plain module, imported as tests/plan_trace.py is): the two measures of the parity tests, the
-`options` context that forces dispatch tunables, the per-tensor gradient rule, the JPEG directory of the loader tests, and the torch fp64
-twin of an engine nn.Sequential."""
+`options` context that forces dispatch tunables, `counter` that reads a launch counter, the per-tensor gradient rule, the JPEG directory
+of the loader tests, and the torch fp64 twin of an engine nn.Sequential."""
+import ctypes
 import os
 
 import numpy as np
@@ -31,6 +32,13 @@ class options:
     def __exit__(self, *exc):
         for k in self.kv:
             self.cg.lib().set_option(k.encode(), -1)
+
+
+def counter(cg, name):
+    """A launch counter kept among the options (CG_WINO3_LAUNCHES, CG_WINO_DGRAD_FUSE_LAUNCHES): how a test tells which kernel ran."""
+    v = ctypes.c_long(-1)
+    assert cg.lib().get_option(name.encode(), ctypes.byref(v)) == 0
+    return v.value
 
 
 def bulk_close(a, b, max_rel=3e-2, mean_rel=2e-3, what=""):

@@ -26,7 +26,7 @@ def test_library_exports_every_declared_symbol(cg):
     for name in protos:
         assert hasattr(dll, name), f"{name} declared in include/catgan.h but not exported"
     L = cg.lib()
-    assert L.abi_version() == 1
+    assert L.abi_version() == 2
     # nothing but extern "C" cg_* entry points with plain C types
     for name, (ret, args) in protos.items():
         assert ret in ("int", "size_t", "const char*")
@@ -44,6 +44,22 @@ def test_argument_validation_fails_loudly(cg):
         L.copy_channels(None, 16, 16, 4, 8, 6, 8, 0, 4)
     assert L.conv2d_workspace_bytes(128, 1, 1, 20480, 256, 1, 1, 0, 0, 0) > 0          # split-K linear head
     assert L.conv2d_workspace_bytes(128, 16, 16, 256, 128, 5, 5, 2, 2, 1) == 0           # big conv: no split
+
+
+def test_packed_operand_size_counts_the_transformed_filters_of_the_64_plane_3x3_layers(cg):
+    """cg_pack_conv_weight_floats: the packed taps, and behind them the 16 x 64 x 64 Winograd-domain filters of csrc/wino3.hip for the one
+    layer shape that kernel serves; the wf / wb given to cg_pack_conv_weight(_batch) hold that many floats."""
+    n = cg.lib().pack_conv_weight_floats
+    assert n(64, 64, 3, 3) == 9 * 4096 + 16 * 4096
+    assert n(64, 64, 5, 5) == 25 * 4096 and n(128, 64, 3, 3) == 9 * 128 * 64 and n(256, 20480, 1, 1) == 256 * 20480
+    assert n(0, 64, 3, 3) == 0
+
+
+def test_wino3_keeps_no_table_of_its_own():
+    """The transformed filters are the host's memory: csrc/wino3.hip allocates nothing and has no process-wide map to guard."""
+    src = open(os.path.join(ROOT, "cat-generator_amd", "csrc", "wino3.hip")).read()
+    for word in ("hipMalloc", "std::mutex", "unordered_map"):
+        assert word not in src, f"csrc/wino3.hip: {word}"
 
 
 def test_missing_library_has_no_fallback(cg, monkeypatch):

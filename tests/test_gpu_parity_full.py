@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import close, options
+from helpers import close, counter, options
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -154,7 +154,10 @@ WINO3_CASES = [(2, 8, 16), (3, 16, 16), (2, 24, 32), (5, 32, 48), (1, 64, 64)]
 @pytest.mark.parametrize("N,H,W", WINO3_CASES)
 def test_fused_winograd_for_the_64_plane_3x3_layers(cg, mode, N, H, W):
     with options(cg, CG_WINO3=mode):
+        before = counter(cg, "CG_WINO3_LAUNCHES")
         run_conv(cg, N, 64, H, W, 64, 3, 0, seed=N + H + W)
+        fused = counter(cg, "CG_WINO3_LAUNCHES") - before
+    assert fused > 0 if mode else fused == 0, f"CG_WINO3 = {mode}: {fused} launches of the fused kernel"
 
 
 def test_direct_kernel_still_covers_the_benchmarked_64_plane_layer(cg):

@@ -29,7 +29,7 @@ def test_mse_entry_points_declared_and_exported(cg):
     assert protos["cg_mse_backward"] == ("int", sig[1][:3] + [("float*", "dx"), ("long", "n")])
     dll = ctypes.CDLL(abi.LIB_PATH)
     assert hasattr(dll, "cg_mse_forward") and hasattr(dll, "cg_mse_backward")
-    assert cg.lib().abi_version() == 1
+    assert cg.lib().abi_version() == 2
 
 
 def test_mse_bad_arguments_raise(cg):

@@ -32,7 +32,7 @@ def test_new_entry_points_exported_with_plain_c_types(cg):
         assert name in protos and hasattr(dll, name)
         ret, args = protos[name]
         assert ret == "int" and all(t in abi._CTYPES for t, _ in args)
-    assert cg.lib().abi_version() == 1
+    assert cg.lib().abi_version() == 2
 
 
 def test_new_entry_points_validate_arguments(cg):
