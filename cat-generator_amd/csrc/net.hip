@@ -18,8 +18,10 @@
 //
 // A plan is compiled by symbolic execution: the module tree is walked once per (input shape, training flags) with tensor
 // descriptors instead of data; every launch becomes a closure over resolved pointers and geometry, appended to a flat op list.
-// Running a pass is a loop over that list.  Random draws (dropout masks) sit at fixed offsets from the counter-stream position
-// the caller passes in, in the order a module-after-module walk draws them, so engine and oracle masks stay bit-identical.
+// The tree has ONE walker, the lockstep one (gfwd / gbwd over G sibling modules): the root, or a branch without a twin, is a group of
+// one and emits the plain single-module launches.  Running a pass is a loop over that list.  Random draws (dropout masks) sit at
+// fixed offsets from the counter-stream position the caller passes in, in the order a module-after-module walk draws them, so
+// engine and oracle masks stay bit-identical.
 //
 // With option "trace" the launches go to recording stubs (net_ktable.inc) instead of the GPU: tests/test_net_plan.py checks the
 // planner's launch sequence, data flow and draw order on a machine without a GPU.
@@ -294,7 +296,7 @@ void trace_note(Net* n, const std::string& s) { if (n->trace) { n->trace_log += 
 // ================================================================================================ the compiler
 namespace {
 
-struct GCtx { vector<long> cur; };   // per-branch positions in the counter stream during a lockstep walk
+struct GCtx { vector<long> cur; };   // per-branch positions in the counter stream during a lockstep walk (a lone module: one branch)
 
 struct Prep { Val x; int wsel; Val out; Geo g; bool ok = true; };
 enum { W_PLAIN_F = 0, W_PH_F, W_PLAIN_B, W_PH_B, W_CANON };
@@ -314,7 +316,7 @@ struct Compiler {
     Prog* pr;
     vector<Op>* ops = nullptr;
     int cs = 0;              // stream index launches are emitted on
-    long rng = 0;            // counter-stream draws so far, relative to the pass's start
+    long rng = 0;            // counter-stream position (relative to the pass's start) of the branch whose module is being emitted (per_branch)
     int dry = 0;             // > 0: shape / draw bookkeeping only (no allocation, no ops, no module state kept)
     bool failed = false;
     int pend[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // deferred weight-gradient reductions queued per stream index
@@ -621,22 +623,12 @@ struct Compiler {
     }
 
     // ---------------------------------------------------------------------------------------- forward of one module
+    // One module with its own launches, drawing at `rng`.  nn.Sequential and nn.ConcatTable are walked by gfwd alone (a lone
+    // module is a lockstep group of one).
     Val fwd(Mod& m, const Val& in) {
         const KTable* k = K();
         MS& s = S(m);
         switch (m.kind) {
-        case K_SEQ: {
-            LocDesc ld;
-            if (match_loc(m, in, ld)) return fwd_loc({&m}, in, ld)[0];
-            S(m).loc_fused = false;
-            return fwd_seq(m, in);
-        }
-        case K_CONCATTABLE: {
-            Val t; t.is_tab = true; t.none = false;
-            for (int c : m.kids) t.tab.push_back(fwd(M(c), in));
-            s.out = t;
-            return t;
-        }
         case K_CONCAT: return fwd_concat(m, in);
         case K_LINEAR: case K_CONV: {
             if (m.kind == K_CONV) {
@@ -819,15 +811,25 @@ struct Compiler {
     static bool stackable(const Mod& m) {
         switch (m.kind) { case K_LRELU: case K_VIEW: case K_AVGPOOL: case K_MAXPOOL: case K_SDROP: case K_AFFMAT: case K_AFFGRID: return true; default: return false; }
     }
-    vector<Val> gfwd_default(const vector<Mod*>& mods, const vector<Val>& ins, GCtx& ctx) {
-        // one call per branch, each at its own position in the counter stream
+    // f(b) for every branch, each at its own position in the counter stream (`rng` while its launches are emitted)
+    template <class F> vector<Val> per_branch(GCtx& ctx, F f) {
         vector<Val> outs;
-        for (size_t b = 0; b < mods.size(); ++b) {
+        for (size_t b = 0; b < ctx.cur.size(); ++b) {
             const long saved = rng; rng = ctx.cur[b];
-            outs.push_back(fwd(*mods[b], ins[b]));
+            outs.push_back(f((int)b));
             ctx.cur[b] = rng; rng = saved;
         }
         return outs;
+    }
+    vector<Val> gfwd_default(const vector<Mod*>& mods, const vector<Val>& ins, GCtx& ctx) {
+        return per_branch(ctx, [&](int b) { return fwd(*mods[b], ins[b]); });
+    }
+    // a stacked tensor as G per-branch values / G per-branch values as one stacked tensor; a group of one is the tensor itself
+    vector<Val> slices(const Val& Y, int G) { return G == 1 ? vector<Val>{Y} : split(Y, G); }
+    Val gather(const Mod& owner, const vector<Val>& xs, const Val& like) {
+        Val X;
+        if (xs.size() == 1) return xs[0];
+        return stacked(xs, &X) ? X : restack(owner, xs, like);
     }
     vector<Val> gfwd_stackable(const vector<Mod*>& mods, const vector<Val>& ins, GCtx& ctx) {
         Mod& m0 = *mods[0];
@@ -844,11 +846,14 @@ struct Compiler {
         Mod& m0 = *mods[0];
         const KTable* k = K();
         const int G = (int)mods.size();
+        // a group of one emits what the module emits on its own: the grouped / stacked / shared forms below are for real groups
+        if (G == 1 && m0.kind != K_SEQ && m0.kind != K_CONCATTABLE) return gfwd_default(mods, ins, ctx);
         switch (m0.kind) {
         case K_SEQ: {
-            // sibling localisation branches on the SAME input (D32_st3's three transformers): one fused launch for the group
+            // a localisation branch, or sibling ones on the SAME input (D32_st3's three transformers): one fused launch for the group
+            // (fuse_locnet 2: ungrouped branches only)
             LocDesc ld;
-            bool same = G <= 4 && net->fuse_locnet != 2 && match_loc(m0, ins[0], ld);
+            bool same = G <= 4 && (G == 1 || net->fuse_locnet != 2) && match_loc(m0, ins[0], ld);
             for (int b = 1; same && b < G; ++b) {
                 LocDesc lb;
                 same = ins[b].key() == ins[0].key() && ins[b].same_shape(ins[0]) && match_loc(*mods[b], ins[b], lb) && lb.S == ld.S && lb.Cin == ld.Cin &&
@@ -877,7 +882,7 @@ struct Compiler {
         case K_AVGPOOL: case K_MAXPOOL: {
             // sibling instances fed the SAME tensor (the localisation nets of D32_st3's three transformer branches all start by
             // pooling the trunk's output, models.lua:843) compute the same thing: one launch, shared result
-            bool same = net->fusion && net->share_pool && G > 1 && !ins[0].is_tab;
+            bool same = net->fusion && net->share_pool && !ins[0].is_tab;
             for (int b = 1; same && b < G; ++b) same = ins[b].key() == ins[0].key() && ins[b].same_shape(ins[0]) && ins[b].fmt == ins[0].fmt && ins[b].ups == ins[0].ups;
             if (same) {
                 Val y = fwd(m0, ins[0]);
@@ -1003,49 +1008,24 @@ struct Compiler {
         }
         return out;
     }
-    Val fwd_seq(Mod& q, const Val& in) {
-        Val cur = in;
-        vector<Seg> pl = plan(q);
-        S(q).ran = pl; S(q).ran_set = true;
-        for (const Seg& sg : pl) {
-            auto kid = [&](int t) -> Mod* { return &M(q.kids[t]); };
-            switch (sg.kind) {
-            case S_ONE: cur = fwd(*kid(sg.i), cur); break;
-            case S_GEMM_ACT: cur = fwd_gemm_act({kid(sg.i)}, {kid(sg.i + 1)}, {cur}, nullptr)[0]; break;
-            case S_ACT_POOL: cur = fwd_act_pool({kid(sg.i)}, {kid(sg.i + 1)}, sg.j - sg.i == 3 ? vector<Mod*>{kid(sg.i + 2)} : vector<Mod*>{}, {cur}, nullptr)[0]; break;
-            case S_VIEW_GEMM: cur = fwd_view_gemm({kid(sg.i)}, {kid(sg.i + 1)}, {}, {cur}, nullptr)[0]; break;
-            case S_VIEW_GEMM_ACT: cur = fwd_view_gemm({kid(sg.i)}, {kid(sg.i + 1)}, {kid(sg.i + 2)}, {cur}, nullptr)[0]; break;
-            case S_CAT_DROP: cur = fwd_concat(*kid(sg.i), cur, kid(sg.i + 1)); break;
-            case S_HEAD: cur = fwd_head(*kid(sg.i), *kid(sg.i + 1), *kid(sg.i + 2), cur); break;
-            default: cur = fwd_gemm_bn_act(*kid(sg.i), *kid(sg.i + 1), *kid(sg.i + 2), cur); break;
-            }
-            if (failed) break;
-        }
-        S(q).out = cur;
-        return cur;
-    }
     vector<Val> gfwd_seq(const vector<Mod*>& qs, const vector<Val>& ins, GCtx& ctx) {
         vector<Val> cur = ins;
         vector<Seg> pl = plan(*qs[0]);
         for (Mod* q : qs) { S(*q).ran = pl; S(*q).ran_set = true; }
         auto col = [&](int t) { vector<Mod*> c; for (Mod* q : qs) c.push_back(&M(q->kids[t])); return c; };
+        auto kid = [&](int b, int t) -> Mod& { return M(qs[b]->kids[t]); };
         for (const Seg& sg : pl) {
+            const int i = sg.i;
             switch (sg.kind) {
-            case S_ONE: cur = gfwd(col(sg.i), cur, ctx); break;
-            case S_GEMM_ACT: cur = fwd_gemm_act(col(sg.i), col(sg.i + 1), cur, &ctx); break;
-            case S_ACT_POOL: cur = fwd_act_pool(col(sg.i), col(sg.i + 1), sg.j - sg.i == 3 ? col(sg.i + 2) : vector<Mod*>{}, cur, &ctx); break;
-            case S_VIEW_GEMM: cur = fwd_view_gemm(col(sg.i), col(sg.i + 1), {}, cur, &ctx); break;
-            case S_VIEW_GEMM_ACT: cur = fwd_view_gemm(col(sg.i), col(sg.i + 1), col(sg.i + 2), cur, &ctx); break;
-            case S_CAT_DROP: case S_HEAD: for (int t = sg.i; t < sg.j; ++t) cur = gfwd(col(t), cur, ctx); break;   // no lockstep form: module by module
-            default: {   // not a lockstep case on the path: branch after branch, each at its own stream position
-                vector<Val> outs;
-                for (size_t b = 0; b < qs.size(); ++b) {
-                    const long saved = rng; rng = ctx.cur[b];
-                    outs.push_back(fwd_gemm_bn_act(M(qs[b]->kids[sg.i]), M(qs[b]->kids[sg.i + 1]), M(qs[b]->kids[sg.i + 2]), cur[b]));
-                    ctx.cur[b] = rng; rng = saved;
-                }
-                cur = outs;
-            } break;
+            case S_ONE: cur = gfwd(col(i), cur, ctx); break;
+            case S_GEMM_ACT: cur = fwd_gemm_act(col(i), col(i + 1), cur, ctx); break;
+            case S_ACT_POOL: cur = fwd_act_pool(col(i), col(i + 1), sg.j - i == 3 ? col(i + 2) : vector<Mod*>{}, cur, ctx); break;
+            case S_VIEW_GEMM: cur = fwd_view_gemm(col(i), col(i + 1), {}, cur, ctx); break;
+            case S_VIEW_GEMM_ACT: cur = fwd_view_gemm(col(i), col(i + 1), col(i + 2), cur, ctx); break;
+            // no lockstep form: the fused segment branch after branch
+            case S_CAT_DROP: cur = per_branch(ctx, [&](int b) { return fwd_concat(kid(b, i), cur[b], &kid(b, i + 1)); }); break;
+            case S_HEAD: cur = per_branch(ctx, [&](int b) { return fwd_head(kid(b, i), kid(b, i + 1), kid(b, i + 2), cur[b]); }); break;
+            default: cur = per_branch(ctx, [&](int b) { return fwd_gemm_bn_act(kid(b, i), kid(b, i + 1), kid(b, i + 2), cur[b]); }); break;
             }
             if (failed) break;
         }
@@ -1055,7 +1035,7 @@ struct Compiler {
 
     // [conv|linear, PReLU|LeakyReLU] x G branches: one (grouped) GEMM launch whose epilogue writes the pre-activation (what the
     // activation's backward needs) and the activation
-    vector<Val> fwd_gemm_act(const vector<Mod*>& convs, const vector<Mod*>& acts, const vector<Val>& xs, GCtx* ctx) {
+    vector<Val> fwd_gemm_act(const vector<Mod*>& convs, const vector<Mod*>& acts, const vector<Val>& xs, GCtx& ctx) {
         const KTable* k = K();
         const int G = (int)convs.size();
         vector<Prep> preps;
@@ -1065,10 +1045,7 @@ struct Compiler {
             wino = wino || (convs[b]->kind == K_CONV && preps[b].x.ups && use_wino(*convs[b], preps[b].x));
             ok = ok && preps[b].g == preps[0].g && epilogue_ok(preps[b].g);
         }
-        if (!ok || wino) {
-            if (G == 1) return {fwd(*acts[0], fwd(*convs[0], xs[0]))};
-            return gfwd(acts, gfwd(convs, xs, *ctx), *ctx);
-        }
+        if (!ok || wino) return gfwd(acts, gfwd(convs, xs, ctx), ctx);
         if (G > 1 && net->stacking) {
             vector<Val> outs; for (auto& p : preps) outs.push_back(p.out);
             if (!stacked(outs, nullptr)) {
@@ -1107,7 +1084,7 @@ struct Compiler {
     }
 
     // [View(C*H*W), Linear, (activation)] x G branches (models.lua:696-698, 849-851): the linear layer consumes the NHWC map
-    vector<Val> fwd_view_gemm(const vector<Mod*>& views, const vector<Mod*>& lins, const vector<Mod*>& acts, vector<Val> xs, GCtx* ctx) {
+    vector<Val> fwd_view_gemm(const vector<Mod*>& views, const vector<Mod*>& lins, const vector<Mod*>& acts, vector<Val> xs, GCtx& ctx) {
         const int G = (int)views.size();
         const Val& x0 = xs[0];
         bool ok = !x0.is_tab && x0.nd == 4 && x0.fmt == NHWC && !x0.ups;
@@ -1124,15 +1101,14 @@ struct Compiler {
         if (ok) {
             for (int b = 0; b < G; ++b) { MS& sv = S(*views[b]); sv.out = Val(); sv.in_nd = 4; for (int i = 0; i < 4; ++i) sv.in_shape[i] = xs[b].d[i]; }
         } else {
-            if (G == 1) xs = {fwd(*views[0], xs[0])}; else xs = gfwd(views, xs, *ctx);
+            xs = gfwd(views, xs, ctx);
         }
         if (!acts.empty()) return fwd_gemm_act(lins, acts, xs, ctx);
-        if (G == 1) return {fwd(*lins[0], xs[0])};
-        return gfwd(lins, xs, *ctx);
+        return gfwd(lins, xs, ctx);
     }
 
     // [PReLU|LeakyReLU, Pool 2x2, (SpatialDropout, training)] x G branches in one pass over the stacked input
-    vector<Val> fwd_act_pool(const vector<Mod*>& acts, const vector<Mod*>& pools, const vector<Mod*>& drops, const vector<Val>& xs, GCtx* ctx) {
+    vector<Val> fwd_act_pool(const vector<Mod*>& acts, const vector<Mod*>& pools, const vector<Mod*>& drops, const vector<Val>& xs, GCtx& ctx) {
         const KTable* k = K();
         const int G = (int)acts.size();
         Mod &a0 = *acts[0], &p0 = *pools[0];
@@ -1152,9 +1128,7 @@ struct Compiler {
             vector<vector<Mod*>> chain = {acts, pools};
             if (!drops.empty()) chain.push_back(drops);
             vector<Val> cur = xs;
-            for (auto& colm : chain) {
-                if (G == 1) cur = {fwd(*colm[0], cur[0])}; else cur = gfwd(colm, cur, *ctx);
-            }
+            for (auto& colm : chain) cur = gfwd(colm, cur, ctx);
             return cur;
         }
         const int code = a0.kind == K_PRELU ? 1 : 2;
@@ -1165,13 +1139,12 @@ struct Compiler {
         if (d0) {
             mask = buf(*d0, "noise.block", {G * N, C}); have_mask = true;
             const float p = d0->fa[0];
-            if (G == 1) {
-                const long off = rng; rng += N * C;
-                emit([=](Run& c) { return k->rng_bernoulli_dev(c.CS(), c.P(mask), N * C, 1.0f - p, 1.0f, c.seed, c.roff + (uint64_t)off, c.rbase); });
+            long offs[4] = {0, 0, 0, 0};
+            for (int b = 0; b < G; ++b) { offs[b] = ctx.cur[b]; ctx.cur[b] += N * C; }
+            const long o0 = offs[0], o1 = offs[1], o2 = offs[2], o3 = offs[3];
+            if (G == 1) {   // the plain entry point
+                emit([=](Run& c) { return k->rng_bernoulli_dev(c.CS(), c.P(mask), N * C, 1.0f - p, 1.0f, c.seed, c.roff + (uint64_t)o0, c.rbase); });
             } else {
-                long offs[4] = {0, 0, 0, 0};
-                for (int b = 0; b < G; ++b) { offs[b] = ctx->cur[b]; ctx->cur[b] += N * C; }
-                const long o0 = offs[0], o1 = offs[1], o2 = offs[2], o3 = offs[3];
                 emit([=](Run& c) {
                     // base-relative positions: the kernel adds *rbase to every one of them
                     return k->rng_bernoulli_dev_grouped(c.CS(), c.P(mask), N * C, G, 1.0f - p, 1.0f, c.seed, c.roff + (uint64_t)o0, G > 1 ? c.roff + (uint64_t)o1 : 0,
@@ -1187,9 +1160,8 @@ struct Compiler {
             return k->act_pool2_mask_forward(c.CS(), c.P(X), c.P(out), have_mask ? c.P(mask) : nullptr, G, (int)N, (int)H, (int)W, (int)C, code, slope,
                                              code == 1 ? al : nullptr, pool_max);
         });
-        vector<Val> outs = G == 1 ? vector<Val>{out} : split(out, G);
-        vector<Val> masks;
-        if (have_mask) masks = G == 1 ? vector<Val>{mask} : split(mask, G);
+        vector<Val> outs = slices(out, G), masks;
+        if (have_mask) masks = slices(mask, G);
         for (int b = 0; b < G; ++b) {
             MS& sa = S(*acts[b]); sa.x = xs[b]; sa.out = Val();
             MS& sp = S(*pools[b]); sp.x = Val(); sp.out = d0 ? Val() : outs[b];
@@ -1324,7 +1296,7 @@ struct Compiler {
             return k->locnet_forward(c.CS(), G, (int)N, c.P(x), 1, w, dd.S, dd.Cin, dd.P, dd.ur, dd.us, dd.ut, dd.slope, dd.Hg, dd.Wg, c.P(pooled), c.P(h1),
                                      c.P(m2), c.P(h2), c.P(h3), c.P(prm), c.P(grid));
         });
-        vector<Val> outs = G == 1 ? vector<Val>{grid} : split(grid, G);
+        vector<Val> outs = slices(grid, G);
         for (int b = 0; b < G; ++b) {
             MS& s = S(*qs[b]);
             s.out = outs[b]; s.loc_fused = true; s.locG = G; s.locN = N;
@@ -1342,9 +1314,7 @@ struct Compiler {
         LocDesc d;
         if (!match_loc(q0, s0.x, d)) { err("cg_net: fused localisation branch lost its shape"); return gouts; }
         const long N = s0.locN, S_ = d.S, Cin = d.Cin, K3 = 16L * (S_ / 2) * (S_ / 2);
-        Val GG;
-        if (G == 1) GG = gouts[0];
-        else if (!stacked(gouts, &GG)) GG = restack(q0, gouts, gouts[0]);
+        Val GG = gather(q0, gouts, gouts[0]);
         Val pooled = buf(q0, "loc.pooled", {G * N, Cin, S_, S_}, NHWC), h1 = buf(q0, "loc.h1", {G * N, 16, S_, S_}, NHWC),
             m2 = buf(q0, "loc.m2", {G * N, 16, S_, S_}, NHWC), h2 = buf(q0, "loc.h2", {G * N, K3}), h3 = buf(q0, "loc.h3", {G * N, 64}),
             prm = buf(q0, "loc.params", {G * N, d.P});
@@ -1396,7 +1366,7 @@ struct Compiler {
             }
             });
         }
-        vector<Val> outs = G == 1 ? vector<Val>{gx} : split(gx, G);
+        vector<Val> outs = slices(gx, G);
         for (int b = 0; b < G; ++b) S(*qs[b]).gin = outs[b];
         return outs;
     }
@@ -1409,12 +1379,12 @@ struct Compiler {
         for (int c : m.kids) s += signature(M(c));
         return s + ")";
     }
-    vector<vector<int>> branch_groups(const Mod& q) {
+    vector<vector<int>> branch_groups(const Mod& q) {   // option grouped 0: every branch a group of its own
         vector<std::pair<std::string, vector<int>>> by;
         for (size_t i = 0; i < q.kids.size(); ++i) {
             std::string sg = signature(M(q.kids[i]));
             bool found = false;
-            for (auto& e : by) if (e.first == sg) { e.second.push_back((int)i); found = true; break; }
+            for (auto& e : by) if (net->grouped && e.first == sg) { e.second.push_back((int)i); found = true; break; }
             if (!found) by.push_back({sg, {(int)i}});
         }
         vector<vector<int>> groups;
@@ -1426,29 +1396,39 @@ struct Compiler {
     // thunks[0] on the current stream, the others forked onto side streams and joined (D32_st3: the long chain of launch-bound
     // kernels of the three transformer branches hides under the big GEMMs of the two-convolution branch)
     void run_groups(const vector<std::function<void()>>& thunks) {
-        const KTable* k = K();
-        const bool multi = net->overlap_groups && thunks.size() > 1 && cs == 0 && thunks.size() <= 4;
+        const bool multi = net->grouped && net->overlap_groups && thunks.size() > 1 && cs == 0 && thunks.size() <= 4;
         if (!multi) { for (auto& f : thunks) f(); return; }
-        emit([=](Run& c) { return c.net->trace ? (trace_note(c.net, "event|record|fork|s0"), 0) : (hipEventRecord(c.net->fork_ev, (hipStream_t)c.S(0)) == hipSuccess ? 0 : 1); });
+        emit_event(EV_RECORD, EV_FORK, 0);
         for (size_t t = 1; t < thunks.size(); ++t) {
             const int sidx = (int)t;
             use_stream(sidx);
             cs = sidx;
-            emit([=](Run& c) { return c.net->trace ? (trace_note(c.net, "event|wait|fork|s" + std::to_string(sidx)), 0)
-                                                    : (hipStreamWaitEvent((hipStream_t)c.S(sidx), c.net->fork_ev, 0) == hipSuccess ? 0 : 1); });
+            emit_event(EV_WAIT, EV_FORK, 0);
             thunks[t]();
             flush_wgrad();
-            emit([=](Run& c) { return c.net->trace ? (trace_note(c.net, "event|record|join" + std::to_string(sidx) + "|s" + std::to_string(sidx)), 0)
-                                                    : (hipEventRecord(c.net->side_ev[sidx - 1], (hipStream_t)c.S(sidx)) == hipSuccess ? 0 : 1); });
+            emit_event(EV_RECORD, EV_JOIN, sidx);
             cs = 0;
         }
         thunks[0]();
-        for (size_t t = 1; t < thunks.size(); ++t) {
-            const int sidx = (int)t;
-            emit([=](Run& c) { return c.net->trace ? (trace_note(c.net, "event|wait|join" + std::to_string(sidx) + "|s0"), 0)
-                                                    : (hipStreamWaitEvent((hipStream_t)c.S(0), c.net->side_ev[sidx - 1], 0) == hipSuccess ? 0 : 1); });
-        }
-        (void)k;
+        for (size_t t = 1; t < thunks.size(); ++t) emit_event(EV_WAIT, EV_JOIN, (int)t);
+    }
+    // Record / wait for an event of the net on the CURRENT stream; in trace mode the line event|<record|wait>|<name>|s<stream index>.
+    // The event is looked up when the op runs (ensure_streams creates them after the plan is compiled): fork_ev, side_ev[k - 1] ("join<k>"),
+    // wg_fork_ev[k] ("wgfork<k>"), wg_join_ev[k] ("wgjoin<k>").
+    enum { EV_RECORD = 0, EV_WAIT = 1 };
+    enum { EV_FORK = 0, EV_JOIN, EV_WGFORK, EV_WGJOIN };
+    void emit_event(int what, int kind, int k) {
+        static const char* const names[] = {"fork", "join", "wgfork", "wgjoin"};
+        const int s = cs;
+        const std::string line = std::string(what == EV_RECORD ? "event|record|" : "event|wait|") + names[kind] + (kind == EV_FORK ? "" : std::to_string(k)) +
+                                 "|s" + std::to_string(s);
+        emit([=](Run& c) {
+            Net* n = c.net;
+            if (n->trace) { trace_note(n, line); return 0; }
+            const hipEvent_t e = kind == EV_FORK ? n->fork_ev : kind == EV_JOIN ? n->side_ev[k - 1] : kind == EV_WGFORK ? n->wg_fork_ev[k] : n->wg_join_ev[k];
+            const hipStream_t st = (hipStream_t)c.S(s);
+            return (what == EV_RECORD ? hipEventRecord(e, st) : hipStreamWaitEvent(st, e, 0)) == hipSuccess ? 0 : 1;
+        });
     }
     void flush_wgrad() {   // reduce the weight-gradient partials queued on the CURRENT stream in one launch
         if (dry || !pend[cs]) return;
@@ -1466,17 +1446,14 @@ struct Compiler {
     bool wg_on() const { return net->wgrad_stream && net->fusion && acc_pass && !dry && cs < 4; }
     void wg_fork() {   // call on stream s where the gradOutput the weight gradient reads is complete
         if (!wg_on()) return;
-        const int s = cs;
-        emit([=](Run& c) { return c.net->trace ? (trace_note(c.net, "event|record|wgfork" + std::to_string(s) + "|s" + std::to_string(s)), 0)
-                                                : (hipEventRecord(c.net->wg_fork_ev[s], (hipStream_t)c.S(s)) == hipSuccess ? 0 : 1); });
+        emit_event(EV_RECORD, EV_WGFORK, cs);
     }
     int wg_enter() {   // later launches go to the weight-gradient stream; returns the stream index to hand back to wg_leave
         const int s = cs;
         if (!wg_on()) return s;
         use_stream(4 + s);
         cs = 4 + s;
-        emit([=](Run& c) { return c.net->trace ? (trace_note(c.net, "event|wait|wgfork" + std::to_string(s) + "|s" + std::to_string(4 + s)), 0)
-                                                : (hipStreamWaitEvent((hipStream_t)c.S(4 + s), c.net->wg_fork_ev[s], 0) == hipSuccess ? 0 : 1); });
+        emit_event(EV_WAIT, EV_WGFORK, s);
         wg_used[s] = true; wg_unjoined[s] = true;
         return s;
     }
@@ -1492,58 +1469,40 @@ struct Compiler {
             if (!wg_used[s]) continue;
             cs = 4 + s;
             flush_wgrad();
-            emit([=](Run& c) { return c.net->trace ? (trace_note(c.net, "event|record|wgjoin" + std::to_string(s) + "|s" + std::to_string(4 + s)), 0)
-                                                    : (hipEventRecord(c.net->wg_join_ev[s], (hipStream_t)c.S(4 + s)) == hipSuccess ? 0 : 1); });
+            emit_event(EV_RECORD, EV_WGJOIN, s);
             cs = 0;
-            emit([=](Run& c) { return c.net->trace ? (trace_note(c.net, "event|wait|wgjoin" + std::to_string(s) + "|s0"), 0)
-                                                    : (hipStreamWaitEvent((hipStream_t)c.S(0), c.net->wg_join_ev[s], 0) == hipSuccess ? 0 : 1); });
+            emit_event(EV_WAIT, EV_WGJOIN, s);
             wg_used[s] = false;
         }
         cs = back;
     }
     long count_draws(Mod& m, const Val& in) {   // counter-stream draws of one forward of `m` (no launches, no state kept)
         Prog tmp; tmp.net = net;
-        Prog* save = pr; const long r0 = rng; vector<Op>* so = ops;
-        pr = &tmp; ++dry; rng = 0;
-        fwd(m, in);
-        const long n = rng;
-        --dry; pr = save; rng = r0; ops = so;
-        return n;
+        Prog* save = pr;
+        pr = &tmp; ++dry;
+        GCtx ctx{{0}};
+        gfwd({&m}, {in}, ctx);
+        --dry; pr = save;
+        return ctx.cur[0];
     }
     // drop: the nn.SpatialDropout (training) right behind this nn.Concat in its Sequential, to run inside the concat launch
     Val fwd_concat(Mod& q, const Val& in, Mod* drop = nullptr) {
         const KTable* k = K();
         const int nb = (int)q.kids.size();
         vector<Val> outs(nb);
-        if (!net->grouped) {
-            for (int i = 0; i < nb; ++i) outs[i] = as_nhwc(fwd(M(q.kids[i]), in));
-        } else {
-            vector<vector<int>> groups = branch_groups(q);
-            vector<long> draws(nb), base(nb);
-            long tot = 0;
-            for (int i = 0; i < nb; ++i) { draws[i] = count_draws(M(q.kids[i]), in); base[i] = rng + tot; tot += draws[i]; }
-            const long end = rng + tot;
-            vector<std::function<void()>> thunks;
-            for (auto& idxs : groups) {
-                thunks.push_back([&, idxs]() {
-                    vector<Val> res;
-                    if (idxs.size() > 1) {
-                        GCtx ctx; vector<Mod*> mods; vector<Val> ins;
-                        for (int i : idxs) { ctx.cur.push_back(base[i]); mods.push_back(&M(q.kids[i])); ins.push_back(in); }
-                        const long saved = rng;
-                        res = gfwd(mods, ins, ctx);
-                        rng = saved;
-                    } else {
-                        const long saved = rng; rng = base[idxs[0]];
-                        res = {fwd(M(q.kids[idxs[0]]), in)};
-                        rng = saved;
-                    }
-                    for (size_t t = 0; t < idxs.size(); ++t) outs[idxs[t]] = as_nhwc(res[t]);
-                });
-            }
-            run_groups(thunks);
-            rng = end;
+        // every branch draws where a branch-after-branch walk would, whatever order (and stream) the groups are emitted in
+        vector<long> base(nb);
+        for (int i = 0; i < nb; ++i) { base[i] = rng; rng += count_draws(M(q.kids[i]), in); }
+        vector<std::function<void()>> thunks;
+        for (auto& idxs : branch_groups(q)) {
+            thunks.push_back([&, idxs]() {
+                GCtx ctx; vector<Mod*> mods; vector<Val> ins;
+                for (int i : idxs) { ctx.cur.push_back(base[i]); mods.push_back(&M(q.kids[i])); ins.push_back(in); }
+                vector<Val> res = gfwd(mods, ins, ctx);
+                for (size_t t = 0; t < idxs.size(); ++t) outs[idxs[t]] = as_nhwc(res[t]);
+            });
         }
+        run_groups(thunks);
         const long N = outs[0].d[0], H = outs[0].d[2], W = outs[0].d[3];
         MS& s = S(q);
         s.sizes.clear();
@@ -1597,8 +1556,8 @@ struct Compiler {
         Val g = as_nhwc(go);
         const long N = g.d[0], Ct = g.d[1], H = g.d[2], W = g.d[3];
         vector<Val> dst(nb); vector<bool> have(nb, false);
-        vector<vector<int>> groups = net->grouped ? branch_groups(q) : vector<vector<int>>{};
-        if (net->grouped && net->stacking) {
+        vector<vector<int>> groups = branch_groups(q);
+        if (net->stacking) {
             for (auto& idxs : groups) {
                 bool eq = idxs.size() > 1;
                 for (int i : idxs) eq = eq && s.sizes[i] == s.sizes[idxs[0]];
@@ -1638,25 +1597,16 @@ struct Compiler {
             }
         }
         vector<Val> grads(nb);
-        if (!net->grouped) {
-            for (int i = 0; i < nb; ++i) grads[i] = as_nhwc(bwd(M(q.kids[i]), in, dst[i], acc));
-        } else {
-            vector<std::function<void()>> thunks;
-            for (auto& idxs : groups) {
-                thunks.push_back([&, idxs]() {
-                    vector<Val> res;
-                    if (idxs.size() > 1) {
-                        GCtx ctx; vector<Mod*> mods; vector<Val> ins, gs;
-                        for (int i : idxs) { ctx.cur.push_back(0); mods.push_back(&M(q.kids[i])); ins.push_back(in); gs.push_back(dst[i]); }
-                        res = gbwd(mods, ins, gs, acc, ctx);
-                    } else {
-                        res = {bwd(M(q.kids[idxs[0]]), in, dst[idxs[0]], acc)};
-                    }
-                    for (size_t t = 0; t < idxs.size(); ++t) grads[idxs[t]] = as_nhwc(res[t]);
-                });
-            }
-            run_groups(thunks);
+        vector<std::function<void()>> thunks;
+        for (auto& idxs : groups) {
+            thunks.push_back([&, idxs]() {
+                vector<Mod*> mods; vector<Val> ins, gs;
+                for (int i : idxs) { mods.push_back(&M(q.kids[i])); ins.push_back(in); gs.push_back(dst[i]); }
+                vector<Val> res = gbwd(mods, ins, gs, acc);
+                for (size_t t = 0; t < idxs.size(); ++t) grads[idxs[t]] = as_nhwc(res[t]);
+            });
         }
+        run_groups(thunks);
         // gradInput = ((g0 + g1) + g2) + g3
         Val accv;
         if (net->fusion && net->cat_fuse && nb >= 2 && nb <= 4 && grads[0].phys() % 4 == 0) {
@@ -1794,15 +1744,7 @@ struct Compiler {
         MS& s = S(m);
         Mod* mp = &m;
         switch (m.kind) {
-        case K_SEQ:
-            if (s.loc_fused && s.locG == 1) return bwd_loc({&m}, {go}, acc)[0];
-            return walk_back(m, in, go, acc, false);
         case K_CONCAT: return bwd_concat(m, in, go, acc);
-        case K_CONCATTABLE: {
-            vector<Val> gs;
-            for (size_t j = 0; j < m.kids.size(); ++j) gs.push_back(bwd(M(m.kids[j]), in, go.tab[j], acc));
-            return table_sum(m, gs);
-        }
         case K_LINEAR: case K_CONV: {
             if (acc) wg_before_dgrad();
             Val gi = dgrad(m, go);
@@ -1975,75 +1917,53 @@ struct Compiler {
     }
 
     // ---------------------------------------------------------------------------------------- nn.Sequential backward
-    Val walk_back(Mod& q, const Val& in, const Val& go, bool acc, bool root) {
-        MS& sq = S(q);
-        vector<Seg> pl = sq.ran;
-        if (!sq.ran_set) for (int t = 0; t < (int)q.kids.size(); ++t) pl.push_back(Seg{S_ONE, t, t + 1});
-        Val cur = go;
-        for (int si = (int)pl.size() - 1; si >= 0; --si) {
-            const Seg& sg = pl[si];
-            auto kid = [&](int t) -> Mod& { return M(q.kids[t]); };
-            Val inp = sg.i == 0 ? in : S(kid(sg.i - 1)).out;
-            if (sg.kind == S_ACT_POOL && S(kid(sg.i)).fused && S(kid(sg.i)).fG == 1) {
-                cur = bwd_act_pool({&kid(sg.i)}, {&kid(sg.i + 1)}, sg.j - sg.i == 3 ? vector<Mod*>{&kid(sg.i + 2)} : vector<Mod*>{}, {cur}, acc)[0];
-            } else if (sg.kind == S_GEMM_BN_ACT && S(kid(sg.i + 1)).bn_fused) {
-                cur = bwd_gemm_bn_act(kid(sg.i), kid(sg.i + 1), kid(sg.i + 2), inp, cur, acc);
-            } else if (sg.kind == S_CAT_DROP) {
-                cur = bwd_concat(kid(sg.i), inp, cur, acc, &kid(sg.i + 1));
-            } else if (sg.kind == S_HEAD && S(kid(sg.i)).head_fused) {
-                cur = bwd_head(kid(sg.i), kid(sg.i + 1), kid(sg.i + 2), cur, acc);
-            } else {   // S_ONE, S_GEMM_ACT (both outputs exist), or a chain whose forward ran unfused
-                for (int t = sg.j - 1; t >= sg.i; --t) {
-                    Val mi = t == sg.i ? inp : S(kid(t - 1)).out;
-                    cur = bwd(kid(t), mi, cur, acc);
-                }
-            }
-            if (root && acc) bucket_done(sg.i);
-            if (failed) break;
-        }
-        sq.gin = cur;
-        return cur;
-    }
-    vector<Val> gbwd_seq(const vector<Mod*>& qs, const vector<Val>& ins, const vector<Val>& gouts, bool acc, GCtx& ctx) {
+    // root: the net's own nn.Sequential, whose gradient buckets are complete segment by segment
+    vector<Val> gbwd_seq(const vector<Mod*>& qs, const vector<Val>& ins, const vector<Val>& gouts, bool acc, bool root) {
         vector<Val> cur = gouts;
         const int G = (int)qs.size();
         MS& s0 = S(*qs[0]);
         vector<Seg> pl = s0.ran;
         if (!s0.ran_set) for (int t = 0; t < (int)qs[0]->kids.size(); ++t) pl.push_back(Seg{S_ONE, t, t + 1});
         auto col = [&](int t) { vector<Mod*> c; for (Mod* q : qs) c.push_back(&M(q->kids[t])); return c; };
+        auto kid = [&](int b, int t) -> Mod& { return M(qs[b]->kids[t]); };
         for (int si = (int)pl.size() - 1; si >= 0; --si) {
             const Seg& sg = pl[si];
+            const int i = sg.i;
             vector<Val> inp;
-            if (sg.i == 0) inp = ins; else for (Mod* q : qs) inp.push_back(S(M(q->kids[sg.i - 1])).out);
-            bool done = false;
-            if (sg.kind == S_ACT_POOL) {
-                bool allG = true, all1 = true;
-                for (Mod* q : qs) { MS& f = S(M(q->kids[sg.i])); all1 = all1 && f.fused && f.fG == 1; }
-                MS& f0 = S(M(qs[0]->kids[sg.i]));
-                allG = f0.fused && f0.fG == G;
-                if (allG) {
-                    cur = bwd_act_pool(col(sg.i), col(sg.i + 1), sg.j - sg.i == 3 ? col(sg.i + 2) : vector<Mod*>{}, cur, acc); done = true;
-                } else if (all1) {   // the forward ran branch after branch
-                    vector<Val> nx;
-                    for (int b = 0; b < G; ++b) {
-                        Mod& q = *qs[b];
-                        nx.push_back(bwd_act_pool({&M(q.kids[sg.i])}, {&M(q.kids[sg.i + 1])}, sg.j - sg.i == 3 ? vector<Mod*>{&M(q.kids[sg.i + 2])} : vector<Mod*>{},
-                                                  {cur[b]}, acc)[0]);
+            if (i == 0) inp = ins; else for (int b = 0; b < G; ++b) inp.push_back(S(kid(b, i - 1)).out);
+            auto drops = [&](int b0, int b1) {   // the SpatialDropouts of an [activation, pool, dropout] segment, branches [b0, b1)
+                vector<Mod*> c; for (int b = b0; b < b1 && sg.j - i == 3; ++b) c.push_back(&kid(b, i + 2)); return c;
+            };
+            // what the forward left says how the segment ran: as one lockstep launch, as a fused launch per branch, or module by module
+            bool own = true;
+            for (int b = 0; b < G; ++b) {
+                switch (sg.kind) {
+                case S_ACT_POOL: own = own && S(kid(b, i)).fused && S(kid(b, i)).fG == 1; break;
+                case S_GEMM_BN_ACT: own = own && S(kid(b, i + 1)).bn_fused; break;
+                case S_CAT_DROP: break;   // bwd_concat takes the dropout behind it either way
+                case S_HEAD: own = own && S(kid(b, i)).head_fused; break;
+                default: own = false; break;
+                }
+            }
+            if (sg.kind == S_ACT_POOL && S(kid(0, i)).fused && S(kid(0, i)).fG == G) {
+                cur = bwd_act_pool(col(i), col(i + 1), drops(0, G), cur, acc);
+            } else if (own) {
+                for (int b = 0; b < G; ++b) {
+                    switch (sg.kind) {
+                    case S_ACT_POOL: cur[b] = bwd_act_pool({&kid(b, i)}, {&kid(b, i + 1)}, drops(b, b + 1), {cur[b]}, acc)[0]; break;
+                    case S_GEMM_BN_ACT: cur[b] = bwd_gemm_bn_act(kid(b, i), kid(b, i + 1), kid(b, i + 2), inp[b], cur[b], acc); break;
+                    case S_CAT_DROP: cur[b] = bwd_concat(kid(b, i), inp[b], cur[b], acc, &kid(b, i + 1)); break;
+                    default: cur[b] = bwd_head(kid(b, i), kid(b, i + 1), kid(b, i + 2), cur[b], acc); break;
                     }
-                    cur = nx; done = true;
                 }
-            } else if (sg.kind == S_GEMM_BN_ACT && S(M(qs[0]->kids[sg.i + 1])).bn_fused) {
-                vector<Val> nx;
-                for (int b = 0; b < G; ++b) { Mod& q = *qs[b]; nx.push_back(bwd_gemm_bn_act(M(q.kids[sg.i]), M(q.kids[sg.i + 1]), M(q.kids[sg.i + 2]), inp[b], cur[b], acc)); }
-                cur = nx; done = true;
-            }
-            if (!done) {
-                for (int t = sg.j - 1; t >= sg.i; --t) {
+            } else {   // S_ONE, S_GEMM_ACT (both outputs exist), or a chain whose forward ran unfused
+                for (int t = sg.j - 1; t >= i; --t) {
                     vector<Val> mi;
-                    if (t == sg.i) mi = inp; else for (Mod* q : qs) mi.push_back(S(M(q->kids[t - 1])).out);
-                    cur = gbwd(col(t), mi, cur, acc, ctx);
+                    if (t == i) mi = inp; else for (int b = 0; b < G; ++b) mi.push_back(S(kid(b, t - 1)).out);
+                    cur = gbwd(col(t), mi, cur, acc);
                 }
             }
+            if (root && acc) bucket_done(i);
             if (failed) break;
         }
         for (int b = 0; b < G; ++b) S(*qs[b]).gin = cur[b];
@@ -2059,33 +1979,31 @@ struct Compiler {
     vector<Val> gbwd_stackable(const vector<Mod*>& mods, const vector<Val>& ins, const vector<Val>& gouts, bool acc) {
         Mod& m0 = *mods[0];
         if (!ran_stacked(m0)) return gbwd_default(mods, ins, gouts, acc);
-        Val X, Gd;
+        Val X;
         stacked(ins, &X);
-        if (!stacked(gouts, &Gd)) {
-            const Val& like = (!S(m0).out.none && !S(m0).out.is_tab) ? S(m0).out : gouts[0];
-            Gd = restack(m0, gouts, like);
-        }
+        Val Gd = gather(m0, gouts, (!S(m0).out.none && !S(m0).out.is_tab) ? S(m0).out : gouts[0]);
         vector<Val> gs = split(bwd(m0, X, Gd, false), (int)mods.size());
         for (size_t b = 0; b < mods.size(); ++b) S(*mods[b]).gin = gs[b];
         return gs;
     }
-    vector<Val> gbwd(const vector<Mod*>& mods, const vector<Val>& ins, const vector<Val>& gouts, bool acc, GCtx& ctx) {
+    vector<Val> gbwd(const vector<Mod*>& mods, const vector<Val>& ins, const vector<Val>& gouts, bool acc, bool root = false) {
         Mod& m0 = *mods[0];
         const KTable* k = K();
         const int G = (int)mods.size();
+        if (G == 1 && m0.kind != K_SEQ && m0.kind != K_CONCATTABLE) return gbwd_default(mods, ins, gouts, acc);   // as in gfwd
         switch (m0.kind) {
         case K_SEQ:
             if (S(m0).loc_fused && S(m0).locG == G) return bwd_loc(mods, gouts, acc);
-            return gbwd_seq(mods, ins, gouts, acc, ctx);
+            return gbwd_seq(mods, ins, gouts, acc, root);
         case K_CONCATTABLE: {
             const size_t nch = m0.kids.size();
             vector<vector<Val>> per_child;
             for (size_t j = 0; j < nch; ++j) {
                 vector<Mod*> col; vector<Val> gj;
                 for (int b = 0; b < G; ++b) { col.push_back(&M(mods[b]->kids[j])); gj.push_back(gouts[b].tab[j]); }
-                per_child.push_back(gbwd(col, ins, gj, acc, ctx));
+                per_child.push_back(gbwd(col, ins, gj, acc));
             }
-            vector<Val> blocks; bool all = net->stacking;
+            vector<Val> blocks; bool all = net->stacking && G > 1;
             for (auto& c_ : per_child) {
                 Val B;
                 bool tens = true; for (auto& t : c_) tens = tens && !t.none && !t.is_tab;
@@ -2191,8 +2109,7 @@ struct Compiler {
             if (net->fusion && stacked(xs, &X) && n % 4 == 0 && G <= 4) {
                 // one launch for the G modules: stacked x / dy / dx, one slope and one gradient accumulator per group
                 vector<Val> gs; for (auto& g : gouts) gs.push_back(match_fmt(g, x0));
-                Val Gd;
-                if (!stacked(gs, &Gd)) Gd = restack(m0, gs, x0);
+                Val Gd = gather(m0, gs, x0);
                 Val bs = x0; bs.d[0] *= G;
                 Val dx = buf_like(m0, "gin.gblock", bs, x0.fmt);
                 if (acc) ws_need(cg_prelu_backward_grouped_workspace_bytes(G, n));
@@ -2217,8 +2134,7 @@ struct Compiler {
                 const Val img = ins[0].tab[0], grids = s0.shared_grids;
                 const Val& gr0 = ins[0].tab[1];
                 const long N = img.d[0], Hi = img.d[1], Wi = img.d[2], C = img.d[3], Ho = gr0.d[1], Wo = gr0.d[2];
-                Val Gd;
-                if (!stacked(gouts, &Gd)) Gd = restack(m0, gouts, gouts[0]);
+                Val Gd = gather(m0, gouts, gouts[0]);
                 Val gimg = buf(m0, "gimg.block", {G * N, Hi, Wi, C}), ggrid = buf(m0, "ggrid.block", {G * N, Ho, Wo, 2});
                 emit([=](Run& c) { return k->bilinear_sampler_backward_shared(c.CS(), G, c.P(img), c.P(grids), c.P(Gd), c.P(gimg), c.P(ggrid), (int)N, (int)Hi, (int)Wi,
                                                                               (int)C, (int)Ho, (int)Wo); });
@@ -2246,9 +2162,7 @@ struct Compiler {
         const Val X = st.fX, mask = st.fmask; const int G = st.fG;
         const long N = st.fN, C = st.fC, H = st.fH, W = st.fW;
         vector<Val> gs; for (auto& g : gouts) gs.push_back(as_nhwc(g));
-        Val Gd;
-        if (G == 1) Gd = gs[0];
-        else if (!stacked(gs, &Gd)) Gd = restack(a0, gs, gs[0]);
+        Val Gd = gather(a0, gs, gs[0]);
         Val dx = buf_like(a0, "gin.fused", X, NHWC);
         const int code = a0.kind == K_PRELU ? 1 : 2;
         const float slope = code == 1 ? 0.f : a0.fa[0];
@@ -2264,7 +2178,7 @@ struct Compiler {
                                               code == 1 ? al : nullptr, want ? ga : nullptr, c.scale, pool_max, want ? c.W() : nullptr,
                                               want ? c.WB() : 0);
         });
-        vector<Val> outs = G == 1 ? vector<Val>{dx} : split(dx, G);
+        vector<Val> outs = slices(dx, G);
         for (int b = 0; b < G; ++b) {
             S(*acts[b]).gin = outs[b]; S(*pools[b]).gin = Val();
             if (!drops.empty()) S(*drops[b]).gin = Val();
@@ -2357,11 +2271,9 @@ void Compiler::buckets_start() {
                 if (!wg_unjoined[s] || 4 + s == here) continue;
                 cs = 4 + s;
                 flush_wgrad();
-                emit([=](Run& c) { return c.net->trace ? (trace_note(c.net, "event|record|wgjoin" + std::to_string(s) + "|s" + std::to_string(4 + s)), 0)
-                                                        : (hipEventRecord(c.net->wg_join_ev[s], (hipStream_t)c.S(4 + s)) == hipSuccess ? 0 : 1); });
+                emit_event(EV_RECORD, EV_WGJOIN, s);
                 cs = here;
-                emit([=](Run& c) { return c.net->trace ? (trace_note(c.net, "event|wait|wgjoin" + std::to_string(s) + "|s" + std::to_string(here)), 0)
-                                                        : (hipStreamWaitEvent((hipStream_t)c.S(here), c.net->wg_join_ev[s], 0) == hipSuccess ? 0 : 1); });
+                emit_event(EV_WAIT, EV_WGJOIN, s);
                 wg_unjoined[s] = false;
             }
             wg_unjoined[s_] = false;
@@ -2727,11 +2639,12 @@ int cg_net_forward(void* net, void* stream, const float* x, int nd, const long* 
         pr->in = in;
         Compiler C(n, pr.get());
         C.ops = &pr->fwd;
-        pr->out = C.fwd(*n->mods[0], in);
+        GCtx ctx{{C.rng}};   // the root module: a group of one at the start of the pass's draws
+        pr->out = C.gfwd({n->mods[0].get()}, {in}, ctx)[0];
         if (C.failed) return cg::fail("%s", n->err);
         CG_REQUIRE(!pr->out.is_tab, "cg_net_forward: the root module returns a table");
         pr->out = C.materialise(pr->out);
-        pr->draws = C.rng;
+        pr->draws = ctx.cur[0];
         if (ensure_streams(n, std::max(pr->nstreams, n->pack_overlap && pr->ups_first_op.size() >= 2 ? 2 : 1), stream)) return 1;
         if (settle_allocs(n)) return 1;
         it = n->progs.emplace(key, std::move(pr)).first;
@@ -2801,7 +2714,7 @@ int cg_net_backward(void* net, void* stream, const float* x, const float* gy, in
         }
         C.bucket_done_upto = (int)root.kids.size();
         Val go = pr->out; go.ext = EXT_GY; go.off = 0; go.p = nullptr; go.fmt = gy_fmt; go.blk = 0; go.gi = go.gc = 0;
-        Val gi = root.kind == K_SEQ ? C.walk_back(root, pr->in, go, acc != 0, true) : C.bwd(root, pr->in, go, acc != 0);
+        Val gi = C.gbwd({&root}, {pr->in}, {go}, acc != 0, true)[0];
         if (C.failed) return cg::fail("%s", n->err);
         if (acc) { C.buckets_start(); C.flush_wgrad(); C.wg_join_all(); }
         CG_REQUIRE(!gi.is_tab, "cg_net_backward: the root module's gradInput is a table");

@@ -4,7 +4,17 @@ flow, counter-stream offsets - against the round-2 Python executor they replace 
 that executor was deleted; regenerate only for a deliberate change of the plan.
 
     python tests/golden/make_net_plan_golden.py
+
+The variant matrix (VARIANTS below) pins the shipped default configuration and every option that decides which path the planner
+takes: three cases as full text (net_plan_variant_*.txt), all the others as a SHA-1 of that text (net_plan_variants.json).
+
+    python tests/golden/make_net_plan_golden.py --variants             # rewrite the variant fixtures
+    python tests/golden/make_net_plan_golden.py --print <variant id>   # one case's text on stdout, to diff two builds of the library
+    python tests/golden/make_net_plan_golden.py --dump <directory>     # every case's text, one file per variant
+    python tests/golden/make_net_plan_golden.py --list                 # the variant ids
 """
+import hashlib
+import json
 import os
 import sys
 
@@ -29,8 +39,67 @@ def text(which, N):
     return "\n".join(out) + "\n"
 
 
+# ---- the variant matrix: (network, batch) x (options over the default), plus the data-parallel cases
+VARIANT_NETS = [("D32_st3", 8), ("D32_st3", 128), ("D32_st3@64", 4), ("G32up-c", 8), ("G32up-c", 128), ("G32up", 16), ("G32up", 256)]
+VARIANT_OPTIONS = [(), (("grouped", 0),), (("stacking", 0),), (("fusion", 0),), (("fuse_locnet", 0),), (("fuse_locnet", 2),), (("view_fuse", 0),),
+                   (("cat_fuse", 0),), (("head_fuse", 0),), (("defer_wgrad", 0),), (("share_pool", 0), ("sampler_shared", 0)),
+                   (("overlap_groups", 0),), (("wgrad_stream", 0),), (("wino_dsplit", 0),), (("winograd22", 0),), (("winograd22", 1),)]
+VARIANT_DP = [(w, 8, dict(world=2, buckets=b)) for w in ("G32up-c", "D32_st3") for b in (True, False)]
+FULL_TEXT = ["D32_st3-N8-default", "G32up-c-N8-default", "D32_st3-N8-grouped=0"]      # committed whole; the others as digests
+DIGESTS = os.path.join(HERE, "net_plan_variants.json")
+
+
+def variant_id(which, N, options=(), dp=None):
+    tag = "+".join(f"{k}={v}" for k, v in options) or "default"
+    if dp:
+        tag = "world%d-%s" % (dp["world"], "buckets" if dp["buckets"] else "nobuckets")
+    return f"{which}-N{N}-{tag}"
+
+
+VARIANTS = {variant_id(w, n, o): (w, n, o, None) for w, n in VARIANT_NETS for o in VARIANT_OPTIONS}
+VARIANTS.update({variant_id(w, n, (), dp): (w, n, (), dp) for w, n, dp in VARIANT_DP})
+
+
+def variant_text(vid):
+    which, N, options, dp = VARIANTS[vid]
+    r = T.trace(which, N, options=list(options), dp=dp)
+    out = [f"# {vid}: draws {r['draws']}", "# stats " + " ".join(f"{k}={v}" for k, v in sorted(r["stats"].items()))]
+    for phase in ("first_forward", "forward", "backward", "updateGradInput"):
+        out.append(f"## {phase}")
+        out += T.canon(r[phase])
+    return "\n".join(out) + "\n"
+
+
+def variant_file(vid):
+    return os.path.join(HERE, "net_plan_variant_%s.txt" % vid.replace("@", "_at_").replace("=", ""))
+
+
+def digest(txt):
+    return hashlib.sha1(txt.encode()).hexdigest()
+
+
 if __name__ == "__main__":
-    for which, N in CASES:
-        fn = os.path.join(HERE, "net_plan_%s_N%d.txt" % (which.replace("@", "_at_"), N))
-        open(fn, "w").write(text(which, N))
-        print(fn)
+    if sys.argv[1:2] == ["--list"]:
+        print("\n".join(VARIANTS))
+    elif sys.argv[1:2] == ["--print"]:
+        sys.stdout.write(variant_text(sys.argv[2]))
+    elif sys.argv[1:2] == ["--dump"]:          # every case's text into a directory
+        os.makedirs(sys.argv[2], exist_ok=True)
+        for vid in VARIANTS:
+            open(os.path.join(sys.argv[2], vid + ".txt"), "w").write(variant_text(vid))
+    elif sys.argv[1:2] == ["--variants"]:
+        sums = {}
+        for vid in VARIANTS:
+            txt = variant_text(vid)
+            if vid in FULL_TEXT:
+                open(variant_file(vid), "w").write(txt)
+                print(variant_file(vid))
+            else:
+                sums[vid] = digest(txt)
+        json.dump(sums, open(DIGESTS, "w"), indent=0, sort_keys=True)
+        print(DIGESTS, len(sums), "digests")
+    else:
+        for which, N in CASES:
+            fn = os.path.join(HERE, "net_plan_%s_N%d.txt" % (which.replace("@", "_at_"), N))
+            open(fn, "w").write(text(which, N))
+            print(fn)

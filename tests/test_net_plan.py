@@ -3,12 +3,14 @@ stub generated from include/catgan.h, so a whole forward / backward of G32up-c /
 640-711,814-906) leaves its launch sequence as text.  What is pinned here:
   * the sequence itself (tests/golden/net_plan_*.txt: entry points, geometry, data flow, counter-stream offsets) - the fixtures
     were checked launch for launch against the round-2 Python executor before it was deleted (make_net_plan_golden.py);
+  * the same for the default configuration and one option at a time over it (net_plan_variant_*.txt, net_plan_variants.json);
   * the structure of the plan: fused segments, grouped / stacked / shared launches of D's three identical branches, the other
     branch group on a side stream between fork / join events, deferred reductions flushed once;
   * data flow: nothing reads a buffer no earlier launch (or the host) wrote;
   * the dropout draws follow the oracle's module-after-module order;
   * data parallelism: sync-BN sums exchanged between statistics and normalisation, gradient buckets started as their layers finish.
 The arithmetic of every launch is the GPU suite's business (tests/test_gpu_parity*.py run the same plans on the MI355X)."""
+import json
 import os
 import re
 import sys
@@ -20,6 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import plan_trace as T  # noqa: E402
+import make_net_plan_golden as G  # noqa: E402
 from make_net_plan_golden import CASES, text  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 
@@ -32,6 +35,28 @@ def test_plan_equals_the_golden_launch_sequence(which, N):
     for i, (a, b) in enumerate(zip(got, want)):
         assert a == b, f"{which} N={N}: line {i} differs\n  plan  : {a[:300]}\n  golden: {b[:300]}"
     assert len(got) == len(want)
+
+
+@pytest.mark.parametrize("vid", list(G.VARIANTS))
+def test_plan_variants_equal_the_recorded_sequences(vid, tmp_path):
+    """The shipped default configuration and every option that decides which path the planner takes, over both networks at small and
+    benchmarked batch sizes and the data-parallel cases: first pass, forward, backward and updateGradInput in canonical form, with the
+    draw count and the plan's statistics.  The fixtures were recorded on the parent commit of the change that made a lone module a
+    lockstep group of one (one tree walker in csrc/net.hip instead of two) and are not regenerated: that walker must emit exactly
+    what the single-branch walker emitted.  Three cases are kept as text, the others as a SHA-1 of it;
+    `make_net_plan_golden.py --print <id>` writes a case's text for a diff between two builds."""
+    got = G.variant_text(vid)
+    if vid in G.FULL_TEXT:
+        want = open(G.variant_file(vid)).read()
+        for i, (a, b) in enumerate(zip(got.split("\n"), want.split("\n"))):
+            assert a == b, f"{vid}: line {i} differs\n  plan    : {a[:300]}\n  recorded: {b[:300]}"
+        assert len(got) == len(want)
+        return
+    want = json.load(open(G.DIGESTS))[vid]
+    if G.digest(got) != want:
+        fn = tmp_path / (vid + ".txt")
+        fn.write_text(got)
+        pytest.fail(f"{vid}: the plan's text (written to {fn}) has SHA-1 {G.digest(got)}, recorded {want}")
 
 
 def test_segments_and_lockstep_branches_of_the_discriminator():
