@@ -315,46 +315,68 @@ __device__ __forceinline__ float scale_axis(const float* w, int base, int Ls, in
     return __fdiv_rn(acc, n);
 #undef s
 }
-__global__ void images_u8_scale_k(const unsigned char* __restrict__ src, float* __restrict__ dst, int N, int Hs, int Ws, int Hd, int Wd, int cs) {
+// output element i = (n, oy, ox) of the pool from the one source image `im`: both scaling kernels' whole arithmetic
+__device__ __forceinline__ void scale_pixel(const unsigned char* __restrict__ im, float* __restrict__ dst, long i, int ox, int oy, int Hs, int Ws,
+                                            int Hd, int Wd, int cs) {
 #pragma clang fp contract(off)
+    // vertical footprint of this output row (the second pass reads the first pass's fp32 rows)
+    int y0 = oy, y1 = oy;
+    if (Hd < Hs) {
+        const float scale = __fdiv_rn((float)Hs, (float)Hd);
+        y0 = oy == 0 ? 0 : (int)((float)oy * scale);
+        y1 = min(Hs - 1, (int)((float)(oy + 1) * scale));
+    } else if (Hd > Hs) {
+        const float scale = __fdiv_rn((float)(Hs - 1), (float)(Hd - 1));
+        y0 = (oy == Hd - 1 || Hs == 1) ? Hs - 1 : (int)((float)oy * scale);
+        y1 = min(Hs - 1, y0 + 1);
+    }
+    float rgb[3];
+    for (int c = 0; c < 3; ++c) {
+        float col[8];   // first pass at column ox for the source rows y0..y1 (<= 8 rows: down-scaling factors up to 6)
+        for (int y = y0; y <= y1 && y - y0 < 8; ++y) {
+            // horizontal footprint of ox in row y
+            int x0 = ox, x1 = ox;
+            if (Wd < Ws) {
+                const float sc = __fdiv_rn((float)Ws, (float)Wd);
+                x0 = ox == 0 ? 0 : (int)((float)ox * sc);
+                x1 = min(Ws - 1, (int)((float)(ox + 1) * sc));
+            } else if (Wd > Ws) {
+                const float sc = __fdiv_rn((float)(Ws - 1), (float)(Wd - 1));
+                x0 = (ox == Wd - 1 || Ws == 1) ? Ws - 1 : (int)((float)ox * sc);
+                x1 = min(Ws - 1, x0 + 1);
+            }
+            float row[8];
+            for (int x = x0; x <= x1 && x - x0 < 8; ++x) row[x - x0] = __fdiv_rn((float)im[((long)y * Ws + x) * 3 + c], 255.f);
+            col[y - y0] = scale_axis(row, x0, Ws, Wd, ox);
+        }
+        rgb[c] = scale_axis(col, y0, Hs, Hd, oy);
+    }
+    store_colorspace(dst, i, rgb[0], rgb[1], rgb[2], cs);
+}
+// output pixel i of an image that has no source (a gathered index outside the set): every plane zero
+__device__ __forceinline__ void store_zero_pixel(float* dst, long i, int cs) {
+    if (cs == CS_Y) dst[i] = 0.f;
+    else { dst[3 * i] = 0.f; dst[3 * i + 1] = 0.f; dst[3 * i + 2] = 0.f; }
+}
+__global__ void images_u8_scale_k(const unsigned char* __restrict__ src, float* __restrict__ dst, int N, int Hs, int Ws, int Hd, int Wd, int cs) {
     const long total = (long)N * Hd * Wd;
     GRID_STRIDE(i, total) {
         const int ox = (int)(i % Wd), oy = (int)((i / Wd) % Hd);
         const long n = i / ((long)Wd * Hd);
-        const unsigned char* im = src + n * (long)Hs * Ws * 3;
-        // vertical footprint of this output row (the second pass reads the first pass's fp32 rows)
-        int y0 = oy, y1 = oy;
-        if (Hd < Hs) {
-            const float scale = __fdiv_rn((float)Hs, (float)Hd);
-            y0 = oy == 0 ? 0 : (int)((float)oy * scale);
-            y1 = min(Hs - 1, (int)((float)(oy + 1) * scale));
-        } else if (Hd > Hs) {
-            const float scale = __fdiv_rn((float)(Hs - 1), (float)(Hd - 1));
-            y0 = (oy == Hd - 1 || Hs == 1) ? Hs - 1 : (int)((float)oy * scale);
-            y1 = min(Hs - 1, y0 + 1);
-        }
-        float rgb[3];
-        for (int c = 0; c < 3; ++c) {
-            float col[8];   // first pass at column ox for the source rows y0..y1 (<= 8 rows: down-scaling factors up to 6)
-            for (int y = y0; y <= y1 && y - y0 < 8; ++y) {
-                // horizontal footprint of ox in row y
-                int x0 = ox, x1 = ox;
-                if (Wd < Ws) {
-                    const float sc = __fdiv_rn((float)Ws, (float)Wd);
-                    x0 = ox == 0 ? 0 : (int)((float)ox * sc);
-                    x1 = min(Ws - 1, (int)((float)(ox + 1) * sc));
-                } else if (Wd > Ws) {
-                    const float sc = __fdiv_rn((float)(Ws - 1), (float)(Wd - 1));
-                    x0 = (ox == Wd - 1 || Ws == 1) ? Ws - 1 : (int)((float)ox * sc);
-                    x1 = min(Ws - 1, x0 + 1);
-                }
-                float row[8];
-                for (int x = x0; x <= x1 && x - x0 < 8; ++x) row[x - x0] = __fdiv_rn((float)im[((long)y * Ws + x) * 3 + c], 255.f);
-                col[y - y0] = scale_axis(row, x0, Ws, Wd, ox);
-            }
-            rgb[c] = scale_axis(col, y0, Hs, Hd, oy);
-        }
-        store_colorspace(dst, i, rgb[0], rgb[1], rgb[2], cs);
+        scale_pixel(src + n * (long)Hs * Ws * 3, dst, i, ox, oy, Hs, Ws, Hd, Wd, cs);
+    }
+}
+// The same over a set that stays resident in device memory (dataset.ResidentSet): image n of the pool comes from set[idx[n]], read in
+// place - the gathered bytes are never copied.  The set may exceed 2^31 bytes: the image's base is a 64-bit product.
+__global__ void images_u8_gather_scale_k(const unsigned char* __restrict__ set, long M, const int32_t* __restrict__ idx, float* __restrict__ dst,
+                                         int N, int Hs, int Ws, int Hd, int Wd, int cs) {
+    const long total = (long)N * Hd * Wd;
+    GRID_STRIDE(i, total) {
+        const int ox = (int)(i % Wd), oy = (int)((i / Wd) % Hd);
+        const long n = i / ((long)Wd * Hd);
+        const long m = idx[n];
+        if (m < 0 || m >= M) store_zero_pixel(dst, i, cs);
+        else scale_pixel(set + m * ((long)Hs * Ws * 3), dst, i, ox, oy, Hs, Ws, Hd, Wd, cs);
     }
 }
 
@@ -385,13 +407,12 @@ __device__ __forceinline__ void warp_taps(float s, int L, int* i0, int* i1, floa
     *f = s - (float)*i0;
     *i1 = min(*i0 + 1, L - 1);
 }
-__global__ void __launch_bounds__(256) images_u8_augment_k(const unsigned char* __restrict__ src, float* __restrict__ dst, int Hs, int Ws,
-                                                            int Hd, int Wd, int cs, const float* __restrict__ desc, float sigma,
-                                                            uint64_t seed, uint64_t offset) {
+// image n of the pool (this workgroup's) from the one source image `im`: both augmentation kernels' whole arithmetic.  n, not the
+// image's place in its set, numbers the noise counters
+__device__ __forceinline__ void augment_image(const unsigned char* __restrict__ im, long n, float* __restrict__ dst, int Hs, int Ws, int Hd, int Wd,
+                                              int cs, const float* __restrict__ desc, float sigma, uint64_t seed, uint64_t offset) {
 #pragma clang fp contract(off)
     extern __shared__ float aug_p[];   // [Hs][Ws][3]
-    const long n = blockIdx.x;
-    const unsigned char* im = src + n * (long)Hs * Ws * 3;
     const float* d = desc + n * 8;
     const float m00 = d[0], m01 = d[1], m02 = d[2], m10 = d[3], m11 = d[4], m12 = d[5], bright = d[6];
     const bool flip = d[7] != 0.f;
@@ -458,6 +479,24 @@ __global__ void __launch_bounds__(256) images_u8_augment_k(const unsigned char* 
         for (int c = 0; c < 3; ++c) rgb[c] = scale_axis(col[c], y0, Hs, Hd, oy);
         store_colorspace(dst, n * (long)Hd * Wd + e, rgb[0], rgb[1], rgb[2], cs);
     }
+}
+__global__ void __launch_bounds__(256) images_u8_augment_k(const unsigned char* __restrict__ src, float* __restrict__ dst, int Hs, int Ws,
+                                                            int Hd, int Wd, int cs, const float* __restrict__ desc, float sigma,
+                                                            uint64_t seed, uint64_t offset) {
+    const long n = blockIdx.x;
+    augment_image(src + n * (long)Hs * Ws * 3, n, dst, Hs, Ws, Hd, Wd, cs, desc, sigma, seed, offset);
+}
+// the gather form (images_u8_gather_scale_k's addressing): the whole workgroup takes the same branch, so the barrier inside stays uniform
+__global__ void __launch_bounds__(256) images_u8_gather_augment_k(const unsigned char* __restrict__ set, long M, const int32_t* __restrict__ idx,
+                                                                   float* __restrict__ dst, int Hs, int Ws, int Hd, int Wd, int cs,
+                                                                   const float* __restrict__ desc, float sigma, uint64_t seed, uint64_t offset) {
+    const long n = blockIdx.x;
+    const long m = idx[n];
+    if (m < 0 || m >= M) {
+        for (int e = threadIdx.x; e < Hd * Wd; e += 256) store_zero_pixel(dst, n * (long)Hd * Wd + e, cs);
+        return;
+    }
+    augment_image(set + m * ((long)Hs * Ws * 3), n, dst, Hs, Ws, Hd, Wd, cs, desc, sigma, seed, offset);
 }
 
 // ---------------------------------------------------------------- activations
@@ -1628,12 +1667,9 @@ int cg_images_u8_scale_to_f32(void* stream, const unsigned char* src, float* dst
     EW_LAUNCH(images_u8_scale_k, total, src, dst, N, Hs, Ws, Hd, Wd, colorspace); return 0;
 }
 
-int cg_images_u8_augment_to_f32(void* stream, const unsigned char* src, float* dst, int N, int Hs, int Ws, int Hd, int Wd, int colorspace,
-                                const float* desc, float noise_std, uint64_t seed, uint64_t offset) {
-    CG_REQUIRE(src && dst && desc && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && colorspace >= CS_RGB && colorspace <= CS_HSL &&
-               noise_std >= 0.f, "cg_images_u8_augment_to_f32: bad arguments");
-    CG_REQUIRE(Hs <= 6 * Hd && Ws <= 6 * Wd, "cg_images_u8_augment_to_f32: down-scaling by more than 6 is not supported");
-    // the pixel stage of one image in the LDS: 64 x 64 sources take 48 KB (three workgroups per CU); above 64 KB a kernel has to ask
+// the pixel stage of one image in the LDS: 64 x 64 sources take 48 KB (three workgroups per CU); above 64 KB a kernel has to ask.  Both
+// augmentation kernels ask together, so one record per thread serves them
+static int augment_lds(const char* who, int Hs, int Ws, long* lds_out) {
     static thread_local int lds_dev = -1, lds_max = 0, lds_asked = 0;
     int dev = 0;
     CG_HIP(hipGetDevice(&dev));
@@ -1642,14 +1678,47 @@ int cg_images_u8_augment_to_f32(void* stream, const unsigned char* src, float* d
         lds_dev = dev; lds_asked = 0;
     }
     const long lds = (long)Hs * Ws * 3 * sizeof(float);
-    CG_REQUIRE(lds <= lds_max, "cg_images_u8_augment_to_f32: a %d x %d source needs %ld bytes of LDS, the device has %d per workgroup", Ws, Hs,
-               lds, lds_max);
+    CG_REQUIRE(lds <= lds_max, "%s: a %d x %d source needs %ld bytes of LDS, the device has %d per workgroup", who, Ws, Hs, lds, lds_max);
     if (lds > 65536 && lds > lds_asked) {
         CG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(images_u8_augment_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
+        CG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(images_u8_gather_augment_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
         lds_asked = lds_max;
     }
+    *lds_out = lds;
+    return 0;
+}
+
+int cg_images_u8_augment_to_f32(void* stream, const unsigned char* src, float* dst, int N, int Hs, int Ws, int Hd, int Wd, int colorspace,
+                                const float* desc, float noise_std, uint64_t seed, uint64_t offset) {
+    CG_REQUIRE(src && dst && desc && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && colorspace >= CS_RGB && colorspace <= CS_HSL &&
+               noise_std >= 0.f, "cg_images_u8_augment_to_f32: bad arguments");
+    CG_REQUIRE(Hs <= 6 * Hd && Ws <= 6 * Wd, "cg_images_u8_augment_to_f32: down-scaling by more than 6 is not supported");
+    long lds = 0;
+    if (int rc = augment_lds("cg_images_u8_augment_to_f32", Hs, Ws, &lds)) return rc;
     hipLaunchKernelGGL(images_u8_augment_k, dim3(N), dim3(256), (size_t)lds, cg::S(stream), src, dst, Hs, Ws, Hd, Wd, colorspace, desc, noise_std,
                        seed, offset);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+int cg_images_u8_gather_scale_to_f32(void* stream, const unsigned char* set, long M, const int32_t* idx, float* dst, int N, int Hs, int Ws,
+                                     int Hd, int Wd, int colorspace) {
+    CG_REQUIRE(set && idx && dst && M > 0 && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && colorspace >= CS_RGB && colorspace <= CS_HSL,
+               "cg_images_u8_gather_scale_to_f32: bad arguments");
+    CG_REQUIRE(Hs <= 6 * Hd && Ws <= 6 * Wd, "cg_images_u8_gather_scale_to_f32: down-scaling by more than 6 is not supported");
+    const long total = (long)N * Hd * Wd;
+    EW_LAUNCH(images_u8_gather_scale_k, total, set, M, idx, dst, N, Hs, Ws, Hd, Wd, colorspace); return 0;
+}
+
+int cg_images_u8_gather_augment_to_f32(void* stream, const unsigned char* set, long M, const int32_t* idx, float* dst, int N, int Hs, int Ws,
+                                       int Hd, int Wd, int colorspace, const float* desc, float noise_std, uint64_t seed, uint64_t offset) {
+    CG_REQUIRE(set && idx && dst && desc && M > 0 && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && colorspace >= CS_RGB &&
+               colorspace <= CS_HSL && noise_std >= 0.f, "cg_images_u8_gather_augment_to_f32: bad arguments");
+    CG_REQUIRE(Hs <= 6 * Hd && Ws <= 6 * Wd, "cg_images_u8_gather_augment_to_f32: down-scaling by more than 6 is not supported");
+    long lds = 0;
+    if (int rc = augment_lds("cg_images_u8_gather_augment_to_f32", Hs, Ws, &lds)) return rc;
+    hipLaunchKernelGGL(images_u8_gather_augment_k, dim3(N), dim3(256), (size_t)lds, cg::S(stream), set, M, idx, dst, Hs, Ws, Hd, Wd, colorspace,
+                       desc, noise_std, seed, offset);
     CG_LAUNCH_CHECK();
     return 0;
 }

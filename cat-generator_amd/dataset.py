@@ -19,9 +19,26 @@ SequentialLoader is the same pipeline over a given file list, in order, in chunk
 search of sample.py --neighbours (nn_utils.findClosestNeighboursOnDevice), which never holds the set.
 
 setAugmentation turns on the augmentation the reference only has as an offline tool (dataset/generate_dataset.py): both loaders then
-draw fresh variants for every epoch pool (augment_images on the host, cg_images_u8_augment_to_f32 on the device, bit-equal)."""
+draw fresh variants for every epoch pool (augment_images on the host, cg_images_u8_augment_to_f32 on the device, bit-equal).
+
+A pack (buildPack / openPack, written by pack_dataset.py) holds a directory's files decoded once, as 8-bit RGB.  ResidentSet keeps a
+pack's pixels in device memory for the whole run and ResidentLoader makes every epoch pool a gather out of it
+(cg_images_u8_gather_scale_to_f32 / cg_images_u8_gather_augment_to_f32) on the training stream: the generator's draws and the pixel
+arithmetic are loadRandomImages', so the pools are too, and no file is decoded after the pack was built.
+
+The pack file images_u8.cgpack, all integers little endian:
+    offset 0   8 bytes   the magic b"CGPACK01" (the last two bytes are the layout's version)
+           8   uint64    M, the number of images
+          16   uint32    Hs      20  uint32  Ws      24  uint32  3 (channels)      28  uint32  0
+          32   uint64    the byte length of the freshness table
+          40   uint64    the offset of the pixel block, a multiple of 4096 (so that the block can be memory-mapped)
+          48   the freshness table: per file, in loadPaths()' sorted order, uint16 length of the base name, the base name (UTF-8), uint64
+               size of the file in bytes, int64 st_mtime_ns - what openPack compares with the directory as it is now
+          ...  zeros up to the pixel block: uint8 [M][Hs][Ws][3], image i = _decode(paths[i]); the file ends with it"""
 import os
+import struct
 import threading
+import warnings
 
 import numpy as np
 
@@ -78,16 +95,20 @@ def restore_state(state):
     _prefetch_state = None
 
 
-def loadPaths():
-    """dataset.lua:57-83: every file with the extension in every directory, sorted."""
-    global paths
+def _list(ds_):
     files = []
-    for d in dirs:
+    for d in ds_:
         for f in os.listdir(d):
             if f.lower().endswith("." + fileExtension.lower()):
                 files.append(os.path.join(d, f))
     files.sort()
-    paths = files
+    return files
+
+
+def loadPaths():
+    """dataset.lua:57-83: every file with the extension in every directory, sorted."""
+    global paths
+    paths = _list(dirs)
     return paths
 
 
@@ -150,14 +171,18 @@ class _Data:
         return self.scaled[i]
 
 
-def _pick(count):
-    """The files of one load: a fresh permutation of the sorted paths, its first `count` entries (dataset.lua:158-163)."""
+def _pick_indices(count):
+    """The files of one load as indices into the sorted paths: a fresh permutation, its first `count` entries (dataset.lua:158-163)."""
     if paths is None:
         loadPaths()
     if not paths:
         raise FileNotFoundError(f"no *.{fileExtension} images under {dirs}")
-    shuffle = _rs.permutation(len(paths))
-    return [paths[shuffle[i]] for i in range(min(len(paths), count))]
+    return _rs.permutation(len(paths))[:min(len(paths), count)]
+
+
+def _pick(count):
+    """The files of one load (the same single draw as _pick_indices)."""
+    return [paths[i] for i in _pick_indices(count)]
 
 
 def pickFiles(count):
@@ -597,3 +622,270 @@ class SequentialLoader(AsyncLoader):
 
     def close(self):
         self._release()
+
+
+# ---------------------------------------------------------------- the decoded set, packed on disk and resident on the device
+PACK_NAME = "images_u8.cgpack"
+PACK_MAGIC = b"CGPACK01"
+_PACK_HEAD = struct.Struct("<8sQIIIIQQ")      # magic, M, Hs, Ws, channels, 0, table bytes, pixel offset
+PACK_MAX_THREADS = 16
+
+
+def packPath(d):
+    return os.path.join(d, PACK_NAME)
+
+
+def _freshness(files):
+    """The table of the pack's header for these files as they are on disk now."""
+    out = []
+    for f in files:
+        st = os.stat(f)
+        name = os.path.basename(f).encode("utf-8")
+        out.append(struct.pack("<H", len(name)) + name + struct.pack("<Qq", st.st_size, st.st_mtime_ns))
+    return b"".join(out)
+
+
+def buildPack(d, threads=8):
+    """Decode every file loadPaths() lists for directory d (sorted; _decode) into d/images_u8.cgpack, image i = paths[i].  `threads`
+    workers (at most PACK_MAX_THREADS) each write the slots of their own images, so the file does not depend on their number; it appears
+    under its name only once it is complete (os.replace).  Every file must have the first one's size: a directory of mixed sizes stays
+    with the file loaders, and the error names the files that differ.  Returns (path, M)."""
+    files = _list([d])
+    if not files:
+        raise FileNotFoundError(f"no *.{fileExtension} images under {d}")
+    threads = max(1, min(int(threads), PACK_MAX_THREADS))
+    table = _freshness(files)
+    first = _decode(files[0])
+    Hs, Ws = first.shape[:2]
+    M = len(files)
+    offset = -(-(_PACK_HEAD.size + len(table)) // 4096) * 4096
+    tmp = packPath(d) + ".tmp%d" % os.getpid()
+    try:
+        with open(tmp, "wb") as f:
+            f.write(_PACK_HEAD.pack(PACK_MAGIC, M, Hs, Ws, 3, 0, len(table), offset))
+            f.write(table)
+            f.truncate(offset + M * Hs * Ws * 3)
+        px = np.memmap(tmp, dtype=np.uint8, mode="r+", offset=offset, shape=(M, Hs, Ws, 3))
+        odd = []
+
+        def work(a):      # a run of consecutive images per task: a 64 x 64 decode is too short to be a task of its own
+            for i in range(a, min(a + 64, M)):
+                im = first if i == 0 else _decode(files[i])
+                if im.shape != (Hs, Ws, 3):
+                    odd.append((i, "%s (%dx%d)" % (files[i], im.shape[1], im.shape[0])))
+                else:
+                    px[i] = im
+        if threads == 1:
+            for a in range(0, M, 64):
+                work(a)
+        else:
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(max_workers=threads) as ex:
+                list(ex.map(work, range(0, M, 64)))
+        if odd:
+            names = ", ".join(n for _, n in sorted(odd)[:8]) + (" ..." if len(odd) > 8 else "")
+            raise ValueError(f"buildPack: {len(odd)} file(s) are not {Ws}x{Hs} like {files[0]}: {names} - a pack holds one source size")
+        px.flush()
+        del px
+        os.replace(tmp, packPath(d))
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return packPath(d), M
+
+
+class Pack:
+    """An open pack: M images of Hs x Ws, `pixels` the memory-mapped uint8 [M][Hs][Ws][3] block, `paths` the files they were decoded from
+    (paths[i] -> pixels[i])."""
+
+    def __init__(self, path, files, pixels):
+        self.path, self.paths, self.pixels = path, files, pixels
+        self.M, self.Hs, self.Ws = pixels.shape[:3]
+
+
+def openPack(d):
+    """The pack of directory d, mapped, if it describes the directory as it is now - else None after one warning that says why (no pack
+    file; a foreign magic; a truncated file; the files listed now differ from the freshness table in name, size or modification time).
+    A stale or damaged pack is never an error and never used: the file loaders serve the directory as before."""
+    path = packPath(d)
+
+    def refuse(why):
+        warnings.warn(f"{path}: {why} - not used (pack_dataset.py --dataDir {d} writes a fresh one)")
+        return None
+    if not os.path.isfile(path):
+        return refuse("no such file")
+    size = os.path.getsize(path)
+    with open(path, "rb") as f:
+        head = f.read(_PACK_HEAD.size)
+        if len(head) < _PACK_HEAD.size or head[:8] != PACK_MAGIC:
+            return refuse("not a pack of this version (magic %r)" % head[:8])
+        _, M, Hs, Ws, C, _, tbytes, offset = _PACK_HEAD.unpack(head)
+        if C != 3 or M < 1 or Hs < 1 or Ws < 1 or offset % 4096 or offset < _PACK_HEAD.size + tbytes:
+            return refuse("a damaged header")
+        if size != offset + M * Hs * Ws * 3:
+            return refuse("truncated (%d bytes, the header promises %d)" % (size, offset + M * Hs * Ws * 3))
+        table = f.read(tbytes)
+    files = _list([d])
+    if len(files) != M:
+        return refuse("stale: it holds %d images, the directory %d" % (M, len(files)))
+    if table != _freshness(files):
+        return refuse("stale: a file was renamed, rewritten or touched since it was built")
+    return Pack(path, files, np.memmap(path, dtype=np.uint8, mode="r", offset=offset, shape=(M, Hs, Ws, 3)))
+
+
+def _check_resident(who, Hs, Ws, aug):
+    if Hs > 6 * height or Ws > 6 * width:
+        raise ValueError(f"{who}: {Ws}x{Hs} sources are more than 6x the {width}x{height} target (the kernels' limit)")
+    if aug and Hs * Ws * 12 > AUG_LDS_BYTES:
+        raise ValueError(f"{who}: {Ws}x{Hs} sources do not fit the augmentation kernel's LDS")
+
+
+class ResidentSet:
+    """A pack's pixel block in device memory, uploaded once: uint8 [M][Hs][Ws][3] at `ptr`.  The buffer belongs to this object (close(), or
+    its collection, frees it).  An allocation that fails raises (CatganError) before anything is kept: the caller falls back."""
+
+    UPLOAD_BYTES = 64 << 20
+
+    def __init__(self, pack):
+        import ctypes
+        from .tensor import lib, stream
+        self.L, self.paths = lib(), list(pack.paths)
+        self.M, self.Hs, self.Ws = int(pack.M), int(pack.Hs), int(pack.Ws)
+        self.per = self.Hs * self.Ws * 3
+        self.nbytes = self.M * self.per
+        dev = ctypes.c_void_p()
+        self.ptr = None
+        self.L.malloc(ctypes.byref(dev), self.nbytes)
+        self.ptr = dev.value
+        step = max(1, self.UPLOAD_BYTES // self.per)
+        try:
+            for a in range(0, self.M, step):      # pageable memory: each piece has left the host when its copy is synchronised
+                part = np.ascontiguousarray(pack.pixels[a:a + step])
+                self.L.memcpy_h2d(stream(), self.ptr + a * self.per, part.ctypes.data, part.nbytes)
+                self.L.stream_sync(stream())
+        except Exception:
+            self.close()
+            raise
+
+    def chunks(self, chunk):
+        """SequentialLoader's contract over the resident set, in the set's (sorted-file) order: an iterable of (pool, index0, n) whose
+        `files` are the set's paths.  Never augmented, the generator never touched."""
+        return _ResidentChunks(self, chunk)
+
+    def close(self):
+        if self.ptr is not None:
+            self.L.free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _ResidentChunks:
+    """cg_images_u8_scale_to_f32 on consecutive slices of a ResidentSet, on the caller's stream, alternating two pools: a pool stays
+    valid until the next-but-one next()."""
+
+    def __init__(self, rset, chunk):
+        from .tensor import Tensor
+        if int(chunk) < 1:
+            raise ValueError(f"ResidentSet.chunks: chunk = {chunk}")
+        _check_resident("ResidentSet.chunks", rset.Hs, rset.Ws, False)
+        self.set, self.files, self.count = rset, rset.paths, min(int(chunk), rset.M)
+        self.C = 1 if colorSpace == "y" else 3
+        self.cs_code = COLOR_SPACES[colorSpace]
+        self.pools = [Tensor.empty((self.count, self.C, height, width), "nhwc") for _ in range(2)]
+        self._pos, self.k = 0, 0
+
+    def next(self):
+        from .tensor import stream
+        s = self.set
+        if self._pos >= s.M:
+            return None
+        index0, n = self._pos, min(self.count, s.M - self._pos)
+        pool = self.pools[self.k]
+        s.L.images_u8_scale_to_f32(stream(), s.ptr + index0 * s.per, pool.ptr, n, s.Hs, s.Ws, height, width, self.cs_code)
+        self._pos += n
+        self.k ^= 1
+        return (pool if n == self.count else pool.rows(1, n)), index0, n
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        item = self.next()
+        if item is None:
+            raise StopIteration
+        return item
+
+    def close(self):
+        self.pools = []
+
+
+class ResidentLoader:
+    """Epoch pools gathered out of a ResidentSet.  next() draws what loadRandomImages(count) draws from the module's generator, in its
+    order (the permutation, then - with setAugmentation on when the loader was built - the pool's augment_draw), stages the indices and
+    the descriptors in page-locked memory, and queues their copies and ONE gather kernel on the training stream: the pool (an engine
+    tensor [n,C,H,W], NHWC memory, as AsyncLoader.next() returns) is ready wherever that stream reads it, and stream order is the only
+    synchronisation - no copy stream, no thread, no prefetch.  So there is never a pick in flight and checkpoint_state() is the blocking
+    loader's.  The staging is rewritten one epoch later, after the event recorded behind its copies; two pools alternate, each valid
+    until the next-but-one next().  A set the kernels cannot serve (more than 6x larger than the target; with augmentation, beyond the
+    LDS) is a ValueError here, and the paths of the set must be the module's."""
+
+    def __init__(self, count, resident_set):
+        import ctypes
+        from .tensor import Tensor, lib
+        s = self.set = resident_set
+        self.aug = augmentation is not None
+        _check_resident(type(self).__name__, s.Hs, s.Ws, self.aug)
+        if (paths if paths is not None else loadPaths()) != s.paths:
+            raise ValueError(f"{type(self).__name__}: the resident set does not hold the files of {dirs}")
+        self.L, self.count = lib(), int(count)
+        n = min(self.count, s.M)
+        self.cs_code = COLOR_SPACES[colorSpace]
+        self.C = 1 if colorSpace == "y" else 3
+        self.pools = [Tensor.empty((n, self.C, height, width), "nhwc") for _ in range(2)]
+        self.k, self.used = 0, False
+        # indices [n] int32, then descriptors [n][8] float32: one page-locked block, one device block
+        self.host, self.dev, self.staged = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        self.L.host_alloc(ctypes.byref(self.host), n * 36)
+        self.L.malloc(ctypes.byref(self.dev), n * 36)
+        self.L.event_create(ctypes.byref(self.staged))
+        self.idx = np.ctypeslib.as_array(ctypes.cast(self.host, ctypes.POINTER(ctypes.c_int32)), shape=(n,))
+        self.desc = np.ctypeslib.as_array(ctypes.cast(ctypes.c_void_p(self.host.value + n * 4), ctypes.POINTER(ctypes.c_float)), shape=(n, 8))
+
+    def next(self):
+        from .tensor import stream
+        L, s, st = self.L, self.set, stream()
+        pick = _pick_indices(self.count)
+        n = len(pick)
+        draw = augment_draw(n) if self.aug else None      # right after the pick, as loadRandomImages
+        if self.used:
+            L.event_sync(self.staged)      # last epoch's copies have left the staging (long ago)
+        self.idx[:n] = pick
+        if self.aug:
+            for i in range(n):
+                self.desc[i] = augment_descriptor(draw, i, s.Hs, s.Ws)
+        L.memcpy_h2d(st, self.dev.value, self.host.value, n * 4)
+        if self.aug:
+            L.memcpy_h2d(st, self.dev.value + len(self.idx) * 4, self.host.value + len(self.idx) * 4, n * 32)
+        L.event_record(self.staged, st)
+        self.used = True
+        pool = self.pools[self.k]
+        self.k ^= 1
+        if self.aug:
+            L.images_u8_gather_augment_to_f32(st, s.ptr, s.M, self.dev.value, pool.ptr, n, s.Hs, s.Ws, height, width, self.cs_code,
+                                              self.dev.value + len(self.idx) * 4, draw["noise_std"], draw["seed"], 0)
+        else:
+            L.images_u8_gather_scale_to_f32(st, s.ptr, s.M, self.dev.value, pool.ptr, n, s.Hs, s.Ws, height, width, self.cs_code)
+        return pool if n == pool.shape[0] else pool.rows(1, n)
+
+    def close(self):
+        if self.host:
+            if self.used:
+                self.L.event_sync(self.staged)
+            self.L.host_free(self.host); self.L.free(self.dev); self.L.event_destroy(self.staged)
+            self.host = self.dev = self.staged = None
+            self.pools = []

@@ -54,6 +54,63 @@ def configure_dataset(o):
     return ds
 
 
+def _resident_set(o):
+    """The training set of o.dataDir in device memory when the directory holds a pack that still describes it (dataset.openPack warns
+    and returns None otherwise) and the device has room; None without a pack file, with --synthetic, or when either refuses."""
+    import warnings
+    from ._abi import CatganError
+    if getattr(o, "synthetic", False) or not os.path.isfile(ds.packPath(o.dataDir)):
+        return None
+    pack = ds.openPack(o.dataDir)
+    if pack is None:
+        return None
+    try:
+        return ds.ResidentSet(pack)
+    except CatganError as e:
+        warnings.warn(f"{pack.path}: the set does not fit the device ({e}): loading from the files")
+        return None
+
+
+def _resident_line(rset):
+    print("<dataset> %d images resident on the device (%s)" % (rset.M, ds.PACK_NAME))
+
+
+def resident_loader(o, count):
+    """The epoch-pool loader over a pack the directory holds, found as train.lua finds g_pretrained_*.net - by the file being there and
+    valid, with no flag: a dataset.ResidentLoader, or None when the file loaders have to do what they always did (no fresh pack,
+    --synthetic, --blockingLoader, a set the gather kernels cannot serve)."""
+    import warnings
+    if getattr(o, "blockingLoader", False):
+        return None
+    rset = _resident_set(o)
+    if rset is None:
+        return None
+    try:
+        loader = ds.ResidentLoader(count, rset)
+    except ValueError as e:
+        warnings.warn(f"{e}: loading from the files")
+        rset.close()
+        return None
+    _resident_line(rset)
+    return loader
+
+
+def resident_chunks(o, chunk):
+    """Likewise for one pass over the whole set (sample.py --neighbours): ResidentSet.chunks, or None."""
+    import warnings
+    rset = _resident_set(o)
+    if rset is None:
+        return None
+    try:
+        chunks = rset.chunks(chunk)
+    except ValueError as e:
+        warnings.warn(f"{e}: loading from the files")
+        rset.close()
+        return None
+    _resident_line(rset)
+    return chunks
+
+
 def synthetic_pool(epoch, n, dims):
     """--synthetic: n uniform-noise images, the same for the same epoch number."""
     return np.random.RandomState(epoch).rand(n, *dims).astype(np.float32)
@@ -150,9 +207,13 @@ class AdamFitter:
     def run(self, o, ds, path, plot):
         """The endless loop of train_v.lua:101-110 / pretrain_g.lua:113-127: per epoch a fresh pool (DATASET.loadRandomImages(OPT.N_epoch)),
         the save to `path` (train_v.lua:203-210, pretrain_g.lua:199-214), plot(trainData, epoch()'s result) unless --noplot; --epochs ends it."""
+        loader = resident_loader(o, o.N_epoch)      # a fresh pack in --dataDir: the pools are gathered on the device, the same pools
         while True:
             print("<trainer> Epoch %d" % self.EPOCH)
-            pool = synthetic_pool(self.EPOCH, o.N_epoch, self.dims) if o.synthetic else ds.loadRandomImages(o.N_epoch).scaled
+            if loader is not None:
+                pool = loader.next()
+            else:
+                pool = synthetic_pool(self.EPOCH, o.N_epoch, self.dims) if o.synthetic else ds.loadRandomImages(o.N_epoch).scaled
             trainData = self.cg.adversarial.TrainData(pool)
             result = self.epoch(trainData)
             if self.EPOCH % o.saveFreq == 0:

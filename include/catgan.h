@@ -130,6 +130,18 @@ int cg_images_u8_scale_to_f32(void* stream, const unsigned char* src, float* dst
  * the device's LDS per workgroup is an error, as are shrink factors above 6 and noise_std < 0. */
 int cg_images_u8_augment_to_f32(void* stream, const unsigned char* src, float* dst, int N, int Hs, int Ws, int Hd, int Wd,
                                 int colorspace, const float* desc, float noise_std, uint64_t seed, uint64_t offset);
+/* The two above over a training set that STAYS in device memory (dataset.ResidentSet: decoded once, 8-bit RGB, [M][Hs][Ws][3]): image n
+ * of the output is, bit for bit, what cg_images_u8_scale_to_f32 / cg_images_u8_augment_to_f32 produce for the source image set[idx[n]]
+ * (idx: N int32 in device memory; repeats and any order are fine).  The kernels read the set in place through 64-bit addresses - no
+ * copy of the gathered bytes exists, and a set beyond 2^31 bytes is fine.  The noise counters (j above) and desc are numbered by the
+ * image's position n in the OUTPUT, not by idx[n]: a pool is the pool the file loaders give for the same draws.  An idx[n] outside
+ * [0, M) is defined behaviour: image n of the output is all zeros and nothing of the set is read for it.  Errors as for the pair above
+ * (null pointers, N <= 0, M <= 0, a bad colorspace, noise_std < 0; shrink factors above 6; a source beyond the LDS), all before any
+ * launch. */
+int cg_images_u8_gather_scale_to_f32(void* stream, const unsigned char* set, long M, const int32_t* idx, float* dst, int N, int Hs, int Ws,
+                                     int Hd, int Wd, int colorspace);
+int cg_images_u8_gather_augment_to_f32(void* stream, const unsigned char* set, long M, const int32_t* idx, float* dst, int N, int Hs, int Ws,
+                                       int Hd, int Wd, int colorspace, const float* desc, float noise_std, uint64_t seed, uint64_t offset);
 /* NN_UTILS.rgbToColorSpace / NN_UTILS.toRgb (utils/nn_utils.lua:188-249) on fp32 NHWC pixels that are already on the device: three
  * floats in per pixel, three out (one for to == 1).  from / to are the colorspace codes above; the pairs are rgb -> y | yuv | hsl and
  * yuv | hsl -> rgb, anything else is an error.  src == dst is allowed when three planes come out.  Per pixel, every operation a single

@@ -96,7 +96,8 @@ def main(argv=None):
     PLOT_DATA = []
     # train.lua:216: the same 100 noise vectors every epoch (a generator of their own: the training streams do not move)
     VIS_NOISE_INPUTS = np.random.RandomState(o.seed).uniform(-1, 1, (100, o.noiseDim)).astype(np.float32)
-    loader = None if (o.synthetic or o.blockingLoader) else ds.AsyncLoader(n_pool)   # the next epoch's pool loads while this one trains
+    # the next epoch's pool loads while this one trains - or, with a fresh pack in --dataDir, is gathered out of the resident set
+    loader = None if (o.synthetic or o.blockingLoader) else (fe.resident_loader(o, n_pool) or ds.AsyncLoader(n_pool))
     while True:                                                    # train.lua:223
         print("Loading new training data...")
         if o.synthetic:
