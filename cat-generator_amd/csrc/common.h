@@ -59,12 +59,15 @@ constexpr int kEwWgsPerCU = 4, kColReduceWgsPerCU = 1;
 enum Opt {
     OPT_SKINNY, OPT_GEMM_BK32, OPT_WINO_BK, OPT_NN_TILE, OPT_TN_TILE, OPT_NN_SPLITS, OPT_TN_SPLITS,
     OPT_XCD_SWIZZLE, OPT_NN_GLDS, OPT_TN_GLDS, OPT_WINO_GLDS, OPT_PAD_SKIP, OPT_WINO3, OPT_WINO_DGRAD_FUSE, OPT_WINO_DGRAD_FUSE_LAUNCHES,
-    OPT_WINO3_LAUNCHES, OPT_COUNT
+    OPT_WINO3_LAUNCHES, OPT_PACK_WIDE, OPT_COUNT
 };
 long opt(Opt o);
 // CG_WINO_DGRAD_FUSE_LAUNCHES and CG_WINO3_LAUNCHES are not tunables but counters kept in the same table (cg_get_option reads them,
 // cg_set_option resets them): the launches of wino_dgrad_fused_kernel (winograd.hip) and of wino3_fused_k (wino3.hip), so that a test can
 // tell that the fused path ran and not its fallback.
+// CG_PACK_WIDE: 1 = the weight re-packing after every parameter update runs in its wide launches (pack_weight_ups2_wide_kernel and
+// pack_weight_batch_wide_kernel in gemm.hip, the both-operand Winograd filter transforms in winograd.hip), 0 = the kernels they replace.
+// The bytes written are the same.
 void opt_count(Opt o);
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
@@ -144,6 +147,28 @@ __device__ __forceinline__ int tile_of_row(int l) {
     const bool ga = l < 4 || (l >= 12 && l < 16) || (l >= 20 && l < 28);
     const int rank = ga ? (l < 4 ? l : (l < 16 ? l - 8 : l - 12)) : (l < 12 ? l - 4 : (l < 20 ? l - 8 : l - 16));
     return (ga ? 0 : 16) + rank;
+}
+// Transformed filters of the fused Winograd 3x3 kernel (wino3.hip) for filter pair idx = co * 64 + ci of a 64 -> 64 plane layer:
+// U[pos][ci / 4][co][4] = (G g G^T)[xi][nu], pos = xi * 4 + nu; uf: the forward's g = w[co][ci][:][:], ub: the data gradient's (planes
+// swapped, taps flipped) g[a][b] = w[ci][co][2 - a][2 - b].  One body for wino3_pack_k and for the batch pack's own workgroups
+// (pack_weight_batch_wide_kernel, gemm.hip), so that both write the same bits.
+__device__ __forceinline__ void wino3_pack_item(const float* __restrict__ w, float* uf, float* ub, int idx) {
+    constexpr int C = 64;
+    const int co = idx / C, ci = idx % C;
+    const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
+    for (int flip = 0; flip < 2; ++flip) {
+        float* U = flip ? ub : uf;
+        if (!U) continue;
+        float g[3][3];
+        for (int a = 0; a < 3; ++a)
+            for (int b = 0; b < 3; ++b) g[a][b] = flip ? w[((long)ci * C + co) * 9 + (2 - a) * 3 + (2 - b)] : w[((long)co * C + ci) * 9 + a * 3 + b];
+        float t[4][3];
+        for (int i = 0; i < 4; ++i)
+            for (int b = 0; b < 3; ++b) t[i][b] = G[i][0] * g[0][b] + G[i][1] * g[1][b] + G[i][2] * g[2][b];
+        for (int i = 0; i < 4; ++i)
+            for (int k = 0; k < 4; ++k)
+                U[(((long)(i * 4 + k) * (C / 4) + ci / 4) * C + co) * 4 + (ci & 3)] = t[i][0] * G[k][0] + t[i][1] * G[k][1] + t[i][2] * G[k][2];
+    }
 }
 // the engine's counter-based generator: splitmix64 of (seed, counter), 24-bit mantissa uniform in [0,1)
 // (host twin tensor.SplitMix, oracle twin orc_rng_u01)

@@ -1857,20 +1857,10 @@ struct PackBatch {
     unsigned long long map_mask;   // bit e: layer e wants the wbT layout (see pack_weight_kernel)
     int n;
 };
-__global__ __launch_bounds__(256) void pack_weight_batch_kernel(PackBatch b) {
-    __shared__ float sh[32][33];
-    int e = 0;
-    while (e + 1 < b.n && (int)blockIdx.x >= b.first[e + 1]) ++e;
-    const float* w = b.w[e]; float* wf = b.wf[e]; float* wb = b.wb[e];
-    const int Cout = b.Cout[e], Cin = b.Cin[e], KK = b.KK[e];
-    const bool wb_map = (b.map_mask >> e) & 1ull;
-    const int nbx = (Cin + 31) / 32, nby = (Cout + 31) / 32;
-    int r = (int)blockIdx.x - b.first[e];
-    const int bx = r % nbx; r /= nbx;
-    const int by = r % nby;
-    const int tap = r / nby;
+// one tap plane of a 32 ci x 32 co block (pack_weight_kernel's body), for the two batch kernels
+__device__ __forceinline__ void pack_block_tap(float (&sh)[32][33], const float* w, float* wf, float* wb, int Cout, int Cin, int KK,
+                                               bool wb_map, int ci0, int co0, int tap) {
     const int lo = threadIdx.x & 31, hi = threadIdx.x >> 5;
-    const int ci0 = bx * 32, co0 = by * 32;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int ci = ci0 + lo, co_l = hi + 8 * j, co = co0 + co_l;
@@ -1887,6 +1877,111 @@ __global__ __launch_bounds__(256) void pack_weight_batch_kernel(PackBatch b) {
         for (int j = 0; j < 4; ++j) {
             const int co = co0 + lo, ci_l = hi + 8 * j, ci = ci0 + ci_l;
             if (ci < Cin && co < Cout) wf[((long)tap * Cin + ci) * Cout + co] = sh[ci_l][lo];
+        }
+    }
+}
+__global__ __launch_bounds__(256) void pack_weight_batch_kernel(PackBatch b) {
+    __shared__ float sh[32][33];
+    int e = 0;
+    while (e + 1 < b.n && (int)blockIdx.x >= b.first[e + 1]) ++e;
+    const int Cout = b.Cout[e], Cin = b.Cin[e], KK = b.KK[e];
+    const int nbx = (Cin + 31) / 32, nby = (Cout + 31) / 32;
+    int r = (int)blockIdx.x - b.first[e];
+    const int bx = r % nbx; r /= nbx;
+    const int by = r % nby;
+    pack_block_tap(sh, b.w[e], b.wf[e], b.wb[e], Cout, Cin, KK, (b.map_mask >> e) & 1ull, bx * 32, by * 32, r / nby);
+}
+
+// The wide form of the batch pack (CG_PACK_WIDE, the default).  The kernel above reads w[co][ci][tap] with a lane stride of KK floats
+// and once per tap: KK workgroups fetch the same lines for 4 bytes of each 32-byte sector (View -> Linear(20480, 256) as an 8 x 8 kernel:
+// 64 times; a linear or 1 x 1 layer has none of this and keeps that body).  Here a workgroup owns a 32 ci x 32 co block and a CHUNK of
+// up to kPackTc taps (all of a 3 x 3 kernel, 7 of the 49 of a 7 x 7, 8 of the map's 64): every (co, ci) contributes one contiguous run
+// of the chunk's taps, read once into LDS, and wb (ci-fastest) and wf (co-fastest) are both stored in whole 128-byte rows from there
+// (row strides 9 and 289 words: no bank conflicts either way).
+// The transformed filters of the 64 -> 64 3x3 layers (wino3.hip), which the separate wino3_pack_k launch wrote behind the operands,
+// are computed by further workgroups of this launch from the same canonical weights (blocks from wino_first on, 16 per layer).
+constexpr int kPackTc = 9, kPackRow = 32 * kPackTc + 1;
+struct PackBatchWide {
+    PackBatch b;                    // first[] counts this kernel's blocks: cdiv(Cin, 32) * cdiv(Cout, 32) * chunks per layer
+    unsigned long long wino_mask;   // bit e: layer e also gets the fused-Winograd filters behind wf / wb
+    int wino_first;                 // first of the workgroups that compute those
+};
+__host__ __device__ static inline int pack_chunks(int KK) { return (KK + (KK <= kPackTc ? kPackTc : 8) - 1) / (KK <= kPackTc ? kPackTc : 8); }
+__global__ __launch_bounds__(256) void pack_weight_batch_wide_kernel(PackBatchWide a) {
+    __shared__ float sh[32 * kPackRow];
+    const PackBatch& b = a.b;
+    if ((int)blockIdx.x >= a.wino_first) {
+        const int r = (int)blockIdx.x - a.wino_first;
+        int e = 0;
+        for (int job = r / 16; e < b.n; ++e)
+            if (((a.wino_mask >> e) & 1ull) && job-- == 0) break;
+        if (e < b.n)
+            cg::wino3_pack_item(b.w[e], b.wf[e] ? b.wf[e] + cg::kWino3UOffset : nullptr, b.wb[e] ? b.wb[e] + cg::kWino3UOffset : nullptr,
+                                (r % 16) * 256 + (int)threadIdx.x);
+        return;
+    }
+    int e = 0;
+    while (e + 1 < b.n && (int)blockIdx.x >= b.first[e + 1]) ++e;
+    const float* w = b.w[e]; float* wf = b.wf[e]; float* wb = b.wb[e];
+    const int Cout = b.Cout[e], Cin = b.Cin[e], KK = b.KK[e];
+    const bool wb_map = (b.map_mask >> e) & 1ull;
+    const int nbx = (Cin + 31) / 32, nby = (Cout + 31) / 32, nch = pack_chunks(KK);
+    const int tc = (KK + nch - 1) / nch;                 // taps per chunk (the last chunk may hold fewer)
+    int r = (int)blockIdx.x - b.first[e];
+    const int bx = r % nbx; r /= nbx;
+    const int by = r % nby;
+    const int tap0 = (r / nby) * tc, nt = min(tc, KK - tap0);
+    const int ci0 = bx * 32, co0 = by * 32;
+    if (KK == 1) {      // linear / 1 x 1 layers: the canonical rows are read coalesced as they are, nothing to stage
+        pack_block_tap(*reinterpret_cast<float (*)[32][33]>(sh), w, wf, wb, Cout, Cin, 1, wb_map, ci0, co0, 0);
+        return;
+    }
+    // stage: wave v takes the block's rows co_l = v, v + 4, ...; a row is 32 runs of nt floats, KK floats apart
+    {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        constexpr int SLOTS = (32 * kPackTc + 63) / 64;
+        int goff[SLOTS], loff[SLOTS];
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const int el = lane + 64 * s, ci_l = el / nt, tt = el - ci_l * nt;
+            const bool ok = ci_l < 32 && ci0 + ci_l < Cin;
+            goff[s] = ok ? ci_l * KK + tt : -1;
+            loff[s] = ci_l * kPackTc + tt;
+        }
+#pragma unroll 2
+        for (int co_l = wave; co_l < 32 && co0 + co_l < Cout; co_l += 4) {
+            const float* src = w + ((long)(co0 + co_l) * Cin + ci0) * KK + tap0;
+            float v[SLOTS];      // every slot loads (an idle one the row's first float), so that the loads are issued together
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s) v[s] = src[max(goff[s], 0)];
+#pragma unroll
+            for (int s = 0; s < SLOTS; ++s)
+                if (goff[s] >= 0) sh[co_l * kPackRow + loff[s]] = v[s];
+        }
+    }
+    __syncthreads();
+    const int lo = threadIdx.x & 31, hi = threadIdx.x >> 5;
+    if (wb && ci0 + lo < Cin) {
+        const int ci = ci0 + lo;
+        for (int tt = 0; tt < nt; ++tt) {
+            const int tap = tap0 + tt;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int co_l = hi + 8 * j, co = co0 + co_l;
+                if (co < Cout)
+                    wb[wb_map ? ((long)co * KK + tap) * Cin + ci : ((long)(KK - 1 - tap) * Cout + co) * Cin + ci] = sh[co_l * kPackRow + lo * kPackTc + tt];
+            }
+        }
+    }
+    if (wf && co0 + lo < Cout) {
+        const int co = co0 + lo;
+        for (int tt = 0; tt < nt; ++tt) {
+            const int tap = tap0 + tt;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int ci_l = hi + 8 * j, ci = ci0 + ci_l;
+                if (ci < Cin) wf[((long)tap * Cin + ci) * Cout + co] = sh[lo * kPackRow + ci_l * kPackTc + tt];
+            }
         }
     }
 }
@@ -1938,6 +2033,74 @@ __global__ __launch_bounds__(256) void pack_weight_ups2_fast_kernel(const float*
                 }
             __syncthreads();
         }
+    }
+}
+
+// The wide form of the same (CG_PACK_WIDE, the default): one workgroup owns ONE phase of a 32 ci x kPackWideCo co block, so the
+// launch has 4 * 32 / kPackWideCo times the workgroups of the kernel above (G32up's 256 -> 128 5x5 layer: 256 instead of 32, its
+// 512 -> 256 3x3 layer: 1024 instead of 128) and no thread walks the four phases in turn.  The canonical taps of a co row of the
+// block are 32 * K * K contiguous floats: they are read coalesced into LDS, and every thread then takes its own K * K taps from there
+// (lane stride K * K words, odd: no bank conflicts).  Each phase tap is the sum of the same source taps, added from 0.f in the same
+// (dy, dx) order as above, so the bits are those of the kernel above; wb is stored ci-fastest straight from the registers, wf
+// co-fastest through an LDS transpose that reuses the staging area.
+constexpr int kPackWideCo = 16;
+template <int K, int P>
+__device__ __forceinline__ void pack_ups2_wide_phase(float* sh, float* wf, float* wb, int Cout, int Cin, int ci0, int co0) {
+    constexpr int KK = K * K, PAD = (K - 1) / 2, KPD = K == 3 ? 2 : 3, KP = KPD * KPD, RUN = 32 * KK, J = kPackWideCo / 8;
+    const int lo = threadIdx.x & 31, hi = threadIdx.x >> 5;
+    const int ci = ci0 + lo;
+    float acc[J][KP];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const float* src = sh + (hi + 8 * j) * RUN + lo * KK;
+        float v[KK];
+#pragma unroll
+        for (int t = 0; t < KK; ++t) v[t] = src[t];
+#pragma unroll
+        for (int t = 0; t < KP; ++t) acc[j][t] = 0.f;
+#pragma unroll
+        for (int dy = 0; dy < K; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < K; ++dx) acc[j][phase_map(P >> 1, dy, PAD) * KPD + phase_map(P & 1, dx, PAD)] += v[dy * K + dx];
+        const int co = co0 + hi + 8 * j;
+        if (wb && ci < Cin && co < Cout) {
+#pragma unroll
+            for (int t = 0; t < KP; ++t) wb[(((long)P * KP + t) * Cout + co) * Cin + ci] = acc[j][t];
+        }
+    }
+    if (wf) {
+        constexpr int LD = kPackWideCo + 1;
+        __syncthreads();      // every thread has its taps in registers: the staging area becomes the [KP][32][LD] transpose buffer
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+#pragma unroll
+            for (int t = 0; t < KP; ++t) sh[(t * 32 + lo) * LD + hi + 8 * j] = acc[j][t];
+        __syncthreads();
+        const int co_l = threadIdx.x % kPackWideCo, co = co0 + co_l;
+#pragma unroll
+        for (int t = 0; t < KP; ++t)
+            for (int ci_l = threadIdx.x / kPackWideCo; ci_l < 32; ci_l += 256 / kPackWideCo)
+                if (ci0 + ci_l < Cin && co < Cout) wf[(((long)P * KP + t) * Cin + ci0 + ci_l) * Cout + co] = sh[(t * 32 + ci_l) * LD + co_l];
+    }
+}
+template <int K>
+__global__ __launch_bounds__(256) void pack_weight_ups2_wide_kernel(const float* w, float* wf, float* wb, int Cout, int Cin) {
+    constexpr int KK = K * K, RUN = 32 * KK;
+    static_assert(kPackWideCo % 8 == 0 && 256 % kPackWideCo == 0 && (K == 3 ? 4 : 9) * 32 * (kPackWideCo + 1) <= kPackWideCo * RUN,
+                  "the transpose buffer lies inside the staging area");
+    __shared__ float sh[kPackWideCo * RUN];
+    const int ci0 = blockIdx.x * 32, co0 = (blockIdx.y / 4) * kPackWideCo, p = blockIdx.y & 3;
+    const int run = min(32, Cin - ci0) * KK;      // floats of a co row that belong to this block
+    for (int idx = threadIdx.x; idx < kPackWideCo * RUN; idx += 256) {
+        const int co_l = idx / RUN, j = idx - co_l * RUN;
+        sh[idx] = co0 + co_l < Cout && j < run ? w[((long)(co0 + co_l) * Cin + ci0) * KK + j] : 0.f;
+    }
+    __syncthreads();
+    switch (p) {      // the phase as a template argument: every accumulator index is a compile-time constant
+        case 0: pack_ups2_wide_phase<K, 0>(sh, wf, wb, Cout, Cin, ci0, co0); break;
+        case 1: pack_ups2_wide_phase<K, 1>(sh, wf, wb, Cout, Cin, ci0, co0); break;
+        case 2: pack_ups2_wide_phase<K, 2>(sh, wf, wb, Cout, Cin, ci0, co0); break;
+        default: pack_ups2_wide_phase<K, 3>(sh, wf, wb, Cout, Cin, ci0, co0); break;
     }
 }
 
@@ -2781,6 +2944,32 @@ int cg_pack_conv_weight_map(void* stream, const float* w, float* wf, float* wbT,
 int cg_pack_conv_weight_batch(void* stream, int n, const float* const* w_canonical, float* const* wf, float* const* wb,
                               const int* Cout, const int* Cin, const int* kH, const int* kW, const int* wb_map) {
     CG_REQUIRE(n >= 0 && w_canonical && wf && wb && Cout && Cin && kH && kW, "cg_pack_conv_weight_batch: null pointer");
+    if (cg::opt(cg::OPT_PACK_WIDE) != 0) {
+        for (int i0 = 0; i0 < n; i0 += kPackBatch) {
+            PackBatchWide a;
+            memset(&a, 0, sizeof(a));
+            PackBatch& b = a.b;
+            b.n = std::min(kPackBatch, n - i0);
+            int blocks = 0, wino = 0;
+            for (int e = 0; e < b.n; ++e) {
+                const int i = i0 + e;
+                CG_REQUIRE(w_canonical[i] && (wf[i] || wb[i]) && Cout[i] > 0 && Cin[i] > 0 && kH[i] > 0 && kW[i] > 0,
+                           "cg_pack_conv_weight_batch: bad layer %d", i);
+                b.w[e] = w_canonical[i]; b.wf[e] = wf[i]; b.wb[e] = wb[i];
+                b.Cout[e] = Cout[i]; b.Cin[e] = Cin[i]; b.KK[e] = kH[i] * kW[i];
+                const bool map = wb_map && wb_map[i];
+                if (map) b.map_mask |= 1ull << e;
+                if (cg::wino3_layer(Cout[i], Cin[i], kH[i], kW[i]) && !map) { a.wino_mask |= 1ull << e; ++wino; }      // wino3_note_pack's rule
+                b.first[e] = blocks;
+                blocks += cg::cdiv(Cin[i], 32) * cg::cdiv(Cout[i], 32) * pack_chunks(b.KK[e]);
+            }
+            b.first[b.n] = blocks;
+            a.wino_first = blocks;
+            hipLaunchKernelGGL(pack_weight_batch_wide_kernel, dim3(blocks + 16 * wino), dim3(256), 0, cg::S(stream), a);
+            CG_LAUNCH_CHECK();
+        }
+        return 0;
+    }
     for (int i0 = 0; i0 < n; i0 += kPackBatch) {
         PackBatch b;
         memset(&b, 0, sizeof(b));
@@ -2821,6 +3010,15 @@ int cg_pack_conv_weight_ups2(void* stream, const float* w, float* wf_ph, float* 
     const int kp = phase_kp(k, pad);
     CG_REQUIRE(k * k <= 448, "cg_pack_conv_weight_ups2: kernel too large (%d taps)", k * k);
     const dim3 fgrid(cg::cdiv(Cin, 32), cg::cdiv(Cout, 32));
+    if ((k == 3 || k == 5) && cg::opt(cg::OPT_PACK_WIDE) != 0) {
+        const dim3 wgrid(cg::cdiv(Cin, 32), cg::cdiv(Cout, kPackWideCo) * 4);
+        if (k == 3)
+            hipLaunchKernelGGL(pack_weight_ups2_wide_kernel<3>, wgrid, dim3(256), 0, cg::S(stream), w, wf_ph, wb_ph, Cout, Cin);
+        else
+            hipLaunchKernelGGL(pack_weight_ups2_wide_kernel<5>, wgrid, dim3(256), 0, cg::S(stream), w, wf_ph, wb_ph, Cout, Cin);
+        CG_LAUNCH_CHECK();
+        return 0;
+    }
     if (k == 3 || k == 5) {
         if (k == 3)
             hipLaunchKernelGGL(pack_weight_ups2_fast_kernel<3>, fgrid, dim3(256), 0, cg::S(stream), w, wf_ph, wb_ph, Cout, Cin);

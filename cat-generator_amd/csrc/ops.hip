@@ -26,7 +26,7 @@ struct OptDef { const char* name; long dflt; };
 const OptDef kOptDefs[OPT_COUNT] = {
     {"CG_SKINNY", 1}, {"CG_GEMM_BK32", 1}, {"CG_WINO_BK", 0}, {"CG_NN_TILE", 0}, {"CG_TN_TILE", 0}, {"CG_NN_SPLITS", 0}, {"CG_TN_SPLITS", 0},
     {"CG_XCD_SWIZZLE", 7}, {"CG_NN_GLDS", 1}, {"CG_TN_GLDS", 1}, {"CG_WINO_GLDS", 1}, {"CG_PAD_SKIP", 20}, {"CG_WINO3", 1},
-    {"CG_WINO_DGRAD_FUSE", 1}, {"CG_WINO_DGRAD_FUSE_LAUNCHES", 0}, {"CG_WINO3_LAUNCHES", 0},
+    {"CG_WINO_DGRAD_FUSE", 1}, {"CG_WINO_DGRAD_FUSE_LAUNCHES", 0}, {"CG_WINO3_LAUNCHES", 0}, {"CG_PACK_WIDE", 1},
 };
 long g_opt_val[OPT_COUNT];
 int g_opt_state[OPT_COUNT];   // 0 = not read yet, 1 = default / environment, 2 = set through the ABI

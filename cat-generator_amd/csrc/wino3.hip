@@ -37,27 +37,10 @@ __device__ __forceinline__ float4 bufld4(__amdgpu_buffer_rsrc_t r, unsigned voff
     return make_float4(f.x, f.y, f.z, f.w);
 }
 
-// U[pos][ci / 4][co][4] = (G g G^T)[xi][nu], pos = xi * 4 + nu, for the filter g of (input plane ci, output plane co) of the convolution
-// the operand serves: forward g = w[co][ci][:][:]; data gradient (planes swapped, taps flipped) g[a][b] = w[ci][co][2 - a][2 - b].
+// U = G g G^T of every filter pair of up to 8 layers (cg::wino3_pack_item, common.h): one thread per (co, ci)
 struct PackJobs { const float* w[8]; float* uf[8]; float* ub[8]; int n; };
 __global__ void wino3_pack_k(PackJobs jobs) {
-    const float* __restrict__ w = jobs.w[blockIdx.y];
-    const int idx = blockIdx.x * 256 + threadIdx.x;      // < C * C
-    const int co = idx / C, ci = idx % C;
-    const float G[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
-    for (int flip = 0; flip < 2; ++flip) {
-        float* U = flip ? jobs.ub[blockIdx.y] : jobs.uf[blockIdx.y];
-        if (!U) continue;
-        float g[3][3];
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) g[a][b] = flip ? w[((long)ci * C + co) * 9 + (2 - a) * 3 + (2 - b)] : w[((long)co * C + ci) * 9 + a * 3 + b];
-        float t[4][3];
-        for (int i = 0; i < 4; ++i)
-            for (int b = 0; b < 3; ++b) t[i][b] = G[i][0] * g[0][b] + G[i][1] * g[1][b] + G[i][2] * g[2][b];
-        for (int i = 0; i < 4; ++i)
-            for (int k = 0; k < 4; ++k)
-                U[(((long)(i * 4 + k) * (C / 4) + ci / 4) * C + co) * 4 + (ci & 3)] = t[i][0] * G[k][0] + t[i][1] * G[k][1] + t[i][2] * G[k][2];
-    }
+    cg::wino3_pack_item(jobs.w[blockIdx.y], jobs.uf[blockIdx.y], jobs.ub[blockIdx.y], blockIdx.x * 256 + threadIdx.x);      // < C * C
 }
 
 using cg::tile_of_row;     // lane -> tile permutation of the ds_read_b128 lane groups (common.h)

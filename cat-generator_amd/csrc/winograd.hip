@@ -94,13 +94,14 @@ __global__ __launch_bounds__(256) void wino_input_transform_kernel(const float* 
 // BWD: src = wb_ph [p][tp][co][ci]  ->  U[xi][p*Cout+co][ci] of the FLIPPED kernel (data gradient operand)
 // One thread per (p, row, column quad) of the [rows][cols] plane (rows x cols = Cin x Cout or Cout x Cin).
 // ---------------------------------------------------------------------------
+// Items first, first + step, ... of the plane: the two kernels below differ only in which workgroups walk which operand.
 template <bool BWD>
-__global__ __launch_bounds__(256) void wino_filter_transform_kernel(const float* __restrict__ src, float* __restrict__ U,
-                                                                    int rows, int cols) {
+__device__ __forceinline__ void wino_filter_transform_items(const float* __restrict__ src, float* __restrict__ U, int rows, int cols,
+                                                            long first, long step) {
     const int cqn = cols >> 2;
     const long plane = (long)rows * cols;
     const long total = 4L * rows * cqn;
-    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += gridDim.x * 256L) {
+    for (long idx = first; idx < total; idx += step) {
         const int cq = (int)(idx % cqn);
         const int row = (int)((idx / cqn) % rows);
         const int p = (int)(idx / ((long)cqn * rows));
@@ -138,6 +139,19 @@ __global__ __launch_bounds__(256) void wino_filter_transform_kernel(const float*
             }
         }
     }
+}
+template <bool BWD>
+__global__ __launch_bounds__(256) void wino_filter_transform_kernel(const float* __restrict__ src, float* __restrict__ U,
+                                                                    int rows, int cols) {
+    wino_filter_transform_items<BWD>(src, U, rows, cols, blockIdx.x * 256L + threadIdx.x, gridDim.x * 256L);
+}
+// Both operands in ONE launch (CG_PACK_WIDE): workgroups [0, nf) walk the forward operand, the others the data gradient's.
+__global__ __launch_bounds__(256) void wino_filter_transform_both_kernel(const float* __restrict__ wf_ph, float* __restrict__ u_fwd,
+                                                                         const float* __restrict__ wb_ph, float* __restrict__ u_bwd,
+                                                                         int Cin, int Cout, int nf) {
+    const int b = blockIdx.x;
+    if (b < nf) wino_filter_transform_items<false>(wf_ph, u_fwd, Cin, Cout, b * 256L + threadIdx.x, nf * 256L);
+    else wino_filter_transform_items<true>(wb_ph, u_bwd, Cout, Cin, (b - nf) * 256L + threadIdx.x, ((int)gridDim.x - nf) * 256L);
 }
 
 // ---------------------------------------------------------------------------
@@ -246,12 +260,12 @@ __global__ __launch_bounds__(256) void wino22_dy_input_transform_kernel(const fl
 // FWD: src = wf_ph [p][tp = ry*2 + rx][ci][co] -> U[p][xi = i*3 + j][ci][co].
 // BWD: src = wb_ph [p][tp][co][ci] -> U[xi][p*Cout + co][ci] of the FLIPPED kernel (data-gradient operand: the four phases side by side along K).
 template <bool BWD>
-__global__ __launch_bounds__(256) void wino22_filter_transform_kernel(const float* __restrict__ src, float* __restrict__ U, int rows,
-                                                                      int cols) {
+__device__ __forceinline__ void wino22_filter_transform_items(const float* __restrict__ src, float* __restrict__ U, int rows, int cols,
+                                                              long first, long step) {
     const int cqn = cols >> 2;
     const long plane = (long)rows * cols;
     const long total = 4L * rows * cqn;
-    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += gridDim.x * 256L) {
+    for (long idx = first; idx < total; idx += step) {
         const int cq = (int)(idx % cqn);
         const int row = (int)((idx / cqn) % rows);
         const int p = (int)(idx / ((long)cqn * rows));
@@ -276,6 +290,19 @@ __global__ __launch_bounds__(256) void wino22_filter_transform_kernel(const floa
             *reinterpret_cast<float4*>(dst + 2 * xstep) = t[i][1];
         }
     }
+}
+template <bool BWD>
+__global__ __launch_bounds__(256) void wino22_filter_transform_kernel(const float* __restrict__ src, float* __restrict__ U, int rows,
+                                                                      int cols) {
+    wino22_filter_transform_items<BWD>(src, U, rows, cols, blockIdx.x * 256L + threadIdx.x, gridDim.x * 256L);
+}
+// Both operands in ONE launch (CG_PACK_WIDE), as wino_filter_transform_both_kernel.
+__global__ __launch_bounds__(256) void wino22_filter_transform_both_kernel(const float* __restrict__ wf_ph, float* __restrict__ u_fwd,
+                                                                           const float* __restrict__ wb_ph, float* __restrict__ u_bwd,
+                                                                           int Cin, int Cout, int nf) {
+    const int b = blockIdx.x;
+    if (b < nf) wino22_filter_transform_items<false>(wf_ph, u_fwd, Cin, Cout, b * 256L + threadIdx.x, nf * 256L);
+    else wino22_filter_transform_items<true>(wb_ph, u_bwd, Cout, Cin, (b - nf) * 256L + threadIdx.x, ((int)gridDim.x - nf) * 256L);
 }
 
 // ---------------------------------------------------------------------------
@@ -1057,6 +1084,13 @@ int cg_conv2d_ups2_wino_pack(void* stream, const float* wf_ph, const float* wb_p
                              int Cin) {
     CG_REQUIRE((wf_ph && u_fwd) || (wb_ph && u_bwd), "cg_conv2d_ups2_wino_pack: null pointer");
     CG_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0, "cg_conv2d_ups2_wino_pack: channel counts must be multiples of 4");
+    if (wf_ph && u_fwd && wb_ph && u_bwd && cg::opt(cg::OPT_PACK_WIDE) != 0) {
+        const int nf = cg::ew_grid(4L * Cin * (Cout / 4)), nb = cg::ew_grid(4L * Cout * (Cin / 4));
+        hipLaunchKernelGGL(wino_filter_transform_both_kernel, dim3(nf + nb), dim3(256), 0, cg::S(stream), wf_ph, u_fwd, wb_ph, u_bwd, Cin,
+                           Cout, nf);
+        CG_LAUNCH_CHECK();
+        return 0;
+    }
     if (wf_ph && u_fwd) {
         const long total = 4L * Cin * (Cout / 4);
         hipLaunchKernelGGL(wino_filter_transform_kernel<false>, dim3(cg::ew_grid(total)), dim3(256), 0, cg::S(stream), wf_ph,
@@ -1172,6 +1206,13 @@ size_t cg_conv2d_ups2_wino22_u_floats(int Cin, int Cout) { return (size_t)4 * 9 
 int cg_conv2d_ups2_wino22_pack(void* stream, const float* wf_ph, const float* wb_ph, float* u_fwd, float* u_bwd, int Cout, int Cin) {
     CG_REQUIRE((wf_ph && u_fwd) || (wb_ph && u_bwd), "cg_conv2d_ups2_wino22_pack: null pointer");
     CG_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0, "cg_conv2d_ups2_wino22_pack: channel counts must be multiples of 4");
+    if (wf_ph && u_fwd && wb_ph && u_bwd && cg::opt(cg::OPT_PACK_WIDE) != 0) {
+        const int nf = cg::ew_grid(4L * Cin * (Cout / 4)), nb = cg::ew_grid(4L * Cout * (Cin / 4));
+        hipLaunchKernelGGL(wino22_filter_transform_both_kernel, dim3(nf + nb), dim3(256), 0, cg::S(stream), wf_ph, u_fwd, wb_ph, u_bwd,
+                           Cin, Cout, nf);
+        CG_LAUNCH_CHECK();
+        return 0;
+    }
     if (wf_ph && u_fwd) {
         hipLaunchKernelGGL(wino22_filter_transform_kernel<false>, dim3(cg::ew_grid(4L * Cin * (Cout / 4))), dim3(256), 0, cg::S(stream), wf_ph,
                            u_fwd, Cin, Cout);

@@ -44,7 +44,7 @@ extern "C" {
  * utils/nn_utils.lua:638-643). */
 int         cg_abi_version(void);
 const char* cg_last_error(void);
-/* Tunables of the kernel dispatch, named like the environment variables that set their defaults (14 names and two counters; value == -1 restores the
+/* Tunables of the kernel dispatch, named like the environment variables that set their defaults (15 names and two counters; value == -1 restores the
  * default).  Results never depend on them beyond fp32 re-association; the parity tests use them to run every compiled kernel variant
  * against the oracle.
  *   CG_NN_TILE / CG_TN_TILE (bm*1000+bn), CG_NN_SPLITS / CG_TN_SPLITS : block tile and split count of the forward (data-gradient) /
@@ -68,6 +68,9 @@ const char* cg_last_error(void);
  *       layer at 16x16 with 14 %).  The weight gradient (round 6: position-major K tiles, igemm_tng_kernel mode 2) takes HALF that share
  *       (7x7, 5x5, the 3x3 layers at 8x8), and with any value > 0 the weight gradient of View -> Linear (an H x W kernel on the H x W map)
  *       is one kernel straight into the canonical gradWeight (csrc/headwg.hip).  0 = image-major tiles everywhere.
+ *   CG_PACK_WIDE : 1 = cg_pack_conv_weight_ups2 (k = 3, 5) packs one phase of a 32 x 16 channel block per workgroup from LDS-staged,
+ *       coalesced reads, and cg_conv2d_ups2_wino_pack / _wino22_pack transform both operands in one launch; 0 = the kernels these
+ *       replace.  Both settings write the same bytes.
  * (CG_SPLIT_TARGET / _MINK, CG_TN_SMAX / _TARGET, CG_EPILOGUE_STATS, CG_COLREDUCE_WGS_PER_CU, CG_EW_WGS_PER_CU became constants in round 6.) */
 int cg_set_option(const char* name, long value);
 int cg_get_option(const char* name, long* value);
