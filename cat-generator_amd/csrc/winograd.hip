@@ -14,6 +14,15 @@
 // planes (the four phase sub-lattices of dy) and flipped kernels.  The weight gradient is taken in the Winograd
 // domain (dU_xi = V_xi^T (A dY A^T)_xi, 16 plain TN GEMMs through cg_conv2d_wgrad) and brought back by G^T . G.
 //
+// F(2x2,2x2) for upsample -> 3x3 convolution (models.lua:211-212) is the same with 2x2 phase kernels and 9 positions.
+// What the two families and their kernels share lives once:
+//   transforms : wino_tile_walk (the (tile, channel quad) walk of all five input-side kernels), wino_load_patch (4x4 patch of a plain
+//                tensor) and wino_load_dy_patch<side, origin> (a patch of dy's phase sub-lattices); a kernel adds its own B^T . B or A . A^T
+//   filters    : wino_filter_transform_items / _kernel / _both_kernel<Family>; WinoF23 and WinoF22 supply the tap count and G g G^T
+//   GEMMs      : wino_place (XCD placement), wino_out_coeffs<NPOS> (A^T (x) A^T), wino_store_generic + wino_store_stats (the generic
+//                store-and-statistics tail) under wino_gemm_kernel (register staging) and wino_gemm_g_kernel (LDS-direct loads)
+//   host       : glds_ok, wino_gemm_launch, wino_pack<Family>, wino_dgrad_pair (transform + GEMMs, K-sliced or not, of both families)
+//
 // Numerics: exact-fp32 MFMA as everywhere; the transforms add a few ulp (entries 0, +-1, +-1/2), the parity
 // tests hold the layer to the same 2e-5*sqrt(K/1024) bound as the direct path.
 #include "common.h"
@@ -26,19 +35,19 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 __device__ __forceinline__ float wf4c(const float4& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
 __device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 f4sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
+__device__ __forceinline__ float4 f4neg(float4 a) { return make_float4(-a.x, -a.y, -a.z, -a.w); }
 
 // ---------------------------------------------------------------------------
-// V[xi][tile][c] = (B^T d B)[xi] of the 4x4 patch around tile (n, ti, tj): rows 2ti-1 .. 2ti+2.
-// MODE 0: d from a plain NHWC tensor [N][Hl][Wl][C].
-// MODE 1: d from the phase sub-lattices of dy [N][2Hl][2Wl][Cs]: channel c = p*Cs + co reads dy[2i+a][2j+b][co].
-// One thread per (tile, channel quad): 16 float4 loads, 16 float4 stores, coalesced along the channels.
+// Input-side transforms: one thread per (tile, channel quad), float4 loads and stores coalesced along the channels.
 // ---------------------------------------------------------------------------
-template <int MODE>
-__global__ __launch_bounds__(256) void wino_input_transform_kernel(const float* __restrict__ src, float* __restrict__ V,
-                                                                   int N, int Hl, int Wl, int C, int Cs) {
+// The walk they share, over the 2x2 tiles of [N][Hl][Wl] and the quads of C channels: body(n, ti, tj, c, off, xs) gets the image, the
+// tile's row and column, the quad's first channel, the offset of plane 0's element [tile][c] and the stride between planes.
+template <class Body>
+__device__ __forceinline__ void wino_tile_walk(int N, int Hl, int Wl, int C, Body body) {
     const int cq_n = C >> 2;
     const int tH = Hl >> 1, tW = Wl >> 1;
     const long T = (long)N * tH * tW;
@@ -49,25 +58,50 @@ __global__ __launch_bounds__(256) void wino_input_transform_kernel(const float* 
         const int tj = (int)(tile % tW);
         const int ti = (int)((tile / tW) % tH);
         const long n = tile / ((long)tW * tH);
-        int pa = 0, pb = 0, cs = cq * 4;
-        if (MODE == 1) {
-            const int p = cs / Cs;
-            cs -= p * Cs;
-            pa = p >> 1; pb = p & 1;
+        body(n, ti, tj, cq * 4, tile * C + cq * 4, T * C);
+    }
+}
+
+// d = the 4x4 patch around tile (n, ti, tj), rows 2ti-1 .. 2ti+2, of a plain NHWC tensor [N][Hl][Wl][C]: zero outside the image
+__device__ __forceinline__ void wino_load_patch(const float* src, long n, int ti, int tj, int Hl, int Wl, int C, int c, float4 (&d)[4][4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) {
+            const int iy = 2 * ti - 1 + r, ix = 2 * tj - 1 + cc;
+            const bool ok = iy >= 0 && iy < Hl && ix >= 0 && ix < Wl;
+            const int cy = min(max(iy, 0), Hl - 1), cx = min(max(ix, 0), Wl - 1);
+            const float4 q = ld4(src + ((n * Hl + cy) * (long)Wl + cx) * C + c);
+            d[r][cc] = ok ? q : make_float4(0.f, 0.f, 0.f, 0.f);
         }
+}
+
+// The same of the phase sub-lattices of dy [N][2Hl][2Wl][Cs]: channel c = p*Cs + co reads dy[2i+a][2j+b][co], (a, b) = phase p.
+// S x S pixels from row 2ti - 1 (BY_PHASE false: F(2x2,3x3)) or from row 2ti - a (true: the window of F(2x2,2x2)'s data gradient).
+template <int S, bool BY_PHASE>
+__device__ __forceinline__ void wino_load_dy_patch(const float* dy, long n, int ti, int tj, int Hl, int Wl, int Cs, int c, float4 (&d)[S][S]) {
+    const int p = c / Cs, cs = c - p * Cs;
+    const int pa = p >> 1, pb = p & 1;
+#pragma unroll
+    for (int r = 0; r < S; ++r)
+#pragma unroll
+        for (int cc = 0; cc < S; ++cc) {
+            const int iy = 2 * ti - (BY_PHASE ? pa : 1) + r, ix = 2 * tj - (BY_PHASE ? pb : 1) + cc;
+            const bool ok = iy >= 0 && iy < Hl && ix >= 0 && ix < Wl;
+            const int cy = min(max(iy, 0), Hl - 1), cx = min(max(ix, 0), Wl - 1);
+            const float4 q = ld4(dy + ((n * 2 * Hl + 2 * cy + pa) * (long)(2 * Wl) + 2 * cx + pb) * Cs + cs);
+            d[r][cc] = ok ? q : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+}
+
+// F(2x2,3x3): V[xi][tile][c] = (B^T d B)[xi] of the 4x4 patch.  MODE 0: d from a plain tensor; MODE 1: from dy's sub-lattices (C = 4 Cs).
+template <int MODE>
+__global__ __launch_bounds__(256) void wino_input_transform_kernel(const float* __restrict__ src, float* __restrict__ V,
+                                                                   int N, int Hl, int Wl, int C, int Cs) {
+    wino_tile_walk(N, Hl, Wl, C, [&](long n, int ti, int tj, int c0, long off, long xs) {
         float4 d[4][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const int iy = 2 * ti - 1 + r, ix = 2 * tj - 1 + c;
-                const bool ok = iy >= 0 && iy < Hl && ix >= 0 && ix < Wl;
-                const int cy = min(max(iy, 0), Hl - 1), cx = min(max(ix, 0), Wl - 1);
-                const float* ptr = MODE == 0 ? src + ((n * Hl + cy) * (long)Wl + cx) * C + cs
-                                             : src + ((n * 2 * Hl + 2 * cy + pa) * (long)(2 * Wl) + 2 * cx + pb) * Cs + cs;
-                const float4 q = ld4(ptr);
-                d[r][c] = ok ? q : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
+        if (MODE == 0) wino_load_patch(src, n, ti, tj, Hl, Wl, C, c0, d);
+        else wino_load_dy_patch<4, false>(src, n, ti, tj, Hl, Wl, Cs, c0, d);
         float4 t[4][4];
 #pragma unroll
         for (int c = 0; c < 4; ++c) {  // B^T d
@@ -76,85 +110,17 @@ __global__ __launch_bounds__(256) void wino_input_transform_kernel(const float* 
             t[2][c] = f4sub(d[2][c], d[1][c]);
             t[3][c] = f4sub(d[1][c], d[3][c]);
         }
-        float* out = V + tile * C + cq * 4;
-        const long xs = T * C;
+        float* out = V + off;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {  // (.) B
-            *reinterpret_cast<float4*>(out + (r * 4 + 0) * xs) = f4sub(t[r][0], t[r][2]);
-            *reinterpret_cast<float4*>(out + (r * 4 + 1) * xs) = f4add(t[r][1], t[r][2]);
-            *reinterpret_cast<float4*>(out + (r * 4 + 2) * xs) = f4sub(t[r][2], t[r][1]);
-            *reinterpret_cast<float4*>(out + (r * 4 + 3) * xs) = f4sub(t[r][1], t[r][3]);
+            st4(out + (r * 4 + 0) * xs, f4sub(t[r][0], t[r][2]));
+            st4(out + (r * 4 + 1) * xs, f4add(t[r][1], t[r][2]));
+            st4(out + (r * 4 + 2) * xs, f4sub(t[r][2], t[r][1]));
+            st4(out + (r * 4 + 3) * xs, f4sub(t[r][1], t[r][3]));
         }
-    }
+    });
 }
 
-// ---------------------------------------------------------------------------
-// U = G g G^T of the phase kernels.
-// FWD: src = wf_ph [p][tp][ci][co]  ->  U[p][xi][ci][co]
-// BWD: src = wb_ph [p][tp][co][ci]  ->  U[xi][p*Cout+co][ci] of the FLIPPED kernel (data gradient operand)
-// One thread per (p, row, column quad) of the [rows][cols] plane (rows x cols = Cin x Cout or Cout x Cin).
-// ---------------------------------------------------------------------------
-// Items first, first + step, ... of the plane: the two kernels below differ only in which workgroups walk which operand.
-template <bool BWD>
-__device__ __forceinline__ void wino_filter_transform_items(const float* __restrict__ src, float* __restrict__ U, int rows, int cols,
-                                                            long first, long step) {
-    const int cqn = cols >> 2;
-    const long plane = (long)rows * cols;
-    const long total = 4L * rows * cqn;
-    for (long idx = first; idx < total; idx += step) {
-        const int cq = (int)(idx % cqn);
-        const int row = (int)((idx / cqn) % rows);
-        const int p = (int)(idx / ((long)cqn * rows));
-        float4 g[3][3];
-#pragma unroll
-        for (int ry = 0; ry < 3; ++ry)
-#pragma unroll
-            for (int rx = 0; rx < 3; ++rx) {
-                const int tp = BWD ? (2 - ry) * 3 + (2 - rx) : ry * 3 + rx;
-                g[ry][rx] = ld4(src + ((long)p * 9 + tp) * plane + (long)row * cols + cq * 4);
-            }
-        float4 t[4][3];  // G g
-#pragma unroll
-        for (int rx = 0; rx < 3; ++rx) {
-            const float4 s = f4add(g[0][rx], g[2][rx]);
-            t[0][rx] = g[0][rx];
-            t[1][rx] = make_float4(0.5f * (s.x + g[1][rx].x), 0.5f * (s.y + g[1][rx].y), 0.5f * (s.z + g[1][rx].z), 0.5f * (s.w + g[1][rx].w));
-            t[2][rx] = make_float4(0.5f * (s.x - g[1][rx].x), 0.5f * (s.y - g[1][rx].y), 0.5f * (s.z - g[1][rx].z), 0.5f * (s.w - g[1][rx].w));
-            t[3][rx] = g[2][rx];
-        }
-#pragma unroll
-        for (int xy = 0; xy < 4; ++xy) {
-            const float4 s = f4add(t[xy][0], t[xy][2]);
-            float4 o[4];
-            o[0] = t[xy][0];
-            o[1] = make_float4(0.5f * (s.x + t[xy][1].x), 0.5f * (s.y + t[xy][1].y), 0.5f * (s.z + t[xy][1].z), 0.5f * (s.w + t[xy][1].w));
-            o[2] = make_float4(0.5f * (s.x - t[xy][1].x), 0.5f * (s.y - t[xy][1].y), 0.5f * (s.z - t[xy][1].z), 0.5f * (s.w - t[xy][1].w));
-            o[3] = t[xy][2];
-#pragma unroll
-            for (int xx = 0; xx < 4; ++xx) {
-                const int xi = xy * 4 + xx;
-                float* dst = BWD ? U + ((long)xi * 4 * rows + (long)p * rows + row) * cols + cq * 4
-                                 : U + (((long)p * 16 + xi) * rows + row) * cols + cq * 4;
-                *reinterpret_cast<float4*>(dst) = o[xx];
-            }
-        }
-    }
-}
-template <bool BWD>
-__global__ __launch_bounds__(256) void wino_filter_transform_kernel(const float* __restrict__ src, float* __restrict__ U,
-                                                                    int rows, int cols) {
-    wino_filter_transform_items<BWD>(src, U, rows, cols, blockIdx.x * 256L + threadIdx.x, gridDim.x * 256L);
-}
-// Both operands in ONE launch (CG_PACK_WIDE): workgroups [0, nf) walk the forward operand, the others the data gradient's.
-__global__ __launch_bounds__(256) void wino_filter_transform_both_kernel(const float* __restrict__ wf_ph, float* __restrict__ u_fwd,
-                                                                         const float* __restrict__ wb_ph, float* __restrict__ u_bwd,
-                                                                         int Cin, int Cout, int nf) {
-    const int b = blockIdx.x;
-    if (b < nf) wino_filter_transform_items<false>(wf_ph, u_fwd, Cin, Cout, b * 256L + threadIdx.x, nf * 256L);
-    else wino_filter_transform_items<true>(wb_ph, u_bwd, Cout, Cin, (b - nf) * 256L + threadIdx.x, ((int)gridDim.x - nf) * 256L);
-}
-
-// ---------------------------------------------------------------------------
 // F(2x2,2x2) for nn.SpatialUpSamplingNearest(2) -> 3x3 convolution (models.lua:211-212; round 4).  After the phase folding, output
 // phase (a,b) is a 2x2-tap convolution of the low-res input whose window starts at row -1 + a, column -1 + b: per 2x2 tile of low-res
 // outputs and phase, 16 multiplies per channel pair; Winograd's minimal form needs 9 (y0 = (d0-d1) g0 + d1 (g0+g1), y1 = d1 (g0+g1) +
@@ -162,33 +128,12 @@ __global__ __launch_bounds__(256) void wino_filter_transform_both_kernel(const f
 // additions).  The four phases' 3x3 windows are the four 3x3 corners of ONE 4x4 patch (rows 2ti-1 .. 2ti+2), so the input transform
 // reads the patch once and writes 4 x 9 planes:  V[(p*9 + xi)][tile][c].  The GEMMs and the output transform are wino_gemm_g_kernel's
 // with 9 positions and V taken per phase.
-// One thread per (tile, channel quad): 16 float4 loads, 36 float4 stores.
-// ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void wino22_input_transform_kernel(const float* __restrict__ src, float* __restrict__ V, int N, int Hl,
                                                                      int Wl, int C) {
-    const int cq_n = C >> 2;
-    const int tH = Hl >> 1, tW = Wl >> 1;
-    const long T = (long)N * tH * tW;
-    const long total = T * cq_n;
-    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += gridDim.x * 256L) {
-        const int cq = (int)(idx % cq_n);
-        const long tile = idx / cq_n;
-        const int tj = (int)(tile % tW);
-        const int ti = (int)((tile / tW) % tH);
-        const long n = tile / ((long)tW * tH);
+    wino_tile_walk(N, Hl, Wl, C, [&](long n, int ti, int tj, int c0, long off, long xs) {
         float4 d[4][4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const int iy = 2 * ti - 1 + r, ix = 2 * tj - 1 + c;
-                const bool ok = iy >= 0 && iy < Hl && ix >= 0 && ix < Wl;
-                const int cy = min(max(iy, 0), Hl - 1), cx = min(max(ix, 0), Wl - 1);
-                const float4 q = ld4(src + ((n * Hl + cy) * (long)Wl + cx) * C + cq * 4);
-                d[r][c] = ok ? q : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        float* out = V + tile * C + cq * 4;
-        const long xs = T * C;
+        wino_load_patch(src, n, ti, tj, Hl, Wl, C, c0, d);
+        float* out = V + off;
 #pragma unroll
         for (int a = 0; a < 2; ++a) {
             float4 t[3][4];   // B^T applied to rows a .. a+2, all four columns
@@ -203,65 +148,133 @@ __global__ __launch_bounds__(256) void wino22_input_transform_kernel(const float
                 const long pbase = (long)(a * 2 + b) * 9;
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
-                    *reinterpret_cast<float4*>(out + (pbase + i * 3 + 0) * xs) = f4sub(t[i][b], t[i][b + 1]);
-                    *reinterpret_cast<float4*>(out + (pbase + i * 3 + 1) * xs) = t[i][b + 1];
-                    *reinterpret_cast<float4*>(out + (pbase + i * 3 + 2) * xs) = f4sub(t[i][b + 2], t[i][b + 1]);
+                    st4(out + (pbase + i * 3 + 0) * xs, f4sub(t[i][b], t[i][b + 1]));
+                    st4(out + (pbase + i * 3 + 1) * xs, t[i][b + 1]);
+                    st4(out + (pbase + i * 3 + 2) * xs, f4sub(t[i][b + 2], t[i][b + 1]));
                 }
             }
         }
-    }
+    });
 }
 
 // Data gradient of the same layers.  dx_lo[u][v] = sum_p sum_r dy_p[u - a + ry][v - b + rx] . g_p[1-ry][1-rx] over the phase
 // sub-lattices dy_p[i][j] = dy[2i+a][2j+b]: per phase a 2x2-tap correlation with the flipped kernel whose window starts at row u - a,
 // the four phases summed - one F(2x2,2x2) problem with the phases side by side along K (K = 4 Cout).
-// V[xi][tile][p*Cs + co] = B^T d B of the 3x3 patch (rows 2ti - a .. 2ti - a + 2 of sub-lattice p).  One thread per (tile, channel
-// quad): 9 float4 loads, 9 float4 stores.
+// V[xi][tile][p*Cs + co] = B^T d B of the 3x3 patch (rows 2ti - a .. 2ti - a + 2 of sub-lattice p).
 __global__ __launch_bounds__(256) void wino22_dy_input_transform_kernel(const float* __restrict__ dy, float* __restrict__ V, int N, int Hl,
                                                                         int Wl, int Cs) {
-    const int C = 4 * Cs, cq_n = C >> 2;
-    const int tH = Hl >> 1, tW = Wl >> 1;
-    const long T = (long)N * tH * tW;
-    const long total = T * cq_n;
-    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += gridDim.x * 256L) {
-        const int cq = (int)(idx % cq_n);
-        const long tile = idx / cq_n;
-        const int tj = (int)(tile % tW);
-        const int ti = (int)((tile / tW) % tH);
-        const long n = tile / ((long)tW * tH);
-        const int p = (cq * 4) / Cs, cs = cq * 4 - p * Cs;
-        const int pa = p >> 1, pb = p & 1;
+    wino_tile_walk(N, Hl, Wl, 4 * Cs, [&](long n, int ti, int tj, int c0, long off, long xs) {
         float4 d[3][3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int iy = 2 * ti - pa + r, ix = 2 * tj - pb + c;
-                const bool ok = iy >= 0 && iy < Hl && ix >= 0 && ix < Wl;
-                const int cy = min(max(iy, 0), Hl - 1), cx = min(max(ix, 0), Wl - 1);
-                const float4 q = ld4(dy + ((n * 2 * Hl + 2 * cy + pa) * (long)(2 * Wl) + 2 * cx + pb) * Cs + cs);
-                d[r][c] = ok ? q : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
+        wino_load_dy_patch<3, true>(dy, n, ti, tj, Hl, Wl, Cs, c0, d);
         float4 t[3][3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) { t[0][c] = f4sub(d[0][c], d[1][c]); t[1][c] = d[1][c]; t[2][c] = f4sub(d[2][c], d[1][c]); }
-        float* out = V + tile * C + cq * 4;
-        const long xs = T * C;
+        float* out = V + off;
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            *reinterpret_cast<float4*>(out + (i * 3 + 0) * xs) = f4sub(t[i][0], t[i][1]);
-            *reinterpret_cast<float4*>(out + (i * 3 + 1) * xs) = t[i][1];
-            *reinterpret_cast<float4*>(out + (i * 3 + 2) * xs) = f4sub(t[i][2], t[i][1]);
+            st4(out + (i * 3 + 0) * xs, f4sub(t[i][0], t[i][1]));
+            st4(out + (i * 3 + 1) * xs, t[i][1]);
+            st4(out + (i * 3 + 2) * xs, f4sub(t[i][2], t[i][1]));
         }
+    });
+}
+
+// Weight gradient of F(2x2,3x3), Winograd domain: Mdy[xi][tile][p*Cout+co] = (A dY_p A^T)[xi] per tile and phase (A = [1 0; 1 1; 1 -1;
+// 0 -1]); then dU_xi = V_xi^T Mdy_xi (plain TN GEMMs) and wino_wgrad_finish_kernel maps G^T dU G back to the 5x5 taps.
+// (gradBias partial sums from this kernel - it reads every dy anyway - were parity-clean but cost the step 0.6 % in round 4: the separate
+// 59 us pass of cg_bias_grad is not on the critical path, the longer transform is.)
+__global__ __launch_bounds__(256) void wino_dy_transform_kernel(const float* __restrict__ dy, float* __restrict__ Mdy, int N,
+                                                                int Hl, int Wl, int Cout) {
+    wino_tile_walk(N, Hl, Wl, 4 * Cout, [&](long n, int ti, int tj, int c0, long off, long xs) {
+        const int p = c0 / Cout, co = c0 - p * Cout;
+        const int pa = p >> 1, pb = p & 1;
+        float4 e[2][2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int v = 0; v < 2; ++v)
+                e[u][v] = ld4(dy + ((n * 2 * Hl + 2 * (2 * ti + u) + pa) * (long)(2 * Wl) + 2 * (2 * tj + v) + pb) * Cout + co);
+        float4 r[4][2];
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            r[0][v] = e[0][v];
+            r[1][v] = f4add(e[0][v], e[1][v]);
+            r[2][v] = f4sub(e[0][v], e[1][v]);
+            r[3][v] = f4neg(e[1][v]);
+        }
+        float* out = Mdy + off;
+#pragma unroll
+        for (int xy = 0; xy < 4; ++xy) {
+            st4(out + (xy * 4 + 0) * xs, r[xy][0]);
+            st4(out + (xy * 4 + 1) * xs, f4add(r[xy][0], r[xy][1]));
+            st4(out + (xy * 4 + 2) * xs, f4sub(r[xy][0], r[xy][1]));
+            st4(out + (xy * 4 + 3) * xs, f4neg(r[xy][1]));
+        }
+    });
+}
+
+// out = the sum of S (2 or 4) partial results `stride` floats apart, in a fixed order: the K slices of a sliced data gradient
+template <int S>
+__global__ __launch_bounds__(256) void wino22_sum_kernel(const float* __restrict__ part, float* __restrict__ out, long n4, long stride) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += gridDim.x * 256L) {
+        const float4 a = ld4(part + 4 * i), b = ld4(part + stride + 4 * i);
+        float4 r = f4add(a, b);
+        if (S == 4) r = f4add(r, f4add(ld4(part + 2 * stride + 4 * i), ld4(part + 3 * stride + 4 * i)));
+        st4(out + 4 * i, r);
     }
 }
 
-// U = G g_p G^T of the 2x2 phase kernels.
-// FWD: src = wf_ph [p][tp = ry*2 + rx][ci][co] -> U[p][xi = i*3 + j][ci][co].
-// BWD: src = wb_ph [p][tp][co][ci] -> U[xi][p*Cout + co][ci] of the FLIPPED kernel (data-gradient operand: the four phases side by side along K).
-template <bool BWD>
-__device__ __forceinline__ void wino22_filter_transform_items(const float* __restrict__ src, float* __restrict__ U, int rows, int cols,
-                                                              long first, long step) {
+// ---------------------------------------------------------------------------
+// U = G g G^T of the phase kernels, R x R taps -> P x P positions.
+// FWD: src = wf_ph [p][tp][ci][co]  ->  U[p][xi][ci][co]
+// BWD: src = wb_ph [p][tp][co][ci]  ->  U[xi][p*Cout+co][ci] of the FLIPPED kernel (data gradient operand: the four phases side by side
+//      along K)
+// One thread per (p, row, column quad) of the [rows][cols] plane (rows x cols = Cin x Cout or Cout x Cin).  A family supplies its tap
+// count, its position count and G g G^T on float4s; the walk, the flip and the destination index are the same for both.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float4 f4half_sum(float4 s, float4 g) {   // 0.5 (s + g)
+    return make_float4(0.5f * (s.x + g.x), 0.5f * (s.y + g.y), 0.5f * (s.z + g.z), 0.5f * (s.w + g.w));
+}
+__device__ __forceinline__ float4 f4half_diff(float4 s, float4 g) {  // 0.5 (s - g)
+    return make_float4(0.5f * (s.x - g.x), 0.5f * (s.y - g.y), 0.5f * (s.z - g.z), 0.5f * (s.w - g.w));
+}
+struct WinoF23 {   // 3x3 phase kernels of the 5x5 layer, G = [1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1]
+    static constexpr int R = 3, P = 4;
+    static __device__ __forceinline__ void ggt(const float4 (&g)[3][3], float4 (&o)[16]) {
+        float4 t[4][3];  // G g
+#pragma unroll
+        for (int rx = 0; rx < 3; ++rx) {
+            const float4 s = f4add(g[0][rx], g[2][rx]);
+            t[0][rx] = g[0][rx];
+            t[1][rx] = f4half_sum(s, g[1][rx]);
+            t[2][rx] = f4half_diff(s, g[1][rx]);
+            t[3][rx] = g[2][rx];
+        }
+#pragma unroll
+        for (int xy = 0; xy < 4; ++xy) {
+            const float4 s = f4add(t[xy][0], t[xy][2]);
+            o[xy * 4 + 0] = t[xy][0];
+            o[xy * 4 + 1] = f4half_sum(s, t[xy][1]);
+            o[xy * 4 + 2] = f4half_diff(s, t[xy][1]);
+            o[xy * 4 + 3] = t[xy][2];
+        }
+    }
+};
+struct WinoF22 {   // 2x2 phase kernels of the 3x3 layer, G = [1 0; 1 1; 0 1]
+    static constexpr int R = 2, P = 3;
+    static __device__ __forceinline__ void ggt(const float4 (&g)[2][2], float4 (&o)[9]) {
+        float4 t[3][2];  // G g
+#pragma unroll
+        for (int rx = 0; rx < 2; ++rx) { t[0][rx] = g[0][rx]; t[1][rx] = f4add(g[0][rx], g[1][rx]); t[2][rx] = g[1][rx]; }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { o[i * 3 + 0] = t[i][0]; o[i * 3 + 1] = f4add(t[i][0], t[i][1]); o[i * 3 + 2] = t[i][1]; }
+    }
+};
+// Items first, first + step, ... of the plane: the two kernels below differ only in which workgroups walk which operand.
+template <class F, bool BWD>
+__device__ __forceinline__ void wino_filter_transform_items(const float* __restrict__ src, float* __restrict__ U, int rows, int cols,
+                                                            long first, long step) {
+    constexpr int R = F::R, NPOS = F::P * F::P;
     const int cqn = cols >> 2;
     const long plane = (long)rows * cols;
     const long total = 4L * rows * cqn;
@@ -269,45 +282,40 @@ __device__ __forceinline__ void wino22_filter_transform_items(const float* __res
         const int cq = (int)(idx % cqn);
         const int row = (int)((idx / cqn) % rows);
         const int p = (int)(idx / ((long)cqn * rows));
-        float4 g[2][2];
+        float4 g[R][R];
 #pragma unroll
-        for (int ry = 0; ry < 2; ++ry)
+        for (int ry = 0; ry < R; ++ry)
 #pragma unroll
-            for (int rx = 0; rx < 2; ++rx) {
-                const int tp = BWD ? (1 - ry) * 2 + (1 - rx) : ry * 2 + rx;
-                g[ry][rx] = ld4(src + ((long)p * 4 + tp) * plane + (long)row * cols + cq * 4);
+            for (int rx = 0; rx < R; ++rx) {
+                const int tp = BWD ? (R - 1 - ry) * R + (R - 1 - rx) : ry * R + rx;
+                g[ry][rx] = ld4(src + ((long)p * (R * R) + tp) * plane + (long)row * cols + cq * 4);
             }
-        float4 t[3][2];   // G g
+        float4 o[NPOS];
+        F::ggt(g, o);
 #pragma unroll
-        for (int rx = 0; rx < 2; ++rx) { t[0][rx] = g[0][rx]; t[1][rx] = f4add(g[0][rx], g[1][rx]); t[2][rx] = g[1][rx]; }
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            float* dst = BWD ? U + ((long)(i * 3) * 4 * rows + (long)p * rows + row) * cols + cq * 4
-                             : U + (((long)p * 9 + i * 3) * rows + row) * cols + cq * 4;
-            const long xstep = BWD ? 4 * plane : plane;   // distance between neighbouring positions xi
-            *reinterpret_cast<float4*>(dst) = t[i][0];
-            *reinterpret_cast<float4*>(dst + xstep) = f4add(t[i][0], t[i][1]);
-            *reinterpret_cast<float4*>(dst + 2 * xstep) = t[i][1];
-        }
+        for (int xi = 0; xi < NPOS; ++xi)
+            st4(BWD ? U + ((long)xi * 4 * rows + (long)p * rows + row) * cols + cq * 4
+                    : U + (((long)p * NPOS + xi) * rows + row) * cols + cq * 4, o[xi]);
     }
 }
-template <bool BWD>
-__global__ __launch_bounds__(256) void wino22_filter_transform_kernel(const float* __restrict__ src, float* __restrict__ U, int rows,
-                                                                      int cols) {
-    wino22_filter_transform_items<BWD>(src, U, rows, cols, blockIdx.x * 256L + threadIdx.x, gridDim.x * 256L);
+template <class F, bool BWD>
+__global__ __launch_bounds__(256) void wino_filter_transform_kernel(const float* __restrict__ src, float* __restrict__ U,
+                                                                    int rows, int cols) {
+    wino_filter_transform_items<F, BWD>(src, U, rows, cols, blockIdx.x * 256L + threadIdx.x, gridDim.x * 256L);
 }
-// Both operands in ONE launch (CG_PACK_WIDE), as wino_filter_transform_both_kernel.
-__global__ __launch_bounds__(256) void wino22_filter_transform_both_kernel(const float* __restrict__ wf_ph, float* __restrict__ u_fwd,
-                                                                           const float* __restrict__ wb_ph, float* __restrict__ u_bwd,
-                                                                           int Cin, int Cout, int nf) {
+// Both operands in ONE launch (CG_PACK_WIDE): workgroups [0, nf) walk the forward operand, the others the data gradient's.
+template <class F>
+__global__ __launch_bounds__(256) void wino_filter_transform_both_kernel(const float* __restrict__ wf_ph, float* __restrict__ u_fwd,
+                                                                         const float* __restrict__ wb_ph, float* __restrict__ u_bwd,
+                                                                         int Cin, int Cout, int nf) {
     const int b = blockIdx.x;
-    if (b < nf) wino22_filter_transform_items<false>(wf_ph, u_fwd, Cin, Cout, b * 256L + threadIdx.x, nf * 256L);
-    else wino22_filter_transform_items<true>(wb_ph, u_bwd, Cout, Cin, (b - nf) * 256L + threadIdx.x, ((int)gridDim.x - nf) * 256L);
+    if (b < nf) wino_filter_transform_items<F, false>(wf_ph, u_fwd, Cin, Cout, b * 256L + threadIdx.x, nf * 256L);
+    else wino_filter_transform_items<F, true>(wb_ph, u_bwd, Cout, Cin, (b - nf) * 256L + threadIdx.x, ((int)gridDim.x - nf) * 256L);
 }
 
 // ---------------------------------------------------------------------------
-// The 16 GEMMs + output transform.  Block tile 64 tiles x 128 columns, K step 16, 4 waves of 32 x 64.
-// grid = (T/64 * Nc/128, 1, P).  LDS: A [k][m] XOR-swizzled, B [k][n], double buffered (same scheme as gemm.hip).
+// The 16 (or 9) GEMMs + output transform.  Block tile 64 tiles x 128 columns, 8 waves of 32 x 32.
+// grid = (T/64 * Nc/128, 1, P or K slices).
 // ---------------------------------------------------------------------------
 struct WinoArgs {
     const float* V;      // [16][T][K]
@@ -325,13 +333,90 @@ struct WinoArgs {
     int lg_tw, lg_th;    // log2(tW), log2(tH) when both are powers of two and the output is below 2 GB (wino_gemm_g_kernel's lean epilogue), else -1
 };
 
-// The register-staged form (8 waves, wave tile 32 x 32; BK = K step): the fallback of wino_gemm_g_kernel below for tensors whose
-// planes a buffer descriptor cannot span, and the reference the LDS-direct kernels are tested against.  (The 4-wave and k-quad
-// instances of rounds 2-4 never won an A/B and were removed in round 5.)
-template <int NW, int BK>
-__global__ __launch_bounds__(64 * NW, 4) void wino_gemm_kernel(WinoArgs a) {
-    static_assert(NW == 8, "8 waves per workgroup");
-    constexpr int BM = 64, BN = 128, NI = 8 / NW, NT = 64 * NW;
+// Which (tile block, column block, phase) a workgroup takes.  With a.xcd the ntn * P workgroups that read the same 64-tile block of V
+// (all column blocks, all phases) are placed on ONE XCD in consecutive dispatch slots, so that V comes out of that XCD's L2 after the
+// first of them has fetched it (workgroup L of the dispatch order runs on XCD L % 8).  Needs a multiple of 8 tile blocks; else the
+// plain (x, z) order.
+struct WinoPlace { int tm, tn, phase; };
+__device__ __forceinline__ WinoPlace wino_place(int xcd, int ntn) {
+    int tn = blockIdx.x % ntn, tm = blockIdx.x / ntn, phase = blockIdx.z;
+    const int tiles_m = gridDim.x / ntn;
+    if (xcd && (tiles_m & 7) == 0) {
+        const int share = ntn * (int)gridDim.z;
+        const int L = (int)blockIdx.z * (int)gridDim.x + (int)blockIdx.x;
+        const int slot = L >> 3, member = slot % share;
+        tm = (slot / share) * 8 + (L & 7);
+        phase = member / ntn;
+        tn = member - phase * ntn;
+    }
+    return {tm, tn, phase};
+}
+
+// The coefficients (0 / +-1, wave-uniform) of a finished M_xi in a tile's four outputs (x: (0,0), y: (0,1), z: (1,0), w: (1,1)): the
+// entries of A^T (x) A^T.  F(2x2,3x3), NPOS 16: A^T = [1 1 1 0; 0 1 -1 -1];  F(2x2,2x2), NPOS 9: A^T = [1 1 0; 0 1 1]
+template <int NPOS>
+__device__ __forceinline__ float4 wino_out_coeffs(int xi) {
+    const int xy = NPOS == 16 ? xi >> 2 : xi / 3, xx = NPOS == 16 ? xi & 3 : xi - 3 * (xi / 3);
+    const float cy0 = NPOS == 16 ? (xy < 3 ? 1.f : 0.f) : (xy < 2 ? 1.f : 0.f);
+    const float cy1 = NPOS == 16 ? (xy == 0 ? 0.f : (xy == 1 ? 1.f : -1.f)) : (xy > 0 ? 1.f : 0.f);
+    const float cx0 = NPOS == 16 ? (xx < 3 ? 1.f : 0.f) : (xx < 2 ? 1.f : 0.f);
+    const float cx1 = NPOS == 16 ? (xx == 0 ? 0.f : (xx == 1 ? 1.f : -1.f)) : (xx > 0 ? 1.f : 0.f);
+    return make_float4(cy0 * cx0, cy0 * cx1, cy1 * cx0, cy1 * cx1);
+}
+
+// The generic store of a wave's 32 x 32 block of the four outputs: accumulator row r holds tile mrow + (r&3) + 8*(r>>2), the lane column
+// col; two integer divisions per row and a 64-bit address per value.  Returns the sums of the stored values and of their squares (stats).
+// REG_STAGED keeps what differed between the two kernels when each had this tail to itself.  wino_gemm_kernel (true) sits at its 128
+// registers: it re-reads the bias per value instead of holding it (bcol unused), and every square joins its sum by one fused
+// multiply-add - the first two as fma(v0, v0, rn(v1 v1)), which is how 0 + v0 v0 + v1 v1 was contracted.  wino_gemm_g_kernel (false)
+// holds the bias in bcol and adds the rounded square; its lean path is its own.
+template <bool REG_STAGED>
+__device__ __forceinline__ float2 wino_store_generic(const WinoArgs& a, float* yout, const f32x16 (&accY)[4], float bcol, int mrow, int col,
+                                                     int pa, int pb) {
+    float st1 = 0.f, st2 = 0.f, v0 = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int m = mrow + (r & 3) + 8 * (r >> 2);
+        if (m >= a.T) continue;
+        const int tj = m % a.tW;
+        const int ti = (m / a.tW) % a.tH;
+        const long n = m / (a.tW * a.tH);
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            const int oy = (2 * ti + (o >> 1)) * a.so + pa, ox = (2 * tj + (o & 1)) * a.so + pb;
+            const float v = accY[o][r] + (REG_STAGED ? (a.bias ? a.bias[col] : 0.f) : bcol);
+            yout[((n * a.Ho + oy) * (long)a.Wo + ox) * a.Nc + col] = v;
+            if (a.stats) {
+                st1 += v;
+                if (REG_STAGED && (r > 0 || o > 1)) st2 = __builtin_fmaf(v, v, st2);
+                else {
+#pragma clang fp contract(off)
+                    const float sq = v * v;
+                    if (!REG_STAGED) st2 += sq;
+                    else if (o == 0) v0 = v;
+                    else st2 = __builtin_fmaf(v0, v0, sq);
+                }
+            }
+        }
+    }
+    return make_float2(st1, st2);
+}
+// ... and the statistics row of (phase, tile block tm, wave row wr): the two lane halves hold the two halves of the block's rows
+__device__ __forceinline__ void wino_store_stats(const WinoArgs& a, int phase, int tm, int wr, int h, int col, float st1, float st2) {
+    const int srow = (phase * (int)((a.T + 63) / 64) + tm) * 2 + wr;
+    const float t1 = st1 + __shfl_xor(st1, 32, 64), t2 = st2 + __shfl_xor(st2, 32, 64);
+    if (h == 0) {
+        a.stats[((long)srow * 2 + 0) * a.Nc + col] = t1;
+        a.stats[((long)srow * 2 + 1) * a.Nc + col] = t2;
+    }
+}
+
+// The register-staged form (BK = K step; LDS: A [k][m] XOR-swizzled, B [k][n], double buffered, the scheme of gemm.hip): the fallback of
+// wino_gemm_g_kernel below for tensors whose planes a buffer descriptor cannot span, and the reference the LDS-direct kernels are tested
+// against.  (The 4-wave and k-quad instances of rounds 2-4 never won an A/B and were removed in round 5.)
+template <int BK>
+__global__ __launch_bounds__(512, 4) void wino_gemm_kernel(WinoArgs a) {
+    constexpr int BM = 64, BN = 128, NT = 512;
     constexpr int KV = BK / 4;                 // float4 per A row per K tile
     constexpr int BQ = BK * 32 / NT;           // B float4 per thread (1 or 2), NT/32 rows apart
     static_assert(BM * KV <= NT && (BQ == 1 || BQ == 2), "staging layout");
@@ -341,22 +426,10 @@ __global__ __launch_bounds__(64 * NW, 4) void wino_gemm_kernel(WinoArgs a) {
     float* Bs = smem + 2 * A_TILE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
-    const int wm0 = (wave & 1) * 32, wn0 = (wave >> 1) * (32 * NI);
-    const int ntn = a.Nc / BN;
-    // The ntn * P workgroups that read the same 64-tile block of V (all column blocks, all phases) are placed on ONE XCD in
-    // consecutive dispatch slots, so that V comes out of that XCD's L2 after the first of them has fetched it (workgroup L of
-    // the dispatch order runs on XCD L % 8).  Needs a multiple of 8 tile blocks; else the plain (x, z) order.
-    int tn = blockIdx.x % ntn, tm = blockIdx.x / ntn, phase = blockIdx.z;
-    const int tiles_m = gridDim.x / ntn;
-    if (a.xcd && (tiles_m & 7) == 0) {
-        const int share = ntn * (int)gridDim.z;
-        const int L = (int)blockIdx.z * (int)gridDim.x + (int)blockIdx.x;
-        const int slot = L >> 3, member = slot % share;
-        tm = (slot / share) * 8 + (L & 7);
-        phase = member / ntn;
-        tn = member - phase * ntn;
-    }
-    const int m0 = tm * BM, n0 = tn * BN;
+    const int wm0 = (wave & 1) * 32, wn0 = (wave >> 1) * 32;
+    const WinoPlace pl = wino_place(a.xcd, a.Nc / BN);
+    const int tm = pl.tm, phase = pl.phase;
+    const int m0 = tm * BM, n0 = pl.tn * BN;
     const int KT = CG_PROBE_HALF(4, a.K / BK);
 
     // staging: A one float4 per thread (row a_r, k quad a_kv); B two float4 per thread
@@ -395,15 +468,13 @@ __global__ __launch_bounds__(64 * NW, 4) void wino_gemm_kernel(WinoArgs a) {
         if (BQ == 2) *reinterpret_cast<float4*>(B + (b_kr + NT / 32) * BN + 4 * b_nv) = breg1;
     };
 
-    f32x16 accM[NI], accY[4][NI];
+    f32x16 accM, accY[4];
 #pragma unroll
-    for (int j = 0; j < NI; ++j)
+    for (int r = 0; r < 16; ++r) {
+        accM[r] = 0.f;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            accM[j][r] = 0.f;
-#pragma unroll
-            for (int o = 0; o < 4; ++o) accY[o][j][r] = 0.f;
-        }
+        for (int o = 0; o < 4; ++o) accY[o][r] = 0.f;
+    }
 
     areg = ld4(Ac);
     breg0 = ld4(Bc);
@@ -419,9 +490,7 @@ __global__ __launch_bounds__(64 * NW, 4) void wino_gemm_kernel(WinoArgs a) {
 #pragma unroll
         for (int kk = 0; kk < BK; kk += 2) {
             const float av = A[(kk + h) * BM + (l31 ^ (BK == 32 ? (((kk >> 2) & 7) << 2) : (((kk >> 2) & 3) << 3)))];
-#pragma unroll
-            for (int j = 0; j < NI; ++j)
-                accM[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, B[(kk + h) * BN + j * 32], accM[j], 0, 0, 0);
+            accM = __builtin_amdgcn_mfma_f32_32x32x2f32(av, B[(kk + h) * BN], accM, 0, 0, 0);
         }
         if (more) store_tile(BUF ^ 1);
         __syncthreads();
@@ -432,57 +501,22 @@ __global__ __launch_bounds__(64 * NW, 4) void wino_gemm_kernel(WinoArgs a) {
             const bool last = kt + 2 == KT;
             k_tile(std::integral_constant<int, 1>{}, !(last && xi == 15), last);
         }
-        // M_xi complete: fold it into the four outputs, A^T = [1 1 1 0; 0 1 -1 -1]
-        const int xy = xi >> 2, xx = xi & 3;
-        const float cy0 = xy < 3 ? 1.f : 0.f, cy1 = xy == 0 ? 0.f : (xy == 1 ? 1.f : -1.f);
-        const float cx0 = xx < 3 ? 1.f : 0.f, cx1 = xx == 0 ? 0.f : (xx == 1 ? 1.f : -1.f);
-        const float c00 = cy0 * cx0, c01 = cy0 * cx1, c10 = cy1 * cx0, c11 = cy1 * cx1;
+        // M_xi complete: fold it into the four outputs, all four products (wino_gemm_g_kernel skips the zero ones)
+        const float4 c = wino_out_coeffs<16>(xi);
 #pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float m = accM[j][r];
-                accY[0][j][r] += c00 * m; accY[1][j][r] += c01 * m;
-                accY[2][j][r] += c10 * m; accY[3][j][r] += c11 * m;
-                accM[j][r] = 0.f;
-            }
+        for (int r = 0; r < 16; ++r) {
+            const float m = accM[r];
+            accY[0][r] += c.x * m; accY[1][r] += c.y * m;
+            accY[2][r] += c.z * m; accY[3][r] += c.w * m;
+            accM[r] = 0.f;
+        }
     }
 
     // ---- epilogue: D[i][j], i = (r&3) + 8*(r>>2) + 4*h (tile), j = l31 (column)
     const int pa = a.so == 2 ? (phase >> 1) : 0, pb = a.so == 2 ? (phase & 1) : 0;
-    float st1[NI], st2[NI];
-#pragma unroll
-    for (int j = 0; j < NI; ++j) { st1[j] = 0.f; st2[j] = 0.f; }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (m >= a.T) continue;
-        const int tj = m % a.tW;
-        const int ti = (m / a.tW) % a.tH;
-        const long n = m / (a.tW * a.tH);
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            const int oy = (2 * ti + (o >> 1)) * a.so + pa, ox = (2 * tj + (o & 1)) * a.so + pb;
-            float* row = a.y + ((n * a.Ho + oy) * (long)a.Wo + ox) * a.Nc + n0 + wn0 + l31;
-#pragma unroll
-            for (int j = 0; j < NI; ++j) {
-                const float v = accY[o][j][r] + (a.bias ? a.bias[n0 + wn0 + j * 32 + l31] : 0.f);
-                row[j * 32] = v;
-                if (a.stats) { st1[j] += v; st2[j] += v * v; }
-            }
-        }
-    }
-    if (a.stats) {
-        const int srow = (phase * (int)((a.T + BM - 1) / BM) + tm) * 2 + (wave & 1);
-#pragma unroll
-        for (int j = 0; j < NI; ++j) {
-            const float t1 = st1[j] + __shfl_xor(st1[j], 32, 64), t2 = st2[j] + __shfl_xor(st2[j], 32, 64);
-            if (h == 0) {
-                a.stats[((long)srow * 2 + 0) * a.Nc + n0 + wn0 + j * 32 + l31] = t1;
-                a.stats[((long)srow * 2 + 1) * a.Nc + n0 + wn0 + j * 32 + l31] = t2;
-            }
-        }
-    }
+    const int col = n0 + wn0 + l31;
+    const float2 st = wino_store_generic<true>(a, a.y, accY, 0.f, m0 + wm0 + 4 * h, col, pa, pb);
+    if (a.stats) wino_store_stats(a, phase, tm, wave & 1, h, col, st.x, st.y);
 }
 
 // ---------------------------------------------------------------------------
@@ -513,18 +547,10 @@ __global__ __launch_bounds__(512, 4) void wino_gemm_g_kernel(WinoArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, h = lane >> 5;
     const int wm0 = (wave & 1) * 32, wn0 = (wave >> 1) * 32;
-    const int ntn = a.Nc / BN;
-    int tn = blockIdx.x % ntn, tm = blockIdx.x / ntn, phase = blockIdx.z;
-    const int tiles_m = gridDim.x / ntn;
-    if (a.xcd && (tiles_m & 7) == 0) {   // the workgroups sharing a V block on one XCD, see wino_gemm_kernel
-        const int share = ntn * (int)gridDim.z;
-        const int L = (int)blockIdx.z * (int)gridDim.x + (int)blockIdx.x;
-        const int slot = L >> 3, member = slot % share;
-        tm = (slot / share) * 8 + (L & 7);
-        phase = member / ntn;
-        tn = member - phase * ntn;
-    }
-    const int m0 = tm * BM, n0 = tn * BN;
+    const WinoPlace pl = wino_place(a.xcd, a.Nc / BN);
+    const int tm = pl.tm;
+    int phase = pl.phase;
+    const int m0 = tm * BM, n0 = pl.tn * BN;
     const int Kext = a.kz ? a.kz : a.K;                           // K rows this workgroup walks, from row koff
     const int koff = a.kz ? phase * a.kz : 0;
     float* const yout = a.y + (a.kz ? (long)phase * a.T * 4 * a.Nc : 0L);
@@ -599,46 +625,32 @@ __global__ __launch_bounds__(512, 4) void wino_gemm_g_kernel(WinoArgs a) {
             k_tile(std::integral_constant<int, 0>{}, true);
             k_tile(std::integral_constant<int, 1>{}, !(kt + 2 == KT && xi == NPOS - 1));
         }
-        // M_xi complete: fold it into the four outputs.  F(2x2,3x3): A^T = [1 1 1 0; 0 1 -1 -1];  F(2x2,2x2): A^T = [1 1 0; 0 1 1]
-        const int xy = NPOS == 16 ? xi >> 2 : xi / 3, xx = NPOS == 16 ? xi & 3 : xi - 3 * (xi / 3);
-        const float cy0 = NPOS == 16 ? (xy < 3 ? 1.f : 0.f) : (xy < 2 ? 1.f : 0.f);
-        const float cy1 = NPOS == 16 ? (xy == 0 ? 0.f : (xy == 1 ? 1.f : -1.f)) : (xy > 0 ? 1.f : 0.f);
-        const float cx0 = NPOS == 16 ? (xx < 3 ? 1.f : 0.f) : (xx < 2 ? 1.f : 0.f);
-        const float cx1 = NPOS == 16 ? (xx == 0 ? 0.f : (xx == 1 ? 1.f : -1.f)) : (xx > 0 ? 1.f : 0.f);
-        const float c00 = cy0 * cx0, c01 = cy0 * cx1, c10 = cy1 * cx0, c11 = cy1 * cx1;
-        // the coefficients are 0 / +-1 and wave-uniform (xi is): a zero term is skipped by a scalar branch - 36 of the 64 products of
-        // F(2x2,3x3) (16 of 36 for F(2x2,2x2)) are non-zero, and fp32 MFMA time is VALU time (round 5)
-        if (c00 != 0.f) {
+        // M_xi complete: fold it into the four outputs.  The coefficients are 0 / +-1 and wave-uniform (xi is): a zero term is skipped by a
+        // scalar branch - 36 of the 64 products of F(2x2,3x3) (16 of 36 for F(2x2,2x2)) are non-zero, and fp32 MFMA time is VALU time
+        // (round 5)
+        const float4 c = wino_out_coeffs<NPOS>(xi);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) accY[0][r] += c00 * accM[r];
-        }
-        if (c01 != 0.f) {
+        for (int o = 0; o < 4; ++o)
+            if (wf4c(c, o) != 0.f) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) accY[1][r] += c01 * accM[r];
-        }
-        if (c10 != 0.f) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) accY[2][r] += c10 * accM[r];
-        }
-        if (c11 != 0.f) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) accY[3][r] += c11 * accM[r];
-        }
+                for (int r = 0; r < 16; ++r) accY[o][r] += wf4c(c, o) * accM[r];
+            }
 #pragma unroll
         for (int r = 0; r < 16; ++r) accM[r] = 0.f;
     }
 
-    // ---- epilogue (as wino_gemm_kernel, NI = 1): D[i][j], i = (r&3) + 8*(r>>2) + 4*h (tile), j = l31 (column)
+    // ---- epilogue: D[i][j], i = (r&3) + 8*(r>>2) + 4*h (tile), j = l31 (column)
     const int pa = a.so == 2 ? (phase >> 1) : 0, pb = a.so == 2 ? (phase & 1) : 0;
     float st1 = 0.f, st2 = 0.f;
-    const float bcol = a.bias ? a.bias[n0 + wn0 + l31] : 0.f;
+    const int col = n0 + wn0 + l31;
+    const float bcol = a.bias ? a.bias[col] : 0.f;
     if (a.lg_tw >= 0) {
         // lean path (round 5): power-of-two tile grids and an output below 2 GB - the tile decode is shifts and masks, the pixel's byte
         // offset one 32-bit value per accumulator row, the four outputs of a tile sit at wave-uniform distances (an SGPR offset of the
-        // buffer store), and a row past the last tile stores to the out-of-range offset.  The generic loop below (two integer divisions
+        // buffer store), and a row past the last tile stores to the out-of-range offset.  The generic store (two integer divisions
         // per row, a 64-bit address per value) was ~1.5 VALU per MFMA of the whole launch.
         const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)yout, 0, 0x7fffffff, 0x00020000);
-        const int colb = (n0 + wn0 + l31) * 4;
+        const int colb = col * 4;
         const int rowp = a.Wo * a.Nc * 4;                      // bytes per output row of pixels
         int soffs[4];
 #pragma unroll
@@ -656,30 +668,11 @@ __global__ __launch_bounds__(512, 4) void wino_gemm_g_kernel(WinoArgs a) {
                 if (a.stats && m < a.T) { st1 += v; st2 += v * v; }
             }
         }
-    } else
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = m0 + wm0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (m >= a.T) continue;
-        const int tj = m % a.tW;
-        const int ti = (m / a.tW) % a.tH;
-        const long n = m / (a.tW * a.tH);
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-            const int oy = (2 * ti + (o >> 1)) * a.so + pa, ox = (2 * tj + (o & 1)) * a.so + pb;
-            const float v = accY[o][r] + bcol;
-            yout[((n * a.Ho + oy) * (long)a.Wo + ox) * a.Nc + n0 + wn0 + l31] = v;
-            if (a.stats) { st1 += v; st2 += v * v; }
-        }
+    } else {
+        const float2 st = wino_store_generic<false>(a, yout, accY, bcol, m0 + wm0 + 4 * h, col, pa, pb);
+        st1 = st.x; st2 = st.y;
     }
-    if (a.stats) {
-        const int srow = (phase * (int)((a.T + BM - 1) / BM) + tm) * 2 + (wave & 1);
-        const float t1 = st1 + __shfl_xor(st1, 32, 64), t2 = st2 + __shfl_xor(st2, 32, 64);
-        if (h == 0) {
-            a.stats[((long)srow * 2 + 0) * a.Nc + n0 + wn0 + l31] = t1;
-            a.stats[((long)srow * 2 + 1) * a.Nc + n0 + wn0 + l31] = t2;
-        }
-    }
+    if (a.stats) wino_store_stats(a, phase, tm, wave & 1, h, col, st1, st2);
 }
 
 // ---------------------------------------------------------------------------
@@ -930,91 +923,6 @@ __global__ __launch_bounds__(512, 2) void wino_dgrad_fused_kernel(WinoFusedArgs 
     }
 }
 
-// ---------------------------------------------------------------------------
-// Weight gradient, Winograd domain.  dM = A dY_p A^T per tile and phase (A = [1 0; 1 1; 1 -1; 0 -1]):
-//   Mdy[xi][tile][p*Cout+co]; then dU_xi = V_xi^T Mdy_xi (plain TN GEMMs), and G^T dU G maps back to the 3x3 phase
-//   kernels, whose taps are scattered onto the canonical 5x5 taps exactly like the direct path's reduce.
-// ---------------------------------------------------------------------------
-// bpart != null (host: the grid's stride is a multiple of the channel quads, so a thread keeps its quad): the kernel also leaves the column
-// sums of the dy it reads - the gradBias partials - per workgroup in bpart[gridDim.x][4*Cout] (wino_bias_finish_kernel adds them in a fixed
-// order): dy is read once for both, where cg_bias_grad was a second 67 MB pass on the weight-gradient stream (59 us in the step).
-__global__ __launch_bounds__(256) void wino_dy_transform_kernel(const float* __restrict__ dy, float* __restrict__ Mdy, int N,
-                                                                int Hl, int Wl, int Cout, float* __restrict__ bpart) {
-    const int C = 4 * Cout, cq_n = C >> 2;
-    float4 bacc = make_float4(0.f, 0.f, 0.f, 0.f);
-    const int tH = Hl >> 1, tW = Wl >> 1;
-    const long T = (long)N * tH * tW;
-    const long total = T * cq_n;
-    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += gridDim.x * 256L) {
-        const int cq = (int)(idx % cq_n);
-        const long tile = idx / cq_n;
-        const int tj = (int)(tile % tW);
-        const int ti = (int)((tile / tW) % tH);
-        const long n = tile / ((long)tW * tH);
-        const int p = (cq * 4) / Cout, co = cq * 4 - p * Cout;
-        const int pa = p >> 1, pb = p & 1;
-        float4 e[2][2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int v = 0; v < 2; ++v)
-                e[u][v] = ld4(dy + ((n * 2 * Hl + 2 * (2 * ti + u) + pa) * (long)(2 * Wl) + 2 * (2 * tj + v) + pb) * Cout + co);
-        bacc = f4add(bacc, f4add(f4add(e[0][0], e[0][1]), f4add(e[1][0], e[1][1])));
-        float4 r[4][2];
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            r[0][v] = e[0][v];
-            r[1][v] = f4add(e[0][v], e[1][v]);
-            r[2][v] = f4sub(e[0][v], e[1][v]);
-            r[3][v] = make_float4(-e[1][v].x, -e[1][v].y, -e[1][v].z, -e[1][v].w);
-        }
-        float* out = Mdy + tile * C + cq * 4;
-        const long xs = T * C;
-#pragma unroll
-        for (int xy = 0; xy < 4; ++xy) {
-            *reinterpret_cast<float4*>(out + (xy * 4 + 0) * xs) = r[xy][0];
-            *reinterpret_cast<float4*>(out + (xy * 4 + 1) * xs) = f4add(r[xy][0], r[xy][1]);
-            *reinterpret_cast<float4*>(out + (xy * 4 + 2) * xs) = f4sub(r[xy][0], r[xy][1]);
-            *reinterpret_cast<float4*>(out + (xy * 4 + 3) * xs) = make_float4(-r[xy][1].x, -r[xy][1].y, -r[xy][1].z, -r[xy][1].w);
-        }
-    }
-    if (bpart) {
-        // threads t and t + cq_n of a workgroup hold the same channel quad when cq_n < 256 (256 % cq_n == 0: host check)
-        __shared__ float4 shb[256];
-        shb[threadIdx.x] = bacc;
-        __syncthreads();
-        const int cq = (int)((blockIdx.x * 256L + threadIdx.x) % cq_n);
-        if (cq_n >= 256) *reinterpret_cast<float4*>(bpart + (long)blockIdx.x * C + cq * 4) = bacc;
-        else if ((int)threadIdx.x < cq_n) {
-            float4 t = shb[threadIdx.x];
-            for (int j = threadIdx.x + cq_n; j < 256; j += cq_n) t = f4add(t, shb[j]);
-            *reinterpret_cast<float4*>(bpart + (long)blockIdx.x * C + cq * 4) = t;
-        }
-    }
-}
-
-// gb[co] += scale * sum over workgroups b and phases p of bpart[b][p*Cout + co]: one workgroup per 32 channels, 8 row lanes, fp64, fixed order
-__global__ __launch_bounds__(256) void wino_bias_finish_kernel(const float* __restrict__ bpart, int nblocks, int Cout, float* __restrict__ gb,
-                                                               float scale) {
-    __shared__ double sh[8][33];
-    const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
-    const int co = blockIdx.x * 32 + cl;
-    double a = 0.0;
-    if (co < Cout)
-        for (int b = rl; b < nblocks; b += 8) {
-            const float* row = bpart + (long)b * 4 * Cout + co;
-            a += ((double)row[0] + (double)row[Cout]) + ((double)row[2 * Cout] + (double)row[3 * Cout]);
-        }
-    sh[rl][cl] = a;
-    __syncthreads();
-    if (rl == 0 && co < Cout) {
-        double t = 0.0;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) t += sh[r][cl];
-        gb[co] += scale * (float)t;
-    }
-}
-
 __device__ __host__ __forceinline__ int wino_phase_map(int a, int d) { return ((a + d - 2) >> 1) - ((a - 2) >> 1); }
 
 // gw[co][ci][5][5] += scale * sum_p (G^T dU_p G)[map_p(dy,dx)];  dUt layout [xi][p*Cout+co][ci].  One thread per (co, ci).
@@ -1058,73 +966,25 @@ __global__ __launch_bounds__(256) void wino_wgrad_finish_kernel(const float* __r
     }
 }
 
-
-__device__ __host__ __forceinline__ int wino22_phase_map(int a, int d) { return ((a + d - 1) >> 1) - ((a - 1) >> 1); }
-
-
-static bool wino_dims_ok(int N, int Hp, int Wp, int Cin, int Cout) {
+// ---------------------------------------------------------------------------
+// Host side
+// ---------------------------------------------------------------------------
+bool wino_dims_ok(int N, int Hp, int Wp, int Cin, int Cout) {
     return N > 0 && Hp > 0 && Wp > 0 && (Hp & 1) == 0 && (Wp & 1) == 0 && Cin > 0 && Cout > 0 && Cin % 128 == 0 &&
            Cout % 128 == 0 /* K % 32, Nc % 128 for both GEMM geometries */ && (long)N * Hp * Wp * std::max(Cin, 4 * Cout) * 4L < (1L << 40);
 }
 
-}  // namespace
-
-extern "C" {
-
-// 1 if the Winograd path covers upsample2 -> conv 5x5 (pad 2) at these dimensions
-size_t cg_conv2d_ups2_wino_supported(int N, int Hp, int Wp, int Cin, int Cout, int k, int pad) {
-    return k == 5 && pad == 2 && wino_dims_ok(N, Hp, Wp, Cin, Cout) ? 1 : 0;
-}
-size_t cg_conv2d_ups2_wino_v_floats(int N, int Hp, int Wp, int C) {  // C = Cin (forward) or 4*Cout (data gradient)
-    return (size_t)16 * ((size_t)N * (Hp / 2) * (Wp / 2)) * C;
-}
-size_t cg_conv2d_ups2_wino_u_floats(int Cin, int Cout) { return (size_t)4 * 16 * Cin * Cout; }
-
-int cg_conv2d_ups2_wino_pack(void* stream, const float* wf_ph, const float* wb_ph, float* u_fwd, float* u_bwd, int Cout,
-                             int Cin) {
-    CG_REQUIRE((wf_ph && u_fwd) || (wb_ph && u_bwd), "cg_conv2d_ups2_wino_pack: null pointer");
-    CG_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0, "cg_conv2d_ups2_wino_pack: channel counts must be multiples of 4");
-    if (wf_ph && u_fwd && wb_ph && u_bwd && cg::opt(cg::OPT_PACK_WIDE) != 0) {
-        const int nf = cg::ew_grid(4L * Cin * (Cout / 4)), nb = cg::ew_grid(4L * Cout * (Cin / 4));
-        hipLaunchKernelGGL(wino_filter_transform_both_kernel, dim3(nf + nb), dim3(256), 0, cg::S(stream), wf_ph, u_fwd, wb_ph, u_bwd, Cin,
-                           Cout, nf);
-        CG_LAUNCH_CHECK();
-        return 0;
-    }
-    if (wf_ph && u_fwd) {
-        const long total = 4L * Cin * (Cout / 4);
-        hipLaunchKernelGGL(wino_filter_transform_kernel<false>, dim3(cg::ew_grid(total)), dim3(256), 0, cg::S(stream), wf_ph,
-                           u_fwd, Cin, Cout);
-        CG_LAUNCH_CHECK();
-    }
-    if (wb_ph && u_bwd) {
-        const long total = 4L * Cout * (Cin / 4);
-        hipLaunchKernelGGL(wino_filter_transform_kernel<true>, dim3(cg::ew_grid(total)), dim3(256), 0, cg::S(stream), wb_ph,
-                           u_bwd, Cout, Cin);
-        CG_LAUNCH_CHECK();
-    }
-    return 0;
+// May wino_gemm_g_kernel take T tiles x K rows x Nc columns: LDS-direct loads are on (CG_WINO_GLDS), and one xi plane of V and the planes
+// of U stay below the 2 GB a buffer offset reaches
+bool glds_ok(long T, int K, int Nc) {
+    return cg::opt(cg::OPT_WINO_GLDS) != 0 && T * K * 4L < 0x7fffffffL && 16L * K * Nc * 4L < 0x7fffffffL;
 }
 
-// The 16 GEMMs + output transform alone, on an already transformed input (what the two entry points below launch after
-// their input transform; exported so that it can be timed / profiled in isolation).
-// dgrad == 0: v [16][T][Cin], u = u_fwd, y [N][2Hp][2Wp][Cout];  dgrad == 1: v [16][T][4*Cout], u = u_bwd, y [N][Hp][Wp][Cin].
-static int wino_gemm_launch(void* stream, const float* v, const float* u, const float* bias, float* y, int N, int Hp, int Wp,
-                            int Cin, int Cout, int dgrad, float* stats, int npos = 16, int kslices = 1);
-
-int cg_conv2d_ups2_wino_gemm(void* stream, const float* v, const float* u, const float* bias, float* y, int N, int Hp, int Wp,
-                             int Cin, int Cout, int dgrad) {
-    return wino_gemm_launch(stream, v, u, bias, y, N, Hp, Wp, Cin, Cout, dgrad, nullptr);
-}
-
-// rows of the [rows][2][Cout] statistics buffer cg_conv2d_ups2_wino_forward_stats fills
-size_t cg_conv2d_ups2_wino_stats_rows(int N, int Hp, int Wp, int Cin, int Cout) {
-    if (!wino_dims_ok(N, Hp, Wp, Cin, Cout)) return 0;
-    return (size_t)4 * cg::cdiv((long)N * (Hp / 2) * (Wp / 2), 64) * 2;
-}
-
-static int wino_gemm_launch(void* stream, const float* v, const float* u, const float* bias, float* y, int N, int Hp, int Wp,
-                            int Cin, int Cout, int dgrad, float* stats, int npos, int kslices) {
+// The GEMMs + output transform on an already transformed input: npos = 16 (F(2x2,3x3)) or 9 (F(2x2,2x2)) positions.
+// dgrad == 0: v [npos][T][Cin] (npos == 9: per phase), u = u_fwd, y [N][2Hp][2Wp][Cout];  dgrad == 1: v [npos][T][4*Cout], u = u_bwd,
+// y [N][Hp][Wp][Cin], or with kslices > 1 that many partial results T*4*Cin floats apart (K slices over blockIdx.z).
+int wino_gemm_launch(void* stream, const float* v, const float* u, const float* bias, float* y, int N, int Hp, int Wp,
+                     int Cin, int Cout, int dgrad, float* stats, int npos, int kslices) {
     CG_REQUIRE(v && u && y, "cg_conv2d_ups2_wino_gemm: null pointer");
     CG_REQUIRE(wino_dims_ok(N, Hp, Wp, Cin, Cout), "cg_conv2d_ups2_wino_gemm: unsupported dimensions");
     const int T = N * (Hp / 2) * (Wp / 2);
@@ -1147,25 +1007,139 @@ static int wino_gemm_launch(void* stream, const float* v, const float* u, const 
     }
     const dim3 grid(cg::cdiv(T, 64) * (a.Nc / 128), 1, dgrad ? (kslices > 1 ? kslices : 1) : 4);
     // K step 32 (half the barriers per MFMA) pays when the launch is at most ~one workgroup per CU - the data-gradient
-    // geometry at batch 128 (0.53 -> 0.41 ms) - and costs 6 % when two workgroups per CU already hide each other's barriers
-    const bool k32 = bk == 32 || (bk == 0 && (long)grid.x * grid.z <= cg::kNumCU * 3 / 2);
-    // LDS-direct loads (CG_WINO_GLDS): one xi plane of V must stay below the 2 GB a buffer offset reaches
-    const bool glds = cg::opt(cg::OPT_WINO_GLDS) != 0 && (long)T * a.K * 4L < 0x7fffffffL &&
-                      16L * a.K * a.Nc * 4L < 0x7fffffffL;
-    if (npos == 9) {     // F(2x2,2x2): the LDS-direct-load kernel only (cg_conv2d_ups2_wino22_supported checks the same conditions)
-        CG_REQUIRE(glds, "wino_gemm: the 9-position form needs the LDS-direct-load kernel (CG_WINO_GLDS)");
-        if (k32 && (a.kz ? a.kz : a.K) % 64 == 0) hipLaunchKernelGGL((wino_gemm_g_kernel<32, 9>), grid, dim3(512), 0, cg::S(stream), a);
-        else hipLaunchKernelGGL((wino_gemm_g_kernel<16, 9>), grid, dim3(512), 0, cg::S(stream), a);
+    // geometry at batch 128 (0.53 -> 0.41 ms) - and costs 6 % when two workgroups per CU already hide each other's barriers;
+    // it needs an even number of K tiles per workgroup
+    const bool k32 = (bk == 32 || (bk == 0 && (long)grid.x * grid.z <= cg::kNumCU * 3 / 2)) && (a.kz ? a.kz : a.K) % 64 == 0;
+    const bool glds = glds_ok(T, a.K, a.Nc);
+    // F(2x2,2x2) has the LDS-direct-load kernel only (cg_conv2d_ups2_wino22_supported asks the same question)
+    CG_REQUIRE(npos == 16 || glds, "wino_gemm: the 9-position form needs the LDS-direct-load kernel (CG_WINO_GLDS)");
+    CG_REQUIRE(kslices <= 1 || glds, "wino_gemm: K slices need the LDS-direct-load kernel (CG_WINO_GLDS)");
+    hipStream_t st = cg::S(stream);
+    if (npos == 9) {
+        if (k32) hipLaunchKernelGGL((wino_gemm_g_kernel<32, 9>), grid, dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((wino_gemm_g_kernel<16, 9>), grid, dim3(512), 0, st, a);
+    } else if (glds) {
+        if (k32) hipLaunchKernelGGL((wino_gemm_g_kernel<32>), grid, dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((wino_gemm_g_kernel<16>), grid, dim3(512), 0, st, a);
+    } else {
+        if (k32) hipLaunchKernelGGL((wino_gemm_kernel<32>), grid, dim3(512), 0, st, a);
+        else hipLaunchKernelGGL((wino_gemm_kernel<16>), grid, dim3(512), 0, st, a);
+    }
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+// Both *_pack entry points: both operands in one launch (CG_PACK_WIDE) or a launch per operand that is asked for
+template <class F>
+int wino_pack(const char* who, void* stream, const float* wf_ph, const float* wb_ph, float* u_fwd, float* u_bwd, int Cout, int Cin) {
+    CG_REQUIRE((wf_ph && u_fwd) || (wb_ph && u_bwd), "%s: null pointer", who);
+    CG_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0, "%s: channel counts must be multiples of 4", who);
+    hipStream_t st = cg::S(stream);
+    const int nf = cg::ew_grid(4L * Cin * (Cout / 4)), nb = cg::ew_grid(4L * Cout * (Cin / 4));
+    if (wf_ph && u_fwd && wb_ph && u_bwd && cg::opt(cg::OPT_PACK_WIDE) != 0) {
+        hipLaunchKernelGGL(wino_filter_transform_both_kernel<F>, dim3(nf + nb), dim3(256), 0, st, wf_ph, u_fwd, wb_ph, u_bwd, Cin, Cout, nf);
         CG_LAUNCH_CHECK();
         return 0;
     }
-    CG_REQUIRE(kslices <= 1 || glds, "wino_gemm: K slices need the LDS-direct-load kernel (CG_WINO_GLDS)");
-    if (glds && k32 && (a.kz ? a.kz : a.K) % 64 == 0) { hipLaunchKernelGGL((wino_gemm_g_kernel<32>), grid, dim3(512), 0, cg::S(stream), a); CG_LAUNCH_CHECK(); return 0; }
-    if (glds) { hipLaunchKernelGGL((wino_gemm_g_kernel<16>), grid, dim3(512), 0, cg::S(stream), a); CG_LAUNCH_CHECK(); return 0; }
-    if (k32 && a.K % 64 == 0) hipLaunchKernelGGL((wino_gemm_kernel<8, 32>), grid, dim3(512), 0, cg::S(stream), a);
-    else hipLaunchKernelGGL((wino_gemm_kernel<8, 16>), grid, dim3(512), 0, cg::S(stream), a);
+    if (wf_ph && u_fwd) {
+        hipLaunchKernelGGL((wino_filter_transform_kernel<F, false>), dim3(nf), dim3(256), 0, st, wf_ph, u_fwd, Cin, Cout);
+        CG_LAUNCH_CHECK();
+    }
+    if (wb_ph && u_bwd) {
+        hipLaunchKernelGGL((wino_filter_transform_kernel<F, true>), dim3(nb), dim3(256), 0, st, wb_ph, u_bwd, Cout, Cin);
+        CG_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+// The unfused data gradient of both families: dy's transform into v_dy, then the GEMMs - in one launch (sl == 1), or with the K rows (the
+// four phases' channels) in sl = 2 or 4 slices over blockIdx.z, each writing a partial dx_lo to part, added in a fixed order.
+int wino_dgrad_pair(void* stream, const float* dy, const float* u_bwd, float* dx_lo, float* v_dy, float* part, int N, int Hp, int Wp,
+                    int Cin, int Cout, int npos, int sl) {
+    hipStream_t st = cg::S(stream);
+    const int T = N * (Hp / 2) * (Wp / 2);
+    const dim3 tgrid(cg::ew_grid((long)T * Cout));
+    if (npos == 16) hipLaunchKernelGGL(wino_input_transform_kernel<1>, tgrid, dim3(256), 0, st, dy, v_dy, N, Hp, Wp, 4 * Cout, Cout);
+    else hipLaunchKernelGGL(wino22_dy_input_transform_kernel, tgrid, dim3(256), 0, st, dy, v_dy, N, Hp, Wp, Cout);
+    CG_LAUNCH_CHECK();
+    if (sl <= 1) return wino_gemm_launch(stream, v_dy, u_bwd, nullptr, dx_lo, N, Hp, Wp, Cin, Cout, 1, nullptr, npos, 1);
+    if (wino_gemm_launch(stream, v_dy, u_bwd, nullptr, part, N, Hp, Wp, Cin, Cout, 1, nullptr, npos, sl)) return 1;
+    const long n = (long)T * 4 * Cin;
+    if (sl == 4) hipLaunchKernelGGL(wino22_sum_kernel<4>, dim3(cg::ew_grid(n / 4)), dim3(256), 0, st, part, dx_lo, n / 4, n);
+    else hipLaunchKernelGGL(wino22_sum_kernel<2>, dim3(cg::ew_grid(n / 4)), dim3(256), 0, st, part, dx_lo, n / 4, n);
     CG_LAUNCH_CHECK();
     return 0;
+}
+
+// K slices of the F(2x2,2x2) data gradient, 1 (unsplit) or 4.  The launch has T/64 x Cin/128 workgroups - 128 on G's 512 -> 256 layer at
+// batch 128, half the chip.  Below ~one workgroup per CU the four phases (K slices of Cout rows) go to blockIdx.z.
+int wino22_dgrad_slices(int N, int Hp, int Wp, int Cin, int Cout) {
+    if (Cout % 64 != 0) return 1;
+    return (long)cg::cdiv(N * (Hp / 2) * (Wp / 2), 64) * (Cin / 128) < cg::kNumCU ? 4 : 1;
+}
+
+// K slices of the F(2x2,3x3) data gradient, 1, 2 or 4: at one workgroup per CU or more the unsplit launch stays (G32up-c's layer at batch
+// 128: 256 workgroups, splitting measured +0.5 % on the step), below that 2 or 4 slices (G32up's 128 -> 256 layer at batch 256: 64
+// workgroups -> 4 slices, config #3 9.52 -> 9.25 ms)
+int wino_dgrad_slices(int N, int Hp, int Wp, int Cin, int Cout) {
+    const long T = (long)N * (Hp / 2) * (Wp / 2);
+    if (!glds_ok(T, 4 * Cout, Cin) || !wino_dims_ok(N, Hp, Wp, Cin, Cout)) return 1;
+    const long wgs = (long)cg::cdiv((int)T, 64) * (Cin / 128);
+    int sl = wgs >= cg::kNumCU ? 1 : (wgs * 2 >= cg::kNumCU ? 2 : 4);
+    while (sl > 1 && (4 * Cout / sl) % 64 != 0) sl >>= 1;
+    return sl;
+}
+
+// With CG_WINO_DGRAD_FUSE != 0 the input transform is fused into the GEMMs (wino_dgrad_fused_kernel) and v_dy is left untouched:
+// 1 (default) where the fused kernel supports the shape and wins - whole 8 x 8 tile blocks and at least one workgroup per CU -, 2 wherever
+// it supports the shape (tests), 0 = the transform + wino_gemm_g_kernel pair everywhere.  Returns true = takes the fused path.
+bool wino_dgrad_fused_takes(const float* dy, const float* u_bwd, const float* dx_lo, int N, int Hp, int Wp, int Cin, int Cout) {
+    const long mode = cg::opt(cg::OPT_WINO_DGRAD_FUSE);
+    if (mode == 0) return false;
+    const int tH = Hp / 2, tW = Wp / 2, bH = cg::cdiv(tH, 8), bW = cg::cdiv(tW, 8);
+    const long wgs = (long)N * bH * bW * (Cin / 64);
+    // one image of dy / of dx_lo and all of U within a buffer descriptor's 2 GB; K = 4 Cout in an even number of 32-plane steps
+    const bool fits = 4L * Hp * Wp * Cout * 4L < 0x7fffffffL && (long)Hp * Wp * Cin * 4L < 0x7fffffffL && 16L * 4L * Cout * Cin * 4L < 0x7fffffffL &&
+                      Cout % 32 == 0 && Cin % 64 == 0 && wgs <= 0x7fffffffL &&
+                      ((uintptr_t)dy % 16) == 0 && ((uintptr_t)u_bwd % 16) == 0 && ((uintptr_t)dx_lo % 4) == 0;
+    if (!fits) return false;
+    return mode == 2 || (tH % 8 == 0 && tW % 8 == 0 && wgs >= cg::kNumCU);
+}
+
+size_t wino_align(size_t b) { return (b + 255) / 256 * 256; }
+// gradBias scratch of the weight gradient's workspace: cg_bias_grad needs Cout doubles; the region keeps the size it had when the dy
+// transform left per-workgroup partial sums there, because compiled plans size and lay out their buffers from the byte count below
+size_t wino_bias_ws_bytes(int Cout) { return wino_align(std::max(sizeof(double) * Cout, (size_t)cg::kNumCU * 8 * 4 * Cout * sizeof(float))); }
+
+}  // namespace
+
+extern "C" {
+
+// 1 if the Winograd path covers upsample2 -> conv 5x5 (pad 2) at these dimensions
+size_t cg_conv2d_ups2_wino_supported(int N, int Hp, int Wp, int Cin, int Cout, int k, int pad) {
+    return k == 5 && pad == 2 && wino_dims_ok(N, Hp, Wp, Cin, Cout) ? 1 : 0;
+}
+size_t cg_conv2d_ups2_wino_v_floats(int N, int Hp, int Wp, int C) {  // C = Cin (forward) or 4*Cout (data gradient)
+    return (size_t)16 * ((size_t)N * (Hp / 2) * (Wp / 2)) * C;
+}
+size_t cg_conv2d_ups2_wino_u_floats(int Cin, int Cout) { return (size_t)4 * 16 * Cin * Cout; }
+
+int cg_conv2d_ups2_wino_pack(void* stream, const float* wf_ph, const float* wb_ph, float* u_fwd, float* u_bwd, int Cout,
+                             int Cin) {
+    return wino_pack<WinoF23>("cg_conv2d_ups2_wino_pack", stream, wf_ph, wb_ph, u_fwd, u_bwd, Cout, Cin);
+}
+
+// The 16 GEMMs + output transform alone, on an already transformed input (what the entry points below launch after
+// their input transform; exported so that it can be timed / profiled in isolation).
+int cg_conv2d_ups2_wino_gemm(void* stream, const float* v, const float* u, const float* bias, float* y, int N, int Hp, int Wp,
+                             int Cin, int Cout, int dgrad) {
+    return wino_gemm_launch(stream, v, u, bias, y, N, Hp, Wp, Cin, Cout, dgrad, nullptr, 16, 1);
+}
+
+// rows of the [rows][2][Cout] statistics buffer cg_conv2d_ups2_wino_forward_stats fills
+size_t cg_conv2d_ups2_wino_stats_rows(int N, int Hp, int Wp, int Cin, int Cout) {
+    if (!wino_dims_ok(N, Hp, Wp, Cin, Cout)) return 0;
+    return (size_t)4 * cg::cdiv((long)N * (Hp / 2) * (Wp / 2), 64) * 2;
 }
 
 // y[N][2Hp][2Wp][Cout] = bias + conv5x5(upsample2(x_lo)); v (cg_conv2d_ups2_wino_v_floats(..., Cin) floats) receives
@@ -1174,12 +1148,11 @@ int cg_conv2d_ups2_wino_forward_stats(void* stream, const float* x_lo, const flo
                                       int N, int Hp, int Wp, int Cin, int Cout, float* stats) {
     CG_REQUIRE(x_lo && u_fwd && y && v, "cg_conv2d_ups2_wino_forward: null pointer");
     CG_REQUIRE(wino_dims_ok(N, Hp, Wp, Cin, Cout), "cg_conv2d_ups2_wino_forward: unsupported dimensions");
-    hipStream_t st = cg::S(stream);
     const int T = N * (Hp / 2) * (Wp / 2);
-    hipLaunchKernelGGL(wino_input_transform_kernel<0>, dim3(cg::ew_grid((long)T * (Cin / 4))), dim3(256), 0, st, x_lo, v, N, Hp,
+    hipLaunchKernelGGL(wino_input_transform_kernel<0>, dim3(cg::ew_grid((long)T * (Cin / 4))), dim3(256), 0, cg::S(stream), x_lo, v, N, Hp,
                        Wp, Cin, Cin);
     CG_LAUNCH_CHECK();
-    return wino_gemm_launch(stream, v, u_fwd, bias, y, N, Hp, Wp, Cin, Cout, 0, stats);
+    return wino_gemm_launch(stream, v, u_fwd, bias, y, N, Hp, Wp, Cin, Cout, 0, stats, 16, 1);
 }
 
 int cg_conv2d_ups2_wino_forward(void* stream, const float* x_lo, const float* u_fwd, const float* bias, float* y, float* v,
@@ -1187,43 +1160,20 @@ int cg_conv2d_ups2_wino_forward(void* stream, const float* x_lo, const float* u_
     return cg_conv2d_ups2_wino_forward_stats(stream, x_lo, u_fwd, bias, y, v, N, Hp, Wp, Cin, Cout, nullptr);
 }
 
-// ---- F(2x2,2x2): upsample2 -> conv 3x3 (pad 1), forward ----
+// ---- F(2x2,2x2): upsample2 -> conv 3x3 (pad 1) ----
 size_t cg_conv2d_ups2_wino22_supported(int N, int Hp, int Wp, int Cin, int Cout) {
-    if (!wino_dims_ok(N, Hp, Wp, Cin, Cout)) return 0;
-    const long T = (long)N * (Hp / 2) * (Wp / 2);
-    const bool glds = cg::opt(cg::OPT_WINO_GLDS) != 0 && T * Cin * 4L < 0x7fffffffL &&
-                      16L * Cin * Cout * 4L < 0x7fffffffL;
-    return glds ? 1 : 0;
+    return wino_dims_ok(N, Hp, Wp, Cin, Cout) && glds_ok((long)N * (Hp / 2) * (Wp / 2), Cin, Cout) ? 1 : 0;
 }
-// the limits cg_conv2d_ups2_wino22_dgrad / _wgrad apply on top of the forward's (a planner that only asked the forward's
+// the limits cg_conv2d_ups2_wino22_dgrad applies on top of the forward's (a planner that only asked the forward's
 // question would compile the forward and fail in Module:backward for a large batch x Cout)
 size_t cg_conv2d_ups2_wino22_dgrad_supported(int N, int Hp, int Wp, int Cin, int Cout) {
-    return cg_conv2d_ups2_wino22_supported(N, Hp, Wp, Cin, Cout) && (long)N * (Hp / 2) * (Wp / 2) * Cout * 16L < 0x7fffffffL ? 1 : 0;
+    return cg_conv2d_ups2_wino22_supported(N, Hp, Wp, Cin, Cout) && glds_ok((long)N * (Hp / 2) * (Wp / 2), 4 * Cout, Cin) ? 1 : 0;
 }
 size_t cg_conv2d_ups2_wino22_v_floats(int N, int Hp, int Wp, int Cin) { return (size_t)36 * ((size_t)N * (Hp / 2) * (Wp / 2)) * Cin; }
 size_t cg_conv2d_ups2_wino22_u_floats(int Cin, int Cout) { return (size_t)4 * 9 * Cin * Cout; }
 
 int cg_conv2d_ups2_wino22_pack(void* stream, const float* wf_ph, const float* wb_ph, float* u_fwd, float* u_bwd, int Cout, int Cin) {
-    CG_REQUIRE((wf_ph && u_fwd) || (wb_ph && u_bwd), "cg_conv2d_ups2_wino22_pack: null pointer");
-    CG_REQUIRE(Cin % 4 == 0 && Cout % 4 == 0, "cg_conv2d_ups2_wino22_pack: channel counts must be multiples of 4");
-    if (wf_ph && u_fwd && wb_ph && u_bwd && cg::opt(cg::OPT_PACK_WIDE) != 0) {
-        const int nf = cg::ew_grid(4L * Cin * (Cout / 4)), nb = cg::ew_grid(4L * Cout * (Cin / 4));
-        hipLaunchKernelGGL(wino22_filter_transform_both_kernel, dim3(nf + nb), dim3(256), 0, cg::S(stream), wf_ph, u_fwd, wb_ph, u_bwd,
-                           Cin, Cout, nf);
-        CG_LAUNCH_CHECK();
-        return 0;
-    }
-    if (wf_ph && u_fwd) {
-        hipLaunchKernelGGL(wino22_filter_transform_kernel<false>, dim3(cg::ew_grid(4L * Cin * (Cout / 4))), dim3(256), 0, cg::S(stream), wf_ph,
-                           u_fwd, Cin, Cout);
-        CG_LAUNCH_CHECK();
-    }
-    if (wb_ph && u_bwd) {
-        hipLaunchKernelGGL(wino22_filter_transform_kernel<true>, dim3(cg::ew_grid(4L * Cout * (Cin / 4))), dim3(256), 0, cg::S(stream), wb_ph,
-                           u_bwd, Cout, Cin);
-        CG_LAUNCH_CHECK();
-    }
-    return 0;
+    return wino_pack<WinoF22>("cg_conv2d_ups2_wino22_pack", stream, wf_ph, wb_ph, u_fwd, u_bwd, Cout, Cin);
 }
 
 // y[N][2Hp][2Wp][Cout] = bias + conv3x3(upsample2(x_lo)); v: scratch of cg_conv2d_ups2_wino22_v_floats floats; stats as
@@ -1235,25 +1185,7 @@ int cg_conv2d_ups2_wino22_forward_stats(void* stream, const float* x_lo, const f
     const int T = N * (Hp / 2) * (Wp / 2);
     hipLaunchKernelGGL(wino22_input_transform_kernel, dim3(cg::ew_grid((long)T * (Cin / 4))), dim3(256), 0, cg::S(stream), x_lo, v, N, Hp, Wp, Cin);
     CG_LAUNCH_CHECK();
-    return wino_gemm_launch(stream, v, u22, bias, y, N, Hp, Wp, Cin, Cout, 0, stats, 9);
-}
-
-// The data gradient's launch has T/64 x Cin/128 workgroups - 128 on G's 512 -> 256 layer at batch 128, half the chip.  Below ~one
-// workgroup per CU the four phases (K slices of Cout rows) go to blockIdx.z, each writing a partial dx_lo behind V in the scratch, and
-// wino22_sum_kernel adds them in a fixed order.
-static int wino22_dgrad_slices(int N, int Hp, int Wp, int Cin, int Cout) {   // 1 (unsplit) or 4 K slices
-    if (Cout % 64 != 0) return 1;
-    return (long)cg::cdiv(N * (Hp / 2) * (Wp / 2), 64) * (Cin / 128) < cg::kNumCU ? 4 : 1;
-}
-
-extern "C++" template <int S>
-__global__ __launch_bounds__(256) void wino22_sum_kernel(const float* __restrict__ part, float* __restrict__ out, long n4, long stride) {
-    for (long i = blockIdx.x * 256L + threadIdx.x; i < n4; i += gridDim.x * 256L) {
-        const float4 a = ld4(part + 4 * i), b = ld4(part + stride + 4 * i);
-        float4 r = f4add(a, b);
-        if (S == 4) r = f4add(r, f4add(ld4(part + 2 * stride + 4 * i), ld4(part + 3 * stride + 4 * i)));
-        *reinterpret_cast<float4*>(out + 4 * i) = r;
-    }
+    return wino_gemm_launch(stream, v, u22, bias, y, N, Hp, Wp, Cin, Cout, 0, stats, 9, 1);
 }
 
 size_t cg_conv2d_ups2_wino22_dgrad_v_floats(int N, int Hp, int Wp, int Cin, int Cout) {
@@ -1268,75 +1200,32 @@ int cg_conv2d_ups2_wino22_dgrad(void* stream, const float* dy, const float* u_bw
                                 int Cout) {
     CG_REQUIRE(dy && u_bwd && dx_lo && v_dy, "cg_conv2d_ups2_wino22_dgrad: null pointer");
     CG_REQUIRE(cg_conv2d_ups2_wino22_dgrad_supported(N, Hp, Wp, Cin, Cout), "cg_conv2d_ups2_wino22_dgrad: unsupported dimensions / options");
-    const int T = N * (Hp / 2) * (Wp / 2);
-    hipLaunchKernelGGL(wino22_dy_input_transform_kernel, dim3(cg::ew_grid((long)T * Cout)), dim3(256), 0, cg::S(stream), dy, v_dy, N, Hp, Wp, Cout);
-    CG_LAUNCH_CHECK();
-    const int sl = wino22_dgrad_slices(N, Hp, Wp, Cin, Cout);
-    if (sl == 1) return wino_gemm_launch(stream, v_dy, u_bwd, nullptr, dx_lo, N, Hp, Wp, Cin, Cout, 1, nullptr, 9);
-    float* part = v_dy + (size_t)36 * T * Cout;
-    if (wino_gemm_launch(stream, v_dy, u_bwd, nullptr, part, N, Hp, Wp, Cin, Cout, 1, nullptr, 9, sl)) return 1;
-    const long n = (long)T * 4 * Cin;
-    if (sl == 4) hipLaunchKernelGGL(wino22_sum_kernel<4>, dim3(cg::ew_grid(n / 4)), dim3(256), 0, cg::S(stream), part, dx_lo, n / 4, n);
-    else hipLaunchKernelGGL(wino22_sum_kernel<2>, dim3(cg::ew_grid(n / 4)), dim3(256), 0, cg::S(stream), part, dx_lo, n / 4, n);
-    CG_LAUNCH_CHECK();
-    return 0;
+    const size_t T = (size_t)N * (Hp / 2) * (Wp / 2);
+    return wino_dgrad_pair(stream, dy, u_bwd, dx_lo, v_dy, v_dy + 36 * T * Cout, N, Hp, Wp, Cin, Cout, 9, wino22_dgrad_slices(N, Hp, Wp, Cin, Cout));
 }
 
 // dx_lo[N][Hp][Wp][Cin] = gradient w.r.t. the low-res input (the upsampling's 2x2 block sum folded in);
-// v_dy: scratch of cg_conv2d_ups2_wino_v_floats(..., 4*Cout) floats.
-// With CG_WINO_DGRAD_FUSE != 0 the input transform is fused into the GEMMs (wino_dgrad_fused_kernel) and v_dy is left untouched:
-// 1 (default) where the fused kernel supports the shape and wins - whole 8 x 8 tile blocks and at least one workgroup per CU -, 2 wherever
-// it supports the shape (tests), 0 = the transform + wino_gemm_g_kernel pair everywhere.  Returns 1 = takes the fused path.
-static bool wino_dgrad_fused_takes(const float* dy, const float* u_bwd, const float* dx_lo, int N, int Hp, int Wp, int Cin, int Cout) {
-    const long mode = cg::opt(cg::OPT_WINO_DGRAD_FUSE);
-    if (mode == 0) return false;
-    const int tH = Hp / 2, tW = Wp / 2, bH = cg::cdiv(tH, 8), bW = cg::cdiv(tW, 8);
-    const long wgs = (long)N * bH * bW * (Cin / 64);
-    // one image of dy / of dx_lo and all of U within a buffer descriptor's 2 GB; K = 4 Cout in an even number of 32-plane steps
-    const bool fits = 4L * Hp * Wp * Cout * 4L < 0x7fffffffL && (long)Hp * Wp * Cin * 4L < 0x7fffffffL && 16L * 4L * Cout * Cin * 4L < 0x7fffffffL &&
-                      Cout % 32 == 0 && Cin % 64 == 0 && wgs <= 0x7fffffffL &&
-                      ((uintptr_t)dy % 16) == 0 && ((uintptr_t)u_bwd % 16) == 0 && ((uintptr_t)dx_lo % 4) == 0;
-    if (!fits) return false;
-    return mode == 2 || (tH % 8 == 0 && tW % 8 == 0 && wgs >= cg::kNumCU);
-}
-
+// v_dy: scratch of cg_conv2d_ups2_wino_v_floats(..., 4*Cout) floats, untouched where the fused kernel runs (wino_dgrad_fused_takes).
 int cg_conv2d_ups2_wino_dgrad(void* stream, const float* dy, const float* u_bwd, float* dx_lo, float* v_dy, int N, int Hp,
                               int Wp, int Cin, int Cout) {
     CG_REQUIRE(dy && u_bwd && dx_lo && v_dy, "cg_conv2d_ups2_wino_dgrad: null pointer");
     CG_REQUIRE(wino_dims_ok(N, Hp, Wp, Cin, Cout), "cg_conv2d_ups2_wino_dgrad: unsupported dimensions");
-    hipStream_t st = cg::S(stream);
     if (wino_dgrad_fused_takes(dy, u_bwd, dx_lo, N, Hp, Wp, Cin, Cout)) {
         WinoFusedArgs f;
         f.dy = dy; f.U = u_bwd; f.y = dx_lo; f.N = N; f.tH = Hp / 2; f.tW = Wp / 2; f.Cs = Cout; f.K = 4 * Cout; f.Nc = Cin;
         f.bH = cg::cdiv(f.tH, 8); f.bW = cg::cdiv(f.tW, 8);
         f.xcd = (int)cg::opt(cg::OPT_XCD_SWIZZLE);
-        hipLaunchKernelGGL(wino_dgrad_fused_kernel, dim3((unsigned)(N * f.bH * f.bW * (Cin / 64))), dim3(512), 0, st, f);
+        hipLaunchKernelGGL(wino_dgrad_fused_kernel, dim3((unsigned)(N * f.bH * f.bW * (Cin / 64))), dim3(512), 0, cg::S(stream), f);
         CG_LAUNCH_CHECK();
         cg::opt_count(cg::OPT_WINO_DGRAD_FUSE_LAUNCHES);
         return 0;
     }
-    const int T = N * (Hp / 2) * (Wp / 2);
-    hipLaunchKernelGGL(wino_input_transform_kernel<1>, dim3(cg::ew_grid((long)T * Cout)), dim3(256), 0, st, dy, v_dy, N, Hp, Wp,
-                       4 * Cout, Cout);
-    CG_LAUNCH_CHECK();
-    return cg_conv2d_ups2_wino_gemm(stream, v_dy, u_bwd, nullptr, dx_lo, N, Hp, Wp, Cin, Cout, 1);
+    return wino_dgrad_pair(stream, dy, u_bwd, dx_lo, v_dy, nullptr, N, Hp, Wp, Cin, Cout, 16, 1);
 }
 
-// The same data gradient with its K rows (the four phases' channels) in 2 or 4 slices over blockIdx.z and a fixed-order sum of the partial
-// results: the unsplit launch has T/64 x Cin/128 workgroups, which leaves most of the chip idle where Cin is 128 (G32up's first 5x5 layer).  part: cg_conv2d_ups2_wino_dgrad_part_floats() floats (0 = keep the unsplit launch).
-static int wino_dgrad_slices(int N, int Hp, int Wp, int Cin, int Cout) {
-    const int force = 0;
-    const long T = (long)N * (Hp / 2) * (Wp / 2);
-    const bool glds = cg::opt(cg::OPT_WINO_GLDS) != 0 && T * 4L * Cout * 4L < 0x7fffffffL &&
-                      16L * 4L * Cout * Cin * 4L < 0x7fffffffL;
-    if (!glds || !wino_dims_ok(N, Hp, Wp, Cin, Cout)) return 1;
-    // workgroups of the unsplit launch: at one per CU or more it stays (G32up-c's layer at batch 128: 256, splitting measured +0.5 % on the
-    // step), below that 2 or 4 slices (G32up's 128 -> 256 layer at batch 256: 64 workgroups -> 4 slices, config #3 9.52 -> 9.25 ms)
-    const long wgs = (long)cg::cdiv((int)T, 64) * (Cin / 128);
-    int sl = force == 1 || force == 2 || force == 4 ? force : (wgs >= cg::kNumCU ? 1 : (wgs * 2 >= cg::kNumCU ? 2 : 4));
-    while (sl > 1 && (4 * Cout / sl) % 64 != 0) sl >>= 1;
-    return sl;
-}
+// The same data gradient with its K rows in 2 or 4 slices (wino_dgrad_slices): the unsplit launch has T/64 x Cin/128 workgroups, which
+// leaves most of the chip idle where Cin is 128 (G32up's first 5x5 layer).  part: cg_conv2d_ups2_wino_dgrad_part_floats() floats
+// (0 = keep the unsplit launch).
 size_t cg_conv2d_ups2_wino_dgrad_part_floats(int N, int Hp, int Wp, int Cin, int Cout) {
     const int sl = wino_dgrad_slices(N, Hp, Wp, Cin, Cout);
     return sl > 1 ? (size_t)sl * N * Hp * Wp * Cin : 0;
@@ -1346,25 +1235,13 @@ int cg_conv2d_ups2_wino_dgrad_split(void* stream, const float* dy, const float* 
     const int sl = wino_dgrad_slices(N, Hp, Wp, Cin, Cout);
     if (sl <= 1 || !part) return cg_conv2d_ups2_wino_dgrad(stream, dy, u_bwd, dx_lo, v_dy, N, Hp, Wp, Cin, Cout);
     CG_REQUIRE(dy && u_bwd && dx_lo && v_dy, "cg_conv2d_ups2_wino_dgrad_split: null pointer");
-    const int T = N * (Hp / 2) * (Wp / 2);
-    hipLaunchKernelGGL(wino_input_transform_kernel<1>, dim3(cg::ew_grid((long)T * Cout)), dim3(256), 0, cg::S(stream), dy, v_dy, N, Hp, Wp, 4 * Cout, Cout);
-    CG_LAUNCH_CHECK();
-    if (wino_gemm_launch(stream, v_dy, u_bwd, nullptr, part, N, Hp, Wp, Cin, Cout, 1, nullptr, 16, sl)) return 1;
-    const long n = (long)T * 4 * Cin;
-    if (sl == 4) hipLaunchKernelGGL(wino22_sum_kernel<4>, dim3(cg::ew_grid(n / 4)), dim3(256), 0, cg::S(stream), part, dx_lo, n / 4, n);
-    else hipLaunchKernelGGL(wino22_sum_kernel<2>, dim3(cg::ew_grid(n / 4)), dim3(256), 0, cg::S(stream), part, dx_lo, n / 4, n);
-    CG_LAUNCH_CHECK();
-    return 0;
+    return wino_dgrad_pair(stream, dy, u_bwd, dx_lo, v_dy, part, N, Hp, Wp, Cin, Cout, 16, sl);
 }
-
-static size_t wino_align(size_t b) { return (b + 255) / 256 * 256; }
 
 size_t cg_conv2d_ups2_wino_wgrad_workspace_bytes(int N, int Hp, int Wp, int Cin, int Cout) {
     if (!wino_dims_ok(N, Hp, Wp, Cin, Cout)) return 0;
     const size_t T = (size_t)N * (Hp / 2) * (Wp / 2);
-    return wino_align(16 * T * 4 * Cout * sizeof(float)) + wino_align((size_t)16 * 4 * Cout * Cin * sizeof(float)) +
-           wino_align(std::max(sizeof(double) * Cout, (size_t)cg::kNumCU * 8 * 4 * Cout * sizeof(float))) +   // gradBias: cg_bias_grad's scratch / the dy transform's partials
-
+    return wino_align(16 * T * 4 * Cout * sizeof(float)) + wino_align((size_t)16 * 4 * Cout * Cin * sizeof(float)) + wino_bias_ws_bytes(Cout) +
            cg_conv2d_wgrad_workspace_bytes_strided(16, (int)T, 1, 1, Cin, 4 * Cout, 1, 1, 0, 0, 0);
 }
 
@@ -1382,36 +1259,21 @@ int cg_conv2d_ups2_wino_wgrad(void* stream, const float* v, const float* dy, flo
     char* base = (char*)ws;
     float* mdy = (float*)base;                    base += wino_align((size_t)16 * T * C4 * sizeof(float));
     float* dut = (float*)base;                    base += wino_align((size_t)16 * C4 * Cin * sizeof(float));
-    const size_t bws_bytes = wino_align(std::max(sizeof(double) * Cout, (size_t)cg::kNumCU * 8 * 4 * Cout * sizeof(float)));
-    void* bws = base;                             base += bws_bytes;
+    void* bws = base;                             base += wino_bias_ws_bytes(Cout);
     void* tws = base;
     const size_t tws_bytes = ws_bytes - (size_t)(base - (char*)ws);
-    // (gradBias partial sums from this transform - it reads every dy anyway - were parity-clean but cost the step 0.6 % in round 4: the
-    // separate 59 us pass is not on the pass's critical path, the longer transform is; the kernel keeps the argument, nobody passes it)
-    const bool fuse = false;
-    const int tgrid = (int)cg::ew_grid((long)T * Cout);
-    hipLaunchKernelGGL(wino_dy_transform_kernel, dim3(tgrid), dim3(256), 0, st, dy, mdy, N, Hp, Wp, Cout, fuse ? (float*)bws : nullptr);
+    hipLaunchKernelGGL(wino_dy_transform_kernel, dim3(cg::ew_grid((long)T * Cout)), dim3(256), 0, st, dy, mdy, N, Hp, Wp, Cout);
     CG_LAUNCH_CHECK();
     CG_HIP(hipMemsetAsync(dut, 0, (size_t)16 * C4 * Cin * sizeof(float), st));
     // 16 TN GEMMs dU_xi^T[pco][ci] = sum_tile Mdy_xi[tile][pco] V_xi[tile][ci]: the planes of V, Mdy and dU are equally spaced, so all
     // 16 run as ONE launch + one reduction (rounds 1-3: four launches of four)
-    const int groups_per_launch = 16;
-    for (int q = 0; q < 16; q += groups_per_launch) {
-        if (cg_conv2d_wgrad_strided(stream, groups_per_launch, v + q * (long)T * Cin, (long)T * Cin, mdy + q * (long)T * C4, (long)T * C4,
-                                    dut + q * (long)C4 * Cin, (long)C4 * Cin, T, 1, 1, Cin, C4, 1, 1, 0, 0, 0, 1.f, tws, tws_bytes)) return 1;
-    }
+    if (cg_conv2d_wgrad_strided(stream, 16, v, (long)T * Cin, mdy, (long)T * C4, dut, (long)C4 * Cin, T, 1, 1, Cin, C4, 1, 1, 0, 0, 0, 1.f,
+                                tws, tws_bytes)) return 1;
     hipLaunchKernelGGL(wino_wgrad_finish_kernel, dim3(cg::ew_grid((long)Cout * Cin)), dim3(256), 0, st, dut, gw_canonical, Cout,
                        Cin, scale);
     CG_LAUNCH_CHECK();
-    if (fuse) {
-        hipLaunchKernelGGL(wino_bias_finish_kernel, dim3(cg::cdiv(Cout, 32)), dim3(256), 0, st, (const float*)bws, tgrid, Cout, gb, scale);
-        CG_LAUNCH_CHECK();
-        return 0;
-    }
     if (gb) return cg_bias_grad(stream, dy, gb, (long)N * 4 * Hp * Wp, Cout, scale, bws, wino_align(sizeof(double) * Cout));
     return 0;
 }
-
-
 
 }  // extern "C"

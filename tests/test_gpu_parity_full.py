@@ -420,7 +420,7 @@ def test_generic_gather_variants(cg):
 
 @pytest.mark.parametrize("bk,stage", [(16, "b32"), (32, "b32"), (16, "glds"), (32, "glds")])
 def test_forced_winograd_variants(cg, bk, stage):
-    """wino_gemm_kernel<8,16>, <8,32> (register staging, the fallback) and the LDS-direct-load kernels wino_gemm_g_kernel<16>, <32> on
+    """wino_gemm_kernel<16>, <32> (register staging, the fallback) and the LDS-direct-load kernels wino_gemm_g_kernel<16>, <32> on
     the F(2x2,3x3) path of upsample2 -> conv5x5 (models.lua:217-218), forward + data gradient + weight gradient (the Winograd-domain
     weight gradient runs on the TN kernels: glds there too), ragged tile count."""
     how = {"b32": dict(CG_WINO_GLDS=0, CG_TN_GLDS=0), "glds": dict(CG_WINO_GLDS=1, CG_TN_GLDS=1)}[stage]
