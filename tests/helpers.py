@@ -1,6 +1,7 @@
 """What several test modules share (a plain module, imported as tests/plan_trace.py is): the two measures of the parity tests, the
 `options` context that forces dispatch tunables, `counter` that reads a launch counter, the per-tensor gradient rule, the JPEG directory
-of the loader tests, and the torch fp64 twin of an engine nn.Sequential."""
+of the loader tests, the torch fp64 twin of an engine nn.Sequential, and the measures, launch arithmetic and inputs of the memory-bound
+edge sweeps."""
 import ctypes
 import os
 
@@ -143,3 +144,93 @@ def torch_twin(net, snap, h, params, taps, masks=None, sides=None):
         else:
             raise AssertionError(t)
     return h
+
+
+# ------------------------------------------------------------------------------ memory-bound edge sweeps (test_gpu_membound_edges.py)
+U24 = 2.0 ** -24          # unit roundoff of fp32: one rounding moves a value by at most U24 of its magnitude
+TINY = 2.0 ** -149        # ... or, where it underflows, by the smallest fp32 denormal
+
+
+def bits_equal(a, b, what=""):
+    """fp32 arrays equal bit for bit (so -0.0 != +0.0), and finite."""
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    assert a.dtype == np.float32 and b.dtype == np.float32 and a.shape == b.shape, f"{what}: {a.dtype}{a.shape} vs {b.dtype}{b.shape}"
+    assert np.isfinite(a).all(), f"{what}: non-finite values"
+    np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32), err_msg=what)
+
+
+def rounding_close(a, ref, terms, r, what="", slack=0.0):
+    """|a - ref| <= r (U24 terms + TINY) + slack per element (per column for a reduction): ref the fp64 value, terms the sum of the
+    magnitudes of the addends of that element, r the number of fp32 roundings on the longest chain of the kernel's expression plus 2,
+    slack an error propagated from an input that is checked on its own.  Nothing here is scaled by a tensor's maximum."""
+    a, ref = np.asarray(a, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    assert a.shape == ref.shape, f"{what}: shape {a.shape} vs {ref.shape}"
+    assert np.isfinite(a).all(), f"{what}: non-finite values"
+    bound = r * (U24 * np.broadcast_to(np.abs(terms), ref.shape) + TINY) + slack
+    d = np.abs(a - ref)
+    worst = float((d / bound).max()) if d.size else 0.0
+    print(f"{what}: worst |d| / bound = {worst:.3f} (r = {r})")
+    assert worst <= 1.0, f"{what}: |d| = {worst:.3f} x the bound of {r} roundings at flat index {int(np.argmax(d / bound))}"
+    return worst
+
+
+def ew_grid(n, cap):
+    """common.h ew_grid(): workgroups of 256 lanes for n items, capped."""
+    return int(max(1, min((n + 255) // 256, cap)))
+
+
+def fixed_channel_grid(n4, C4, cap):
+    """fused.hip fixed_channel_grid(): ew_grid rounded down to a multiple of C4 / gcd(C4, 256), at least that multiple."""
+    import math
+    b = min((n4 + 255) // 256, cap)
+    if 256 % C4:
+        m = C4 // math.gcd(C4, 256)
+        b = max(m, b // m * m)
+    return int(max(1, b))
+
+
+def col_launch(M, C, v4, wgs):
+    """ops.hip colreduce_launch() / fused.hip cg_bn_act_backward_stats(): channel blocks, row chunks and rows per chunk of a column
+    reduction over [M][C]; v4: the float4 kernels (C % 4 == 0, aligned), wgs: kNumCU * kColReduceWgsPerCU."""
+    qb = 32 if C >= 128 else 16
+    cblocks = -(-(C // 4) // qb) if v4 else -(-C // 64)
+    chunks = max(1, min((M + 63) // 64, wgs // cblocks))
+    rows = (-(-M // chunks) + 3) // 4 * 4
+    chunks = -(-M // rows)
+    return dict(qb=qb, RL=256 // qb if v4 else 4, cblocks=cblocks, chunks=chunks, rows=rows)
+
+
+def col_tree(chunks):
+    """common.h col_tree_layout(): chunks per group, groups, size of the last group."""
+    G = max(16, -(-chunks // 32))
+    ngroups = -(-chunks // G)
+    return dict(G=G, ngroups=ngroups, last=chunks - (ngroups - 1) * G)
+
+
+def edge_normal(rng, shape, plant=True):
+    """Seeded fp32 normal data, channels last, |mean| <= std per channel (well conditioned), with +0.0, -0.0 and +-1e-30 planted at the
+    first and last element and at random places.  rng: a numpy Generator."""
+    C = shape[-1]
+    std = rng.uniform(0.5, 2.0, C).astype(np.float32)
+    mean = (rng.uniform(-1.0, 1.0, C) * std).astype(np.float32)
+    x = rng.standard_normal(shape, dtype=np.float32) * std + mean
+    if plant:
+        flat = x.reshape(-1)
+        vals = np.array([0.0, -0.0, 1e-30, -1e-30], np.float32)
+        k = int(min(64, max(1, flat.size // 8)))
+        pos = rng.integers(0, flat.size, 4 * k)
+        pos[:4] = [0, flat.size - 1, flat.size // 2, flat.size // 3]
+        flat[pos] = np.tile(vals, k)
+    return x
+
+
+def duplicate_in_windows(rng, x, frac=0.2):
+    """x: [N][H][W][C].  In a fraction of the 2x2 windows copy one element over one, two or all three of the others (ties for a max)."""
+    N, H, W, C = x.shape
+    w = x.reshape(N, H // 2, 2, W // 2, 2, C)
+    pick = rng.random((N, H // 2, W // 2, C)) < frac
+    src = w[:, :, 1, :, 0, :].copy()                      # the third element in scan order: a tie must still go to an earlier one
+    for iy, ix in ((0, 0), (0, 1), (1, 1)):
+        sel = pick & (rng.random(pick.shape) < 0.6)
+        w[:, :, iy, :, ix, :] = np.where(sel, src, w[:, :, iy, :, ix, :])
+    return x
