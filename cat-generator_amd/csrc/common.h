@@ -134,6 +134,12 @@ static inline int ew_grid(long n, int per_block = 256) {
     return (int)b;
 }
 
+// The float4 form of a memory-bound kernel runs when the count it walks divides by 4 and every tensor consulted sits on a 16-byte
+// boundary (a null pointer counts as aligned).  Which count and which tensors is each entry point's own business.
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+template <class... P>
+static inline bool vec_ok(long n, const P*... p) { return n % 4 == 0 && (al16(p) && ...); }
+
 // ---- device-side helpers -------------------------------------------------
 // The fused-transform Winograd kernels (wino3.hip, wino_dgrad_fused_kernel in winograd.hip) read their A operand from an LDS patch with
 // ds_read_b128, which the LDS serves in 16-lane groups {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} (+32).  Row i of an MFMA tile (= lane & 31
@@ -314,6 +320,106 @@ __device__ __forceinline__ double block_sum_256(double v, double* sh /*[4]*/) {
     if (threadIdx.x == 0) r = sh[0] + sh[1] + sh[2] + sh[3];
     __syncthreads();
     return r;
+}
+
+// ---- element arithmetic of the memory-bound kernels ------------------------------------------------------------------
+// ops.hip, fused.hip, the GEMM epilogue (gemm.hip) and the localisation launch (locnet.hip) promise each other's bits: a fused kernel
+// those of the kernels it replaces, a float4 kernel those of its scalar twin.  They hold because every expression below is written
+// ONCE and every twin is one template over Vec<VW>.  The build contracts a * b + c into an fma where the product feeds the sum
+// directly; an edit here moves all users together.
+#define CG_GRID_STRIDE(i, n) \
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
+
+// VW floats of one lane: one 16-byte access at VW == 4 (the pointer must be 16-byte aligned), one dword at VW == 1.  T is the raw lane
+// type with its operations as static functions: bilinear_bwd_det_k (ops.hip) keeps its register arrays in T, and from arrays of a
+// wrapping struct the compiler forms other code - and, where it fuses a product into a sum, other bits (found with the pins of
+// tests/test_gpu_membound_bits.py).  The elementwise kernels hold one Vec and address its lanes with [].  dot() and fma() state their
+// operation order; their arguments are taken by value for the same reason.
+template <int VW> struct Vec;
+template <> struct Vec<1> {
+    typedef float T;
+    static __device__ __forceinline__ T zero() { return 0.f; }
+    static __device__ __forceinline__ T ld(const float* p) { return *p; }
+    static __device__ __forceinline__ void st(float* p, T v) { *p = v; }
+    static __device__ __forceinline__ float dot(T a, T b) { return a * b; }
+    static __device__ __forceinline__ void fma(T& acc, float w, T g) { acc += w * g; }
+    T v;
+    __device__ __forceinline__ float& operator[](int) { return v; }
+    __device__ __forceinline__ float operator[](int) const { return v; }
+    // lane i of a tensor; per-channel parameter c
+    static __device__ __forceinline__ Vec load(const float* p, long i) { return Vec{p[i]}; }
+    __device__ __forceinline__ void store(float* p, long i) const { p[i] = v; }
+    static __device__ __forceinline__ Vec ldc(const float* p, int c) { return Vec{p[c]}; }
+};
+template <> struct Vec<4> {
+    typedef float4 T;
+    static __device__ __forceinline__ T zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+    static __device__ __forceinline__ T ld(const float* p) { return *reinterpret_cast<const float4*>(p); }
+    static __device__ __forceinline__ void st(float* p, T v) { *reinterpret_cast<float4*>(p) = v; }
+    static __device__ __forceinline__ float dot(T a, T b) { return ((a.x * b.x + a.y * b.y) + a.z * b.z) + a.w * b.w; }
+    static __device__ __forceinline__ void fma(T& acc, float w, T g) { acc.x += w * g.x; acc.y += w * g.y; acc.z += w * g.z; acc.w += w * g.w; }
+    T v;
+    __device__ __forceinline__ float& operator[](int k) { return (&v.x)[k]; }
+    __device__ __forceinline__ float operator[](int k) const { return (&v.x)[k]; }
+    // lane i of a tensor walked four floats at a time; per-channel parameters are views into the flat parameter vector (any 4-byte
+    // alignment): four scalar loads of channels 4 c ..
+    static __device__ __forceinline__ Vec load(const float* p, long i) { return Vec{ld(p + 4 * i)}; }
+    __device__ __forceinline__ void store(float* p, long i) const { st(p + 4 * i, v); }
+    static __device__ __forceinline__ Vec ldc(const float* p, int c) { return Vec{make_float4(p[4 * c], p[4 * c + 1], p[4 * c + 2], p[4 * c + 3])}; }
+};
+
+// act: 0 identity, 1 PReLU, 2 LeakyReLU.  The side of the kink is decided here and nowhere else: x itself passes through LeakyReLU
+// unscaled (x >= 0) and takes PReLU's slope (x > 0 fails), for the value and for the derivative alike
+__device__ __forceinline__ bool act_passes(int act, float x) { return act == 0 || (act == 1 ? x > 0.f : x >= 0.f); }
+__device__ __forceinline__ float act(int act, float v, float a) { return act_passes(act, v) ? v : a * v; }
+// d(act)/dx at x applied to an incoming gradient d
+__device__ __forceinline__ float dact(int act, float x, float d, float a) { return act_passes(act, x) ? d : a * d; }
+// PReLU's slope gradient: s += sum over the lanes of (x <= 0 ? x d : 0).  Each width keeps its own sequence of roundings, which the
+// pins of tests/test_gpu_membound_bits.py hold: one lane fuses its product into the running sum and adds nothing for x > 0; four lanes
+// round their products, add them left to right (zeros for x > 0) and add that to the running sum.
+__device__ __forceinline__ float slope_term(float x, float d) { return x <= 0.f ? x * d : 0.f; }
+template <int VW>
+__device__ __forceinline__ void slope_acc(float& s, const Vec<VW>& x, const Vec<VW>& d) {
+    if constexpr (VW == 1) {
+        if (x[0] <= 0.f) s = fmaf(x[0], d[0], s);
+    } else {
+        float t = slope_term(x[0], d[0]);
+#pragma unroll
+        for (int k = 1; k < VW; ++k) t += slope_term(x[k], d[k]);
+        s += t;
+    }
+}
+// PReLU backward of one workgroup's lanes of a grid-stride walk over n lanes of VW floats: dx = x > 0 ? dy : a dy, and, where
+// `partial` is given, the workgroup's slope-gradient sum into it (cg_prelu_backward: x, dy, dx whole; cg_prelu_backward_grouped: at
+// the group's base with the group's slope)
+template <int VW>
+__device__ __forceinline__ void prelu_bwd_walk(const float* x, const float* dy, float a, float* dx, long n, double* partial) {
+    __shared__ double sh[4];
+    float s = 0.f;
+    CG_GRID_STRIDE(i, n) {
+        const Vec<VW> v = Vec<VW>::load(x, i), g = Vec<VW>::load(dy, i);
+        Vec<VW> o;
+#pragma unroll
+        for (int k = 0; k < VW; ++k) o[k] = dact(1, v[k], g[k], a);
+        o.store(dx, i);
+        slope_acc(s, v, g);
+    }
+    if (!partial) return;
+    const double t = block_sum_256((double)s, sh);
+    if (threadIdx.x == 0) *partial = t;
+}
+// the sum of such partials by one workgroup of 256 in a fixed order; valid in thread 0
+__device__ __forceinline__ double partials_sum_256(const double* part, int nparts) {
+    __shared__ double sh[4];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
+    return block_sum_256(s, sh);
+}
+// batch norm: xhat, y = xhat gamma + beta, dx = gamma invstd (dy - mean(dy) - xhat mean(dy xhat))
+__device__ __forceinline__ float bn_xhat(float x, float m, float s) { return (x - m) * s; }
+__device__ __forceinline__ float bn_norm(float x, float m, float s, float g, float b) { return bn_xhat(x, m, s) * g + b; }
+__device__ __forceinline__ float bn_dx(float x, float dy, float g, float m, float s, float m1, float m2) {
+    return g * s * (dy - m1 - bn_xhat(x, m, s) * m2);
 }
 
 }  // namespace cg

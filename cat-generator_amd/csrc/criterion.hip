@@ -81,8 +81,6 @@ __global__ __launch_bounds__(kThreads) void mse_bwd_k(const float* __restrict__ 
     }
 }
 
-inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 }  // namespace cg
 
@@ -103,7 +101,7 @@ int cg_mse_forward(void* stream, const float* x, const float* t, float* loss, lo
         part = (double*)(scr + 256);
         static_assert(256 + sizeof(double) * kMaxPartials <= kColScratchBytes, "partials exceed the scratch");
     }
-    if (n % 4 == 0 && al16(x) && al16(t))
+    if (vec_ok(n, x, t))
         hipLaunchKernelGGL(mse_fwd_k<true>, dim3(P), dim3(kThreads), 0, S(stream), x, t, loss, n, nchunks, counter, part);
     else
         hipLaunchKernelGGL(mse_fwd_k<false>, dim3(P), dim3(kThreads), 0, S(stream), x, t, loss, n, nchunks, counter, part);
@@ -115,7 +113,7 @@ int cg_mse_backward(void* stream, const float* x, const float* t, float* dx, lon
     using namespace cg;
     CG_REQUIRE(x && t && dx, "cg_mse_backward: null pointer");
     CG_REQUIRE(n > 0, "cg_mse_backward: bad length n = %ld", n);
-    if (n % 4 == 0 && al16(x) && al16(t) && al16(dx))
+    if (vec_ok(n, x, t, dx))
         hipLaunchKernelGGL(mse_bwd_k<true>, dim3(ew_grid(n / 4, kThreads)), dim3(kThreads), 0, S(stream), x, t, dx, n);
     else
         hipLaunchKernelGGL(mse_bwd_k<false>, dim3(ew_grid(n, kThreads)), dim3(kThreads), 0, S(stream), x, t, dx, n);

@@ -1,6 +1,7 @@
 // Fused memory-bound chains of the G+D step: what Torch7 runs as separate modules, one pass over HBM each, runs
-// here as one kernel per chain.  Arithmetic per element is exactly that of the unfused kernels in ops.hip (same
-// operation order), so switching the fusion on or off changes no bit of the forward results.
+// here as one kernel per chain.  Switching the fusion on or off changes no bit of the forward results: the arithmetic per element is
+// not restated here but called - cg::act / dact / slope_term / bn_xhat / bn_norm / bn_dx of common.h, which the unfused kernels of
+// ops.hip call too.
 //
 //   act -> pool(2x2) -> spatial dropout        models.lua:649-651 (PReLU, AvgPool, SpatialDropout .2),
 //                                              :656-658 / :682-684 (PReLU, MaxPool, SpatialDropout .2),
@@ -17,25 +18,19 @@
 namespace {
 using cg::block_sum_256;
 
-#define V4_LOOP(i, n4) \
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n4); i += (long)gridDim.x * blockDim.x)
-__device__ __forceinline__ float4 ldv(const float* p, long i) { return reinterpret_cast<const float4*>(p)[i]; }
-__device__ __forceinline__ void stv(float* p, long i, float4 v) { reinterpret_cast<float4*>(p)[i] = v; }
-__device__ __forceinline__ float4 ldc(const float* p, int c4) { return make_float4(p[4 * c4], p[4 * c4 + 1], p[4 * c4 + 2], p[4 * c4 + 3]); }
+typedef cg::Vec<4> V4;   // every kernel here walks float4 lanes
+__device__ __forceinline__ void mul(V4& v, const V4& m) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] *= m[k];
+}
 
 struct AlphaTab { const float* a0; const float* a1; const float* a2; const float* a3; };
 __device__ __forceinline__ const float* tab_sel(const AlphaTab& t, int g) { return g == 0 ? t.a0 : (g == 1 ? t.a1 : (g == 2 ? t.a2 : t.a3)); }
 
-// act: 0 identity, 1 PReLU (x > 0 ? x : a x), 2 LeakyReLU (x >= 0 ? x : a x)   [ops.hip prelu_fwd / lrelu_fwd]
-__device__ __forceinline__ float actf(int act, float v, float a) {
-    return act == 0 ? v : (act == 1 ? (v > 0.f ? v : a * v) : (v >= 0.f ? v : a * v));
-}
-__device__ __forceinline__ float4 act4(int act, float4 v, float a) {
-    return make_float4(actf(act, v.x, a), actf(act, v.y, a), actf(act, v.z, a), actf(act, v.w, a));
-}
-// d(act)/dx applied to an incoming gradient d
-__device__ __forceinline__ float dactf(int act, float x, float d, float a) {
-    return act == 0 ? d : (act == 1 ? (x > 0.f ? d : a * d) : (x >= 0.f ? d : a * d));
+__device__ __forceinline__ V4 act4(int act, V4 v, float a) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = cg::act(act, v[k], a);
+    return v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -47,7 +42,7 @@ __global__ __launch_bounds__(256) void act_pool2_fwd_k(const float* __restrict__
                                                        const float* __restrict__ mask, AlphaTab at, int act, float slope,
                                                        int NG, long total4, int H, int W, int C4) {
     const int Ho = H >> 1, Wo = W >> 1;
-    V4_LOOP(i, total4) {
+    CG_GRID_STRIDE(i, total4) {
         const int c4 = (int)(i % C4);
         long r = i / C4;
         const int ox = (int)(r % Wo); r /= Wo;
@@ -55,26 +50,23 @@ __global__ __launch_bounds__(256) void act_pool2_fwd_k(const float* __restrict__
         const long n = r / Ho;
         const float a = act == 1 ? *tab_sel(at, (int)(n / NG)) : slope;
         const long b = ((n * H + 2 * oy) * W + 2 * ox) * C4 + c4;
-        const float4 v00 = act4(act, ldv(x, b), a), v01 = act4(act, ldv(x, b + C4), a);
-        const float4 v10 = act4(act, ldv(x, b + (long)W * C4), a), v11 = act4(act, ldv(x, b + (long)W * C4 + C4), a);
-        float4 o;
-#define POOL1(f)                                                        \
-        if (MAX) {                                                      \
-            float m = v00.f;                                            \
-            if (v01.f > m) m = v01.f;                                   \
-            if (v10.f > m) m = v10.f;                                   \
-            if (v11.f > m) m = v11.f;                                   \
-            o.f = m;                                                    \
-        } else {                                                        \
-            o.f = (v00.f + v01.f + v10.f + v11.f) * 0.25f;              \
+        const V4 v00 = act4(act, V4::load(x, b), a), v01 = act4(act, V4::load(x, b + C4), a);
+        const V4 v10 = act4(act, V4::load(x, b + (long)W * C4), a), v11 = act4(act, V4::load(x, b + (long)W * C4 + C4), a);
+        V4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (MAX) {
+                float m = v00[k];
+                if (v01[k] > m) m = v01[k];
+                if (v10[k] > m) m = v10[k];
+                if (v11[k] > m) m = v11[k];
+                o[k] = m;
+            } else {
+                o[k] = (v00[k] + v01[k] + v10[k] + v11[k]) * 0.25f;
+            }
         }
-        POOL1(x) POOL1(y) POOL1(z) POOL1(w)
-#undef POOL1
-        if (mask) {
-            const float4 mk = ldc(mask, (int)(n * C4 + c4));
-            o.x *= mk.x; o.y *= mk.y; o.z *= mk.z; o.w *= mk.w;
-        }
-        stv(y, i, o);
+        if (mask) mul(o, V4::ldc(mask, (int)(n * C4 + c4)));
+        o.store(y, i);
     }
 }
 
@@ -91,46 +83,40 @@ __global__ __launch_bounds__(256) void act_pool2_bwd_k(const float* __restrict__
     const float a = act == 1 ? *tab_sel(at, grp) : slope;
     const long base4 = (long)grp * per_group4;      // first pooled float4 of this group
     float s = 0.f;
-    V4_LOOP(j, per_group4) {
+    CG_GRID_STRIDE(j, per_group4) {
         const long i = base4 + j;
         const int c4 = (int)(i % C4);
         long r = i / C4;
         const int ox = (int)(r % Wo); r /= Wo;
         const int oy = (int)(r % Ho);
         const long n = r / Ho;
-        float4 g = ldv(gy, i);
-        if (mask) {
-            const float4 mk = ldc(mask, (int)(n * C4 + c4));
-            g.x *= mk.x; g.y *= mk.y; g.z *= mk.z; g.w *= mk.w;
-        }
+        V4 g = V4::load(gy, i);
+        if (mask) mul(g, V4::ldc(mask, (int)(n * C4 + c4)));
         const long b = ((n * H + 2 * oy) * W + 2 * ox) * C4 + c4;
         const long o01 = C4, o10 = (long)W * C4, o11 = (long)W * C4 + C4;
-        const float4 x00 = ldv(x, b), x01 = ldv(x, b + o01), x10 = ldv(x, b + o10), x11 = ldv(x, b + o11);
-        float4 d00, d01, d10, d11;
-#define BWD1(f)                                                                                         \
-        {                                                                                               \
-            float e00, e01, e10, e11;                                                                   \
-            if (MAX) {   /* first maximum of act(x) in scan order takes the gradient (maxpool2_bwd_k) */ \
-                const float v00 = actf(act, x00.f, a), v01 = actf(act, x01.f, a);                      \
-                const float v10 = actf(act, x10.f, a), v11 = actf(act, x11.f, a);                      \
-                int arg = 0; float m = v00;                                                             \
-                if (v01 > m) { m = v01; arg = 1; }                                                      \
-                if (v10 > m) { m = v10; arg = 2; }                                                      \
-                if (v11 > m) { m = v11; arg = 3; }                                                      \
-                e00 = arg == 0 ? g.f : 0.f; e01 = arg == 1 ? g.f : 0.f;                                 \
-                e10 = arg == 2 ? g.f : 0.f; e11 = arg == 3 ? g.f : 0.f;                                 \
-            } else {                                                                                    \
-                e00 = e01 = e10 = e11 = g.f * 0.25f;                                                    \
-            }                                                                                           \
-            d00.f = dactf(act, x00.f, e00, a); d01.f = dactf(act, x01.f, e01, a);                       \
-            d10.f = dactf(act, x10.f, e10, a); d11.f = dactf(act, x11.f, e11, a);                       \
-            if (act == 1)                                                                               \
-                s += (x00.f <= 0.f ? x00.f * e00 : 0.f) + (x01.f <= 0.f ? x01.f * e01 : 0.f) +          \
-                     (x10.f <= 0.f ? x10.f * e10 : 0.f) + (x11.f <= 0.f ? x11.f * e11 : 0.f);           \
+        const V4 x00 = V4::load(x, b), x01 = V4::load(x, b + o01), x10 = V4::load(x, b + o10), x11 = V4::load(x, b + o11);
+        V4 d00, d01, d10, d11;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float e00, e01, e10, e11;
+            if (MAX) {   // first maximum of act(x) in scan order takes the gradient (maxpool2_bwd_k)
+                const float v00 = cg::act(act, x00[k], a), v01 = cg::act(act, x01[k], a);
+                const float v10 = cg::act(act, x10[k], a), v11 = cg::act(act, x11[k], a);
+                int arg = 0; float m = v00;
+                if (v01 > m) { m = v01; arg = 1; }
+                if (v10 > m) { m = v10; arg = 2; }
+                if (v11 > m) { m = v11; arg = 3; }
+                e00 = arg == 0 ? g[k] : 0.f; e01 = arg == 1 ? g[k] : 0.f;
+                e10 = arg == 2 ? g[k] : 0.f; e11 = arg == 3 ? g[k] : 0.f;
+            } else {
+                e00 = e01 = e10 = e11 = g[k] * 0.25f;
+            }
+            d00[k] = cg::dact(act, x00[k], e00, a); d01[k] = cg::dact(act, x01[k], e01, a);
+            d10[k] = cg::dact(act, x10[k], e10, a); d11[k] = cg::dact(act, x11[k], e11, a);
+            if (act == 1)
+                s += cg::slope_term(x00[k], e00) + cg::slope_term(x01[k], e01) + cg::slope_term(x10[k], e10) + cg::slope_term(x11[k], e11);
         }
-        BWD1(x) BWD1(y) BWD1(z) BWD1(w)
-#undef BWD1
-        stv(dx, b, d00); stv(dx, b + o01, d01); stv(dx, b + o10, d10); stv(dx, b + o11, d11);
+        d00.store(dx, b); d01.store(dx, b + o01); d10.store(dx, b + o10); d11.store(dx, b + o11);
     }
     if (!gpart) return;
     const double t = block_sum_256((double)s, sh);
@@ -142,7 +128,7 @@ __global__ __launch_bounds__(256) void act_pool2_bwd_k(const float* __restrict__
 struct Cat4 { float* p0; float* p1; float* p2; float* p3; int c0, c1, c2, c3; };
 template <bool SPLIT>
 __global__ __launch_bounds__(256) void concat4_v4k(Cat4 b, float* __restrict__ whole, long total4, int Ct4) {
-    V4_LOOP(i, total4) {
+    CG_GRID_STRIDE(i, total4) {
         const int c = (int)(i % Ct4);
         const long m = i / Ct4;
         float* p; int cl, cw;
@@ -150,20 +136,24 @@ __global__ __launch_bounds__(256) void concat4_v4k(Cat4 b, float* __restrict__ w
         else if (c < b.c0 + b.c1) { p = b.p1; cl = c - b.c0; cw = b.c1; }
         else if (c < b.c0 + b.c1 + b.c2) { p = b.p2; cl = c - b.c0 - b.c1; cw = b.c2; }
         else { p = b.p3; cl = c - b.c0 - b.c1 - b.c2; cw = b.c3; }
-        if (SPLIT) stv(p, m * cw + cl, ldv(whole, i));
-        else stv(whole, i, ldv(p, m * cw + cl));
+        if (SPLIT) V4::load(whole, i).store(p, m * cw + cl);
+        else V4::load(p, m * cw + cl).store(whole, i);
     }
 }
 // out = ((a + b) + c) + d: the accumulation order of nn.Concat's gradInput (copy, then one add per further branch)
 __global__ __launch_bounds__(256) void sum4_v4k(const float* a, const float* b, const float* c, const float* d, float* out, int n,
                                                long n4) {
-    V4_LOOP(i, n4) {
-        float4 s = ldv(a, i);
-        const float4 u = ldv(b, i);
-        s.x += u.x; s.y += u.y; s.z += u.z; s.w += u.w;
-        if (n > 2) { const float4 v = ldv(c, i); s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-        if (n > 3) { const float4 v = ldv(d, i); s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; }
-        stv(out, i, s);
+    CG_GRID_STRIDE(i, n4) {
+        V4 s = V4::load(a, i);
+        auto add = [&](const float* p) {
+            const V4 u = V4::load(p, i);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s[k] += u[k];
+        };
+        add(b);
+        if (n > 2) add(c);
+        if (n > 3) add(d);
+        s.store(out, i);
     }
 }
 
@@ -175,7 +165,7 @@ __global__ __launch_bounds__(256) void concat4_drop_v4k(Cat4 b, float* __restric
                                                         long HW, float keep, float value, uint64_t seed, uint64_t offset,
                                                         const uint64_t* __restrict__ base) {
     if (DROPFWD && base) offset += *base;
-    V4_LOOP(i, total4) {
+    CG_GRID_STRIDE(i, total4) {
         const int c = (int)(i % Ct4);
         const long m = i / Ct4;
         const long n = m / HW;
@@ -187,20 +177,17 @@ __global__ __launch_bounds__(256) void concat4_drop_v4k(Cat4 b, float* __restric
         const long mi = n * Ct4 + c;
         if (DROPFWD) {
             const uint64_t ctr = offset + (uint64_t)mi * 4u;
-            float4 mk;
-            mk.x = cg::u01(seed, ctr) < keep ? value : 0.f;
-            mk.y = cg::u01(seed, ctr + 1) < keep ? value : 0.f;
-            mk.z = cg::u01(seed, ctr + 2) < keep ? value : 0.f;
-            mk.w = cg::u01(seed, ctr + 3) < keep ? value : 0.f;
-            if (m == n * HW) stv(noise, mi, mk);
-            float4 v = ldv(p, m * cw + cl);
-            v.x *= mk.x; v.y *= mk.y; v.z *= mk.z; v.w *= mk.w;
-            stv(whole, i, v);
+            V4 mk;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) mk[k] = cg::u01(seed, ctr + k) < keep ? value : 0.f;
+            if (m == n * HW) mk.store(noise, mi);
+            V4 v = V4::load(p, m * cw + cl);
+            mul(v, mk);
+            v.store(whole, i);
         } else {
-            const float4 mk = ldv(noise, mi);
-            float4 v = ldv(whole, i);
-            v.x *= mk.x; v.y *= mk.y; v.z *= mk.z; v.w *= mk.w;
-            stv(p, m * cw + cl, v);
+            V4 v = V4::load(whole, i);
+            mul(v, V4::load(noise, mi));
+            v.store(p, m * cw + cl);
         }
     }
 }
@@ -285,39 +272,24 @@ __global__ __launch_bounds__(256) void head_bwd_k(const float* __restrict__ dp, 
 }
 
 struct GalphaTab { float* g0; float* g1; float* g2; float* g3; };
-// galpha[group] += scale * sum_b gpart[group][b]: one workgroup per group, fixed summation order
+// galpha[group] += scale * sum_b gpart[group][b]: one workgroup per group, fixed summation order.  The sum is rounded to fp32 and
+// scaled there; prelu_galpha_reduce_k (ops.hip) scales in fp64 and rounds once.  The two differ in that rounding and stay as they are.
 __global__ __launch_bounds__(256) void galpha_groups_reduce_k(const double* gpart, int nparts, GalphaTab gt, float scale) {
-    __shared__ double sh[4];
     const int grp = blockIdx.x;
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 256) s += gpart[(long)grp * nparts + i];
-    const double t = block_sum_256(s, sh);
+    const double t = cg::partials_sum_256(gpart + (long)grp * nparts, nparts);
     float* ga = grp == 0 ? gt.g0 : (grp == 1 ? gt.g1 : (grp == 2 ? gt.g2 : gt.g3));
     if (threadIdx.x == 0 && ga) *ga += scale * (float)t;
 }
 
 // PReLU backward over a stacked batch of G equal groups, each with its own slope (D32_st3's identical branches):
-// dx = x > 0 ? dy : a_g dy;  gpart[g][block] = sum_{x <= 0} x dy     (prelu_bwd_v4k of ops.hip, one launch for G modules)
+// dx = x > 0 ? dy : a_g dy;  gpart[g][block] = sum_{x <= 0} x dy: the walk of ops.hip's prelu_bwd_k<4> from the group's base with the
+// group's slope, one launch for G modules
 __global__ __launch_bounds__(256) void prelu_bwd_groups_v4k(const float* __restrict__ x, const float* __restrict__ dy, AlphaTab at,
                                                             float* __restrict__ dx, long per_group4, double* __restrict__ gpart) {
-    __shared__ double sh[4];
     const int grp = blockIdx.y;
-    const float a = *tab_sel(at, grp);
-    const long base4 = (long)grp * per_group4;
-    float s = 0.f;
-    V4_LOOP(j, per_group4) {
-        const long i = base4 + j;
-        const float4 v = ldv(x, i), g = ldv(dy, i);
-        float4 o;
-        o.x = v.x > 0.f ? g.x : a * g.x; o.y = v.y > 0.f ? g.y : a * g.y;
-        o.z = v.z > 0.f ? g.z : a * g.z; o.w = v.w > 0.f ? g.w : a * g.w;
-        stv(dx, i, o);
-        s += (v.x <= 0.f ? v.x * g.x : 0.f) + (v.y <= 0.f ? v.y * g.y : 0.f) + (v.z <= 0.f ? v.z * g.z : 0.f) +
-             (v.w <= 0.f ? v.w * g.w : 0.f);
-    }
-    if (!gpart) return;
-    const double t = block_sum_256((double)s, sh);
-    if (threadIdx.x == 0) gpart[(long)grp * gridDim.x + blockIdx.x] = t;
+    const long base = 4 * (long)grp * per_group4;
+    cg::prelu_bwd_walk<4>(x + base, dy + base, *tab_sel(at, grp), dx + base, per_group4,
+                          gpart ? gpart + (long)grp * gridDim.x + blockIdx.x : nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -396,17 +368,13 @@ __global__ __launch_bounds__(256) void bn_act_fwd_v4k(const float* __restrict__ 
         mu[k] = (float)mean;
         is[k] = (float)(1.0 / sqrt(var + (double)eps));
     }
-    const float4 g = ldc(gamma, c4), b = ldc(beta, c4);
+    const V4 g = V4::ldc(gamma, c4), b = V4::ldc(beta, c4);
     const float a = alpha ? *alpha : 1.f;
     for (long i = i0; i < n4; i += (long)gridDim.x * 256) {
-        float4 v = ldv(x, i);
-        v.x = (v.x - mu[0]) * is[0] * g.x + b.x; v.y = (v.y - mu[1]) * is[1] * g.y + b.y;
-        v.z = (v.z - mu[2]) * is[2] * g.z + b.z; v.w = (v.w - mu[3]) * is[3] * g.w + b.w;
-        if (alpha) {
-            v.x = v.x > 0.f ? v.x : a * v.x; v.y = v.y > 0.f ? v.y : a * v.y;
-            v.z = v.z > 0.f ? v.z : a * v.z; v.w = v.w > 0.f ? v.w : a * v.w;
-        }
-        stv(y, i, v);
+        V4 v = V4::load(x, i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = cg::act(alpha ? 1 : 0, cg::bn_norm(v[k], mu[k], is[k], g[k], b[k]), a);
+        v.store(y, i);
     }
 }
 
@@ -435,38 +403,40 @@ __global__ __launch_bounds__(256) void bn_act_bwd_stats_k(const float* __restric
     double ga = 0.0;
     const float al = alpha ? *alpha : 1.f;
     if (q < cq) {
-        const float4 mu = ldc(mean, q), is = ldc(invstd, q), g = ldc(gamma, q), b = ldc(beta, q);
+        const V4 mu = V4::ldc(mean, q), is = V4::ldc(invstd, q), g = V4::ldc(gamma, q), b = V4::ldc(beta, q);
         for (long rb = r0 + rl; rb < r1; rb += 64L * RL) {
             const long re = min(r1, rb + 64L * RL);
-            float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+            V4 s1{V4::zero()}, s2 = s1;
             float sg = 0.f;
-#define ST1(f)                                                          \
-                {                                                       \
-                    const float xh = (v.f - mu.f) * is.f;               \
-                    const float u = xh * g.f + b.f;                     \
-                    const float dd = (!alpha || u > 0.f) ? d.f : al * d.f; \
-                    s1.f += dd; s2.f += dd * xh;                        \
-                    if (alpha && u <= 0.f) sg += u * d.f;               \
+            // one row of the lane's quad: d = dy through PReLU's derivative at u = BN(x); the slope sum takes the ROUNDED product of each
+            // lane in turn (cg::slope_term, as the float4 walks do - not the fused product of the scalar prelu_bwd_k<1>)
+            auto row = [&](const V4& v, const V4& d) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float xh = cg::bn_xhat(v[k], mu[k], is[k]);
+                    const float u = cg::bn_norm(v[k], mu[k], is[k], g[k], b[k]);
+                    const float dd = cg::dact(alpha ? 1 : 0, u, d[k], al);
+                    s1[k] += dd; s2[k] += dd * xh;
+                    if (alpha) sg += cg::slope_term(u, d[k]);
                 }
+            };
             // Batches of UB rows: all 2 UB loads of a batch are issued before the first value is used.  Beside another queue's GEMM this
             // kernel gets ONE workgroup per CU at best, so the bytes in flight per wave decide its rate (round 5; same summation order)
             constexpr int UB = 8;
             long r = rb;
             for (; r + (UB - 1) * RL < re; r += UB * RL) {
-                float4 vv[UB], dv[UB];
+                V4 vv[UB], dv[UB];
 #pragma unroll
-                for (int k = 0; k < UB; ++k) { const long i = (r + (long)k * RL) * cq + q; vv[k] = ldv(x, i); dv[k] = ldv(dy, i); }
+                for (int k = 0; k < UB; ++k) { const long i = (r + (long)k * RL) * cq + q; vv[k] = V4::load(x, i); dv[k] = V4::load(dy, i); }
 #pragma unroll
-                for (int k = 0; k < UB; ++k) { const float4 v = vv[k], d = dv[k]; ST1(x) ST1(y) ST1(z) ST1(w) }
+                for (int k = 0; k < UB; ++k) row(vv[k], dv[k]);
             }
             for (; r < re; r += RL) {
                 const long i = r * cq + q;
-                const float4 v = ldv(x, i), d = ldv(dy, i);
-                ST1(x) ST1(y) ST1(z) ST1(w)
+                row(V4::load(x, i), V4::load(dy, i));
             }
-#undef ST1
-            a1[0] += s1.x; a1[1] += s1.y; a1[2] += s1.z; a1[3] += s1.w;
-            a2[0] += s2.x; a2[1] += s2.y; a2[2] += s2.z; a2[3] += s2.w;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { a1[k] += s1[k]; a2[k] += s2[k]; }
             ga += sg;
         }
     }
@@ -516,7 +486,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_v4k(const float* __restrict__ 
     const long i0 = blockIdx.x * 256L + threadIdx.x;
     if (i0 >= n4) return;
     const int c4 = (int)(i0 % C4);
-    const float4 g = ldc(gamma, c4), b = ldc(beta, c4), mu = ldc(mean, c4), is = ldc(invstd, c4);
+    const V4 g = V4::ldc(gamma, c4), b = V4::ldc(beta, c4), mu = V4::ldc(mean, c4), is = V4::ldc(invstd, c4);
     float m1[4], m2[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -525,24 +495,20 @@ __global__ __launch_bounds__(256) void bn_act_bwd_v4k(const float* __restrict__ 
     }
     const float al = alpha ? *alpha : 1.f;
     for (long i = i0; i < n4; i += (long)gridDim.x * 256) {
-        const float4 v = ldv(x, i), d = ldv(dy, i);
-        float4 o;
-#define BW1(f, k)                                                       \
-        {                                                               \
-            const float xh = (v.f - mu.f) * is.f;                       \
-            const float u = xh * g.f + b.f;                             \
-            const float dd = (!alpha || u > 0.f) ? d.f : al * d.f;      \
-            o.f = g.f * is.f * (dd - m1[k] - xh * m2[k]);               \
+        const V4 v = V4::load(x, i), d = V4::load(dy, i);
+        V4 o;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float u = cg::bn_norm(v[k], mu[k], is[k], g[k], b[k]);
+            o[k] = cg::bn_dx(v[k], cg::dact(alpha ? 1 : 0, u, d[k], al), g[k], mu[k], is[k], m1[k], m2[k]);
         }
-        BW1(x, 0) BW1(y, 1) BW1(z, 2) BW1(w, 3)
-#undef BW1
-        stv(dx, i, o);
+        o.store(dx, i);
     }
 }
 
 }  // namespace
 
-static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+using cg::al16;
 
 // grid whose stride (grid * 256 float4s) is a multiple of C4, so that a thread's channel quad is loop invariant
 static int fixed_channel_grid(long n4, int C4) {
@@ -565,7 +531,7 @@ int cg_act_pool2_mask_forward(void* stream, const float* x, float* y, const floa
                               int W, int C, int act, float slope, const float* const* alpha, int pool_max) {
     CG_REQUIRE(x && y, "cg_act_pool2_mask_forward: null pointer");
     CG_REQUIRE(ngroups >= 1 && ngroups <= 4 && n_per_group > 0 && H > 0 && W > 0 && C > 0, "cg_act_pool2_mask_forward: bad dims");
-    CG_REQUIRE((H & 1) == 0 && (W & 1) == 0 && C % 4 == 0 && al16(x) && al16(y),
+    CG_REQUIRE((H & 1) == 0 && (W & 1) == 0 && cg::vec_ok(C, x, y),
                "cg_act_pool2_mask_forward: needs even H, W, C %% 4 == 0 and 16-byte aligned tensors");
     CG_REQUIRE(act >= 0 && act <= 2, "cg_act_pool2_mask_forward: unknown activation %d", act);
     AlphaTab at{nullptr, nullptr, nullptr, nullptr};
@@ -600,7 +566,7 @@ int cg_act_pool2_mask_backward(void* stream, const float* x, const float* gy, co
                                float* const* galpha, float scale, int pool_max, void* ws, size_t ws_bytes) {
     CG_REQUIRE(x && gy && dx, "cg_act_pool2_mask_backward: null pointer");
     CG_REQUIRE(ngroups >= 1 && ngroups <= 4 && n_per_group > 0 && H > 0 && W > 0 && C > 0, "cg_act_pool2_mask_backward: bad dims");
-    CG_REQUIRE((H & 1) == 0 && (W & 1) == 0 && C % 4 == 0 && al16(x) && al16(gy) && al16(dx),
+    CG_REQUIRE((H & 1) == 0 && (W & 1) == 0 && cg::vec_ok(C, x, gy, dx),
                "cg_act_pool2_mask_backward: needs even H, W, C %% 4 == 0 and 16-byte aligned tensors");
     CG_REQUIRE(act >= 0 && act <= 2, "cg_act_pool2_mask_backward: unknown activation %d", act);
     AlphaTab at{nullptr, nullptr, nullptr, nullptr};
@@ -651,7 +617,7 @@ size_t cg_prelu_backward_grouped_workspace_bytes(int ngroups, long n_per_group) 
 int cg_prelu_backward_grouped(void* stream, const float* x, const float* dy, const float* const* alpha, float* dx,
                               float* const* galpha, float scale, int ngroups, long n_per_group, void* ws, size_t ws_bytes) {
     CG_REQUIRE(x && dy && dx && alpha, "cg_prelu_backward_grouped: null pointer");
-    CG_REQUIRE(ngroups >= 1 && ngroups <= 4 && n_per_group > 0 && n_per_group % 4 == 0 && al16(x) && al16(dy) && al16(dx),
+    CG_REQUIRE(ngroups >= 1 && ngroups <= 4 && n_per_group > 0 && cg::vec_ok(n_per_group, x, dy, dx),
                "cg_prelu_backward_grouped: 1..4 groups of a multiple of 4 elements, 16-byte aligned");
     const float* t[4] = {nullptr, nullptr, nullptr, nullptr};
     float* gp[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -688,7 +654,7 @@ static int cat4_launch(void* stream, int n, float* const* parts, const int* C, f
     int c4[4] = {0, 0, 0, 0};
     long Ct = 0;
     for (int i = 0; i < n; ++i) {
-        CG_REQUIRE(parts[i] && C[i] > 0 && C[i] % 4 == 0 && al16(parts[i]), "%s: part %d needs C %% 4 == 0 and 16-byte alignment", who, i);
+        CG_REQUIRE(parts[i] && C[i] > 0 && cg::vec_ok(C[i], parts[i]), "%s: part %d needs C %% 4 == 0 and 16-byte alignment", who, i);
         p[i] = parts[i]; c4[i] = C[i] / 4; Ct += C[i];
     }
     CG_REQUIRE(al16(whole), "%s: unaligned tensor", who);
@@ -707,7 +673,7 @@ int cg_split_channels(void* stream, int n, const float* src, float* const* dst, 
     return cat4_launch(stream, n, dst, C, (float*)src, M, true, "cg_split_channels");
 }
 int cg_sum_n(void* stream, int n, const float* const* src, float* out, long count) {
-    CG_REQUIRE(n >= 2 && n <= 4 && src && out && count > 0 && count % 4 == 0 && al16(out), "cg_sum_n: 2..4 aligned tensors of a multiple of 4 elements");
+    CG_REQUIRE(n >= 2 && n <= 4 && src && out && count > 0 && cg::vec_ok(count, out), "cg_sum_n: 2..4 aligned tensors of a multiple of 4 elements");
     for (int i = 0; i < n; ++i) CG_REQUIRE(src[i] && al16(src[i]), "cg_sum_n: tensor %d", i);
     hipLaunchKernelGGL(sum4_v4k, dim3(cg::ew_grid(count / 4)), dim3(256), 0, cg::S(stream), src[0], src[1], n > 2 ? src[2] : nullptr,
                        n > 3 ? src[3] : nullptr, out, n, count / 4);
@@ -720,7 +686,7 @@ static int cat4_drop_args(int n, float* const* p, const int* C, const float* who
     float* pp[4] = {nullptr, nullptr, nullptr, nullptr}; int c4[4] = {0, 0, 0, 0};
     Ct = 0;
     for (int i = 0; i < n; ++i) {
-        CG_REQUIRE(p[i] && C[i] > 0 && C[i] % 4 == 0 && al16(p[i]), "%s: branch %d needs a multiple of 4 channels and an aligned tensor", who, i);
+        CG_REQUIRE(p[i] && C[i] > 0 && cg::vec_ok(C[i], p[i]), "%s: branch %d needs a multiple of 4 channels and an aligned tensor", who, i);
         pp[i] = p[i]; c4[i] = C[i] / 4; Ct += C[i];
     }
     CG_REQUIRE(al16(whole) && al16(noise), "%s: unaligned tensor", who);
@@ -796,7 +762,7 @@ int cg_bn_act_forward(void* stream, const float* x, float* y, const float* gamma
                       double count, long M, int C, float eps, float momentum, float* running_mean, float* running_var,
                       float* save_mean, float* save_invstd, const float* alpha) {
     CG_REQUIRE(x && y && gamma && beta && sums && save_mean && save_invstd && C > 0 && count > 0 && M > 0, "cg_bn_act_forward: bad args");
-    if (C % 4 == 0 && al16(x) && al16(y)) {
+    if (cg::vec_ok(C, x, y)) {
         const long n4 = M * (C / 4);
         hipLaunchKernelGGL(bn_act_fwd_v4k, dim3(fixed_channel_grid(n4, C / 4)), dim3(256), 0, cg::S(stream), x, y, gamma, beta, sums,
                            count, eps, momentum, running_mean, running_var, save_mean, save_invstd, alpha, n4, C / 4);
@@ -814,7 +780,7 @@ size_t cg_bn_act_backward_sums(int C) { return C > 0 ? (size_t)2 * C + 1 : 0; }
 int cg_bn_act_backward_stats(void* stream, const float* x, const float* dy, const float* save_mean, const float* save_invstd,
                              const float* gamma, const float* beta, const float* alpha, long M, int C, double* sums) {
     CG_REQUIRE(x && dy && save_mean && save_invstd && gamma && beta && sums && C > 0 && M > 0, "cg_bn_act_backward_stats: bad args");
-    CG_REQUIRE(C % 4 == 0 && al16(x) && al16(dy), "cg_bn_act_backward_stats: needs C %% 4 == 0 and 16-byte aligned tensors");
+    CG_REQUIRE(cg::vec_ok(C, x, dy), "cg_bn_act_backward_stats: needs C %% 4 == 0 and 16-byte aligned tensors");
     const int qb = C >= 128 ? 32 : 16;
     const int cblocks = cg::cdiv(C / 4, qb);
     const int cmul = cg::kColReduceWgsPerCU;
@@ -842,7 +808,7 @@ int cg_bn_act_backward(void* stream, const float* x, const float* dy, const floa
                        float scale) {
     CG_REQUIRE(x && dy && gamma && beta && save_mean && save_invstd && sums && local_sums && dx && C > 0 && count > 0 && M > 0,
                "cg_bn_act_backward: bad args");
-    CG_REQUIRE(C % 4 == 0 && al16(x) && al16(dy) && al16(dx), "cg_bn_act_backward: needs C %% 4 == 0 and 16-byte aligned tensors");
+    CG_REQUIRE(cg::vec_ok(C, x, dy, dx), "cg_bn_act_backward: needs C %% 4 == 0 and 16-byte aligned tensors");
     const long n4 = M * (C / 4);
     hipLaunchKernelGGL(bn_act_bwd_v4k, dim3(fixed_channel_grid(n4, C / 4)), dim3(256), 0, cg::S(stream), x, dy, gamma, beta, save_mean,
                        save_invstd, alpha, sums, count, local_sums, n4, C / 4, dx, ggamma, gbeta, galpha, scale);

@@ -120,10 +120,6 @@ struct NNArgs {
     int xcd_swizzle;
 };
 
-__device__ __forceinline__ float apply_act(int act, float v, float a) {
-    return act == 1 ? (v > 0.f ? v : a * v) : (v >= 0.f ? v : a * v);
-}
-
 struct TNArgs {
     const float* x0; const float* x1; const float* x2; const float* x3;
     const float* d0; const float* d1; const float* d2; const float* d3;   // dy per group
@@ -254,7 +250,7 @@ __device__ __forceinline__ void nn_store_lean(const f32x16 (&acc)[MI][NI], const
             for (int j = 0; j < NI; ++j) {
                 const float v = acc[i][j][r] + bj[j];
                 __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), ry, (int)(vo + j * 128), soff, 0);
-                if (ACT) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(apply_act(act, v, aslope)), rz, (int)(vo + j * 128), soff, 0);
+                if (ACT) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(cg::act(act, v, aslope)), rz, (int)(vo + j * 128), soff, 0);
             }
         }
     }
@@ -373,7 +369,7 @@ __device__ __forceinline__ void nn_epilogue(const f32x16 (&acc)[BM / WM / 32][BN
                 if (n < g.Cout) {
                     const float v = acc[i][j][r] + bj[j];
                     yout[ro + n] = v;
-                    if (act) zout[ro + n] = apply_act(act, v, aslope);
+                    if (act) zout[ro + n] = cg::act(act, v, aslope);
                     if (stats) { s1[j] += v; s2[j] = NI == 1 ? __builtin_fmaf(v, v, s2[j]) : s2[j] + v * v; }
                 }
             }
@@ -938,7 +934,7 @@ __global__ __launch_bounds__(256) void nn_splitk_reduce_kernel(NNArgs a, int S) 
             if (a.act) {
                 const float al = a.act == 1 ? *sel4(group, a.al0, a.al1, a.al2, a.al3) : a.slope;
                 *reinterpret_cast<float4*>(sel4(group, a.z0, a.z1, a.z2, a.z3) + o) =
-                    make_float4(apply_act(a.act, s.x, al), apply_act(a.act, s.y, al), apply_act(a.act, s.z, al), apply_act(a.act, s.w, al));
+                    make_float4(cg::act(a.act, s.x, al), cg::act(a.act, s.y, al), cg::act(a.act, s.z, al), cg::act(a.act, s.w, al));
             }
         }
         return;
@@ -974,7 +970,7 @@ __global__ __launch_bounds__(256) void nn_splitk_reduce_kernel(NNArgs a, int S) 
         gy[o] = s;
         if (a.act) {
             const float al = a.act == 1 ? *sel4(group, a.al0, a.al1, a.al2, a.al3) : a.slope;
-            sel4(group, a.z0, a.z1, a.z2, a.z3)[o] = apply_act(a.act, s, al);
+            sel4(group, a.z0, a.z1, a.z2, a.z3)[o] = cg::act(a.act, s, al);
         }
     }
 }

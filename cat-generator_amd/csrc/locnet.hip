@@ -41,8 +41,6 @@ struct LocBwd {
     float *ga1, *ga2, *g3, *g4, *gx;
 };
 
-__device__ __forceinline__ float lrelu(float v, float s) { return v >= 0.f ? v : s * v; }
-
 // 3x3 / pad 1 convolution of one sample held in LDS, register-tiled: an item is 4 pixels x 4 output planes (16 accumulators; per
 // (tap, input plane) one broadcast float4 of weights and four activations feed 16 FMAs).  The four pixels of an item lie a quarter
 // of the image apart (pixel g + q*S*S/4), so that consecutive lanes own consecutive pixels: with the odd channel stride CP their
@@ -196,7 +194,7 @@ __global__ __launch_bounds__(NT) void locnet_fwd_k(LocFwd a) {
     conv3x3_lds(p, CP, Cin, w1l, LC, zero, S, LC, h1, LC + 1, part);
     for (int i = tid; i < S2 * LC; i += NT) {
         const int c = i % LC, pix = i / LC;
-        const float v = lrelu(h1[pix * (LC + 1) + c] + w.b1[c], sl);
+        const float v = cg::act(2, h1[pix * (LC + 1) + c] + w.b1[c], sl);
         h1[pix * (LC + 1) + c] = v;
         a.h1buf[((size_t)smp * S2 + pix) * LC + c] = v;
     }
@@ -205,7 +203,7 @@ __global__ __launch_bounds__(NT) void locnet_fwd_k(LocFwd a) {
     conv3x3_lds(h1, LC + 1, LC, w2l, LC, zero, S, LC, m2, LC + 1, part);
     for (int i = tid; i < S2 * LC; i += NT) {
         const int c = i % LC, pix = i / LC;
-        const float v = lrelu(m2[pix * (LC + 1) + c] + w.b2[c], sl);
+        const float v = cg::act(2, m2[pix * (LC + 1) + c] + w.b2[c], sl);
         m2[pix * (LC + 1) + c] = v;
         a.m2buf[((size_t)smp * S2 + pix) * LC + c] = v;
     }
@@ -241,7 +239,7 @@ __global__ __launch_bounds__(NT) void locnet_fwd_k(LocFwd a) {
                 for (int off = 32; off > 0; off >>= 1) sv += __shfl_down(sv, off, 64);
                 if (lane == 0) {
                     const int o = wv * 8 + oo;
-                    const float v = lrelu(sv + w.b3[o], sl);
+                    const float v = cg::act(2, sv + w.b3[o], sl);
                     h3[o] = v;
                     a.h3buf[(size_t)smp * LH + o] = v;
                 }
@@ -347,7 +345,7 @@ __global__ __launch_bounds__(NT) void locnet_bwd_k(LocBwd a) {
         float s = 0.f;
         for (int q = 0; q < a.P; ++q) s += w.w4[q * LH + tid] * g4s[q];
         const float h = a.h3buf[(size_t)smp * LH + tid];
-        const float v = h >= 0.f ? s : sl * s;
+        const float v = cg::dact(2, h, s, sl);
         g3s[tid] = v;
         a.g3[(size_t)smp * LH + tid] = v;
     }
@@ -377,7 +375,7 @@ __global__ __launch_bounds__(NT) void locnet_bwd_k(LocBwd a) {
         const int c = i % LC, pix = i / LC, y = pix / S, x = pix % S;
         const float gv = gh2[c * Sh * Sh + (y >> 1) * Sh + (x >> 1)] * 0.25f;
         const float m = a.m2buf[((size_t)smp * S2 + pix) * LC + c];
-        const float v = m >= 0.f ? gv : sl * gv;
+        const float v = cg::dact(2, m, gv, sl);
         ga2[pix * (LC + 1) + c] = v;
         a.ga2[((size_t)smp * S2 + pix) * LC + c] = v;
     }
@@ -388,7 +386,7 @@ __global__ __launch_bounds__(NT) void locnet_bwd_k(LocBwd a) {
         const int c = i % LC, pix = i / LC;
         const float h = a.h1buf[((size_t)smp * S2 + pix) * LC + c];
         const float r = ga1[pix * (LC + 1) + c];
-        const float v = h >= 0.f ? r : sl * r;
+        const float v = cg::dact(2, h, r, sl);
         ga1[pix * (LC + 1) + c] = v;
         a.ga1[((size_t)smp * S2 + pix) * LC + c] = v;
     }
@@ -563,7 +561,7 @@ __global__ __launch_bounds__(NT2) void locnet_fwd2_k(LocFwd a) {
                 float v = red[pix * C::RS + c];
 #pragma unroll
                 for (int q = 1; q < NW; ++q) v += red[(q * S2 + pix) * C::RS + c];     // fixed order
-                v = lrelu(v + w.b1[c], sl);
+                v = cg::act(2, v + w.b1[c], sl);
                 h1P[pp(pix, S, SP) * C::CP2 + c] = v;
                 a.h1buf[((size_t)smp * S2 + pix) * LC + c] = v;
             }
@@ -574,7 +572,7 @@ __global__ __launch_bounds__(NT2) void locnet_fwd2_k(LocFwd a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int pix = (wv * C::NMT1 + m) * 16 + kq * 4 + r;
-                    const float v = lrelu(acc[m][r] + bias, sl);
+                    const float v = cg::act(2, acc[m][r] + bias, sl);
                     h1P[pp(pix, S, SP) * C::CP2 + n] = v;
                     a.h1buf[((size_t)smp * S2 + pix) * LC + n] = v;
                 }
@@ -597,7 +595,7 @@ __global__ __launch_bounds__(NT2) void locnet_fwd2_k(LocFwd a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int pix = (wv * C::NMT2 + m) * 16 + kq * 4 + r;
-                const float v = lrelu(acc[m][r] + bias, sl);
+                const float v = cg::act(2, acc[m][r] + bias, sl);
                 m2[pix * (LC + 1) + n] = v;
                 a.m2buf[((size_t)smp * S2 + pix) * LC + n] = v;
             }
@@ -636,7 +634,7 @@ __global__ __launch_bounds__(NT2) void locnet_fwd2_k(LocFwd a) {
                 sv = cg::wave_sum(sv);
                 if (lane == 0) {
                     const int o = 16 * wv + ob + r;
-                    const float v = lrelu(sv + w.b3[o], sl);
+                    const float v = cg::act(2, sv + w.b3[o], sl);
                     h3[o] = v;
                     a.h3buf[(size_t)smp * LH + o] = v;
                 }
@@ -740,7 +738,7 @@ __global__ __launch_bounds__(NT2) void locnet_bwd2_k(LocBwd a) {
         float s = 0.f;
         for (int q = 0; q < a.P; ++q) s += w.w4[q * LH + tid] * g4s[q];
         const float h = a.h3buf[(size_t)smp * LH + tid];
-        const float v = h >= 0.f ? s : sl * s;
+        const float v = cg::dact(2, h, s, sl);
         g3s[tid] = v;
         a.g3[(size_t)smp * LH + tid] = v;
     }
@@ -774,7 +772,7 @@ __global__ __launch_bounds__(NT2) void locnet_bwd2_k(LocBwd a) {
         const int c = i & (LC - 1), pix = i >> 4, y = pix / S, x = pix % S;
         const float gv = gh2[c * Sh * Sh + (y >> 1) * Sh + (x >> 1)] * 0.25f;
         const float m = a.m2buf[((size_t)smp * S2 + pix) * LC + c];
-        const float v = m >= 0.f ? gv : sl * gv;
+        const float v = cg::dact(2, m, gv, sl);
         ga2P[pp(pix, S, SP) * C::CP2 + c] = v;
         a.ga2[((size_t)smp * S2 + pix) * LC + c] = v;
     }
@@ -795,7 +793,7 @@ __global__ __launch_bounds__(NT2) void locnet_bwd2_k(LocBwd a) {
             for (int r = 0; r < 4; ++r) {
                 const int pix = (wv * C::NMT2 + m) * 16 + kq * 4 + r;
                 const float h = a.h1buf[((size_t)smp * S2 + pix) * LC + n];
-                const float v = h >= 0.f ? acc[m][r] : sl * acc[m][r];
+                const float v = cg::dact(2, h, acc[m][r], sl);
                 ga1P[pp(pix, S, SP) * C::CP2 + n] = v;
                 a.ga1[((size_t)smp * S2 + pix) * LC + n] = v;
             }

@@ -193,8 +193,7 @@ using cg::block_sum_256;
 using cg::last_block_arrives;
 using cg::wave_sum;
 
-#define GRID_STRIDE(i, n) \
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
+#define GRID_STRIDE(i, n) CG_GRID_STRIDE(i, n)
 
 // ---------------------------------------------------------------- input pipeline
 // NN_UTILS.rgbToColorSpace / toRgb (utils/nn_utils.lua:188-249) for one pixel.  'y' is the reference's own weighting (:253-277); 'yuv' and
@@ -500,159 +499,68 @@ __global__ void __launch_bounds__(256) images_u8_gather_augment_k(const unsigned
 }
 
 // ---------------------------------------------------------------- activations
-// Memory-bound elementwise kernels move 16 B per lane (float4) when the buffers are 16-B aligned; `n4` counts
-// whole float4s, the (<4)-element tail is handled by the last lanes with scalar accesses.
-#define V4_LOOP(i, n4) \
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n4); i += (long)gridDim.x * blockDim.x)
-__device__ __forceinline__ float4 ldv(const float* p, long i) { return reinterpret_cast<const float4*>(p)[i]; }
-__device__ __forceinline__ void stv(float* p, long i, float4 v) { reinterpret_cast<float4*>(p)[i] = v; }
-// per-channel parameters are views into the flat vector (any 4-B alignment): four scalar loads
-__device__ __forceinline__ float4 ldc(const float* p, int c4) { return make_float4(p[4 * c4], p[4 * c4 + 1], p[4 * c4 + 2], p[4 * c4 + 3]); }
+// Memory-bound elementwise operators: one source each over cg::Vec<VW>.  VW = 4 moves 16 B per lane where the entry point finds
+// cg::vec_ok() (n then counts float4s), VW = 1 is the scalar twin for the rest; a lane's arithmetic is cg::act / cg::dact of common.h.
+using cg::Vec;
 
-__global__ void prelu_fwd_v4k(const float* x, const float* alpha, float* y, long n4) {
-    const float a = *alpha;
-    V4_LOOP(i, n4) {
-        float4 v = ldv(x, i);
-        v.x = v.x > 0.f ? v.x : a * v.x; v.y = v.y > 0.f ? v.y : a * v.y;
-        v.z = v.z > 0.f ? v.z : a * v.z; v.w = v.w > 0.f ? v.w : a * v.w;
-        stv(y, i, v);
-    }
-}
-__global__ void prelu_bwd_v4k(const float* x, const float* dy, const float* alpha, float* dx, double* gpart, long n4) {
-    __shared__ double sh[4];
-    const float a = *alpha;
-    float s = 0.f;
-    V4_LOOP(i, n4) {
-        const float4 v = ldv(x, i), g = ldv(dy, i);
-        float4 o;
-        o.x = v.x > 0.f ? g.x : a * g.x; o.y = v.y > 0.f ? g.y : a * g.y;
-        o.z = v.z > 0.f ? g.z : a * g.z; o.w = v.w > 0.f ? g.w : a * g.w;
-        stv(dx, i, o);
-        s += (v.x <= 0.f ? v.x * g.x : 0.f) + (v.y <= 0.f ? v.y * g.y : 0.f) + (v.z <= 0.f ? v.z * g.z : 0.f) +
-             (v.w <= 0.f ? v.w * g.w : 0.f);
-    }
-    if (!gpart) return;
-    const double t = block_sum_256((double)s, sh);
-    if (threadIdx.x == 0) gpart[blockIdx.x] = t;
-}
-__global__ void lrelu_fwd_v4k(const float* x, float* y, float s, long n4) {
-    V4_LOOP(i, n4) {
-        float4 v = ldv(x, i);
-        v.x = v.x >= 0.f ? v.x : s * v.x; v.y = v.y >= 0.f ? v.y : s * v.y;
-        v.z = v.z >= 0.f ? v.z : s * v.z; v.w = v.w >= 0.f ? v.w : s * v.w;
-        stv(y, i, v);
-    }
-}
-__global__ void lrelu_bwd_v4k(const float* x, const float* dy, float* dx, float s, long n4) {
-    V4_LOOP(i, n4) {
-        const float4 v = ldv(x, i);
-        float4 g = ldv(dy, i);
-        g.x = v.x >= 0.f ? g.x : s * g.x; g.y = v.y >= 0.f ? g.y : s * g.y;
-        g.z = v.z >= 0.f ? g.z : s * g.z; g.w = v.w >= 0.f ? g.w : s * g.w;
-        stv(dx, i, g);
-    }
-}
-__global__ void add_v4k(const float* a, const float* b, float* o, long n4) {
-    V4_LOOP(i, n4) {
-        const float4 u = ldv(a, i), v = ldv(b, i);
-        stv(o, i, make_float4(u.x + v.x, u.y + v.y, u.z + v.z, u.w + v.w));
-    }
-}
-__global__ void axpy_v4k(float al, const float* x, float* y, long n4) {
-    V4_LOOP(i, n4) {
-        const float4 u = ldv(x, i);
-        float4 v = ldv(y, i);
-        v.x += al * u.x; v.y += al * u.y; v.z += al * u.z; v.w += al * u.w;
-        stv(y, i, v);
-    }
-}
-// spatial dropout with C % 4 == 0: mask[n][c..c+3] is one float4
-__global__ void mask_mul_sp_v4k(const float* x, const float* mask, float* y, long n4, long HWC4, int C4) {
-    V4_LOOP(i, n4) {
-        const long n = i / HWC4;
-        const float4 m = ldc(mask, (int)(n * C4 + (i % C4)));
-        float4 v = ldv(x, i);
-        v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
-        stv(y, i, v);
-    }
-}
-__global__ void mask_mul_v4k(const float* x, const float* mask, float* y, long n4) {
-    V4_LOOP(i, n4) {
-        const float4 m = ldv(mask, i);
-        float4 v = ldv(x, i);
-        v.x *= m.x; v.y *= m.y; v.z *= m.z; v.w *= m.w;
-        stv(y, i, v);
-    }
-}
-// batch-norm apply / backward with C % 4 == 0
-__global__ void bn_apply_v4k(const float* x, float* y, const float* gamma, const float* beta, const float* mean,
-                             const float* invstd, long n4, int C4) {
-    V4_LOOP(i, n4) {
-        const int c = (int)(i % C4);
-        const float4 g = ldc(gamma, c), b = ldc(beta, c), m = ldc(mean, c), s = ldc(invstd, c);
-        float4 v = ldv(x, i);
-        v.x = (v.x - m.x) * s.x * g.x + b.x; v.y = (v.y - m.y) * s.y * g.y + b.y;
-        v.z = (v.z - m.z) * s.z * g.z + b.z; v.w = (v.w - m.w) * s.w * g.w + b.w;
-        stv(y, i, v);
-    }
-}
-__global__ void bn_bwd_v4k(const float* x, const float* dy, const float* gamma, const float* mean, const float* invstd,
-                           const double* sums, double count, long n4, int C4, float* dx) {
-    V4_LOOP(i, n4) {
-        const int c = (int)(i % C4);
-        const float4 g = ldc(gamma, c), m = ldc(mean, c), s = ldc(invstd, c);
-        const float4 v = ldv(x, i), d = ldv(dy, i);
-        const int C = C4 * 4;
-        float4 o;
-#define BNB(f, k)                                                                      \
-        {                                                                              \
-            const float xh = (v.f - m.f) * s.f;                                        \
-            const float m1 = (float)(sums[4 * c + k] / count), m2 = (float)(sums[C + 4 * c + k] / count); \
-            o.f = g.f * s.f * (d.f - m1 - xh * m2);                                    \
-        }
-        BNB(x, 0) BNB(y, 1) BNB(z, 2) BNB(w, 3)
-#undef BNB
-        stv(dx, i, o);
-    }
-}
-
+template <int VW>
 __global__ void prelu_fwd_k(const float* x, const float* alpha, float* y, long n) {
     const float a = *alpha;
-    GRID_STRIDE(i, n) {
-        const float v = x[i];
-        y[i] = v > 0.f ? v : a * v;
+    CG_GRID_STRIDE(i, n) {
+        Vec<VW> v = Vec<VW>::load(x, i);
+#pragma unroll
+        for (int k = 0; k < VW; ++k) v[k] = cg::act(1, v[k], a);
+        v.store(y, i);
     }
 }
+// gpart[workgroup] = its sum over x <= 0 of x dy, for prelu_galpha_reduce_k
+template <int VW>
 __global__ void prelu_bwd_k(const float* x, const float* dy, const float* alpha, float* dx, double* gpart, long n) {
-    __shared__ double sh[4];
-    const float a = *alpha;
-    float s = 0.f;
-    GRID_STRIDE(i, n) {
-        const float v = x[i], g = dy[i];
-        dx[i] = v > 0.f ? g : a * g;
-        if (v <= 0.f) s += v * g;
-    }
-    if (!gpart) return;
-    const double t = block_sum_256((double)s, sh);
-    if (threadIdx.x == 0) gpart[blockIdx.x] = t;
+    cg::prelu_bwd_walk<VW>(x, dy, *alpha, dx, n, gpart ? gpart + blockIdx.x : nullptr);
 }
 // *galpha += scale * sum of the per-workgroup partials, in a fixed order (one same-address float atomic per
-// workgroup costs ~12 ns each on this part: 25 us for a 2048-workgroup launch, and is order-dependent)
+// workgroup costs ~12 ns each on this part: 25 us for a 2048-workgroup launch, and is order-dependent).  The scale is applied in
+// fp64 and the product rounded once; galpha_groups_reduce_k (fused.hip) rounds the sum first and multiplies in fp32.
 __global__ void prelu_galpha_reduce_k(const double* gpart, int nparts, float* galpha, float scale) {
-    __shared__ double sh[4];
-    double s = 0.0;
-    for (int i = threadIdx.x; i < nparts; i += 256) s += gpart[i];
-    const double t = block_sum_256(s, sh);
+    const double t = cg::partials_sum_256(gpart, nparts);
     if (threadIdx.x == 0) *galpha += (float)(t * scale);
 }
+template <int VW>
 __global__ void lrelu_fwd_k(const float* x, float* y, float s, long n) {
-    GRID_STRIDE(i, n) {
-        const float v = x[i];
-        y[i] = v >= 0.f ? v : s * v;
+    CG_GRID_STRIDE(i, n) {
+        Vec<VW> v = Vec<VW>::load(x, i);
+#pragma unroll
+        for (int k = 0; k < VW; ++k) v[k] = cg::act(2, v[k], s);
+        v.store(y, i);
     }
 }
+template <int VW>
 __global__ void lrelu_bwd_k(const float* x, const float* dy, float* dx, float s, long n) {
-    GRID_STRIDE(i, n) { dx[i] = x[i] >= 0.f ? dy[i] : s * dy[i]; }
+    CG_GRID_STRIDE(i, n) {
+        const Vec<VW> v = Vec<VW>::load(x, i);
+        Vec<VW> g = Vec<VW>::load(dy, i);
+#pragma unroll
+        for (int k = 0; k < VW; ++k) g[k] = cg::dact(2, v[k], g[k], s);
+        g.store(dx, i);
+    }
+}
+template <int VW>
+__global__ void add_k(const float* a, const float* b, float* o, long n) {
+    CG_GRID_STRIDE(i, n) {
+        Vec<VW> u = Vec<VW>::load(a, i);
+        const Vec<VW> v = Vec<VW>::load(b, i);
+#pragma unroll
+        for (int k = 0; k < VW; ++k) u[k] += v[k];
+        u.store(o, i);
+    }
+}
+template <int VW>
+__global__ void axpy_k(float al, const float* x, float* y, long n) {
+    CG_GRID_STRIDE(i, n) {
+        Vec<VW> v = Vec<VW>::load(y, i);
+        Vec<VW>::fma(v.v, al, Vec<VW>::load(x, i).v);
+        v.store(y, i);
+    }
 }
 __global__ void sigmoid_fwd_k(const float* x, float* y, long n) {
     GRID_STRIDE(i, n) { y[i] = 1.f / (1.f + expf(-x[i])); }
@@ -710,7 +618,7 @@ __global__ __launch_bounds__(256) void colreduce_k(const float* x, const float* 
                 s1 += v; s2 += v * v;
             } else if (MODE == 1) {
                 const float g = dy[i];
-                s1 += g; s2 += g * ((x[i] - mu) * is);
+                s1 += g; s2 += g * cg::bn_xhat(x[i], mu, is);
             } else {
                 s1 += dy[i];
             }
@@ -748,30 +656,34 @@ __global__ __launch_bounds__(256) void colreduce4_k(const float* x, const float*
     const long r1 = min(M, r0 + rows_per_block);
     double a1[4] = {0.0, 0.0, 0.0, 0.0}, a2[4] = {0.0, 0.0, 0.0, 0.0};
     if (q < cq) {
-        float4 mu = make_float4(0.f, 0.f, 0.f, 0.f), is = mu;
-        if (MODE == 1) { mu = ldc(mean, q); is = ldc(invstd, q); }
+        typedef Vec<4> V4;
+        V4 mu{V4::zero()}, is = mu;
+        if (MODE == 1) { mu = V4::ldc(mean, q); is = V4::ldc(invstd, q); }
         for (long rb = r0 + rl; rb < r1; rb += 64L * RL) {
             const long re = min(r1, rb + 64L * RL);
-            float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+            V4 s1{V4::zero()}, s2 = s1;
 #pragma unroll 4
             for (long r = rb; r < re; r += RL) {
                 const long i = r * cq + q;
                 if (MODE == 0) {
-                    const float4 v = ldv(x, i);
-                    s1.x += v.x; s1.y += v.y; s1.z += v.z; s1.w += v.w;
-                    s2.x += v.x * v.x; s2.y += v.y * v.y; s2.z += v.z * v.z; s2.w += v.w * v.w;
-                } else if (MODE == 1) {
-                    const float4 g = ldv(dy, i), v = ldv(x, i);
-                    s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
-                    s2.x += g.x * ((v.x - mu.x) * is.x); s2.y += g.y * ((v.y - mu.y) * is.y);
-                    s2.z += g.z * ((v.z - mu.z) * is.z); s2.w += g.w * ((v.w - mu.w) * is.w);
+                    const V4 v = V4::load(x, i);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s1[k] += v[k];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s2[k] += v[k] * v[k];
                 } else {
-                    const float4 g = ldv(dy, i);
-                    s1.x += g.x; s1.y += g.y; s1.z += g.z; s1.w += g.w;
+                    const V4 g = V4::load(dy, i);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) s1[k] += g[k];
+                    if (MODE == 1) {
+                        const V4 v = V4::load(x, i);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) s2[k] += g[k] * cg::bn_xhat(v[k], mu[k], is[k]);
+                    }
                 }
             }
-            a1[0] += s1.x; a1[1] += s1.y; a1[2] += s1.z; a1[3] += s1.w;
-            a2[0] += s2.x; a2[1] += s2.y; a2[2] += s2.z; a2[3] += s2.w;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { a1[k] += s1[k]; a2[k] += s2[k]; }
         }
     }
 #pragma unroll
@@ -811,11 +723,18 @@ __global__ void bn_prepare_k(const double* sums, double count, int C, float eps,
         }
     }
 }
+// apply / backward over n lanes of VW channels (VW = 4: C % 4 == 0 and 16-byte aligned tensors), CV = C / VW
+template <int VW>
 __global__ void bn_apply_k(const float* x, float* y, const float* gamma, const float* beta, const float* mean,
-                           const float* invstd, long total, int C) {
-    GRID_STRIDE(i, total) {
-        const int c = (int)(i % C);
-        y[i] = (x[i] - mean[c]) * invstd[c] * gamma[c] + beta[c];
+                           const float* invstd, long n, int CV) {
+    typedef Vec<VW> V;
+    CG_GRID_STRIDE(i, n) {
+        const int c = (int)(i % CV);
+        const V g = V::ldc(gamma, c), b = V::ldc(beta, c), m = V::ldc(mean, c), s = V::ldc(invstd, c);
+        V v = V::load(x, i);
+#pragma unroll
+        for (int k = 0; k < VW; ++k) v[k] = cg::bn_norm(v[k], m[k], s[k], g[k], b[k]);
+        v.store(y, i);
     }
 }
 __global__ void bn_eval_k(const float* x, float* y, const float* gamma, const float* beta, const float* rm,
@@ -825,15 +744,22 @@ __global__ void bn_eval_k(const float* x, float* y, const float* gamma, const fl
         y[i] = (x[i] - rm[c]) / sqrtf(rv[c] + eps) * gamma[c] + beta[c];
     }
 }
+template <int VW>
 __global__ void bn_bwd_k(const float* x, const float* dy, const float* gamma, const float* mean, const float* invstd,
-                         const double* sums, double count, long total, int C, float* dx) {
-    GRID_STRIDE(i, total) {
-        const int c = (int)(i % C);
-        const float is = invstd[c];
-        const float xh = (x[i] - mean[c]) * is;
-        const float m1 = (float)(sums[c] / count);
-        const float m2 = (float)(sums[C + c] / count);
-        dx[i] = gamma[c] * is * (dy[i] - m1 - xh * m2);
+                         const double* sums, double count, long n, int CV, float* dx) {
+    typedef Vec<VW> V;
+    const int C = CV * VW;
+    CG_GRID_STRIDE(i, n) {
+        const int c = (int)(i % CV);
+        const V g = V::ldc(gamma, c), m = V::ldc(mean, c), s = V::ldc(invstd, c);
+        const V v = V::load(x, i), d = V::load(dy, i);
+        V o;
+#pragma unroll
+        for (int k = 0; k < VW; ++k) {
+            const float m1 = (float)(sums[VW * c + k] / count), m2 = (float)(sums[C + VW * c + k] / count);
+            o[k] = cg::bn_dx(v[k], d[k], g[k], m[k], s[k], m1, m2);
+        }
+        o.store(dx, i);
     }
 }
 __global__ void bn_bwd_param_k(const double* local_sums, int C, float* ggamma, float* gbeta, float scale) {
@@ -931,16 +857,17 @@ __global__ void maxpool2_bwd_k(const float* x, const float* dy, float* dx, int N
 }
 
 // -------------------------------------------------------------------- dropout
-__global__ void mask_mul_k(const float* x, const float* mask, float* y, long total, long HWC, int C, int spatial) {
-    GRID_STRIDE(i, total) {
-        float m;
-        if (spatial) {
-            const long n = i / HWC;
-            m = mask[n * C + (i % C)];
-        } else {
-            m = mask[i];
-        }
-        y[i] = x[i] * m;
+// y = x * mask over n lanes of VW floats.  SPATIAL: mask[sample][channel] (CV = C / VW, HWCV lanes per sample; VW = 4 needs C % 4 == 0,
+// the mask itself any alignment), else a full-size mask (VW = 4: 16-byte aligned)
+template <int VW, bool SPATIAL>
+__global__ void mask_mul_k(const float* x, const float* mask, float* y, long n, long HWCV, int CV) {
+    typedef Vec<VW> V;
+    CG_GRID_STRIDE(i, n) {
+        const V m = SPATIAL ? V::ldc(mask, (int)((i / HWCV) * CV + (i % CV))) : V::load(mask, i);
+        V v = V::load(x, i);
+#pragma unroll
+        for (int k = 0; k < VW; ++k) v[k] *= m[k];
+        v.store(y, i);
     }
 }
 using cg::u01;
@@ -1013,8 +940,6 @@ __global__ void gather_rows_k(const float* src, const int32_t* idx, float* dst, 
     }
 }
 __global__ void fill_k(float* x, float v, long n) { GRID_STRIDE(i, n) x[i] = v; }
-__global__ void add_k(const float* a, const float* b, float* o, long n) { GRID_STRIDE(i, n) o[i] = a[i] + b[i]; }
-__global__ void axpy_k(float al, const float* x, float* y, long n) { GRID_STRIDE(i, n) y[i] += al * x[i]; }
 __global__ void axpy_sign_k(float al, const float* x, float* y, long n) {
     GRID_STRIDE(i, n) {
         const float v = x[i];
@@ -1137,44 +1062,31 @@ __device__ __forceinline__ BilinTaps bilin_taps(float yf, float xf, int Hi, int 
 }
 // Nimg: the image batch; sample n of the grid / output batch reads image n % Nimg (cg_bilinear_sampler_*_shared: G sibling
 // transformers sampling the SAME images with their own grids, as one launch over G * Nimg samples)
-__global__ void bilinear_fwd_k(const float* img, const float* grid, float* out, int N, int Nimg, int Hi, int Wi, int C, int Ho,
-                               int Wo) {
-    const long total = (long)N * Ho * Wo * C;
-    GRID_STRIDE(i, total) {
-        const int c = (int)(i % C);
-        const long pix = i / C;
+// One lane per VW channels: VW = 4 where C % 4 == 0, the tensors are 16-byte aligned and the grid 8-byte (the taps are then derived once
+// per four outputs), else 1; CV = C / VW.  Per channel the operations and their order do not depend on VW.
+template <int VW>
+__global__ __launch_bounds__(256) void bilinear_fwd_k(const float* __restrict__ img, const float* __restrict__ grid,
+                                                      float* __restrict__ out, int N, int Nimg, int Hi, int Wi, int CV, int Ho, int Wo) {
+    typedef Vec<VW> V;
+    const long total = (long)N * Ho * Wo * CV;
+    CG_GRID_STRIDE(i, total) {
+        const int c = (int)(i % CV);
+        const long pix = i / CV;
         const long n = (pix / ((long)Ho * Wo)) % Nimg;
-        const BilinTaps t = bilin_taps(grid[pix * 2], grid[pix * 2 + 1], Hi, Wi);
-        const float* b = img + (((n * Hi + t.y0) * (long)Wi + t.x0)) * C + c;
-        float v = 0.f;
-        if (t.in00) v += t.wx0 * t.wy0 * b[0];
-        if (t.in01) v += (1.f - t.wx0) * t.wy0 * b[C];
-        if (t.in10) v += t.wx0 * (1.f - t.wy0) * b[(long)Wi * C];
-        if (t.in11) v += (1.f - t.wx0) * (1.f - t.wy0) * b[(long)Wi * C + C];
-        out[i] = v;
-    }
-}
-// the same with one lane per channel QUAD (C % 4 == 0, 16-B aligned tensors): the taps are derived once per four outputs and
-// every access moves 16 B; per channel the operations and their order are those of the scalar kernel (bit-identical)
-__global__ __launch_bounds__(256) void bilinear_fwd_v4k(const float* __restrict__ img, const float* __restrict__ grid,
-                                                        float* __restrict__ out, int N, int Nimg, int Hi, int Wi, int C4, int Ho, int Wo) {
-    const long total = (long)N * Ho * Wo * C4;
-    GRID_STRIDE(i, total) {
-        const int c = (int)(i % C4);
-        const long pix = i / C4;
-        const long n = (pix / ((long)Ho * Wo)) % Nimg;
-        const float2 gyx = *reinterpret_cast<const float2*>(grid + pix * 2);
-        const BilinTaps t = bilin_taps(gyx.x, gyx.y, Hi, Wi);
-        const long b = (((n * Hi + t.y0) * (long)Wi + t.x0)) * C4 + c;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        float gy = 0.f, gx = 0.f;
+        if constexpr (VW == 4) { const float2 g = *reinterpret_cast<const float2*>(grid + pix * 2); gy = g.x; gx = g.y; }
+        else { gy = grid[pix * 2]; gx = grid[pix * 2 + 1]; }
+        const BilinTaps t = bilin_taps(gy, gx, Hi, Wi);
+        const float* b = img + ((((n * Hi + t.y0) * (long)Wi + t.x0)) * CV + c) * VW;
+        V v{V::zero()};
         auto tap = [&](bool in, float w, long off) {
-            if (in) { const float4 q = ldv(img, b + off); v.x += w * q.x; v.y += w * q.y; v.z += w * q.z; v.w += w * q.w; }
+            if (in) V::fma(v.v, w, V::ld(b + off * VW));
         };
         tap(t.in00, t.wx0 * t.wy0, 0);
-        tap(t.in01, (1.f - t.wx0) * t.wy0, C4);
-        tap(t.in10, t.wx0 * (1.f - t.wy0), (long)Wi * C4);
-        tap(t.in11, (1.f - t.wx0) * (1.f - t.wy0), (long)Wi * C4 + C4);
-        stv(out, i, v);
+        tap(t.in01, (1.f - t.wx0) * t.wy0, CV);
+        tap(t.in10, t.wx0 * (1.f - t.wy0), (long)Wi * CV);
+        tap(t.in11, (1.f - t.wx0) * (1.f - t.wy0), (long)Wi * CV + CV);
+        v.store(out, i);
     }
 }
 // G lanes per output pixel (64/G pixels per wave), lanes stride the channels; G = smallest power of two >= min(C, 64)
@@ -1233,24 +1145,6 @@ __global__ __launch_bounds__(256) void bilinear_bwd_k(const float* img, const fl
 // G = lanes per pixel (smallest power of two >= min(C, 64)); CACC = channels per lane.
 // VW = floats per lane access: 4 when C % 4 == 0 and the tensors are 16-B aligned (a wave then covers 64 / G pixels with G = C / 4
 // lanes each instead of one pixel per 64 channels), else 1.  A lane owns channels (sub + G * k) * VW .. + VW - 1.
-template <int VW> struct BVec;
-template <> struct BVec<1> {
-    typedef float T;
-    static __device__ __forceinline__ T zero() { return 0.f; }
-    static __device__ __forceinline__ T ld(const float* p) { return *p; }
-    static __device__ __forceinline__ void st(float* p, T v) { *p = v; }
-    static __device__ __forceinline__ float dot(T a, T b) { return a * b; }
-    static __device__ __forceinline__ void fma(T& acc, float w, T g) { acc += w * g; }
-};
-template <> struct BVec<4> {
-    typedef float4 T;
-    static __device__ __forceinline__ T zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
-    static __device__ __forceinline__ T ld(const float* p) { return *reinterpret_cast<const float4*>(p); }
-    static __device__ __forceinline__ void st(float* p, T v) { *reinterpret_cast<float4*>(p) = v; }
-    static __device__ __forceinline__ float dot(T a, T b) { return ((a.x * b.x + a.y * b.y) + a.z * b.z) + a.w * b.w; }
-    static __device__ __forceinline__ void fma(T& acc, float w, T g) { acc.x += w * g.x; acc.y += w * g.y; acc.z += w * g.z; acc.w += w * g.w; }
-};
-
 template <int G, int CACC, int VW>
 __global__ __launch_bounds__(256) void bilinear_bwd_det_k(const float* __restrict__ img, const float* __restrict__ grid,
                                                           const float* __restrict__ gout, float* __restrict__ gimg,
@@ -1350,7 +1244,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_det_k(const float* __restric
             for (int k = 0; k < CACC; ++k) {
                 const int c = (sub + G * k) * VW;
                 if (c < C) {
-                    typedef BVec<VW> V;
+                    typedef Vec<VW> V;
                     const typename V::T g = V::ld(gsample + (long)p * C + c);
                     const typename V::T i00 = (yin0 && xin0) ? V::ld(isample + b + c) : V::zero(), i01 = (yin0 && xin1) ? V::ld(isample + b + o01 + c) : V::zero();
                     const typename V::T i10 = (yin1 && xin0) ? V::ld(isample + b + o10 + c) : V::zero(), i11 = (yin1 && xin1) ? V::ld(isample + b + o11 + c) : V::zero();
@@ -1386,7 +1280,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_det_k(const float* __restric
         const int s3 = cstart[c00 + CW + 1], n3 = ccnt[c00 + CW + 1];
         const int e1 = n0, e2 = n0 + n1, e3 = n0 + n1 + n2, total = e3 + n3;
         if (total > kHeavy) { any_heavy = true; continue; }
-        typedef BVec<VW> V;
+        typedef Vec<VW> V;
         typename V::T acc[CACC];
 #pragma unroll
         for (int k = 0; k < CACC; ++k) acc[k] = V::zero();
@@ -1430,7 +1324,7 @@ __global__ __launch_bounds__(256) void bilinear_bwd_det_k(const float* __restric
     // takes the taps r, r + ngrp, ... in bucket order, the ngrp partial sums are added in group order - a fixed order again, so the result
     // is reproducible (it differs from the one-group order by fp32 re-association only, and only where more than kHeavy taps meet).
     if (__syncthreads_or(any_heavy ? 1 : 0)) {
-        typedef BVec<VW> V;
+        typedef Vec<VW> V;
         for (int j = 0; j < S; ++j) {
             const int q = chunk * S + j;
             if (q >= Q) break;
@@ -1557,7 +1451,6 @@ __global__ void confusion_k(const float* out, const float* tgt, int32_t* counts,
 
 }  // namespace
 
-static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 #define EW_LAUNCH(kern, n, ...)                                                                  \
     do {                                                                                         \
         if ((n) > 0) {                                                                           \
@@ -1732,15 +1625,16 @@ int cg_colorspace_convert(void* stream, const float* src, float* dst, long npixe
 
 int cg_prelu_forward(void* stream, const float* x, const float* alpha, float* y, long n) {
     CG_REQUIRE(x && alpha && y, "cg_prelu_forward: null pointer");
-    if (n % 4 == 0 && al16(x) && al16(y)) { EW_LAUNCH(prelu_fwd_v4k, n / 4, x, alpha, y, n / 4); return 0; }
-    EW_LAUNCH(prelu_fwd_k, n, x, alpha, y, n); return 0;
+    if (cg::vec_ok(n, x, y)) EW_LAUNCH(prelu_fwd_k<4>, n / 4, x, alpha, y, n / 4);
+    else EW_LAUNCH(prelu_fwd_k<1>, n, x, alpha, y, n);
+    return 0;
 }
 size_t cg_prelu_backward_workspace_bytes(long n) { return n > 0 ? sizeof(double) * (size_t)cg::ew_grid(n) : 0; }
 int cg_prelu_backward(void* stream, const float* x, const float* dy, const float* alpha, float* dx, float* galpha,
                       float scale, long n, void* ws, size_t ws_bytes) {
     CG_REQUIRE(x && dy && alpha && dx, "cg_prelu_backward: null pointer");
     if (n <= 0) return 0;
-    const bool v4 = n % 4 == 0 && al16(x) && al16(dy) && al16(dx);
+    const bool v4 = cg::vec_ok(n, x, dy, dx);
     const int nblk = cg::ew_grid(v4 ? n / 4 : n);
     double* gpart = nullptr;
     if (galpha) {
@@ -1748,8 +1642,8 @@ int cg_prelu_backward(void* stream, const float* x, const float* dy, const float
                    "cg_prelu_backward: workspace too small (%zu < %zu)", ws_bytes, sizeof(double) * nblk);
         gpart = (double*)ws;
     }
-    if (v4) EW_LAUNCH(prelu_bwd_v4k, n / 4, x, dy, alpha, dx, gpart, n / 4);
-    else EW_LAUNCH(prelu_bwd_k, n, x, dy, alpha, dx, gpart, n);
+    if (v4) EW_LAUNCH(prelu_bwd_k<4>, n / 4, x, dy, alpha, dx, gpart, n / 4);
+    else EW_LAUNCH(prelu_bwd_k<1>, n, x, dy, alpha, dx, gpart, n);
     if (galpha) {
         hipLaunchKernelGGL(prelu_galpha_reduce_k, dim3(1), dim3(256), 0, cg::S(stream), gpart, nblk, galpha, scale);
         CG_LAUNCH_CHECK();
@@ -1758,13 +1652,15 @@ int cg_prelu_backward(void* stream, const float* x, const float* dy, const float
 }
 int cg_leakyrelu_forward(void* stream, const float* x, float* y, float slope, long n) {
     CG_REQUIRE(x && y, "cg_leakyrelu_forward: null pointer");
-    if (n % 4 == 0 && al16(x) && al16(y)) { EW_LAUNCH(lrelu_fwd_v4k, n / 4, x, y, slope, n / 4); return 0; }
-    EW_LAUNCH(lrelu_fwd_k, n, x, y, slope, n); return 0;
+    if (cg::vec_ok(n, x, y)) EW_LAUNCH(lrelu_fwd_k<4>, n / 4, x, y, slope, n / 4);
+    else EW_LAUNCH(lrelu_fwd_k<1>, n, x, y, slope, n);
+    return 0;
 }
 int cg_leakyrelu_backward(void* stream, const float* x, const float* dy, float* dx, float slope, long n) {
     CG_REQUIRE(x && dy && dx, "cg_leakyrelu_backward: null pointer");
-    if (n % 4 == 0 && al16(x) && al16(dy) && al16(dx)) { EW_LAUNCH(lrelu_bwd_v4k, n / 4, x, dy, dx, slope, n / 4); return 0; }
-    EW_LAUNCH(lrelu_bwd_k, n, x, dy, dx, slope, n); return 0;
+    if (cg::vec_ok(n, x, dy, dx)) EW_LAUNCH(lrelu_bwd_k<4>, n / 4, x, dy, dx, slope, n / 4);
+    else EW_LAUNCH(lrelu_bwd_k<1>, n, x, dy, dx, slope, n);
+    return 0;
 }
 int cg_sigmoid_forward(void* stream, const float* x, float* y, long n) {
     CG_REQUIRE(x && y, "cg_sigmoid_forward: null pointer");
@@ -1787,7 +1683,7 @@ int cg_bce_backward(void* stream, const float* p, const float* t, float* dp, lon
 static int colreduce_launch(void* stream, int mode, const float* x, const float* dy, const float* mean,
                             const float* invstd, long M, int C, double* sums, int nsums) {
     if (M <= 0) { CG_HIP(hipMemsetAsync(sums, 0, sizeof(double) * nsums * C, cg::S(stream))); return 0; }
-    const bool v4 = C % 4 == 0 && (!x || al16(x)) && (!dy || al16(dy));
+    const bool v4 = cg::vec_ok(C, x, dy);
     const int qb = C >= 128 ? 32 : 16;   // channel quads per block in the float4 form
     const int cblocks = v4 ? cg::cdiv(C / 4, qb) : cg::cdiv(C, 64);
     // row chunks: every chunk ends in one double atomic per channel, and same-address atomics serialise (~10 ns each),
@@ -1834,12 +1730,8 @@ int cg_bn_forward(void* stream, const float* x, float* y, const float* gamma, co
     CG_REQUIRE(x && y && gamma && beta && sums && save_mean && save_invstd && C > 0 && count > 0, "cg_bn_forward: bad args");
     EW_LAUNCH(bn_prepare_k, (long)C, sums, count, C, eps, momentum, running_mean, running_var, save_mean, save_invstd);
     const long total = M * C;
-    if (C % 4 == 0 && al16(x) && al16(y)) {
-        EW_LAUNCH(bn_apply_v4k, total / 4, x, y, gamma, beta, (const float*)save_mean, (const float*)save_invstd, total / 4,
-                  C / 4);
-        return 0;
-    }
-    EW_LAUNCH(bn_apply_k, total, x, y, gamma, beta, (const float*)save_mean, (const float*)save_invstd, total, C);
+    if (cg::vec_ok(C, x, y)) EW_LAUNCH(bn_apply_k<4>, total / 4, x, y, gamma, beta, (const float*)save_mean, (const float*)save_invstd, total / 4, C / 4);
+    else EW_LAUNCH(bn_apply_k<1>, total, x, y, gamma, beta, (const float*)save_mean, (const float*)save_invstd, total, C);
     return 0;
 }
 int cg_bn_forward_eval(void* stream, const float* x, float* y, const float* gamma, const float* beta,
@@ -1860,11 +1752,8 @@ int cg_bn_backward(void* stream, const float* x, const float* dy, const float* g
     CG_REQUIRE(x && dy && gamma && save_mean && save_invstd && sums && local_sums && dx && C > 0 && count > 0,
                "cg_bn_backward: bad args");
     const long total = M * C;
-    if (C % 4 == 0 && al16(x) && al16(dy) && al16(dx)) {
-        EW_LAUNCH(bn_bwd_v4k, total / 4, x, dy, gamma, save_mean, save_invstd, sums, count, total / 4, C / 4, dx);
-    } else {
-        EW_LAUNCH(bn_bwd_k, total, x, dy, gamma, save_mean, save_invstd, sums, count, total, C, dx);
-    }
+    if (cg::vec_ok(C, x, dy, dx)) EW_LAUNCH(bn_bwd_k<4>, total / 4, x, dy, gamma, save_mean, save_invstd, sums, count, total / 4, C / 4, dx);
+    else EW_LAUNCH(bn_bwd_k<1>, total, x, dy, gamma, save_mean, save_invstd, sums, count, total, C, dx);
     EW_LAUNCH(bn_bwd_param_k, (long)C, local_sums, C, ggamma, gbeta, scale);
     return 0;
 }
@@ -1903,13 +1792,13 @@ int cg_maxpool2_backward(void* stream, const float* x, const float* dy, float* d
 int cg_mask_mul(void* stream, const float* x, const float* mask, float* y, int N, long HW, int C, int spatial) {
     CG_REQUIRE(x && mask && y, "cg_mask_mul: null pointer");
     const long total = (long)N * HW * C;
-    if (al16(x) && al16(y)) {
-        if (spatial && C % 4 == 0) {
-            EW_LAUNCH(mask_mul_sp_v4k, total / 4, x, mask, y, total / 4, HW * C / 4, C / 4); return 0;
-        }
-        if (!spatial && total % 4 == 0 && al16(mask)) { EW_LAUNCH(mask_mul_v4k, total / 4, x, mask, y, total / 4); return 0; }
-    }
-    EW_LAUNCH(mask_mul_k, total, x, mask, y, total, HW * C, C, spatial); return 0;
+    // three forms: a [N][C] mask with C % 4 == 0, a full-size aligned mask with total % 4 == 0, and the scalar kernel for the rest
+    const bool v4 = spatial ? cg::vec_ok(C, x, y) : cg::vec_ok(total, x, y, mask);
+    if (v4 && spatial) EW_LAUNCH((mask_mul_k<4, true>), total / 4, x, mask, y, total / 4, HW * C / 4, C / 4);
+    else if (v4) EW_LAUNCH((mask_mul_k<4, false>), total / 4, x, mask, y, total / 4, 0L, 0);
+    else if (spatial) EW_LAUNCH((mask_mul_k<1, true>), total, x, mask, y, total, HW * C, C);
+    else EW_LAUNCH((mask_mul_k<1, false>), total, x, mask, y, total, 0L, 0);
+    return 0;
 }
 int cg_rng_bernoulli_dev(void* stream, float* out, long n, float keep_prob, float value, uint64_t seed, uint64_t offset,
                          const uint64_t* base) {
@@ -1977,13 +1866,15 @@ int cg_fill(void* stream, float* x, float value, long n) {
 }
 int cg_add(void* stream, const float* a, const float* b, float* out, long n) {
     CG_REQUIRE(a && b && out, "cg_add: null pointer");
-    if (n % 4 == 0 && al16(a) && al16(b) && al16(out)) { EW_LAUNCH(add_v4k, n / 4, a, b, out, n / 4); return 0; }
-    EW_LAUNCH(add_k, n, a, b, out, n); return 0;
+    if (cg::vec_ok(n, a, b, out)) EW_LAUNCH(add_k<4>, n / 4, a, b, out, n / 4);
+    else EW_LAUNCH(add_k<1>, n, a, b, out, n);
+    return 0;
 }
 int cg_axpy(void* stream, float alpha, const float* x, float* y, long n) {
     CG_REQUIRE(x && y, "cg_axpy: null pointer");
-    if (n % 4 == 0 && al16(x) && al16(y)) { EW_LAUNCH(axpy_v4k, n / 4, alpha, x, y, n / 4); return 0; }
-    EW_LAUNCH(axpy_k, n, alpha, x, y, n); return 0;
+    if (cg::vec_ok(n, x, y)) EW_LAUNCH(axpy_k<4>, n / 4, alpha, x, y, n / 4);
+    else EW_LAUNCH(axpy_k<1>, n, alpha, x, y, n);
+    return 0;
 }
 int cg_axpy_sign(void* stream, float alpha, const float* x, float* y, long n) {
     CG_REQUIRE(x && y, "cg_axpy_sign: null pointer");
@@ -2035,11 +1926,9 @@ namespace {
 int sampler_forward(void* stream, const float* img, const float* grid, float* out, int N, int Nimg, int Hi, int Wi, int C, int Ho,
                     int Wo) {
     const long total = (long)N * Ho * Wo * C;
-    if (C % 4 == 0 && al16(img) && al16(out) && (uintptr_t)grid % 8 == 0) {
-        EW_LAUNCH(bilinear_fwd_v4k, total / 4, img, grid, out, N, Nimg, Hi, Wi, C / 4, Ho, Wo);
-        return 0;
-    }
-    EW_LAUNCH(bilinear_fwd_k, total, img, grid, out, N, Nimg, Hi, Wi, C, Ho, Wo); return 0;
+    if (cg::vec_ok(C, img, out) && (uintptr_t)grid % 8 == 0) EW_LAUNCH(bilinear_fwd_k<4>, total / 4, img, grid, out, N, Nimg, Hi, Wi, C / 4, Ho, Wo);
+    else EW_LAUNCH(bilinear_fwd_k<1>, total, img, grid, out, N, Nimg, Hi, Wi, C, Ho, Wo);
+    return 0;
 }
 
 int sampler_backward(void* stream, const float* img, const float* grid, const float* gout, float* gimg, float* ggrid, int N, int Nimg,
@@ -2047,7 +1936,7 @@ int sampler_backward(void* stream, const float* img, const float* grid, const fl
     const long P = (long)Ho * Wo, Q = (long)Hi * Wi;
     const size_t shb = ((size_t)6 * P + 2 * ((size_t)(Hi + 1) * (Wi + 1)) + 1) * 4;
     if (shb <= 140 * 1024 && C <= 256 && N > 0) {   // deterministic gather form
-        const bool v4 = C % 4 == 0 && al16(img) && al16(gout) && al16(gimg);
+        const bool v4 = cg::vec_ok(C, img, gout, gimg);
         const int units = v4 ? C / 4 : C;                  // lane-sized channel units per pixel
         int G = 4;
         while (G < 64 && G < units) G <<= 1;

@@ -41,7 +41,7 @@ def ew_cap(L):
 
 
 def group_cap(L):
-    """act_pool_bwd_blocks' cap (fused.hip:590): workgroups per group of the stacked-group backward kernels."""
+    """act_pool_bwd_blocks' cap (fused.hip): workgroups per group of the stacked-group backward kernels."""
     return int(L.act_pool2_mask_backward_workspace_bytes(1, 1 << 20, 64, 64, 64)) // 8
 
 
@@ -61,7 +61,7 @@ ACT_CASES = [
 
 
 def act_regime(L, n, misaligned):
-    v4 = n % 4 == 0 and not misaligned                                           # ops.hip:1735, :1743, :1761, :1766
+    v4 = n % 4 == 0 and not misaligned                                           # cg::vec_ok in cg_prelu_* / cg_leakyrelu_*
     return v4, ew_regime(n // 4 if v4 else n, ew_cap(L))
 
 
@@ -71,12 +71,12 @@ GROUPED_PRELU_CASES = [(1, 4, (1, False)), (2, 1028, (2, False)), (4, 2052, (3, 
 
 def grouped_regime(L, n_per_group4):
     cap = group_cap(L)
-    blocks = max(1, min((n_per_group4 + 255) // 256, cap))                       # fused.hip:590
+    blocks = max(1, min((n_per_group4 + 255) // 256, cap))                       # act_pool_bwd_blocks
     return (None if blocks == cap else blocks), n_per_group4 > blocks * 256
 
 
 # C, M, what is run, the regime.  v4: the float4 kernels; chunks / ngroups / last: the ColTree; second_block: live channels of the last
-# channel block where there are two; trips: of the rb loop (ops.hip:753, fused.hip:439); apply: the bn_act apply kernels' regime.
+# channel block where there are two; trips: of the rb loop (colreduce4_k, bn_act_bwd_stats_k); apply: the bn_act apply kernels' regime.
 BN_CASES = [
     (3, 1, "all", dict(v4=False, chunks=1, ngroups=1, last=1)),
     (3, 5, "all", dict(v4=False, chunks=1, ngroups=1, last=1)),
@@ -110,7 +110,7 @@ BN_CASES = [
 
 
 def bn_regime(L, C, M, misaligned=False):
-    v4 = C % 4 == 0 and not misaligned                                           # ops.hip:1790, :1837, :1863, fused.hip:799
+    v4 = C % 4 == 0 and not misaligned                                           # cg::vec_ok in colreduce_launch, cg_bn_*
     cl = col_launch(M, C, v4, COL_WGS)
     tr = col_tree(cl["chunks"])
     got = dict(v4=v4, chunks=cl["chunks"], ngroups=tr["ngroups"], last=tr["last"])
@@ -124,7 +124,7 @@ def bn_regime(L, C, M, misaligned=False):
     trips = -(-cl["rows"] // (64 * cl["RL"]))
     if trips > 1:
         got["trips"] = trips
-    if v4 and C > 8:                                                             # the apply kernels of bn_act (fused.hip:801, :847)
+    if v4 and C > 8:                                                             # the apply kernels of bn_act (cg_bn_act_forward / _backward)
         cap, n4, C4 = ew_cap(L), M * (C // 4), C // 4
         grid = fixed_channel_grid(n4, C4, cap)
         assert (grid * 256) % C4 == 0, "the stride must keep a thread on one channel quad"
@@ -242,8 +242,8 @@ def test_activation_twins_and_wraps(cg, n, misaligned, regime):
     dx_ref = np.where(pos, dy, a * dy)
     bits_equal(host(dx), dx_ref, "prelu dx")
     prod = (x.astype(f64) * dy.astype(f64))[~pos]
-    # prelu_bwd_v4k (ops.hip:531): a product, the 3 sums beside it, one sum into s per pass and two passes at most; the cast and the +=
-    # of prelu_galpha_reduce_k (ops.hip:646): 1 + 3 + 2 + 2, + 2
+    # prelu_bwd_k<4> (cg::slope_acc): a product, the 3 sums beside it, one sum into s per pass and two passes at most; the cast and the +=
+    # of prelu_galpha_reduce_k: 1 + 3 + 2 + 2, + 2
     assert n <= 2 * 4 * ew_cap(L) * 256
     rounding_close(host(ga), [1.0 + 0.5 * prod.sum()], [1.0 + 0.5 * np.abs(prod).sum()], 10, "prelu galpha")
     dx2 = out_like(n, misaligned)
@@ -285,7 +285,7 @@ def test_prelu_backward_over_stacked_groups(cg, G, n, regime):
         pos = x[g] > 0
         bits_equal(got[g], np.where(pos, dy[g], slopes[g] * dy[g]), f"group {g} dx")
         prod = (x[g].astype(f64) * dy[g].astype(f64))[~pos]
-        # prelu_bwd_groups_v4k (fused.hip:315) adds as prelu_bwd_v4k does: 6; galpha_groups_reduce_k (fused.hip:296): cast, product, sum
+        # prelu_bwd_groups_v4k adds as prelu_bwd_k<4> does (both are cg::prelu_bwd_walk<4>): 6; galpha_groups_reduce_k: cast, product, sum
         rounding_close(host(ga[g]), [1.0 + 0.5 * prod.sum()], [1.0 + 0.5 * np.abs(prod).sum()], 11, f"group {g} galpha")
 
 
@@ -293,7 +293,7 @@ def test_prelu_backward_over_stacked_groups(cg, G, n, regime):
 def stat_bounds(x64, M, eps):
     """fp64 statistics of the columns of x and how far the device's may lie from them: its sums are 66-rounding sums (fp32 partials of at
     most 64 rows - `cnt == 64` in colreduce_k, `64L * RL` in colreduce4_k - then fp64), var = E[x^2] - mean^2 in fp64 from those sums
-    (bn_prepare_k, ops.hip:801-804), the results cast to fp32."""
+    (bn_prepare_k), the results cast to fp32."""
     s1, s2, a1 = x64.sum(0), (x64 * x64).sum(0), np.abs(x64).sum(0)
     a2 = s2
     mean = s1 / M
@@ -333,13 +333,13 @@ def test_column_reductions_and_batchnorm(cg, C, M, run, regime):
         mean, inv = host(sm), host(si)
         rounding_close(mean, S["mean"], np.abs(S["mean"]), 1, "save_mean", slack=S["dmean"])
         rounding_close(inv, S["inv"], S["inv"], 1, "save_invstd", slack=S["dinv"])
-        # bn_prepare_k (ops.hip:807, :810): 1 - momentum, two products, one sum: 4, + 2
+        # bn_prepare_k's running statistics: 1 - momentum, two products, one sum: 4, + 2
         rounding_close(host(rm), 0.9 * rm0.astype(f64) + 0.1 * S["mean"], 0.9 * np.abs(rm0) + 0.1 * np.abs(S["mean"]), 6, "running_mean",
                        slack=0.1 * (S["dmean"] + U24 * np.abs(S["mean"])))
         unb, dunb = (S["var"] * M / (M - 1.0), S["dvar"] * M / (M - 1.0)) if M > 1 else (S["var"], S["dvar"])
         rounding_close(host(rv), 0.9 * rv0.astype(f64) + 0.1 * unb, 0.9 * np.abs(rv0) + 0.1 * unb, 6, "running_var",
                        slack=0.1 * (dunb + U24 * unb))
-        # ---- apply, against fp64 WITH the device's statistics.  bn_apply_k (ops.hip:818): difference, two products, sum: 4, + 2
+        # ---- apply, against fp64 WITH the device's statistics.  bn_apply_k (cg::bn_norm): difference, two products, sum: 4, + 2
         xh = (x64 - mean) * inv.astype(f64)
         rounding_close(host(y, (M, C)), xh * g64 + b64, np.abs(xh * g64) + np.abs(b64), 6, "bn_forward y")
         # ---- backward sums (mode 1).  The term dy * xhat is built from two more roundings: 68
@@ -348,7 +348,7 @@ def test_column_reductions_and_batchnorm(cg, C, M, run, regime):
         hb = bs.cpu().numpy()
         rounding_close(hb[:C], dy64.sum(0), np.abs(dy64).sum(0), 66, "bn_backward_stats sum dy")
         rounding_close(hb[C:], (dy64 * xh).sum(0), np.abs(dy64 * xh).sum(0), 68, "bn_backward_stats sum dy xhat")
-        # ---- backward apply with the device's sums.  bn_bwd_k (ops.hip:833-836): xhat 2, the cast of m2 1, xhat m2 1, two differences 1
+        # ---- backward apply with the device's sums.  bn_bwd_k (cg::bn_dx): xhat 2, the cast of m2 1, xhat m2 1, two differences 1
         # (the other one is off the chain), gamma invstd beside it, the last product 1: 7, + 2
         dx, gg, gb = out_like(M * C, mis), dev(np.ones(C, f32)), dev(np.ones(C, f32))
         L.bn_backward(st, p(xt), p(dyt), p(gt), p(sm), p(si), p(bs), cnt, p(bs), M, C, p(dx), p(gg), p(gb), 0.5)
@@ -356,14 +356,14 @@ def test_column_reductions_and_batchnorm(cg, C, M, run, regime):
         gi = g64 * inv.astype(f64)
         rounding_close(host(dx, (M, C)), gi * (dy64 - m1 - xh * m2), np.abs(gi) * (np.abs(dy64) + np.abs(m1) + np.abs(xh * m2)), 9,
                        "bn_backward dx")
-        # bn_bwd_param_k (ops.hip:841): cast, product, sum: 3, + 2; accumulates onto 1 with scale 0.5
+        # bn_bwd_param_k: cast, product, sum: 3, + 2; accumulates onto 1 with scale 0.5
         rounding_close(host(gb), 1.0 + 0.5 * hb[:C], 1.0 + 0.5 * np.abs(hb[:C]), 5, "gbeta")
         rounding_close(host(gg), 1.0 + 0.5 * hb[C:], 1.0 + 0.5 * np.abs(hb[C:]), 5, "ggamma")
         # ---- bias gradient (mode 2): the 66-rounding sum, cast, product, sum
         gbias, ws = dev(np.ones(C, f32)), dsums(C)
         L.bias_grad(st, p(dyt), p(gbias), M, C, 0.5, p(ws), 8 * C)
         rounding_close(host(gbias), 1.0 + 0.5 * dy64.sum(0), 1.0 + 0.5 * np.abs(dy64).sum(0), 69, "bias_grad")
-        # ---- evaluation mode.  bn_eval_k (ops.hip:825): difference, rv + eps, square root, quotient, product, sum: 6, + 2
+        # ---- evaluation mode.  bn_eval_k: difference, rv + eps, square root, quotient, product, sum: 6, + 2
         ye = out_like(M * C, mis)
         rme, rve = dev(rm0), dev(rv0)
         L.bn_forward_eval(st, p(xt), p(ye), p(gt), p(bt), p(rme), p(rve), M, C, eps)
@@ -377,7 +377,7 @@ def test_column_reductions_and_batchnorm(cg, C, M, run, regime):
         al = scalar(alpha) if with_alpha else None
         L.bn_act_forward(st, p(xt), p(y2), p(gt), p(bt), p(sums), cnt, M, C, eps, mom, p(rm2), p(rv2), p(sm2), p(si2), p(al) if al is not None else None)
         mean, inv = host(sm2), host(si2)
-        if full:   # bn_act_fwd_v4k derives them "exactly as bn_prepare_k does" (fused.hip:372-384): the bits of cg_bn_forward's
+        if full:   # bn_act_fwd_v4k derives them "exactly as bn_prepare_k does": the bits of cg_bn_forward's
             bits_equal(mean, host(sm), "bn_act save_mean"); bits_equal(inv, host(si), "bn_act save_invstd")
             bits_equal(host(rm2), host(rm), "bn_act running_mean"); bits_equal(host(rv2), host(rv), "bn_act running_var")
         else:
@@ -396,10 +396,10 @@ def test_column_reductions_and_batchnorm(cg, C, M, run, regime):
             flips = int((pos != (u > 0)).sum())
             print(f"kink: {int(near.sum())} of {u.size} elements within 4 roundings of zero, {flips} on the other side")
             assert near.sum() <= 1e-3 * u.size
-            # bn_act_fwd_v4k (fused.hip:403-407): the 4 of the apply and the slope's product: 5, + 2
+            # bn_act_fwd_v4k (cg::bn_norm, cg::act): the 4 of the apply and the slope's product: 5, + 2
             rounding_close(yd, np.where(pos, u, f64(alpha) * u), tu, 7, "bn_act_forward y")
         if not regime["v4"]:
-            continue                                                             # cg_bn_act_backward* take C % 4 == 0 only (fused.hip:817, :845)
+            continue                                                             # cg_bn_act_backward* take C % 4 == 0 only (their CG_REQUIRE)
         bs = dsums(2 * C + 1)
         L.bn_act_backward_stats(st, p(xt), p(dyt), p(sm2), p(si2), p(gt), p(bt), p(al) if al is not None else None, M, C, p(bs))
         hb = bs.cpu().numpy()
@@ -407,7 +407,7 @@ def test_column_reductions_and_batchnorm(cg, C, M, run, regime):
         rounding_close(hb[:C], dd.sum(0), np.abs(dd).sum(0), 66, "bn_act_backward_stats sum d")
         rounding_close(hb[C:2 * C], (dd * xh).sum(0), np.abs(dd * xh).sum(0), 68, "bn_act_backward_stats sum d xhat")
         if with_alpha:
-            # sg of bn_act_bwd_stats_k (fused.hip:449): 4 channels x 64 rows added in fp32 per lane, u 4 and its product 1: 261, + 2
+            # sg of bn_act_bwd_stats_k: 4 channels x 64 rows added in fp32 per lane, u 4 and its product 1: 261, + 2
             ud = (u * dy64)[~pos]
             rounding_close(hb[2 * C:], [ud.sum()], [np.abs(ud).sum()], 263, "bn_act_backward_stats sum u dy")
         else:
@@ -419,7 +419,7 @@ def test_column_reductions_and_batchnorm(cg, C, M, run, regime):
                           p(dx), p(gg), p(gb), p(ga), 0.5)
         m1, m2 = (hb[:C] / cnt).astype(f32).astype(f64), (hb[C:2 * C] / cnt).astype(f32).astype(f64)
         gi = g64 * inv.astype(f64)
-        # bn_act_bwd_v4k (fused.hip:532-535): bn_bwd_k's 7 and the slope's product on dd: 8, + 2
+        # bn_act_bwd_v4k (cg::bn_dx of cg::dact): bn_bwd_k's 7 and the slope's product on dd: 8, + 2
         rounding_close(host(dx, (M, C)), gi * (dd - m1 - xh * m2), np.abs(gi) * (np.abs(dd) + np.abs(m1) + np.abs(xh * m2)), 10,
                        "bn_act_backward dx")
         rounding_close(host(gb), 1.0 + 0.5 * hb[:C], 1.0 + 0.5 * np.abs(hb[:C]), 5, "bn_act gbeta")
@@ -481,14 +481,14 @@ def test_act_pool_mask_over_groups(cg, G, NG, H, W, C, masked, acts, slopes, reg
                 if pool_max or act == 0:
                     bits_equal(yd[sl], nhwc(pooled) * mb[sl] if mask is not None else nhwc(pooled), what + " y")
                 else:
-                    # act_pool2_fwd_k (fused.hip:69): the slope's product feeds the sum: 1 + 3 sums + the (exact) quarter and mask: 4, + 2
+                    # act_pool2_fwd_k's average: the slope's product feeds the sum: 1 + 3 sums + the (exact) quarter and mask: 4, + 2
                     h64 = nhwc(h).astype(f64).reshape(NG, Ho, 2, Wo, 2, C)
                     mbs = mb[sl] if mask is not None else 1.0
                     rounding_close(yd[sl], h64.sum((2, 4)) * 0.25 * mbs, np.abs(h64).sum((2, 4)) * 0.25 * mbs, 6, what + " y")
                 if act == 1:
                     neg = xn[sl] <= 0
                     prod = (xn[sl].astype(f64) * e.astype(f64))[neg]
-                    # act_pool2_bwd_k (fused.hip:128): a product, the 3 sums beside it, 4 sums into s per float4 and two passes at most,
+                    # act_pool2_bwd_k (cg::slope_term): a product, the 3 sums beside it, 4 sums into s per float4 and two passes at most,
                     # then galpha_groups_reduce_k's cast, product and sum: 1 + 3 + 8 + 3, + 2
                     rounding_close(host(ga[g]), [1.0 + 0.5 * prod.sum()], [1.0 + 0.5 * np.abs(prod).sum()], 17, what + " galpha")
                     if slopes[g] == 0.0 and pool_max:
@@ -565,7 +565,7 @@ def test_concat_split_sum_and_dropout(cg, Cs, N, HW, regime):
     L.split_channels(st, n, wt.data_ptr(), ptrs(outs), cc, M)
     for o, c, ref in zip(outs, Cs, np.split(whole, np.cumsum(Cs)[:-1], axis=1)):
         bits_equal(host(o, (M, c)), ref, "split")
-    if n >= 2:     # sum4_v4k (fused.hip:161-165): ((a + b) + c) + d
+    if n >= 2:     # sum4_v4k: ((a + b) + c) + d
         same = [edge_normal(rng, (M, 4)) for _ in range(n)]
         s = out_like(M * 4)
         L.sum_n(st, n, ptrs([dev(a) for a in same]), s.data_ptr(), M * 4)
@@ -605,7 +605,7 @@ MASK_RUNS = ((False, False, 1), (True, False, 1), (False, False, 0), (False, Tru
 
 
 def mask_path(total, C, spatial, x_aligned, mask_aligned):
-    """cg_mask_mul's dispatch (ops.hip:1906-1912)."""
+    """cg_mask_mul's dispatch."""
     if x_aligned and spatial and C % 4 == 0:
         return "spatial v4"
     if x_aligned and not spatial and total % 4 == 0 and mask_aligned:
@@ -651,23 +651,23 @@ def head_check(cg, N, F, Oo, rng):
     bits_equal(host(xd, (N, F)), xdr, "head xd")
     what = f"head N={N} F={F} O={Oo}"
     w64, xd64 = w.astype(f64), xdr.astype(f64)
-    # head_fwd_k (fused.hip:228-234): a product, ceil(F / 64) sums per lane, 6 levels of wave_sum, the bias
+    # head_fwd_k: a product, ceil(F / 64) sums per lane, 6 levels of wave_sum, the bias
     per = -(-F // 64)
     zd = host(z, (N, Oo))
     rounding_close(zd, xd64 @ w64.T + b, np.abs(xd64) @ np.abs(w64).T + np.abs(b), per + 8 + 2, what + " z")
-    # p = 1 / (1 + expf(-z)) from the device's z (fused.hip:236): expf within 1 ulp (2 roundings' worth), sum, quotient: 4, + 2
+    # p = 1 / (1 + expf(-z)) from the device's z (head_fwd_k): expf within 1 ulp (2 roundings' worth), sum, quotient: 4, + 2
     pd = host(p, (N, Oo))
     pr = 1.0 / (1.0 + np.exp(-zd.astype(f64)))
     rounding_close(pd, pr, pr, 6, what + " p")
     gx, gw, gb = out_like(N * F), dev(np.ones((Oo, F), f32)), dev(np.ones(Oo, f32))   # accumulate semantics: start at 1, scale 0.5
     L.drop_linear_sigmoid_backward(st, dpt.data_ptr(), p.data_ptr(), xd.data_ptr(), nz.data_ptr(), wt.data_ptr(), gx.data_ptr(), gw.data_ptr(),
                                    gb.data_ptr(), N, F, Oo, 0.5)
-    gz = dp.astype(f64) * (1.0 - pd) * pd                                         # head_bwd_k (fused.hip:251): 3 roundings
-    # gx (fused.hip:265-266): gz 3, a product, O sums, the mask: O + 5, + 2
+    gz = dp.astype(f64) * (1.0 - pd) * pd                                         # head_bwd_k: 3 roundings
+    # gx (head_bwd_k's sample loop): gz 3, a product, O sums, the mask: O + 5, + 2
     rounding_close(host(gx, (N, F)), (gz @ w64) * mk, (np.abs(gz) @ np.abs(w64)) * mk, Oo + 7, what + " gx")
-    # gw (fused.hip:265, :276-277): gz 3, a product, ceil(N / 4) sums per lane, 3 sums over the lanes, scale, +=: ceil(N / 4) + 9, + 2
+    # gw (the sample loop, then the four lanes' partials): gz 3, a product, ceil(N / 4) sums per lane, 3 sums over the lanes, scale, +=: ceil(N / 4) + 9, + 2
     rounding_close(host(gw, (Oo, F)), 1.0 + 0.5 * gz.T @ xd64, 1.0 + 0.5 * np.abs(gz).T @ np.abs(xd64), -(-N // 4) + 9 + 2, what + " gw")
-    # gb (fused.hip:282-283): gz 3, N sums, scale, +=
+    # gb (head_bwd_k's last block): gz 3, N sums, scale, +=
     rounding_close(host(gb), 1.0 + 0.5 * gz.sum(0), 1.0 + 0.5 * np.abs(gz).sum(0), N + 5 + 2, what + " gb")
     gx2 = out_like(N * F)
     L.drop_linear_sigmoid_backward(st, dpt.data_ptr(), p.data_ptr(), None, nz.data_ptr(), wt.data_ptr(), gx2.data_ptr(), None, None, N, F, Oo, 0.0)
@@ -715,7 +715,7 @@ def test_optimiser_kernels_past_the_wrap(cg):
     p0, g = edge_normal(rng, (n, 1)).ravel(), edge_normal(rng, (n, 1)).ravel()
     m0, v0 = (rng.standard_normal(n) * 0.1).astype(f32), (rng.random(n) * 0.1).astype(f32)
     lr, b1, b2, eps = 1e-3, 0.9, 0.999, 1e-8
-    # adam_k (ops.hip:1513-1516) and O.adam's fp32 restatement each stay within r roundings of the exact update, so of one another
+    # adam_k and O.adam's fp32 restatement each stay within r roundings of the exact update, so of one another
     # within 2 r.  m: 1 - b1, two products, sum: 4.  v: 1 - b2, three products, sum: 5, halved by the root.  p: m 4, v 3, root, + eps,
     # step product, quotient, difference: 12, + 2.  One difference between the two is no rounding of an operation: the kernel forms 1 - b
     # in fp32 from the fp32 b (exactly), optim.adam and the oracle round the double 1 - b.  The two weights differ by the rounding of
@@ -736,13 +736,13 @@ def test_optimiser_kernels_past_the_wrap(cg):
         dstep = U24 * (1 + t * b1 ** t / (1 - b1 ** t) + 0.5 * t * b2 ** t / (1 - b2 ** t))
         rounding_close(host(pt), po, np.abs(p0.astype(f64)) + step * tm / den, 2 * 14, f"adam p, t = {t}",
                        slack=step * (dm + tm * 0.5 * dv / np.maximum(tv, 1e-300) + tm * dstep) / den)
-        # the replay-safe form reads t from device memory and derives the same step (ops.hip:1501-1504): the same bits
+        # the replay-safe form reads t from device memory and derives the same step (adam_k's `t_dev` branch): the same bits
         p2, g2, m2, v2 = dev(p0), dev(g), dev(m0), dev(v0)
         td = torch.tensor([t], dtype=torch.int64, device="cuda")
         L.adam_step_dev(st, p2.data_ptr(), g2.data_ptr(), m2.data_ptr(), v2.data_ptr(), n, lr, b1, b2, eps, td.data_ptr(), 0.0, 0.0, 0.0, 0)
         for a, b, what in ((p2, pt, "p"), (m2, mt, "m"), (v2, vt, "v")):
             bits_equal(host(a), host(b), f"adam_step_dev {what}, t = {t}")
-    # sgd_k (ops.hip:1534-1535): 1 - dampening, two products, sum, lr product, difference: 6, + 2; without momentum 2, + 2; the same
+    # sgd_k: 1 - dampening, two products, sum, lr product, difference: 6, + 2; without momentum 2, + 2; the same
     # slack for 1 - dampening
     for mom in (0.0, 0.9):
         po, st_o = p0.copy(), ({"v": m0.copy()} if mom else {})
@@ -754,7 +754,7 @@ def test_optimiser_kernels_past_the_wrap(cg):
         rounding_close(host(pt), po, np.abs(p0.astype(f64)) + 0.02 * d, 2 * (8 if mom else 4), f"sgd p, momentum {mom}", slack=0.02 * dd)
         if mom:
             rounding_close(host(vt), st_o["v"], d, 2 * 6, "sgd v", slack=dd)
-    # adagrad_k (ops.hip:1544-1546): var 2, halved by the root 1, root, + 1e-10, lr product, quotient, difference: 6, + 2
+    # adagrad_k: var 2, halved by the root 1, root, + 1e-10, lr product, quotient, difference: 6, + 2
     po, st_o = p0.copy(), {"var": v0.copy()}
     O.adagrad(po, g, st_o, lr=1e-3)
     pt, gt, vt = dev(p0), dev(g), dev(v0)
