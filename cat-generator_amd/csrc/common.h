@@ -421,5 +421,15 @@ __device__ __forceinline__ float bn_norm(float x, float m, float s, float g, flo
 __device__ __forceinline__ float bn_dx(float x, float dy, float g, float m, float s, float m1, float m2) {
     return g * s * (dy - m1 - bn_xhat(x, m, s) * m2);
 }
+// tf.warp(order 1, mode="nearest") as the augmentation kernels (ops.hip) and the face extraction (faces.hip) restate it in fp32:
+// one axis of the warp's source position: clamped to [0, L-1] (NaN -> 0), split into the two taps and the fraction
+__device__ __forceinline__ void warp_taps(float s, int L, int* i0, int* i1, float* f) {
+#pragma clang fp contract(off)
+    const float hi = (float)(L - 1);
+    s = !(s >= 0.f) ? 0.f : (s > hi ? hi : s);
+    *i0 = (int)s;
+    *f = s - (float)*i0;
+    *i1 = min(*i0 + 1, L - 1);
+}
 
 }  // namespace cg

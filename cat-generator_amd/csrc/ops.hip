@@ -397,15 +397,7 @@ __device__ __forceinline__ float augment_noise(uint64_t seed, uint64_t ctr) {
     }
     return (float)((int)S - 393210) * (1.0f / 65536.0f);   // |S - 393210| < 2^24 and a power of two: both steps exact
 }
-// one axis of the warp's source position: clamped to [0, L-1] (NaN -> 0), split into the two taps and the fraction
-__device__ __forceinline__ void warp_taps(float s, int L, int* i0, int* i1, float* f) {
-#pragma clang fp contract(off)
-    const float hi = (float)(L - 1);
-    s = !(s >= 0.f) ? 0.f : (s > hi ? hi : s);
-    *i0 = (int)s;
-    *f = s - (float)*i0;
-    *i1 = min(*i0 + 1, L - 1);
-}
+using cg::warp_taps;
 // image n of the pool (this workgroup's) from the one source image `im`: both augmentation kernels' whole arithmetic.  n, not the
 // image's place in its set, numbers the noise counters
 __device__ __forceinline__ void augment_image(const unsigned char* __restrict__ im, long n, float* __restrict__ dst, int Hs, int Ws, int Hd, int Wd,

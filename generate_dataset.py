@@ -1,0 +1,175 @@
+#!/usr/bin/env python
+"""Build the face set from the raw 10k-cats download (dataset/generate_dataset.py of the reference): every x.jpg of --path's CAT_*
+folders that has its x.jpg.cat keypoints becomes the S x S face NNNNNN_000.jpg in <out>/out_unaug_SxS and <out>/out_aug_SxS - eye line
+levelled, face rectangle of method 4, Pillow's bilinear resize, Pillow's default JPEG settings; cat-generator_amd/faces.py holds the
+semantics.  The pixel work runs on the device (cg_faces_u8_extract); --host runs its numpy restatement instead, which writes the same
+bytes and needs neither a GPU nor the library.
+
+Files are taken in sorted order (folder by folder, then by name; the reference's os.listdir order is unspecified).  An image is skipped
+with one warning line - and consumes no index - when it has no .cat file, its .cat line has fewer than nine points, both eyes are on one
+pixel, or its rectangle is degenerate (no rectangle the reference would accept, or a side under 8 pixels).  Two runs over the same input
+write byte-identical files.
+
+out_aug_SxS also gets --augmentations variants NNNNNN_001 ... per face.  They are the project's own augmentation
+(dataset.augment_descriptors and cg_images_u8_augment_to_f32 at equal source and target size, colour space rgb, re-quantised by
+(u8)(v 255 + 0.5), draws seeded by --seed) and differ from the reference's nine in that they are warped from the finished S x S face with
+edge replication, not from the padded full-resolution crop.  The recommended use is --augmentations 0 together with the trainers'
+--augment, which draws fresh variants for every epoch pool.
+
+    python generate_dataset.py --path /data/10k_cats --augmentations 0 --pack
+"""
+import argparse
+import glob
+import importlib
+import os
+import sys
+from collections import deque
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+BATCH_BYTES = 256 << 20      # decoded source bytes per device call: batches are bounded by bytes, the images differ in size
+MAX_THREADS = 16
+LOOKAHEAD = 64               # files being decoded, or decoded and waiting for their batch
+MIN_SIDE = 8                 # cg_faces_u8_extract's smallest rectangle side
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(description="Normalise (and augment) the 10k cats dataset.")
+    ap.add_argument("--path", required=True, help="the directory that holds the CAT_* folders")
+    ap.add_argument("--out", default="dataset", help="where out_unaug_SxS and out_aug_SxS are written")
+    ap.add_argument("--scale", type=int, default=64, help="S, the side of the faces")
+    ap.add_argument("--augmentations", type=int, default=9, help="variants per face in out_aug_SxS, beside _000")
+    ap.add_argument("--threads", type=int, default=8, help="decoding threads (at most 16); the files do not depend on their number")
+    ap.add_argument("--seed", type=int, default=42, help="seed of the variants' draws")
+    ap.add_argument("--host", action="store_true", help="compute the faces with the numpy restatement: no GPU, no library")
+    ap.add_argument("--pack", action="store_true", help="finish with dataset.buildPack on out_aug_SxS (pack_dataset.py)")
+    o = ap.parse_args(argv)
+    if o.threads < 1 or not 8 <= o.scale <= 128 or not 0 <= o.augmentations <= 999:
+        ap.error("--threads must be positive, --scale in 8..128, --augmentations in 0..999")
+    return o
+
+
+def list_raw(path):
+    """The .jpg files of path's CAT_* folders: folder by folder, then by name."""
+    files = []
+    for d in sorted(glob.glob(os.path.join(path, "CAT_*"))):
+        if os.path.isdir(d):
+            files += sorted(os.path.join(d, f) for f in os.listdir(d) if f.endswith(".jpg") and os.path.isfile(os.path.join(d, f)))
+    return files
+
+
+def _load(fp):
+    """One raw file -> (fp, decoded image, geometry) or (fp, None, why it is skipped).  Runs on the decoding threads."""
+    F = importlib.import_module("cat-generator_amd.faces")
+    ds = importlib.import_module("cat-generator_amd.dataset")
+    if not os.path.isfile(fp + ".cat"):
+        return fp, None, "it has no .cat file"
+    img = ds._decode(fp)
+    with open(fp + ".cat") as f:
+        kp = F.parse_cat(f.read(), img.shape[0], img.shape[1])
+    if kp is None:
+        return fp, None, "its .cat line has fewer than nine points"
+    g = F.face_geometry(kp, img.shape[0], img.shape[1])
+    if not isinstance(g, str) and min(g["rect"][2:]) < MIN_SIDE:
+        g = "its face rectangle is degenerate"
+    return (fp, None, g) if isinstance(g, str) else (fp, img, g)
+
+
+def _loaded(ex, files):
+    """_load over the files, in their order whatever the threads do, with a bounded look-ahead: decoded sources wait here, never the
+    whole set."""
+    ahead = deque()
+    for fp in files:
+        ahead.append(ex.submit(_load, fp))
+        if len(ahead) >= LOOKAHEAD:
+            yield ahead.popleft().result()
+    while ahead:
+        yield ahead.popleft().result()
+
+
+def _variants(face, index, n, noise_seed, host):
+    """The n augmented variants of one finished face, uint8 [n, S, S, 3]; `index` numbers the face among the accepted ones and with it
+    the noise counters, so the variants do not depend on how the faces were batched."""
+    ds = importlib.import_module("cat-generator_amd.dataset")
+    S = face.shape[0]
+    draw = ds.augment_draw(n)
+    desc = ds.augment_descriptors(n, S, S, draw)
+    u8 = np.ascontiguousarray(np.broadcast_to(face, (n, S, S, 3)))
+    if host:
+        v = ds.augment_images(u8, desc, draw["noise_std"], noise_seed, 0, index0=index * n).transpose(0, 2, 3, 1)
+    else:
+        import torch
+        cg = importlib.import_module("cat-generator_amd")
+        src, dsc = torch.from_numpy(u8).to(cg.tensor.device()), torch.from_numpy(desc).to(cg.tensor.device())
+        dst = torch.empty((n, S, S, 3), dtype=torch.float32, device=cg.tensor.device())
+        cg.lib().images_u8_augment_to_f32(cg.tensor.stream(), src.data_ptr(), dst.data_ptr(), n, S, S, S, S, 0, dsc.data_ptr(),
+                                          draw["noise_std"], noise_seed, 3 * index * n * S * S * 3)
+        v = dst.cpu().numpy()
+    return (v * np.float32(255.0) + np.float32(0.5)).astype(np.int32).astype(np.uint8)
+
+
+def main(argv=None):
+    o = parse(argv)
+    from PIL import Image
+    F = importlib.import_module("cat-generator_amd.faces")
+    ds = importlib.import_module("cat-generator_amd.dataset")
+    S, A = o.scale, o.augmentations
+    if A and S * S * 12 > ds.AUG_LDS_BYTES:
+        raise SystemExit(f"generate_dataset: variants of {S} x {S} faces do not fit the augmentation kernel's LDS; use --augmentations 0")
+    files = list_raw(o.path)
+    if not files:
+        raise SystemExit(f"generate_dataset: no CAT_*/*.jpg under {o.path}")
+    unaug, aug = (os.path.join(o.out, f"out_{k}_{S}x{S}") for k in ("unaug", "aug"))
+    os.makedirs(unaug, exist_ok=True)
+    os.makedirs(aug, exist_ok=True)
+    ds.seed(o.seed)
+    ds.setAugmentation(True)
+    noise_seed = int(ds.augment_draw(1)["seed"])
+    written = skipped = 0
+
+    def flush(batch):
+        nonlocal written
+        if not batch:
+            return
+        imgs, geoms = [b[1] for b in batch], [b[2] for b in batch]
+        if o.host:
+            faces = np.stack([F.resize_np(F.warp_rect_np(im, g["inv"], g["rect"]), S) for im, g in zip(imgs, geoms)])
+        else:
+            faces = F.extract_faces_device(imgs, geoms, S)
+        for face in faces:
+            name = "{:0>6}_{:0>3}.jpg".format(written, 0)
+            Image.fromarray(face).save(os.path.join(unaug, name))
+            Image.fromarray(face).save(os.path.join(aug, name))
+            if A:
+                for a, v in enumerate(_variants(face, written, A, noise_seed, o.host)):
+                    Image.fromarray(v).save(os.path.join(aug, "{:0>6}_{:0>3}.jpg".format(written, a + 1)))
+            written += 1
+
+    batch, nbytes = [], 0
+    with ThreadPoolExecutor(max_workers=min(o.threads, MAX_THREADS)) as ex:
+        for fp, img, g in _loaded(ex, files):
+            if img is None:
+                print(f"<dataset> warning: {fp} skipped: {g}")
+                skipped += 1
+                continue
+            if batch and nbytes + img.nbytes > BATCH_BYTES:
+                flush(batch)
+                batch, nbytes = [], 0
+            batch.append((fp, img, g))
+            nbytes += img.nbytes
+        flush(batch)
+    ds.setAugmentation(False)
+    print(f"<dataset> {written} faces of {S}x{S} ({skipped} images skipped) -> {unaug}, {aug} (+{A} variants each)")
+    if o.pack:
+        ds.setFileExtension("jpg")
+        path, M = ds.buildPack(aug, o.threads)
+        print(f"<dataset> {M} images -> {path}")
+    return written, skipped
+
+
+if __name__ == "__main__":
+    main()

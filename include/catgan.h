@@ -145,6 +145,37 @@ int cg_images_u8_gather_scale_to_f32(void* stream, const unsigned char* set, lon
                                      int Hd, int Wd, int colorspace);
 int cg_images_u8_gather_augment_to_f32(void* stream, const unsigned char* set, long M, const int32_t* idx, float* dst, int N, int Hs, int Ws,
                                        int Hd, int Wd, int colorspace, const float* desc, float noise_std, uint64_t seed, uint64_t offset);
+/* The reference's offline dataset tool for its un-augmented variant (dataset/generate_dataset.py:53-91: remove_rotation,
+ * dataset/dataset.py:152-181; extract_face with method-4's rectangle, :191-239, 602-676, whose 30 px padding unpad(30) takes off again;
+ * resize, :127-139): N faces, each cut out of its own decoded source image (8-bit RGB, [Hs][Ws][3], sizes differ per face) and
+ * resampled to out x out, 8-bit RGB, dst [N][out][out][3].  The host decides everything that is not pixel work (the keypoints, the eye
+ * angle, the rectangle, the tap tables: faces.py); the device does, per face f and per pixel (y, x) of the rectangle
+ * [y0, y0 + Hr) x [x0, x0 + Wr) ONLY - the warp is pointwise, so this equals warping the whole image and cropping:
+ *   warp (tf.warp(image, F^-1, mode="nearest"), order 1, dataset.py:173, then np.array(w * 255, dtype=np.uint8), :174)
+ *     p = u8 / 255; sx = (m00 x + m01 y) + m02, sy = (m10 x + m11 y) + m12 with (m00 .. m12) = inv[f][0..5], the first two rows of the
+ *     INVERSE map in fp32 (no trigonometry runs on the device), clamped to [0, Ws-1] x [0, Hs-1] (edge replication, NaN -> 0);
+ *     x0 = (int)sx, fx = sx - x0, x1 = min(x0 + 1, Ws-1), likewise y; top = (1-fx) p[y0][x0] + fx p[y0][x1], bot likewise on y1,
+ *     w = (1-fy) top + fy bot; q = (u8)(w * 255), truncated.  Every operation is a single correctly rounded fp32 one in the order
+ *     written - cg_images_u8_augment_to_f32's warp;
+ *   resize (misc.imresize(face, (out, out)) = Pillow's Image.resize(BILINEAR) on 8-bit data, in integers): the horizontal pass into 8 bits,
+ *     then the vertical pass, each  clip8((2^21 + sum_i pixel[lo + i] k[i]) >> 22)  in int32 over the sample's `count` taps.
+ * Arrays, all in device memory:
+ *   src      the decoded sources back to back, src_bytes bytes; src_off [N] = the byte offset of face f's source (faces may share one);
+ *   geom     [N][8] int32: Hs Ws y0 x0 Hr Wr kx ky, with ksize k = 2 ceil(max(side / out, 1)) + 1 per axis;
+ *   inv      [N][6] float;
+ *   taps     ntaps int32: tables of one axis, each  [out][2] (lo, count)  followed by  [out][k] taps  (int(0.5 + w 2^22) of the
+ *            normalised triangle weights, computed on the host in double: faces.resize_taps); tap_off [N][2] = where face f's
+ *            horizontal and vertical tables start, in int32 elements (faces of one side may share a table);
+ *   workspace  at least 16 N + 48 + 3 out sum_f Hr bytes: the band map of the first kernel and the horizontal pass' result, the only
+ *            thing that goes to memory between the passes.
+ * The descriptors are read back and checked on the host before anything is launched - this entry point synchronises the stream and
+ * cannot be captured into a graph; the two kernels are then enqueued on it.  Errors: a null pointer; N outside 1..2^20; out outside
+ * 8..128; Hs or Ws outside 8..8192; a rectangle side outside 8..4096; a rectangle not inside its source; a source not inside src; a
+ * ksize that disagrees with the side; a table not inside taps, or a sample whose taps leave the side or exceed ksize; a workspace too
+ * small.  dst is untouched on error. */
+int cg_faces_u8_extract(void* stream, const unsigned char* src, size_t src_bytes, const uint64_t* src_off, const int32_t* geom,
+                        const float* inv, const int32_t* taps, size_t ntaps, const uint64_t* tap_off, unsigned char* dst, int N, int out,
+                        void* workspace, size_t workspace_bytes);
 /* NN_UTILS.rgbToColorSpace / NN_UTILS.toRgb (utils/nn_utils.lua:188-249) on fp32 NHWC pixels that are already on the device: three
  * floats in per pixel, three out (one for to == 1).  from / to are the colorspace codes above; the pairs are rgb -> y | yuv | hsl and
  * yuv | hsl -> rgb, anything else is an error.  src == dst is allowed when three planes come out.  Per pixel, every operation a single
