@@ -66,7 +66,7 @@ long opt(Opt o);
 // cg_set_option resets them): the launches of wino_dgrad_fused_kernel (winograd.hip) and of wino3_fused_k (wino3.hip), so that a test can
 // tell that the fused path ran and not its fallback.
 // CG_PACK_WIDE: 1 = the weight re-packing after every parameter update runs in its wide launches (pack_weight_ups2_wide_kernel and
-// pack_weight_batch_wide_kernel in gemm.hip, the both-operand Winograd filter transforms in winograd.hip), 0 = the kernels they replace.
+// pack_weight_batch_wide_kernel in pack.hip, the both-operand Winograd filter transforms in winograd.hip), 0 = the kernels they replace.
 // The bytes written are the same.
 void opt_count(Opt o);
 
@@ -90,6 +90,38 @@ void* col_scratch(hipStream_t stream);   // nullptr + cg::fail() on error
 // queue class c": class 0 = the caller's own queue, 1..3 = the other three, numbered in the order the probe meets them.
 hipStream_t queue_stream(hipStream_t ref, int cls, int slot);   // nullptr + cg::fail() on error
 int queue_class(hipStream_t ref, hipStream_t s);                // class of a pool stream (or of ref itself: 0); -1 unknown
+
+// ---- what gemm.hip, wgrad_finish.hip and pack.hip share ----------------------------------------------------------------------------
+constexpr int MAXG = 4;  // groups per launch: same geometry, separate tensors (D32_st3's identical branches)
+constexpr int kMaxStridedGroups = 36;   // ... or up to 36 equally spaced ones (cg_conv2d_wgrad_strided: 16 planes of F(2x2,3x3), 4 x 9 of F(2x2,2x2))
+template <typename T>
+__device__ __forceinline__ T sel4(int i, T a, T b, T c, T d) { return i == 0 ? a : (i == 1 ? b : (i == 2 ? c : d)); }
+__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ float f4c(const float4& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
+// the four-pointer fields of the kernel arguments (x0 .. x3 and their like: scalars, no arrays - runtime indexing would go to scratch)
+// from an array of n <= MAXG group pointers
+template <typename T>
+static inline void set4(T& p0, T& p1, T& p2, T& p3, const T* src, int n) {
+    T* const dst[MAXG] = {&p0, &p1, &p2, &p3};
+    for (int i = 0; i < MAXG; ++i) *dst[i] = (src && i < n) ? src[i] : nullptr;
+}
+// upsample(2) -> conv k x k as four phase convolutions on the low-res input: canonical tap d of a k-tap kernel (pad p) seen from output
+// phase a -> index of the low-res tap it folds into; kp = low-res taps per dimension
+__device__ __host__ __forceinline__ int phase_map(int a, int d, int pad) { return ((a + d - pad) >> 1) - ((a - pad) >> 1); }
+static inline int phase_kp(int k, int pad) { return phase_map(0, k - 1, pad) + 1; }
+
+// The finish of a weight gradient (csrc/wgrad_finish.hip): what a weight-gradient launch left in its workspace and where it goes.
+struct WgradParts {
+    const float* part;        // [S][ngroups][P][taps * Cin][Cout]: P = 4 phases of kp x kp taps behind an upsampling, else 1 of kH x kW
+    const float* bias_part;   // [S][ngroups][P][Cout] column sums of dy, or null: no bias gradient
+    float* const* gw;         // canonical [Cout][Cin][kH][kW] per group, accumulated into
+    float* const* gb;         // [Cout] per group; null, or null entries, where there is none
+    long gws;                 // != 0: equally spaced groups, group g accumulates into gw[0] + g * gws
+    int ngroups, S, Cin, Cout, kH, kW, pad, ups;
+    float scale;
+};
+// defer: a small finish is queued on the stream for cg_conv2d_wgrad_flush, which runs all queued ones in one launch
+int wgrad_finish(hipStream_t st, const WgradParts& w, bool defer);
 // Drop every weight-gradient reduction still queued by cg_conv2d_wgrad_*_deferred (any stream): a pass that failed half way must not
 // leave partial sums behind for the next flush to add to a gradient.
 void wgrad_discard_all();
@@ -157,7 +189,7 @@ __device__ __forceinline__ int tile_of_row(int l) {
 // Transformed filters of the fused Winograd 3x3 kernel (wino3.hip) for filter pair idx = co * 64 + ci of a 64 -> 64 plane layer:
 // U[pos][ci / 4][co][4] = (G g G^T)[xi][nu], pos = xi * 4 + nu; uf: the forward's g = w[co][ci][:][:], ub: the data gradient's (planes
 // swapped, taps flipped) g[a][b] = w[ci][co][2 - a][2 - b].  One body for wino3_pack_k and for the batch pack's own workgroups
-// (pack_weight_batch_wide_kernel, gemm.hip), so that both write the same bits.
+// (pack_weight_batch_wide_kernel, pack.hip), so that both write the same bits.
 __device__ __forceinline__ void wino3_pack_item(const float* __restrict__ w, float* uf, float* ub, int idx) {
     constexpr int C = 64;
     const int co = idx / C, ci = idx % C;

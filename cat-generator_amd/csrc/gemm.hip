@@ -5,16 +5,16 @@
 // cudnn.SpatialConvolution (models.lua:206,212,218,222), nn.SpatialConvolution
 // (models.lua:646-685,844-846) and nn.Linear (models.lua:199,697,700,850,853):
 //   igemm_nn : updateOutput and updateGradInput  (Y[m][n] = sum_k A(m,k) W[k][n])
-//   igemm_tn : accGradParameters                 (dW[k][n] = sum_m A(m,k) dY[m][n])
+//   igemm_tn : accGradParameters                 (dW[k][n] = sum_m A(m,k) dY[m][n], as split partial sums: wgrad_finish.hip reduces them)
 // A(m,k) is never materialised: m -> grid pixel (n,oy,ox), k -> (tap,ci), gathered from the NHWC tensor.
 //
 // nn.SpatialUpSamplingNearest(2) -> conv (models.lua:205-206,211-212,217-218) is executed as FOUR PHASE
 // CONVOLUTIONS on the low-resolution input: output pixel (2i+a, 2j+b) only ever sees ceil((k+1)/2)^2 distinct
 // low-res taps, so the k x k weights are pre-summed per phase (a,b) into k' x k' kernels (k'=2 for k=3, 3 for
 // k=5): 2.25x / 2.78x fewer MACs than convolving the materialised upsampled map, identical up to fp32
-// re-association of the weight sums.  The data gradient w.r.t. the low-res input (upsampling's 2x2 block sum
+// re-association of the weight sums (the packs: pack.hip).  The data gradient w.r.t. the low-res input (upsampling's 2x2 block sum
 // folded in) is ONE GEMM over the 4 phases' taps; the weight gradient is taken per phase and mapped back onto
-// the canonical taps by the reduce kernel.
+// the canonical taps by the finish (wgrad_finish.hip).
 //
 // fp32 MFMA issues at exactly the fp32 VALU rate, so every VALU instruction in the main loop costs MFMA
 // throughput (measured: 4.9 VALU per MFMA = 73 % pipe utilisation).  The FAST path therefore keeps the gather
@@ -32,14 +32,21 @@
 // What the two staging families of a GEMM have in common is written once: the blockIdx.z decode and operand selection (nn_tile / tn_tile),
 // the NN epilogue (nn_epilogue: bias, activation, statistics, the lean and the generic stores), the TN partial store (tn_store_partials) and
 // the host's packing of the four-pointer argument fields (set4).  The skinny 3x3 layers (<= 3 output planes) have their kernels, MFMA and
-// VALU, in skinny.hip; this file only decides which of them runs (cg::skinny_ok, CG_SKINNY).
+// VALU, in skinny.hip; this file only decides which of them runs (cg::skinny_ok, CG_SKINNY).  What follows a weight-gradient launch - the
+// reduction of its partials into the canonical gradients, now or deferred - is cg::wgrad_finish (wgrad_finish.hip); the re-packing of the
+// canonical weights into this file's operands is pack.hip.
 #include "common.h"
 #include <stdlib.h>
 #include <algorithm>
-#include <mutex>
 #include <type_traits>
-#include <unordered_map>
-#include <vector>
+
+using cg::f4c;
+using cg::kMaxStridedGroups;
+using cg::ld4;
+using cg::MAXG;
+using cg::phase_kp;
+using cg::sel4;
+using cg::set4;
 
 namespace {
 
@@ -95,9 +102,6 @@ struct Geom {
     int pmn, pm_lg;
 };
 
-constexpr int MAXG = 4;  // groups per launch: same geometry, separate tensors (D32_st3's identical branches)
-constexpr int kMaxStridedGroups = 36;   // ... or up to 36 equally spaced ones (cg_conv2d_wgrad_strided: 16 planes of F(2x2,3x3), 4 x 9 of F(2x2,2x2))
-
 struct NNArgs {
     const float* x0; const float* x1; const float* x2; const float* x3;   // per group (no arrays: see TapDesc)
     const float* w0; const float* w1; const float* w2; const float* w3;   // [nphase][Ktot][Cout]
@@ -134,8 +138,6 @@ struct TNArgs {
                         // Winograd-domain weight-gradient GEMMs of winograd.hip in one launch), x1.. / d1.. unused
 };
 
-template <typename T>
-__device__ __forceinline__ T sel4(int i, T a, T b, T c, T d) { return i == 0 ? a : (i == 1 ? b : (i == 2 ? c : d)); }
 
 // blockIdx.z = group * nphase + phase of every GEMM launch, phase bits (pa, pb); with the operands of that group (w: this phase's kernel)
 struct ZTile { int group, phase, pa, pb; };
@@ -157,8 +159,6 @@ __device__ __forceinline__ TNTile tn_tile(const TNArgs& a, int zz) {
             a.dgs ? a.d0 + (long)z.group * a.dgs : sel4(z.group, a.d0, a.d1, a.d2, a.d3)};
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float f4c(const float4& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // NOTE: cast the WHOLE vector.  Extracting the four dwords one by one (bit_cast(float, v.x) ...) makes LLVM's
@@ -1496,648 +1496,6 @@ __global__ __launch_bounds__(256, 2) void igemm_tng_kernel(TNArgs a, int mode) {
     tn_store_partials<MI, NI>(acc, pout, g, m0, n0, wm0, wn0, l31, h);
 }
 
-// canonical tap d of a k-tap kernel (pad p) seen from output phase a -> index of the low-res tap it folds into
-__device__ __host__ __forceinline__ int phase_map(int a, int d, int pad) { return ((a + d - pad) >> 1) - ((a - pad) >> 1); }
-
-// Split-K reduce + transpose into Torch7's canonical layout, accumulate semantics:
-//   plain: gw[co][ci][tap] += scale * sum_s part[s][tap*Cin+ci][co]
-//   UPS  : gw[co][ci][dy][dx] += scale * sum_s sum_{a,b} part[s][2a+b][(map(a,dy)*kp + map(b,dx))*Cin + ci][co]
-// One workgroup owns CI_T input channels x 32 output channels x all taps: reads are coalesced along co, the sums
-// are transposed through LDS, writes are contiguous runs of CI_T*KK floats per co.
-template <bool UPS>
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* part, float* gw, int Cin, int Cout, int k, int KK,
-                                                           int pad, int kp, int S, float scale, int CI_T, long sstride) {
-    extern __shared__ float sh[];  // [CI_T][KK][33]
-    const int ci0 = blockIdx.x * CI_T, co0 = blockIdx.y * 32;
-    const long plane = (long)(UPS ? kp * kp : KK) * Cin * Cout;
-    const int n1 = KK * CI_T * 32;
-    if (UPS && k == 3 && kp == 2 && pad == 1 && co0 + 32 <= Cout && ci0 + CI_T <= Cin && (CI_T & 31) == 0 && (Cout & 3) == 0 && ((uintptr_t)part & 15) == 0 &&
-        (sstride & 3) == 0) {
-        // 3x3 behind an upsampling, full block, 16-byte loads (round 5): a thread owns four output channels of one input channel and
-        // reads each of the 16 (phase, low-res tap) partial elements of a split ONCE (the scalar form below re-reads them per canonical
-        // tap: 36 loads for 16 values), adding them to the nine canonical taps in the same order - split by split, phase by phase.
-        const int c4 = threadIdx.x & 7;
-        for (int ci_l = threadIdx.x >> 3; ci_l < CI_T; ci_l += 32) {
-            float4 acc[9];
-#pragma unroll
-            for (int t = 0; t < 9; ++t) acc[t] = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float* base = part + (long)(ci0 + ci_l) * Cout + co0 + 4 * c4;
-            for (int sp = 0; sp < S; ++sp) {
-                float4 v[4][4];
-#pragma unroll
-                for (int p = 0; p < 4; ++p)
-#pragma unroll
-                    for (int tp = 0; tp < 4; ++tp) v[p][tp] = ld4(base + (long)sp * sstride + (long)p * plane + (long)tp * Cin * Cout);
-#pragma unroll
-                for (int t = 0; t < 9; ++t) {
-                    const int dy = t / 3, dx = t - 3 * (t / 3);
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const float4 q = v[p][phase_map(p >> 1, dy, 1) * 2 + phase_map(p & 1, dx, 1)];
-                        acc[t].x += q.x; acc[t].y += q.y; acc[t].z += q.z; acc[t].w += q.w;
-                    }
-                }
-            }
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                float* d = sh + (ci_l * KK + t) * 33 + 4 * c4;
-                d[0] = acc[t].x; d[1] = acc[t].y; d[2] = acc[t].z; d[3] = acc[t].w;
-            }
-        }
-    } else
-    for (int idx = threadIdx.x; idx < n1; idx += 256) {
-        const int co_l = idx & 31;
-        const int r = idx >> 5;
-        const int ci_l = r % CI_T, tap = r / CI_T;
-        const int ci = ci0 + ci_l, co = co0 + co_l;
-        float s = 0.f;
-        if (ci < Cin && co < Cout) {
-            if (UPS) {
-                const int dy = tap / k, dx = tap - dy * k;
-                for (int sp = 0; sp < S; ++sp)
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const int tp = phase_map(p >> 1, dy, pad) * kp + phase_map(p & 1, dx, pad);
-                        s += part[(long)sp * sstride + (long)p * plane + ((long)tp * Cin + ci) * Cout + co];
-                    }
-            } else {
-                const long o = ((long)tap * Cin + ci) * Cout + co;
-                for (int sp = 0; sp < S; ++sp) s += part[(long)sp * sstride + o];
-            }
-        }
-        sh[(ci_l * KK + tap) * 33 + co_l] = s;   // row = position in the output run: the transposed read below walks rows with stride 33 (odd: conflict-free)
-    }
-    __syncthreads();
-    const int run = CI_T * KK;
-    for (int idx = threadIdx.x; idx < n1; idx += 256) {
-        const int j = idx % run, co_l = idx / run;
-        const int ci_l = j / KK, tap = j - ci_l * KK;
-        const int ci = ci0 + ci_l, co = co0 + co_l;
-        if (ci < Cin && co < Cout) {
-            float* dst = gw + ((long)co * Cin + ci) * KK + tap;
-            *dst += scale * sh[j * 33 + co_l];
-        }
-    }
-}
-
-// Same reduction for small weight tensors (where the tiled form above would not fill the chip), all groups of a
-// grouped launch and their bias gradients in ONE launch: grid (weight blocks + bias blocks, ngroups); a workgroup
-// owns 32 consecutive partial elements (or 32 bias channels) and splits the S partials over 8 lanes.
-struct RedPtrs { float* gw0; float* gw1; float* gw2; float* gw3; float* gb0; float* gb1; float* gb2; float* gb3;
-                 long gws; };   // gws != 0: group g accumulates into gw0 + g * gws (strided groups, no bias gradients)
-
-template <bool UPS>
-__device__ __forceinline__ void wgrad_reduce_small_body(float (*sh)[33], int bx, int group, const float* part, const float* bias_part,
-                                                        const RedPtrs& rp, int Cin, int Cout, int k, int KK, int pad, int kp, int S,
-                                                        int P, float scale, long sstride, long gstride, long bsstride, int wblocks) {
-    const int ol = threadIdx.x & 31, ln = threadIdx.x >> 5;
-    float s = 0.f;
-    if (bx < wblocks) {
-        const long total = (long)KK * Cin * Cout;
-        const long plane = (long)(UPS ? kp * kp : KK) * Cin * Cout;
-        const long i = bx * 32L + ol;
-        const float* pg = part + (long)group * gstride;
-        int co = 0, ci = 0, tap = 0;
-        if (i < total) {
-            co = (int)(i % Cout);
-            const long r = i / Cout;
-            ci = (int)(r % Cin);
-            tap = (int)(r / Cin);
-            if (UPS) {
-                const int dy = tap / k, dx = tap - dy * k;
-                for (int sp = ln; sp < S; sp += 8)
-#pragma unroll
-                    for (int p = 0; p < 4; ++p) {
-                        const int tp = phase_map(p >> 1, dy, pad) * kp + phase_map(p & 1, dx, pad);
-                        s += pg[(long)sp * sstride + (long)p * plane + ((long)tp * Cin + ci) * Cout + co];
-                    }
-            } else {
-#pragma unroll 4
-                for (int sp = ln; sp < S; sp += 8) s += pg[(long)sp * sstride + i];
-            }
-        }
-        sh[ln][ol] = s;
-        __syncthreads();
-        if (ln == 0 && i < total) {
-            float t = 0.f;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) t += sh[r][ol];
-            float* gw = rp.gws ? rp.gw0 + (long)group * rp.gws : sel4(group, rp.gw0, rp.gw1, rp.gw2, rp.gw3);
-            gw[((long)co * Cin + ci) * KK + tap] += scale * t;
-        }
-    } else {
-        float* gb = sel4(group, rp.gb0, rp.gb1, rp.gb2, rp.gb3);
-        if (!gb) return;
-        const int c = (bx - wblocks) * 32 + ol;
-        const float* bp = bias_part + (long)group * P * Cout;
-        if (c < Cout)
-            for (int i = ln; i < S * P; i += 8) s += bp[(long)(i / P) * bsstride + (long)(i % P) * Cout + c];
-        sh[ln][ol] = s;
-        __syncthreads();
-        if (ln == 0 && c < Cout) {
-            float t = 0.f;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) t += sh[r][ol];
-            gb[c] += scale * t;
-        }
-    }
-}
-
-// The plain (not phase-folded) weight blocks with 16-byte loads (round 5): a workgroup owns 128 consecutive partial elements - lane ol
-// the float4 at bx * 128 + 4 ol, the S partial planes split over the 8 lane groups as above, four planes in flight per thread - and
-// 128 threads add the eight lane sums in the same order and scatter them to the canonical layout.  Same bits as the 32-element form
-// (per element: lane group ln adds planes ln, ln + 8, ..., then groups 0..7 in order); a quarter of the workgroups and load instructions.
-__device__ __forceinline__ void wgrad_reduce_small_body_v4(float* shf, int bx, int group, const float* part, const RedPtrs& rp, int Cin,
-                                                           int Cout, int KK, int S, float scale, long sstride, long gstride) {
-    float4* sh4 = reinterpret_cast<float4*>(shf);     // [8][32]
-    const int ol = threadIdx.x & 31, ln = threadIdx.x >> 5;
-    const long total = (long)KK * Cin * Cout;
-    const long i = bx * 128L + 4 * ol;
-    const float* pg = part + (long)group * gstride + i;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (i < total) {
-        int sp = ln;
-        for (; sp + 24 < S; sp += 32) {
-            const float4 p0 = ld4(pg + (long)sp * sstride), p1 = ld4(pg + (long)(sp + 8) * sstride);
-            const float4 p2 = ld4(pg + (long)(sp + 16) * sstride), p3 = ld4(pg + (long)(sp + 24) * sstride);
-            s.x += p0.x; s.y += p0.y; s.z += p0.z; s.w += p0.w;
-            s.x += p1.x; s.y += p1.y; s.z += p1.z; s.w += p1.w;
-            s.x += p2.x; s.y += p2.y; s.z += p2.z; s.w += p2.w;
-            s.x += p3.x; s.y += p3.y; s.z += p3.z; s.w += p3.w;
-        }
-        for (; sp < S; sp += 8) {
-            const float4 p0 = ld4(pg + (long)sp * sstride);
-            s.x += p0.x; s.y += p0.y; s.z += p0.z; s.w += p0.w;
-        }
-    }
-    sh4[ln * 32 + ol] = s;
-    __syncthreads();
-    if (ln < 4 && i < total) {
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) t += f4c(sh4[r * 32 + ol], ln);
-        const long e = i + ln;                      // element (tap, ci, co) of the partial plane
-        const int co = (int)(e % Cout);
-        const long rr = e / Cout;
-        const int ci = (int)(rr % Cin), tap = (int)(rr / Cin);
-        float* gw = rp.gws ? rp.gw0 + (long)group * rp.gws : sel4(group, rp.gw0, rp.gw1, rp.gw2, rp.gw3);
-        gw[((long)co * Cin + ci) * KK + tap] += scale * t;
-    }
-}
-
-template <bool UPS>
-__global__ __launch_bounds__(256) void wgrad_reduce_small_kernel(const float* part, const float* bias_part, RedPtrs rp, int Cin,
-                                                                 int Cout, int k, int KK, int pad, int kp, int S, int P,
-                                                                 float scale, long sstride, long gstride, long bsstride,
-                                                                 int wblocks, int nblocks, int v4) {
-    __shared__ __attribute__((aligned(16))) float sh[32][33];
-    // blockIdx.x walks the group's wblocks + bblocks blocks with stride gridDim.x (= all of them for short launches)
-    for (int bx = (int)blockIdx.x; bx < nblocks; bx += (int)gridDim.x) {
-        if (!UPS && v4 && bx < wblocks)
-            wgrad_reduce_small_body_v4(&sh[0][0], bx, (int)blockIdx.y, part, rp, Cin, Cout, KK, S, scale, sstride, gstride);
-        else
-            wgrad_reduce_small_body<UPS>(sh, bx, (int)blockIdx.y, part, bias_part, rp, Cin, Cout, k, KK, pad, kp, S, P, scale,
-                                         sstride, gstride, bsstride, wblocks);
-        __syncthreads();
-    }
-}
-
-// KK == 1 (linear layers, the Winograd-domain products of winograd.hip): canonical gw[co][ci] += scale * sum_s part[s][ci][co] is a
-// TRANSPOSE of the partial planes.  The generic kernels above give a workgroup 32 consecutive partial elements and scatter them to
-// addresses Cin floats apart: 65 536 workgroups of 1 KB for the 16 Winograd products - 69 us alone, 295 us beside the data-gradient
-// chain (profiles/r04_eager_breakdown.txt).  Here: 32 x 32 tiles through LDS, 128-byte rows both ways, splits added in order.
-__device__ __forceinline__ void wgrad_reduce_t_tile(float (*t)[33], const float* __restrict__ pg, float* __restrict__ gw, int ci0, int co0,
-                                                    int Cin, int Cout, int S, long sstride, float scale) {
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    if ((Cout & 3) == 0 && (sstride & 3) == 0 && ((uintptr_t)pg & 15) == 0) {
-        // 16-byte loads (round 5): thread = (row r = tid / 8, four columns), the S planes in order, four in flight
-        const int r = threadIdx.x >> 3, c4 = threadIdx.x & 7;
-        const float* src = pg + (long)(ci0 + r) * Cout + co0 + 4 * c4;
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        int sp = 0;
-        for (; sp + 4 <= S; sp += 4) {
-            const float4 p0 = ld4(src + (long)sp * sstride), p1 = ld4(src + (long)(sp + 1) * sstride);
-            const float4 p2 = ld4(src + (long)(sp + 2) * sstride), p3 = ld4(src + (long)(sp + 3) * sstride);
-            s.x += p0.x; s.y += p0.y; s.z += p0.z; s.w += p0.w;
-            s.x += p1.x; s.y += p1.y; s.z += p1.z; s.w += p1.w;
-            s.x += p2.x; s.y += p2.y; s.z += p2.z; s.w += p2.w;
-            s.x += p3.x; s.y += p3.y; s.z += p3.z; s.w += p3.w;
-        }
-        for (; sp < S; ++sp) {
-            const float4 p0 = ld4(src + (long)sp * sstride);
-            s.x += p0.x; s.y += p0.y; s.z += p0.z; s.w += p0.w;
-        }
-        t[r][4 * c4] = s.x; t[r][4 * c4 + 1] = s.y; t[r][4 * c4 + 2] = s.z; t[r][4 * c4 + 3] = s.w;
-    } else
-#pragma unroll
-    for (int r = ty; r < 32; r += 8) {
-        const long off = (long)(ci0 + r) * Cout + co0 + tx;
-        float s = 0.f;
-        for (int sp = 0; sp < S; ++sp) s += pg[(long)sp * sstride + off];      // fixed order
-        t[r][tx] = s;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = ty; r < 32; r += 8) gw[(long)(co0 + r) * Cin + ci0 + tx] += scale * t[tx][r];
-}
-__global__ __launch_bounds__(256) void wgrad_reduce_t_kernel(const float* __restrict__ part, float* __restrict__ gw0, long gws, int Cin,
-                                                             int Cout, int S, long sstride, long gstride, float scale) {
-    __shared__ float t[32][33];
-    const int group = blockIdx.z;
-    wgrad_reduce_t_tile(t, part + (long)group * gstride, gw0 + (long)group * gws, blockIdx.x * 32, blockIdx.y * 32, Cin, Cout, S, sstride, scale);
-}
-
-// The same reduction for SEVERAL layers in one launch (cg_conv2d_wgrad_flush): the deferred form of cg_conv2d_wgrad* runs only
-// its GEMM and queues one RedJob; a dozen ~10 us reductions, each a short dependent chain, then overlap instead of queueing
-// up behind one another.  Workgroup b belongs to the job whose [block0, block0 + ngroups * (wblocks + bblocks)) holds b.
-struct RedJob {
-    const float* part; const float* bias_part;
-    RedPtrs rp;
-    long sstride, gstride, bsstride;
-    int Cin, Cout, k, KK, pad, kp, S, P, ups, wblocks, bblocks, block0;
-    float scale;
-    int tr;      // KK == 1, planes multiples of 32: the weight blocks are 32 x 32 transpose tiles (wgrad_reduce_t_tile), not 32-element runs
-    int v4;      // plain layout, Cout % 4 == 0, 16-byte aligned planes: the weight blocks are 128-element runs (wgrad_reduce_small_body_v4)
-};
-constexpr int kRedJobs = 20;
-struct RedJobTable { RedJob j[kRedJobs]; int n; };
-
-// A workgroup walks blocks b, b + gridDim.x, ... of the `total` 32-element blocks (round 4: the launch used to have one workgroup per
-// block - 31 000 of them for D's flush, each waiting for a slot of its own beside the GEMMs of the other queues; see ew_grid)
-__global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(RedJobTable t, int total) {
-    __shared__ __attribute__((aligned(16))) float sh[32][33];
-    for (int b = (int)blockIdx.x; b < total; b += (int)gridDim.x) {
-        int ji = 0;
-        for (int q = 1; q < t.n; ++q)
-            if (b >= t.j[q].block0) ji = q;
-        const RedJob& J = t.j[ji];
-        const int per = J.wblocks + J.bblocks;
-        const int group = (b - J.block0) / per, bx = (b - J.block0) - group * per;
-        if (J.tr && bx < J.wblocks) {
-            const int nci = J.Cin / 32;
-            float* gw = J.rp.gws ? J.rp.gw0 + (long)group * J.rp.gws : sel4(group, J.rp.gw0, J.rp.gw1, J.rp.gw2, J.rp.gw3);
-            wgrad_reduce_t_tile(sh, J.part + (long)group * J.gstride, gw, (bx % nci) * 32, (bx / nci) * 32, J.Cin, J.Cout, J.S, J.sstride, J.scale);
-        } else if (J.v4 && bx < J.wblocks)
-            wgrad_reduce_small_body_v4(&sh[0][0], bx, group, J.part, J.rp, J.Cin, J.Cout, J.KK, J.S, J.scale, J.sstride, J.gstride);
-        else if (J.ups)
-            wgrad_reduce_small_body<true>(sh, bx, group, J.part, J.bias_part, J.rp, J.Cin, J.Cout, J.k, J.KK, J.pad, J.kp, J.S, J.P, J.scale,
-                                          J.sstride, J.gstride, J.bsstride, J.wblocks);
-        else
-            wgrad_reduce_small_body<false>(sh, bx, group, J.part, J.bias_part, J.rp, J.Cin, J.Cout, J.k, J.KK, J.pad, J.kp, J.S, J.P, J.scale,
-                                           J.sstride, J.gstride, J.bsstride, J.wblocks);
-        __syncthreads();   // the block's sums have been read out of `sh` before the next block overwrites them
-    }
-}
-
-// gb[c] += scale * sum_{s,p} bias_part[s*P+p][c]; 32 channels x 8 partial-sum lanes per workgroup
-// (S splits x P phases of one group; consecutive splits are `sstride` floats apart)
-__global__ __launch_bounds__(256) void bias_part_reduce_kernel(const float* bp, float* gb, int S, int P, long sstride,
-                                                               int Cout, float scale) {
-    __shared__ float sh[8][33];
-    const int cl = threadIdx.x & 31, ln = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cl;
-    float s = 0.f;
-    if (c < Cout)
-        for (int i = ln; i < S * P; i += 8) s += bp[(long)(i / P) * sstride + (long)(i % P) * Cout + c];
-    sh[ln][cl] = s;
-    __syncthreads();
-    if (ln == 0 && c < Cout) {
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) t += sh[r][cl];
-        gb[c] += scale * t;
-    }
-}
-
-// canonical [Cout][Cin][KK] -> wf[tap*Cin+ci][Cout], wb[(KK-1-tap)*Cout+co][Cin]
-// (the parameters change every step, so this runs every step).  One workgroup owns a 32 ci x 32 co block: thread
-// (ci_l, co_l + 8j) reads its canonical tap run, writes wb directly (ci-fastest, coalesced) and transposes the
-// 32x32 plane of each tap through LDS for wf (co-fastest).
-// wb_map != 0: wb receives the row-permuted canonical matrix wbT[co][tap*Cin + ci] instead of the flipped-tap data-gradient
-// operand - the backward operand of a LINEAR layer that consumes an NHWC map directly (its canonical [out][C*H*W] weight is
-// the canonical weight of a k = H x W convolution on that map; see cg_pack_conv_weight_map).
-__global__ __launch_bounds__(256) void pack_weight_kernel(const float* w, float* wf, float* wb, int Cout, int Cin, int KK,
-                                                          int wb_map) {
-    __shared__ float sh[32][33];
-    const int lo = threadIdx.x & 31, hi = threadIdx.x >> 5;
-    const int ci0 = blockIdx.x * 32, co0 = blockIdx.y * 32;
-    {
-        const int tap = blockIdx.z;  // one tap plane per workgroup: KK independent workgroups instead of KK serial rounds
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ci = ci0 + lo, co_l = hi + 8 * j, co = co0 + co_l;
-            float v = 0.f;
-            if (ci < Cin && co < Cout) {
-                v = w[((long)co * Cin + ci) * KK + tap];
-                if (wb) wb[wb_map ? ((long)co * KK + tap) * Cin + ci : ((long)(KK - 1 - tap) * Cout + co) * Cin + ci] = v;
-            }
-            sh[lo][co_l] = v;
-        }
-        if (wf) {
-            __syncthreads();
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int co = co0 + lo, ci_l = hi + 8 * j, ci = ci0 + ci_l;
-                if (ci < Cin && co < Cout) wf[((long)tap * Cin + ci) * Cout + co] = sh[ci_l][lo];
-            }
-        }
-    }
-}
-
-// The same for up to kPackBatch layers in ONE launch (all of D32_st3's 28 convolution / linear layers re-pack after every
-// Adam step: 28 launches of a few microseconds each otherwise).  A workgroup finds its layer by its block index.
-constexpr int kPackBatch = 48;
-struct PackBatch {
-    const float* w[kPackBatch]; float* wf[kPackBatch]; float* wb[kPackBatch];
-    int Cout[kPackBatch], Cin[kPackBatch], KK[kPackBatch], first[kPackBatch + 1];
-    unsigned long long map_mask;   // bit e: layer e wants the wbT layout (see pack_weight_kernel)
-    int n;
-};
-// one tap plane of a 32 ci x 32 co block (pack_weight_kernel's body), for the two batch kernels
-__device__ __forceinline__ void pack_block_tap(float (&sh)[32][33], const float* w, float* wf, float* wb, int Cout, int Cin, int KK,
-                                               bool wb_map, int ci0, int co0, int tap) {
-    const int lo = threadIdx.x & 31, hi = threadIdx.x >> 5;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int ci = ci0 + lo, co_l = hi + 8 * j, co = co0 + co_l;
-        float v = 0.f;
-        if (ci < Cin && co < Cout) {
-            v = w[((long)co * Cin + ci) * KK + tap];
-            if (wb) wb[wb_map ? ((long)co * KK + tap) * Cin + ci : ((long)(KK - 1 - tap) * Cout + co) * Cin + ci] = v;
-        }
-        sh[lo][co_l] = v;
-    }
-    if (wf) {
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int co = co0 + lo, ci_l = hi + 8 * j, ci = ci0 + ci_l;
-            if (ci < Cin && co < Cout) wf[((long)tap * Cin + ci) * Cout + co] = sh[ci_l][lo];
-        }
-    }
-}
-__global__ __launch_bounds__(256) void pack_weight_batch_kernel(PackBatch b) {
-    __shared__ float sh[32][33];
-    int e = 0;
-    while (e + 1 < b.n && (int)blockIdx.x >= b.first[e + 1]) ++e;
-    const int Cout = b.Cout[e], Cin = b.Cin[e], KK = b.KK[e];
-    const int nbx = (Cin + 31) / 32, nby = (Cout + 31) / 32;
-    int r = (int)blockIdx.x - b.first[e];
-    const int bx = r % nbx; r /= nbx;
-    const int by = r % nby;
-    pack_block_tap(sh, b.w[e], b.wf[e], b.wb[e], Cout, Cin, KK, (b.map_mask >> e) & 1ull, bx * 32, by * 32, r / nby);
-}
-
-// The wide form of the batch pack (CG_PACK_WIDE, the default).  The kernel above reads w[co][ci][tap] with a lane stride of KK floats
-// and once per tap: KK workgroups fetch the same lines for 4 bytes of each 32-byte sector (View -> Linear(20480, 256) as an 8 x 8 kernel:
-// 64 times; a linear or 1 x 1 layer has none of this and keeps that body).  Here a workgroup owns a 32 ci x 32 co block and a CHUNK of
-// up to kPackTc taps (all of a 3 x 3 kernel, 7 of the 49 of a 7 x 7, 8 of the map's 64): every (co, ci) contributes one contiguous run
-// of the chunk's taps, read once into LDS, and wb (ci-fastest) and wf (co-fastest) are both stored in whole 128-byte rows from there
-// (row strides 9 and 289 words: no bank conflicts either way).
-// The transformed filters of the 64 -> 64 3x3 layers (wino3.hip), which the separate wino3_pack_k launch wrote behind the operands,
-// are computed by further workgroups of this launch from the same canonical weights (blocks from wino_first on, 16 per layer).
-constexpr int kPackTc = 9, kPackRow = 32 * kPackTc + 1;
-struct PackBatchWide {
-    PackBatch b;                    // first[] counts this kernel's blocks: cdiv(Cin, 32) * cdiv(Cout, 32) * chunks per layer
-    unsigned long long wino_mask;   // bit e: layer e also gets the fused-Winograd filters behind wf / wb
-    int wino_first;                 // first of the workgroups that compute those
-};
-__host__ __device__ static inline int pack_chunks(int KK) { return (KK + (KK <= kPackTc ? kPackTc : 8) - 1) / (KK <= kPackTc ? kPackTc : 8); }
-__global__ __launch_bounds__(256) void pack_weight_batch_wide_kernel(PackBatchWide a) {
-    __shared__ float sh[32 * kPackRow];
-    const PackBatch& b = a.b;
-    if ((int)blockIdx.x >= a.wino_first) {
-        const int r = (int)blockIdx.x - a.wino_first;
-        int e = 0;
-        for (int job = r / 16; e < b.n; ++e)
-            if (((a.wino_mask >> e) & 1ull) && job-- == 0) break;
-        if (e < b.n)
-            cg::wino3_pack_item(b.w[e], b.wf[e] ? b.wf[e] + cg::kWino3UOffset : nullptr, b.wb[e] ? b.wb[e] + cg::kWino3UOffset : nullptr,
-                                (r % 16) * 256 + (int)threadIdx.x);
-        return;
-    }
-    int e = 0;
-    while (e + 1 < b.n && (int)blockIdx.x >= b.first[e + 1]) ++e;
-    const float* w = b.w[e]; float* wf = b.wf[e]; float* wb = b.wb[e];
-    const int Cout = b.Cout[e], Cin = b.Cin[e], KK = b.KK[e];
-    const bool wb_map = (b.map_mask >> e) & 1ull;
-    const int nbx = (Cin + 31) / 32, nby = (Cout + 31) / 32, nch = pack_chunks(KK);
-    const int tc = (KK + nch - 1) / nch;                 // taps per chunk (the last chunk may hold fewer)
-    int r = (int)blockIdx.x - b.first[e];
-    const int bx = r % nbx; r /= nbx;
-    const int by = r % nby;
-    const int tap0 = (r / nby) * tc, nt = min(tc, KK - tap0);
-    const int ci0 = bx * 32, co0 = by * 32;
-    if (KK == 1) {      // linear / 1 x 1 layers: the canonical rows are read coalesced as they are, nothing to stage
-        pack_block_tap(*reinterpret_cast<float (*)[32][33]>(sh), w, wf, wb, Cout, Cin, 1, wb_map, ci0, co0, 0);
-        return;
-    }
-    // stage: wave v takes the block's rows co_l = v, v + 4, ...; a row is 32 runs of nt floats, KK floats apart
-    {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        constexpr int SLOTS = (32 * kPackTc + 63) / 64;
-        int goff[SLOTS], loff[SLOTS];
-#pragma unroll
-        for (int s = 0; s < SLOTS; ++s) {
-            const int el = lane + 64 * s, ci_l = el / nt, tt = el - ci_l * nt;
-            const bool ok = ci_l < 32 && ci0 + ci_l < Cin;
-            goff[s] = ok ? ci_l * KK + tt : -1;
-            loff[s] = ci_l * kPackTc + tt;
-        }
-#pragma unroll 2
-        for (int co_l = wave; co_l < 32 && co0 + co_l < Cout; co_l += 4) {
-            const float* src = w + ((long)(co0 + co_l) * Cin + ci0) * KK + tap0;
-            float v[SLOTS];      // every slot loads (an idle one the row's first float), so that the loads are issued together
-#pragma unroll
-            for (int s = 0; s < SLOTS; ++s) v[s] = src[max(goff[s], 0)];
-#pragma unroll
-            for (int s = 0; s < SLOTS; ++s)
-                if (goff[s] >= 0) sh[co_l * kPackRow + loff[s]] = v[s];
-        }
-    }
-    __syncthreads();
-    const int lo = threadIdx.x & 31, hi = threadIdx.x >> 5;
-    if (wb && ci0 + lo < Cin) {
-        const int ci = ci0 + lo;
-        for (int tt = 0; tt < nt; ++tt) {
-            const int tap = tap0 + tt;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int co_l = hi + 8 * j, co = co0 + co_l;
-                if (co < Cout)
-                    wb[wb_map ? ((long)co * KK + tap) * Cin + ci : ((long)(KK - 1 - tap) * Cout + co) * Cin + ci] = sh[co_l * kPackRow + lo * kPackTc + tt];
-            }
-        }
-    }
-    if (wf && co0 + lo < Cout) {
-        const int co = co0 + lo;
-        for (int tt = 0; tt < nt; ++tt) {
-            const int tap = tap0 + tt;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int ci_l = hi + 8 * j, ci = ci0 + ci_l;
-                if (ci < Cin) wf[((long)tap * Cin + ci) * Cout + co] = sh[lo * kPackRow + ci_l * kPackTc + tt];
-            }
-        }
-    }
-}
-
-// phase-summed weights, k in {3, 5} (the generator's layers): same 32x32 blocking as pack_weight_kernel, the tap
-// sums fully unrolled so every accumulator index is a compile-time constant.
-template <int K>
-__global__ __launch_bounds__(256) void pack_weight_ups2_fast_kernel(const float* w, float* wf, float* wb, int Cout, int Cin) {
-    constexpr int KK = K * K, PAD = (K - 1) / 2, KPD = K == 3 ? 2 : 3, KP = KPD * KPD;
-    __shared__ float sh[KP][32][33];
-    const int lo = threadIdx.x & 31, hi = threadIdx.x >> 5;
-    const int ci0 = blockIdx.x * 32, co0 = blockIdx.y * 32;
-    float v[4][KK];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int ci = ci0 + lo, co = co0 + hi + 8 * j;
-        const bool ok = ci < Cin && co < Cout;
-        const float* src = w + ((long)co * Cin + ci) * KK;
-#pragma unroll
-        for (int t = 0; t < KK; ++t) v[j][t] = ok ? src[t] : 0.f;
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float acc[KP];
-#pragma unroll
-            for (int t = 0; t < KP; ++t) acc[t] = 0.f;
-#pragma unroll
-            for (int dy = 0; dy < K; ++dy)
-#pragma unroll
-                for (int dx = 0; dx < K; ++dx)
-                    acc[phase_map(p >> 1, dy, PAD) * KPD + phase_map(p & 1, dx, PAD)] += v[j][dy * K + dx];
-            const int ci = ci0 + lo, co_l = hi + 8 * j, co = co0 + co_l;
-#pragma unroll
-            for (int t = 0; t < KP; ++t) {
-                if (wb && ci < Cin && co < Cout) wb[(((long)p * KP + t) * Cout + co) * Cin + ci] = acc[t];
-                sh[t][lo][co_l] = acc[t];
-            }
-        }
-        if (wf) {
-            __syncthreads();
-#pragma unroll
-            for (int t = 0; t < KP; ++t)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int co = co0 + lo, ci_l = hi + 8 * j, ci = ci0 + ci_l;
-                    if (ci < Cin && co < Cout) wf[(((long)p * KP + t) * Cin + ci) * Cout + co] = sh[t][ci_l][lo];
-                }
-            __syncthreads();
-        }
-    }
-}
-
-// The wide form of the same (CG_PACK_WIDE, the default): one workgroup owns ONE phase of a 32 ci x kPackWideCo co block, so the
-// launch has 4 * 32 / kPackWideCo times the workgroups of the kernel above (G32up's 256 -> 128 5x5 layer: 256 instead of 32, its
-// 512 -> 256 3x3 layer: 1024 instead of 128) and no thread walks the four phases in turn.  The canonical taps of a co row of the
-// block are 32 * K * K contiguous floats: they are read coalesced into LDS, and every thread then takes its own K * K taps from there
-// (lane stride K * K words, odd: no bank conflicts).  Each phase tap is the sum of the same source taps, added from 0.f in the same
-// (dy, dx) order as above, so the bits are those of the kernel above; wb is stored ci-fastest straight from the registers, wf
-// co-fastest through an LDS transpose that reuses the staging area.
-constexpr int kPackWideCo = 16;
-template <int K, int P>
-__device__ __forceinline__ void pack_ups2_wide_phase(float* sh, float* wf, float* wb, int Cout, int Cin, int ci0, int co0) {
-    constexpr int KK = K * K, PAD = (K - 1) / 2, KPD = K == 3 ? 2 : 3, KP = KPD * KPD, RUN = 32 * KK, J = kPackWideCo / 8;
-    const int lo = threadIdx.x & 31, hi = threadIdx.x >> 5;
-    const int ci = ci0 + lo;
-    float acc[J][KP];
-#pragma unroll
-    for (int j = 0; j < J; ++j) {
-        const float* src = sh + (hi + 8 * j) * RUN + lo * KK;
-        float v[KK];
-#pragma unroll
-        for (int t = 0; t < KK; ++t) v[t] = src[t];
-#pragma unroll
-        for (int t = 0; t < KP; ++t) acc[j][t] = 0.f;
-#pragma unroll
-        for (int dy = 0; dy < K; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < K; ++dx) acc[j][phase_map(P >> 1, dy, PAD) * KPD + phase_map(P & 1, dx, PAD)] += v[dy * K + dx];
-        const int co = co0 + hi + 8 * j;
-        if (wb && ci < Cin && co < Cout) {
-#pragma unroll
-            for (int t = 0; t < KP; ++t) wb[(((long)P * KP + t) * Cout + co) * Cin + ci] = acc[j][t];
-        }
-    }
-    if (wf) {
-        constexpr int LD = kPackWideCo + 1;
-        __syncthreads();      // every thread has its taps in registers: the staging area becomes the [KP][32][LD] transpose buffer
-#pragma unroll
-        for (int j = 0; j < J; ++j)
-#pragma unroll
-            for (int t = 0; t < KP; ++t) sh[(t * 32 + lo) * LD + hi + 8 * j] = acc[j][t];
-        __syncthreads();
-        const int co_l = threadIdx.x % kPackWideCo, co = co0 + co_l;
-#pragma unroll
-        for (int t = 0; t < KP; ++t)
-            for (int ci_l = threadIdx.x / kPackWideCo; ci_l < 32; ci_l += 256 / kPackWideCo)
-                if (ci0 + ci_l < Cin && co < Cout) wf[(((long)P * KP + t) * Cin + ci0 + ci_l) * Cout + co] = sh[(t * 32 + ci_l) * LD + co_l];
-    }
-}
-template <int K>
-__global__ __launch_bounds__(256) void pack_weight_ups2_wide_kernel(const float* w, float* wf, float* wb, int Cout, int Cin) {
-    constexpr int KK = K * K, RUN = 32 * KK;
-    static_assert(kPackWideCo % 8 == 0 && 256 % kPackWideCo == 0 && (K == 3 ? 4 : 9) * 32 * (kPackWideCo + 1) <= kPackWideCo * RUN,
-                  "the transpose buffer lies inside the staging area");
-    __shared__ float sh[kPackWideCo * RUN];
-    const int ci0 = blockIdx.x * 32, co0 = (blockIdx.y / 4) * kPackWideCo, p = blockIdx.y & 3;
-    const int run = min(32, Cin - ci0) * KK;      // floats of a co row that belong to this block
-    for (int idx = threadIdx.x; idx < kPackWideCo * RUN; idx += 256) {
-        const int co_l = idx / RUN, j = idx - co_l * RUN;
-        sh[idx] = co0 + co_l < Cout && j < run ? w[((long)(co0 + co_l) * Cin + ci0) * KK + j] : 0.f;
-    }
-    __syncthreads();
-    switch (p) {      // the phase as a template argument: every accumulator index is a compile-time constant
-        case 0: pack_ups2_wide_phase<K, 0>(sh, wf, wb, Cout, Cin, ci0, co0); break;
-        case 1: pack_ups2_wide_phase<K, 1>(sh, wf, wb, Cout, Cin, ci0, co0); break;
-        case 2: pack_ups2_wide_phase<K, 2>(sh, wf, wb, Cout, Cin, ci0, co0); break;
-        default: pack_ups2_wide_phase<K, 3>(sh, wf, wb, Cout, Cin, ci0, co0); break;
-    }
-}
-
-// phase-summed weights for upsample(2) -> conv k x k:
-//   wf[p][(t'*Cin+ci)][co] = sum_{(dy,dx) -> t' under phase p} w[co][ci][dy][dx]
-//   wb[((p*kp*kp + t')*Cout + co)][ci] = the same value (data-gradient operand)
-// Same LDS staging as pack_weight_kernel.
-__global__ __launch_bounds__(256) void pack_weight_ups2_kernel(const float* w, float* wf, float* wb, int Cout, int Cin, int k,
-                                                               int pad, int kp, int CI_T) {
-    extern __shared__ float sh[];  // [32][CI_T*KK + 1]
-    const int KK = k * k, KP = kp * kp;
-    const int run = CI_T * KK, ld = run + 1;
-    const int ci0 = blockIdx.x * CI_T, co0 = blockIdx.y * 32;
-    const int cis = min(CI_T, Cin - ci0);
-    for (int idx = threadIdx.x; idx < 32 * run; idx += 256) {
-        const int j = idx % run, co_l = idx / run;
-        if (co0 + co_l < Cout && j < cis * KK) sh[co_l * ld + j] = w[((long)(co0 + co_l) * Cin + ci0) * KK + j];
-    }
-    __syncthreads();
-    const int n = 4 * KP * CI_T * 32;
-    for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 0 ? wf == nullptr : wb == nullptr) continue;
-        for (int idx = threadIdx.x; idx < n; idx += 256) {
-            int co_l, ci_l, q;
-            if (pass == 0) { co_l = idx & 31; const int r = idx >> 5; ci_l = r % CI_T; q = r / CI_T; }
-            else { ci_l = idx % CI_T; const int r = idx / CI_T; co_l = r & 31; q = r >> 5; }
-            if (co0 + co_l >= Cout || ci_l >= cis) continue;
-            const int tp = q % KP, p = q / KP;
-            const int ry = tp / kp, rx = tp - ry * kp;
-            const float* src = sh + co_l * ld + ci_l * KK;
-            float s = 0.f;
-            for (int dy = 0; dy < k; ++dy) {
-                if (phase_map(p >> 1, dy, pad) != ry) continue;
-                for (int dx = 0; dx < k; ++dx)
-                    if (phase_map(p & 1, dx, pad) == rx) s += src[dy * k + dx];
-            }
-            if (pass == 0) wf[(((long)p * KP + tp) * Cin + ci0 + ci_l) * Cout + co0 + co_l] = s;
-            else wb[(((long)p * KP + tp) * Cout + co0 + co_l) * Cin + ci0 + ci_l] = s;
-        }
-    }
-}
 
 // ---- host-side dispatch -----------------------------------------------------
 struct TileCfg { int bm, bn; };
@@ -2320,8 +1678,6 @@ static int geom_plain(Geom& g, int N, int Hp, int Wp, int Cin, int Cout, int kH,
     return finish_geom(g, N);
 }
 
-static int phase_kp(int k, int pad) { return phase_map(0, k - 1, pad) + 1; }
-
 // upsample(2) -> conv, forward / weight-gradient view: 4 phases over the low-res grid
 static int geom_phase_fwd(Geom& g, int N, int Hp, int Wp, int Cin, int Cout, int k, int pad) {
     memset(&g, 0, sizeof(g));
@@ -2447,14 +1803,6 @@ static long pad_skip_valid(const Geom& g, const TileCfg& tc) {
                 valid += (unsigned)(oy + ty) < (unsigned)g.Hv && (unsigned)(ox + tx) < (unsigned)g.Wv;
             }
     return (long)hw * g.ntaps * (100 - thr) >= valid * 100 ? valid : 0;
-}
-
-// the four-pointer fields of the kernel arguments (x0 .. x3 and their like: scalars, see TapDesc) from an array of n <= MAXG group pointers
-// (or none at all); the fields past n stay null
-template <typename T>
-static void set4(T& p0, T& p1, T& p2, T& p3, const T* src, int n) {
-    T* const dst[MAXG] = {&p0, &p1, &p2, &p3};
-    for (int i = 0; i < MAXG; ++i) *dst[i] = (src && i < n) ? src[i] : nullptr;
 }
 
 static int run_nn(hipStream_t st, const Geom& g, int ngroups, const float* const* x, const float* const* w,
@@ -2658,35 +2006,6 @@ size_t cg_conv2d_wgrad_workspace_bytes(int N, int Hp, int Wp, int Cin, int Cout,
 }
 
 namespace {
-// reductions queued by the deferred entry points, per stream (one host thread per stream, but several streams may queue)
-std::mutex g_red_mu;
-std::unordered_map<hipStream_t, std::vector<RedJob>> g_red_queue;
-
-// Workgroups of a partial-sum reduction launch: one per 32-element block.  Unlike the grid-stride element-wise kernels (cg::ew_grid)
-// these do NOT gain from fewer, longer-lived workgroups (round 4, same box: 6.32 / 6.38 / 6.40 ms per step at 0 / 8 / 32 per CU): a
-// block is a short dependent chain (strided partial loads -> LDS -> one add), so walking blocks serialises latency.
-long red_cap() { return 0x7fffffffL; }
-
-int small_reduce(hipStream_t st, bool defer, const RedJob& job, int ngroups) {
-    if (defer) {
-        std::lock_guard<std::mutex> lk(g_red_mu);
-        g_red_queue[st].push_back(job);
-        g_red_queue[st].back().block0 = ngroups;   // the group count rides here until the flush lays the blocks out
-        return 0;
-    }
-    const int nblocks = job.wblocks + job.bblocks;
-    const long cap = std::max<long>(1, red_cap() / std::max(1, ngroups));   // workgroups per group
-    dim3 sgrid((unsigned)std::min<long>(nblocks, cap), ngroups);
-    if (job.ups)
-        hipLaunchKernelGGL(wgrad_reduce_small_kernel<true>, sgrid, dim3(256), 0, st, job.part, job.bias_part, job.rp, job.Cin, job.Cout,
-                           job.k, job.KK, job.pad, job.kp, job.S, job.P, job.scale, job.sstride, job.gstride, job.bsstride, job.wblocks, nblocks, 0);
-    else
-        hipLaunchKernelGGL(wgrad_reduce_small_kernel<false>, sgrid, dim3(256), 0, st, job.part, job.bias_part, job.rp, job.Cin, job.Cout,
-                           job.k, job.KK, job.pad, job.kp, job.S, job.P, job.scale, job.sstride, job.gstride, job.bsstride, job.wblocks, nblocks, job.v4);
-    CG_LAUNCH_CHECK();
-    return 0;
-}
-
 int wgrad_impl(void* stream, int ngroups, const float* const* x, const float* const* dy, float* const* gw, float* const* gb, int N,
                int Hp, int Wp, int Cin, int Cout, int kH, int kW, int padH, int padW, int ups, float scale, void* ws, size_t ws_bytes,
                bool defer, long xgs = 0, long dgs = 0, long gws = 0, bool gemm_only = false);
@@ -2728,42 +2047,23 @@ int cg_conv2d_wgrad_gemm(void* stream, const float* x, const float* dy, int N, i
     return wgrad_impl(stream, 1, &x, &dy, &gw, nullptr, N, Hp, Wp, Cin, Cout, kH, kW, padH, padW, ups, 1.f, ws, ws_bytes, false, 0, 0, 0, true);
 }
 
-int cg_conv2d_wgrad_pending(void* stream, int* njobs) {
-    CG_REQUIRE(njobs, "cg_conv2d_wgrad_pending: null pointer");
-    std::lock_guard<std::mutex> lk(g_red_mu);
-    auto it = g_red_queue.find(cg::S(stream));
-    *njobs = it == g_red_queue.end() ? 0 : (int)it->second.size();
-    return 0;
-}
-
-int cg_conv2d_wgrad_flush(void* stream) {
-    hipStream_t st = cg::S(stream);
-    std::vector<RedJob> jobs;
-    {
-        std::lock_guard<std::mutex> lk(g_red_mu);
-        auto it = g_red_queue.find(st);
-        if (it == g_red_queue.end() || it->second.empty()) return 0;
-        jobs.swap(it->second);
-    }
-    for (size_t j0 = 0; j0 < jobs.size(); j0 += kRedJobs) {
-        RedJobTable t;
-        memset(&t, 0, sizeof(t));
-        t.n = (int)std::min<size_t>(kRedJobs, jobs.size() - j0);
-        int blocks = 0;
-        for (int q = 0; q < t.n; ++q) {
-            t.j[q] = jobs[j0 + q];
-            const int ngroups = t.j[q].block0;
-            t.j[q].block0 = blocks;
-            blocks += ngroups * (t.j[q].wblocks + t.j[q].bblocks);
-        }
-        const int wgs = (int)std::min<long>(blocks, red_cap());
-        hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3(wgs), dim3(256), 0, st, t, blocks);
-        CG_LAUNCH_CHECK();
-    }
-    return 0;
-}
-
 namespace {
+// the compiled block tiles of the two staging families (tng: LDS-direct loads)
+void launch_tn_tile(const TNArgs& a, const TileCfg& tc, bool tng, dim3 grid, hipStream_t st, bool veca, bool vecb) {
+    if (tng) {
+        if (tc.bm == 128 && tc.bn == 128) launch_tng<128, 128, 2, 2>(a, grid, st);
+        else if (tc.bm == 64 && tc.bn == 128) launch_tng<64, 128, 2, 2>(a, grid, st);
+        else if (tc.bm == 128 && tc.bn == 64) launch_tng<128, 64, 2, 2>(a, grid, st);
+        else if (tc.bm == 64 && tc.bn == 64) launch_tng<64, 64, 2, 2>(a, grid, st);
+        else launch_tng<128, 32, 4, 1>(a, grid, st);
+    }
+    else if (tc.bm == 128 && tc.bn == 128) launch_tn<128, 128, 2, 2>(a, grid, st, veca, vecb);
+    else if (tc.bm == 64 && tc.bn == 128) launch_tn<64, 128, 2, 2>(a, grid, st, veca, vecb);
+    else if (tc.bm == 128 && tc.bn == 64) launch_tn<128, 64, 2, 2>(a, grid, st, veca, vecb);
+    else if (tc.bm == 64 && tc.bn == 64) launch_tn<64, 64, 2, 2>(a, grid, st, veca, vecb);
+    else launch_tn<128, 32, 4, 1>(a, grid, st, veca, vecb);
+}
+
 int wgrad_impl(void* stream, int ngroups, const float* const* x, const float* const* dy, float* const* gw, float* const* gb, int N,
                int Hp, int Wp, int Cin, int Cout, int kH, int kW, int padH, int padW, int ups, float scale, void* ws, size_t ws_bytes,
                bool defer, long xgs, long dgs, long gws_, bool gemm_only) {
@@ -2775,6 +2075,7 @@ int wgrad_impl(void* stream, int ngroups, const float* const* x, const float* co
     memset(&a, 0, sizeof(a));
     if (conv_geom(a.g, N, Hp, Wp, Cin, Cout, kH, kW, padH, padW, ups)) return 1;
     const Geom& g = a.g;
+    // 1. the shortcuts: a skinny layer's own kernels (their partial planes finish like the GEMM's), the head's one-kernel gradient
     if (!strided && cg::skinny_ok(ngroups, Cin, Cout, kH, kW, padH, padW, ups) && x[0] && dy[0] && gw[0] && (uintptr_t)x[0] % 16 == 0 && ws &&
         ws_bytes >= cg::skinny_wgrad_ws_bytes(Cin, Cout) && (long)N * Hp * Wp < 0x7fffffffL) {
         hipStream_t st = cg::S(stream);
@@ -2791,20 +2092,15 @@ int wgrad_impl(void* stream, int ngroups, const float* const* x, const float* co
         }
         else cg::skinny_valu_wgrad(st, x[0], dy[0], part, gb0 ? bpart : nullptr, N, Hp, Wp, Cin, Cout, blocks, ppb);
         CG_LAUNCH_CHECK();
-        RedJob job;
-        memset(&job, 0, sizeof(job));
-        job.part = part; job.bias_part = bpart;
-        job.rp.gw0 = gw[0]; job.rp.gb0 = gb0;
-        job.Cin = Cin; job.Cout = Cout; job.k = 3; job.KK = 9; job.pad = 1; job.S = blocks; job.P = 1; job.scale = scale;
-        job.sstride = 9L * Cin * Cout; job.gstride = 0; job.bsstride = Cout;
-        job.wblocks = cg::cdiv(9L * Cin * Cout, 32); job.bblocks = gb0 ? cg::cdiv(Cout, 32) : 0;
-        return small_reduce(st, defer, job, 1);
+        const cg::WgradParts parts{part, gb0 ? bpart : nullptr, gw, gb, 0, 1, blocks, Cin, Cout, 3, 3, 1, 0, scale};
+        return cg::wgrad_finish(st, parts, defer);
     }
     // nn.View -> nn.Linear (an H x W kernel on the H x W map, 1 x 1 grid): one kernel straight into gradWeight (headwg.hip)
     if (!strided && !gemm_only && ngroups == 1 && !ups && kH == Hp && kW == Wp && padH == 0 && padW == 0 && cg::opt(cg::OPT_PAD_SKIP) > 0 &&
         cg::opt(cg::OPT_TN_GLDS) && cg::head_wgrad_ok(N, kH * kW, Cin, Cout) && x[0] && dy[0] && gw[0] && (uintptr_t)x[0] % 16 == 0 &&
         (uintptr_t)dy[0] % 16 == 0 && (uintptr_t)gw[0] % 4 == 0)
         return cg::head_wgrad(cg::S(stream), x[0], dy[0], gw[0], gb ? gb[0] : nullptr, N, kH * kW, Cin, Cout, scale) != 0;
+    // 2. the TN launch: split partials [splits][groups * phases][taps * Cin][Cout] and, behind them, the bias partials into ws
     TNPlan p = plan_tn(g, ngroups);
     const size_t need = tn_ws_bytes(g, p, ngroups);
     CG_REQUIRE(ws && ws_bytes >= need, "cg_conv2d_wgrad: workspace too small (%zu < %zu)", ws_bytes, need);
@@ -2829,71 +2125,12 @@ int wgrad_impl(void* stream, int ngroups, const float* const* x, const float* co
     hipStream_t st = cg::S(stream);
     dim3 grid(cg::cdiv(g.Ktot, p.tc.bm) * cg::cdiv(g.Cout, p.tc.bn), p.splits, ZP);
     if (p.pm && veca && vecb) a.pm_n = g.M / (g.Hg * g.Wg);
-    if (a.pm_n || tng_ok(g, p.pchunk, veca, vecb)) {
-        if (p.tc.bm == 128 && p.tc.bn == 128) launch_tng<128, 128, 2, 2>(a, grid, st);
-        else if (p.tc.bm == 64 && p.tc.bn == 128) launch_tng<64, 128, 2, 2>(a, grid, st);
-        else if (p.tc.bm == 128 && p.tc.bn == 64) launch_tng<128, 64, 2, 2>(a, grid, st);
-        else if (p.tc.bm == 64 && p.tc.bn == 64) launch_tng<64, 64, 2, 2>(a, grid, st);
-        else launch_tng<128, 32, 4, 1>(a, grid, st);
-    }
-    else if (p.tc.bm == 128 && p.tc.bn == 128) launch_tn<128, 128, 2, 2>(a, grid, st, veca, vecb);
-    else if (p.tc.bm == 64 && p.tc.bn == 128) launch_tn<64, 128, 2, 2>(a, grid, st, veca, vecb);
-    else if (p.tc.bm == 128 && p.tc.bn == 64) launch_tn<128, 64, 2, 2>(a, grid, st, veca, vecb);
-    else if (p.tc.bm == 64 && p.tc.bn == 64) launch_tn<64, 64, 2, 2>(a, grid, st, veca, vecb);
-    else launch_tn<128, 32, 4, 1>(a, grid, st, veca, vecb);
+    launch_tn_tile(a, p.tc, a.pm_n || tng_ok(g, p.pchunk, veca, vecb), grid, st, veca, vecb);
     CG_LAUNCH_CHECK();
     if (gemm_only) return 0;   // cg_conv2d_wgrad_gemm: the partial sums stay in ws
-    const int KK = kH * kW;
-    int ci_t = KK == 1 ? 64 : 8;
-    while (ci_t > 1 && (size_t)KK * ci_t * 33 * sizeof(float) > 60000) ci_t >>= 1;
-    const size_t shb = (size_t)KK * ci_t * 33 * sizeof(float);
-    dim3 rgrid(cg::cdiv(Cin, ci_t), cg::cdiv(Cout, 32));
-    const long relems = (long)KK * Cin * Cout;
-    const long sstride = (long)ZP * wplane;                 // floats between consecutive splits
-    const int kp = ups ? phase_kp(kH, padH) : 0;
-    if (strided && KK == 1 && !ups && !any_gb && Cin % 32 == 0 && Cout % 32 == 0 && g.nphase == 1) {
-        hipLaunchKernelGGL(wgrad_reduce_t_kernel, dim3(Cin / 32, Cout / 32, ngroups), dim3(256), 0, st, (const float*)ws, gw[0], gws_, Cin, Cout,
-                           p.splits, sstride, (long)g.nphase * wplane, scale);
-        CG_LAUNCH_CHECK();
-        return 0;
-    }
-    if ((long)rgrid.x * rgrid.y < cg::kNumCU) {
-        RedJob job;
-        memset(&job, 0, sizeof(job));
-        job.rp.gws = strided ? gws_ : 0;
-        set4(job.rp.gw0, job.rp.gw1, job.rp.gw2, job.rp.gw3, gw, nptr);
-        set4(job.rp.gb0, job.rp.gb1, job.rp.gb2, job.rp.gb3, gb, nptr);
-        job.part = (const float*)ws; job.bias_part = a.bias_part;
-        job.Cin = Cin; job.Cout = Cout; job.k = kH; job.KK = KK; job.pad = padH; job.kp = ups ? kp : 0; job.S = p.splits; job.P = g.nphase;
-        job.ups = ups ? 1 : 0; job.scale = scale;
-        job.sstride = sstride; job.gstride = (long)g.nphase * wplane; job.bsstride = (long)ZP * Cout;
-        job.wblocks = cg::cdiv(relems, 32); job.bblocks = any_gb ? cg::cdiv(Cout, 32) : 0;
-        // a queued KK == 1 job (nn.Linear; D's 20480 -> 256 head is 5.2 M elements = 164 000 32-element blocks) reduces as transpose tiles
-        if (defer && KK == 1 && !ups && Cin % 32 == 0 && Cout % 32 == 0 && g.nphase == 1) {
-            job.tr = 1; job.wblocks = (Cin / 32) * (Cout / 32);
-        } else if (!ups && Cout % 4 == 0 && (uintptr_t)ws % 16 == 0 && sstride % 4 == 0 && job.gstride % 4 == 0) {
-            job.v4 = 1; job.wblocks = cg::cdiv(relems, 128);
-        }
-        return small_reduce(st, defer, job, ngroups);
-    }
-    for (int gi = 0; gi < ngroups; ++gi) {
-        const float* pg = (const float*)ws + (long)gi * g.nphase * wplane;
-        float* gwi = strided ? gw[0] + (long)gi * gws_ : gw[gi];
-        if (ups)
-            hipLaunchKernelGGL(wgrad_reduce_kernel<true>, rgrid, dim3(256), shb, st, pg, gwi, Cin, Cout, kH, KK, padH, kp,
-                               p.splits, scale, ci_t, sstride);
-        else
-            hipLaunchKernelGGL(wgrad_reduce_kernel<false>, rgrid, dim3(256), shb, st, pg, gwi, Cin, Cout, kH, KK, padH,
-                               0, p.splits, scale, ci_t, sstride);
-        CG_LAUNCH_CHECK();
-        if (gb && gb[gi]) {
-            hipLaunchKernelGGL(bias_part_reduce_kernel, dim3(cg::cdiv(Cout, 32)), dim3(256), 0, st,
-                               (const float*)a.bias_part + (long)gi * g.nphase * Cout, gb[gi], p.splits, g.nphase,
-                               (long)ZP * Cout, Cout, scale);
-            CG_LAUNCH_CHECK();
-        }
-    }
-    return 0;
+    // 3. the finish: the partials into the canonical gradients, now or with the stream's other deferred ones
+    const cg::WgradParts parts{(const float*)ws, a.bias_part, gw, gb, strided ? gws_ : 0, ngroups, p.splits, Cin, Cout, kH, kW, padH, ups, scale};
+    return cg::wgrad_finish(st, parts, defer);
 }
 
 }  // namespace
@@ -2905,135 +2142,4 @@ int cg_conv2d_wgrad(void* stream, const float* x, const float* dy, float* gw, fl
                                    ws_bytes);
 }
 
-// input channels per pack workgroup: the largest power of two with ci_t*KK <= 448 floats per output channel (57 KB of LDS)
-static int pack_ci_tile(int Cin, int KK) {
-    int t = 1;
-    while (t * 2 * KK <= 448 && t < Cin) t *= 2;
-    return t;
-}
-
-int cg_pack_conv_weight(void* stream, const float* w, float* wf, float* wb, int Cout, int Cin, int kH, int kW) {
-    CG_REQUIRE(w && (wf || wb), "cg_pack_conv_weight: null pointer");
-    CG_REQUIRE(Cout > 0 && Cin > 0 && kH > 0 && kW > 0, "cg_pack_conv_weight: bad dims");
-    const int KK = kH * kW;
-    hipLaunchKernelGGL(pack_weight_kernel, dim3(cg::cdiv(Cin, 32), cg::cdiv(Cout, 32), KK), dim3(256), 0, cg::S(stream), w,
-                       wf, wb, Cout, Cin, KK, 0);
-    CG_LAUNCH_CHECK();
-    return cg::wino3_note_pack(cg::S(stream), 1, &w, &wf, &wb, &Cout, &Cin, &kH, &kW, nullptr);
-}
-
-// nn.View(C*H*W) -> nn.Linear(C*H*W -> Cout) on an NHWC map (models.lua:696-697, 849-850) without materialising the NCHW
-// view: the canonical [Cout][C*H*W] weight IS the canonical weight of a convolution C -> Cout with an H x W kernel, no
-// padding, on the H x W map (output 1 x 1).  wf (forward / weight-gradient view) is cg_pack_conv_weight's;
-// wbT[co][(h*W+w)*C + c] = w[co][c][h][w] is the [K = Cout][N = H*W*C] operand of the data gradient, run as a linear layer:
-//   cg_conv2d_forward(dy [N][Cout], wbT, NULL, dx [N][H*W*C] = NHWC, N, 1, 1, Cout, H*W*C, 1, 1, 0, 0, 0)
-int cg_pack_conv_weight_map(void* stream, const float* w, float* wf, float* wbT, int Cout, int Cin, int kH, int kW) {
-    CG_REQUIRE(w && (wf || wbT), "cg_pack_conv_weight_map: null pointer");
-    CG_REQUIRE(Cout > 0 && Cin > 0 && kH > 0 && kW > 0, "cg_pack_conv_weight_map: bad dims");
-    const int KK = kH * kW;
-    hipLaunchKernelGGL(pack_weight_kernel, dim3(cg::cdiv(Cin, 32), cg::cdiv(Cout, 32), KK), dim3(256), 0, cg::S(stream), w,
-                       wf, wbT, Cout, Cin, KK, 1);
-    CG_LAUNCH_CHECK();
-    return 0;
-}
-
-int cg_pack_conv_weight_batch(void* stream, int n, const float* const* w_canonical, float* const* wf, float* const* wb,
-                              const int* Cout, const int* Cin, const int* kH, const int* kW, const int* wb_map) {
-    CG_REQUIRE(n >= 0 && w_canonical && wf && wb && Cout && Cin && kH && kW, "cg_pack_conv_weight_batch: null pointer");
-    if (cg::opt(cg::OPT_PACK_WIDE) != 0) {
-        for (int i0 = 0; i0 < n; i0 += kPackBatch) {
-            PackBatchWide a;
-            memset(&a, 0, sizeof(a));
-            PackBatch& b = a.b;
-            b.n = std::min(kPackBatch, n - i0);
-            int blocks = 0, wino = 0;
-            for (int e = 0; e < b.n; ++e) {
-                const int i = i0 + e;
-                CG_REQUIRE(w_canonical[i] && (wf[i] || wb[i]) && Cout[i] > 0 && Cin[i] > 0 && kH[i] > 0 && kW[i] > 0,
-                           "cg_pack_conv_weight_batch: bad layer %d", i);
-                b.w[e] = w_canonical[i]; b.wf[e] = wf[i]; b.wb[e] = wb[i];
-                b.Cout[e] = Cout[i]; b.Cin[e] = Cin[i]; b.KK[e] = kH[i] * kW[i];
-                const bool map = wb_map && wb_map[i];
-                if (map) b.map_mask |= 1ull << e;
-                if (cg::wino3_layer(Cout[i], Cin[i], kH[i], kW[i]) && !map) { a.wino_mask |= 1ull << e; ++wino; }      // wino3_note_pack's rule
-                b.first[e] = blocks;
-                blocks += cg::cdiv(Cin[i], 32) * cg::cdiv(Cout[i], 32) * pack_chunks(b.KK[e]);
-            }
-            b.first[b.n] = blocks;
-            a.wino_first = blocks;
-            hipLaunchKernelGGL(pack_weight_batch_wide_kernel, dim3(blocks + 16 * wino), dim3(256), 0, cg::S(stream), a);
-            CG_LAUNCH_CHECK();
-        }
-        return 0;
-    }
-    for (int i0 = 0; i0 < n; i0 += kPackBatch) {
-        PackBatch b;
-        memset(&b, 0, sizeof(b));
-        b.n = std::min(kPackBatch, n - i0);
-        int blocks = 0;
-        for (int e = 0; e < b.n; ++e) {
-            const int i = i0 + e;
-            CG_REQUIRE(w_canonical[i] && (wf[i] || wb[i]) && Cout[i] > 0 && Cin[i] > 0 && kH[i] > 0 && kW[i] > 0,
-                       "cg_pack_conv_weight_batch: bad layer %d", i);
-            b.w[e] = w_canonical[i]; b.wf[e] = wf[i]; b.wb[e] = wb[i];
-            b.Cout[e] = Cout[i]; b.Cin[e] = Cin[i]; b.KK[e] = kH[i] * kW[i];
-            if (wb_map && wb_map[i]) b.map_mask |= 1ull << e;
-            b.first[e] = blocks;
-            blocks += cg::cdiv(Cin[i], 32) * cg::cdiv(Cout[i], 32) * b.KK[e];
-        }
-        b.first[b.n] = blocks;
-        hipLaunchKernelGGL(pack_weight_batch_kernel, dim3(blocks), dim3(256), 0, cg::S(stream), b);
-        CG_LAUNCH_CHECK();
-    }
-    return cg::wino3_note_pack(cg::S(stream), n, w_canonical, wf, wb, Cout, Cin, kH, kW, wb_map);
-}
-
-size_t cg_pack_conv_weight_floats(int Cout, int Cin, int kH, int kW) {
-    if (Cout <= 0 || Cin <= 0 || kH <= 0 || kW <= 0) return 0;
-    return (size_t)kH * kW * Cin * Cout + (cg::wino3_layer(Cout, Cin, kH, kW) ? cg::kWino3UFloats : 0);
-}
-
-size_t cg_pack_conv_weight_ups2_floats(int Cout, int Cin, int k, int pad) {
-    if (Cout <= 0 || Cin <= 0 || k <= 0 || (k & 1) == 0 || pad != (k - 1) / 2) return 0;
-    const int kp = phase_kp(k, pad);
-    return (size_t)4 * kp * kp * Cin * Cout;
-}
-
-int cg_pack_conv_weight_ups2(void* stream, const float* w, float* wf_ph, float* wb_ph, int Cout, int Cin, int k, int pad) {
-    CG_REQUIRE(w && (wf_ph || wb_ph), "cg_pack_conv_weight_ups2: null pointer");
-    CG_REQUIRE(Cout > 0 && Cin > 0 && k > 0 && (k & 1) == 1 && pad == (k - 1) / 2,
-               "cg_pack_conv_weight_ups2: needs an odd kernel with pad=(k-1)/2");
-    const int kp = phase_kp(k, pad);
-    CG_REQUIRE(k * k <= 448, "cg_pack_conv_weight_ups2: kernel too large (%d taps)", k * k);
-    const dim3 fgrid(cg::cdiv(Cin, 32), cg::cdiv(Cout, 32));
-    if ((k == 3 || k == 5) && cg::opt(cg::OPT_PACK_WIDE) != 0) {
-        const dim3 wgrid(cg::cdiv(Cin, 32), cg::cdiv(Cout, kPackWideCo) * 4);
-        if (k == 3)
-            hipLaunchKernelGGL(pack_weight_ups2_wide_kernel<3>, wgrid, dim3(256), 0, cg::S(stream), w, wf_ph, wb_ph, Cout, Cin);
-        else
-            hipLaunchKernelGGL(pack_weight_ups2_wide_kernel<5>, wgrid, dim3(256), 0, cg::S(stream), w, wf_ph, wb_ph, Cout, Cin);
-        CG_LAUNCH_CHECK();
-        return 0;
-    }
-    if (k == 3 || k == 5) {
-        if (k == 3)
-            hipLaunchKernelGGL(pack_weight_ups2_fast_kernel<3>, fgrid, dim3(256), 0, cg::S(stream), w, wf_ph, wb_ph, Cout, Cin);
-        else
-            hipLaunchKernelGGL(pack_weight_ups2_fast_kernel<5>, fgrid, dim3(256), 0, cg::S(stream), w, wf_ph, wb_ph, Cout, Cin);
-        CG_LAUNCH_CHECK();
-        return 0;
-    }
-    const int ci_t = pack_ci_tile(Cin, k * k);
-    hipLaunchKernelGGL(pack_weight_ups2_kernel, dim3(cg::cdiv(Cin, ci_t), cg::cdiv(Cout, 32)), dim3(256),
-                       (size_t)32 * (ci_t * k * k + 1) * sizeof(float), cg::S(stream), w, wf_ph, wb_ph, Cout, Cin, k, pad, kp,
-                       ci_t);
-    CG_LAUNCH_CHECK();
-    return 0;
-}
-
 }  // extern "C"
-
-void cg::wgrad_discard_all() {
-    std::lock_guard<std::mutex> lk(g_red_mu);
-    for (auto& kv : g_red_queue) kv.second.clear();
-}

@@ -14,7 +14,7 @@
 // Executed MFMA work = 16 / 36 of the direct count; results differ from the direct kernel by fp32 re-association only (the transforms'
 // coefficients are 0, +-1, +-1/2).  Measured alone at batch 128 (profiles/r06_wino_lab.txt): 32 x 32: 61 us against 96 us direct.
 //
-// The transformed filters ride behind the packed operand: cg_pack_conv_weight* (gemm.hip) call wino3_note_pack for every 64 -> 64 3x3
+// The transformed filters ride behind the packed operand: cg_pack_conv_weight* (pack.hip) call wino3_note_pack for every 64 -> 64 3x3
 // layer they pack, which writes U for the forward operand at wf + 9 * 64 * 64 and the flipped, transposed U for the data-gradient operand
 // at wb + 9 * 64 * 64 from the canonical weights in the same stream, whatever CG_WINO3 says (cg_pack_conv_weight_floats() sizes the
 // buffers).  The host owns that memory like any other operand; nothing is allocated, cached or looked up here.
@@ -30,7 +30,7 @@ constexpr int PLD = 68;        // floats per patch pixel
 constexpr int PW = 18, PH = 10;
 constexpr int kUFloats = cg::kWino3UFloats;
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+using cg::ld4;
 __device__ __forceinline__ float4 bufld4(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff) {
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
     const f32x4 f = __builtin_bit_cast(f32x4, v);        // cast the WHOLE vector (see gemm.hip)

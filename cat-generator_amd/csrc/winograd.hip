@@ -34,9 +34,9 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+using cg::ld4;
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ float wf4c(const float4& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : (i == 2 ? v.z : v.w)); }
+using cg::f4c;
 __device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 __device__ __forceinline__ float4 f4sub(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ __forceinline__ float4 f4neg(float4 a) { return make_float4(-a.x, -a.y, -a.z, -a.w); }
@@ -615,7 +615,7 @@ __global__ __launch_bounds__(512, 4) void wino_gemm_g_kernel(WinoArgs a) {
             const float4 af = A4[qa_rd[gq]];
 #pragma unroll
             for (int sidx = 0; sidx < 4; ++sidx)
-                accM = __builtin_amdgcn_mfma_f32_32x32x2f32(wf4c(af, sidx), B[(8 * gq + sidx) * BN], accM, 0, 0, 0);
+                accM = __builtin_amdgcn_mfma_f32_32x32x2f32(f4c(af, sidx), B[(8 * gq + sidx) * BN], accM, 0, 0, 0);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -631,9 +631,9 @@ __global__ __launch_bounds__(512, 4) void wino_gemm_g_kernel(WinoArgs a) {
         const float4 c = wino_out_coeffs<NPOS>(xi);
 #pragma unroll
         for (int o = 0; o < 4; ++o)
-            if (wf4c(c, o) != 0.f) {
+            if (f4c(c, o) != 0.f) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) accY[o][r] += wf4c(c, o) * accM[r];
+                for (int r = 0; r < 16; ++r) accY[o][r] += f4c(c, o) * accM[r];
             }
 #pragma unroll
         for (int r = 0; r < 16; ++r) accM[r] = 0.f;
@@ -823,7 +823,7 @@ __global__ __launch_bounds__(512, 2) void wino_dgrad_fused_kernel(WinoFusedArgs 
         auto frag = [&](int comp, float (&o)[4]) {     // e = d[I1] -+ d[I2] per patch column, then B's columns: e0 - e2, e1 + e2, e2 - e1, e1 - e3
             float e[4];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) e[c] = __builtin_fmaf(sgn, wf4c(d2[c], comp), wf4c(d1[c], comp));
+            for (int c = 0; c < 4; ++c) e[c] = __builtin_fmaf(sgn, f4c(d2[c], comp), f4c(d1[c], comp));
             o[0] = e[0] - e[2]; o[1] = e[1] + e[2]; o[2] = e[2] - e[1]; o[3] = e[1] - e[3];
         };
         float b[2][8], v[2][4];      // [k pair & 1][position nu * 2 + column tile ni], [k pair & 1][nu]

@@ -1,10 +1,11 @@
-"""Bit-for-bit pins of the implicit-GEMM kernels of csrc/gemm.hip and of the VALU skinny kernels of csrc/skinny.hip.
+"""Bit-for-bit pins of the implicit-GEMM kernels of csrc/gemm.hip, of the weight-gradient finishes of csrc/wgrad_finish.hip and of the VALU
+skinny kernels of csrc/skinny.hip.
 
 The four GEMM kernels (igemm_nn / igemm_nng / igemm_tn / igemm_tng) share their epilogues, their tile decode and their host-side
 argument packing; a restructuring of those must not move a single bit.  Every case below forces ONE branch of the shared code through
 `cg_set_option` (reset afterwards), runs a small layer forward and backward on fixed inputs and takes one sha256 over the raw bytes of
 output, gradInput, gradWeight and gradBias.  tests/golden/gemm_bits.json holds the digests, RECORDED ON A BUILD OF THE COMMIT BEFORE THE
-RESTRUCTURING by this same file:
+RESTRUCTURING by this same file (the finish cases at the end: before the finishes moved out of gemm.hip):
 
     CG_GEMM_BITS_RECORD=<file.json> pytest tests/test_gpu_gemm_bits.py      # writes the digests instead of comparing them
 
@@ -118,7 +119,9 @@ def planned_bits(cg, build, x, fusion, seed):
     p, g = net.getParameters()
     rs = np.random.RandomState(seed)
     p.copy(p.numpy() + (rs.randn(p.nElement()) * 0.01).astype(f32))
-    xin = cg.nn.as_nhwc(cg.Tensor.from_numpy(x))
+    xin = cg.Tensor.from_numpy(x)
+    if x.ndim == 4:
+        xin = cg.nn.as_nhwc(xin)
     pn = net._planned_net()
     assert pn is not None
     cg.lib().net_set_option(pn.h, b"fusion", int(fusion))
@@ -210,3 +213,42 @@ def test_valu_skinny_kernels(cg, golden, shape):
     N, Cin, H, W, Cout = shape
     with options(cg, CG_SKINNY=2):
         check(golden, f"skinny valu {shape}", *conv_bits(cg, N, Cin, H, W, Cout, 3, 0, seed=N + Cin + H + W + Cout))
+
+
+# The finishes of the weight gradient (csrc/wgrad_finish.hip).  The cases above all land in the small forms with 1 or 3 splits; these reach
+# the tiled kernels (Cin / 8 x Cout / 32 blocks, not fewer than the chip has CUs) and the long small forms, where a lane group adds more
+# than one split.  (N, Cin, H, W, Cout, k, ups) and the forced TN split count; which kernels each launches: profiles/finish_cases_kernels.txt
+FINISHES = {
+    "tiled plain": ((2, 256, 8, 8, 256, 3, 0), 3),              # wgrad_reduce_kernel<false> + bias_part_reduce_kernel, 32 x 8 full blocks
+    "tiled plain, ragged": ((2, 260, 8, 8, 250, 3, 0), 3),      # 33 x 8 blocks, guards in both dimensions
+    "tiled ups": ((2, 256, 4, 4, 256, 3, 1), 3),                # wgrad_reduce_kernel<true> (M = 32 pixels per phase: the plan makes 2 splits of 3)
+    "small v4, long": ((11, 64, 8, 8, 64, 3, 0), 44),           # M = 704 = 44 K tiles: lane group 0 adds 0, 8, 16, 24 in one round, then 32, 40
+    "small scalar, long": ((11, 64, 8, 8, 6, 3, 0), 44),        # Cout % 4 != 0: the 32-element form and its bias blocks
+    "small ups, long": ((11, 32, 8, 8, 8, 3, 1), 44),           # the phase fold with the eight-lane interleave
+}
+
+
+@pytest.mark.parametrize("finish", list(FINISHES))
+def test_wgrad_finishes(cg, golden, finish):
+    """Split-K partials -> canonical gradWeight / gradBias through each finish: tiled (splits in order, phases inside a split) and small
+    (lane group ln adds splits ln, ln + 8, ..., then the groups in order)."""
+    shape, splits = FINISHES[finish]
+    with options(cg, CG_TN_SPLITS=splits, **NO_OTHER):
+        check(golden, f"finish {finish} / splits {splits}", *conv_bits(cg, *shape, seed=len(finish)))
+
+
+def test_deferred_transpose_and_v4_jobs(cg, golden):
+    """Two linear layers through the planned executor queue their finishes and flush them in ONE wgrad_reduce_batch_kernel launch: the first
+    (64 -> 32, both multiples of 32) as transpose tiles, the second (32 -> 4) as a 16-byte job.  CG_PAD_SKIP = 0 keeps headwg.hip out."""
+    def build():
+        return cg.nn.Sequential().add(cg.nn.Linear(64, 32)).add(cg.nn.LeakyReLU(0.2)).add(cg.nn.Linear(32, 4))
+    x = np.random.RandomState(21).randn(64, 64).astype(f32)
+    with options(cg, CG_PAD_SKIP=0, **NO_OTHER):
+        check(golden, "deferred linear 64 -> 32 -> 4", *planned_bits(cg, build, x, 1, seed=21)[0])
+
+
+def test_mfma_skinny_finish(cg, golden):
+    """skinny.hip's MFMA weight gradient (CG_SKINNY = 1) leaves 256 partial planes and their bias partials to the small finish."""
+    shape = (2, 128, 32, 32, 3)
+    with options(cg, CG_SKINNY=1):
+        check(golden, f"skinny mfma {shape}", *conv_bits(cg, *shape, 3, 0, seed=sum(shape)))

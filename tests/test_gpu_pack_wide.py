@@ -3,12 +3,12 @@
 A re-pack is a permutation of the canonical weights plus, behind a folded upsampling, a few tap sums added in a fixed order, so the wide
 kernels are held to the BYTES of the old ones, not to a tolerance:
 
-* cg_pack_conv_weight_ups2 (pack_weight_ups2_wide_kernel, csrc/gemm.hip): full 32 x 16 blocks, ragged blocks in both dimensions and fewer
+* cg_pack_conv_weight_ups2 (pack_weight_ups2_wide_kernel, csrc/pack.hip): full 32 x 16 blocks, ragged blocks in both dimensions and fewer
   than 32 channels, both operands and each one alone.  The phase sums are also restated in numpy float32 in the kernels' (dy, dx) order,
   which is exact, so both settings are held to that as well; every output is pre-filled with a sentinel no sum can produce and is followed
   by a guard that must stay untouched.
 * cg_conv2d_ups2_wino_pack / cg_conv2d_ups2_wino22_pack (both operands in one launch, csrc/winograd.hip) on the benchmarked layers.
-* cg_pack_conv_weight_batch (pack_weight_batch_wide_kernel, csrc/gemm.hip): tap chunks of 9 (3x3), 7 (7x7), 4 (the View -> Linear map
+* cg_pack_conv_weight_batch (pack_weight_batch_wide_kernel, csrc/pack.hip): tap chunks of 9 (3x3), 7 (7x7), 4 (the View -> Linear map
   layout) and 1 taps, a short last chunk (5x5), ragged blocks, a missing wb; the tap permutation is also held to numpy's, and the
   fused-Winograd filters behind the 64 -> 64 layer's operands, which the wide launch computes in workgroups of its own, to those of
   wino3_pack_k through the single-layer entry point.

@@ -13,7 +13,7 @@ def phase_map(a, d, pad=2):
 
 
 def phase_kernels(w):
-    """w [5][5] -> g[p][3][3]: the taps of output phase p=(a,b) folded onto the low-res grid (gemm.hip pack_weight_ups2)."""
+    """w [5][5] -> g[p][3][3]: the taps of output phase p=(a,b) folded onto the low-res grid (pack.hip pack_weight_ups2)."""
     g = np.zeros((4, 3, 3))
     for p in range(4):
         for dy in range(5):
@@ -89,7 +89,7 @@ AT22 = np.array([[1, 1, 0], [0, 1, 1]], dtype=np.float64)
 
 
 def phase_kernels_3x3(w):
-    """w [3][3] (pad 1) -> g[p][2][2]: output phase (a, b) reads low-res rows -1 + a + {0, 1} (gemm.hip pack_weight_ups2)."""
+    """w [3][3] (pad 1) -> g[p][2][2]: output phase (a, b) reads low-res rows -1 + a + {0, 1} (pack.hip pack_weight_ups2)."""
     g = np.zeros((4, 2, 2))
     for p in range(4):
         for dy in range(3):
