@@ -406,7 +406,8 @@ __global__ __launch_bounds__(NT) void locnet_bwd_k(LocBwd a) {
 // The kernels above keep one sample's maps AND kernels in ~100 KB of LDS (one workgroup of 768 threads per CU, the 384 samples of
 // the three branch transformers in 1.5 rounds) and run the two convolutions at VALU + LDS-read rates with the nine taps split over
 // threads whose partial sums meet in LDS: 114 us forward / 116-166 us backward for the three-branch launch at batch 128, ~0.01 of any
-// roofline (profiles/r03_locnet_phases.txt).  Here, for the shapes D32_st3 uses at 32x32 (S 16 / 3 planes; S 8 / 64 planes):
+// roofline (profiles/r03_locnet_phases.txt).  Here, for the shapes D32_st3 uses at 32x32 (S 16 / 3 planes; S 8 / 64 planes) and for its
+// branch transformers at 16x16 (S 4 / 64 planes, one M tile per sample: the note above has()):
 //   * both convolutions are implicit GEMMs on v_mfma_f32_16x16x4_f32 (M = 16 pixels, N = the 16 output planes, K = 4 input planes of
 //     one tap per instruction): the A operand is ONE ds_read_b32 per lane out of a zero-haloed [(S+2)^2][C + 2] image - no bounds
 //     test, the tap a compile-time address offset, pixel stride = 2 (mod 32) so that 16 pixels x 2 K-lanes fill 32 distinct banks -
@@ -430,10 +431,11 @@ template <int S_, int CIN_> struct Cfg {
     static constexpr bool KSPLIT = CIN >= 4 * NW * 4;   // conv 1: input planes over the waves (else: M tiles over the waves)
     static constexpr int NCH1 = KSPLIT ? CK1 / (4 * NW) : CK1 / 4;   // K-steps per tap a wave runs in conv 1
     static constexpr int NMT1 = KSPLIT ? MT : MT / NW;  // M tiles per wave in conv 1
-    static constexpr int NMT2 = MT / NW;                // ... in conv 2 (M split)
+    static constexpr int W2 = MT >= NW ? NW : MT;        // waves that run conv 2 and its data gradient: M tiles over the waves, and a
+    static constexpr int NMT2 = MT / W2;                 // 4x4 map is ONE tile - wave 0 runs its 36 MFMAs (see the note above has())
     static constexpr int Sh = S / 2, K3 = LC * Sh * Sh;
     static constexpr int RS = 20;                        // row stride of the K-split partials
-    static_assert(MT % NW == 0 && (S & (S - 1)) == 0, "shape");
+    static_assert(MT % W2 == 0 && (MT >= NW || (KSPLIT && CIN >= 16 * NW)) && (S & (S - 1)) == 0, "shape");
     // forward LDS (floats)
     static constexpr int F_P = 0, F_H1 = F_P + NP * CP1, F_M2 = F_H1 + NP * CP2, F_H2 = F_M2 + S2 * (LC + 1), F_H3 = F_H2 + K3, F_PRM = F_H3 + LH,
                          F_TOT = F_PRM + 8;
@@ -580,7 +582,7 @@ __global__ __launch_bounds__(NT2) void locnet_fwd2_k(LocFwd a) {
     }
     __syncthreads();
     // (4) conv3x3 16 -> 16, bias, LeakyReLU
-    {
+    if (C::W2 == NW || wv < C::W2) {
         f4 acc[C::NMT2];
         int ab[C::NMT2];
 #pragma unroll
@@ -612,7 +614,24 @@ __global__ __launch_bounds__(NT2) void locnet_fwd2_k(LocFwd a) {
     __syncthreads();
     // (6) Linear(K3 -> 64) + LeakyReLU: a wave takes 16 outputs, RB rows at a time; lane l holds input elements 4l + 256j .. +3 and
     // reads the same columns of every row as 16-byte loads (a row = K3 / 256 coalesced 1 KB requests per wave)
-    {
+    if constexpr (C::K3 == 64) {
+        // K3 = 64 (S = 4): a row is one 256-byte request; lane l holds input element l, the wave's 16 rows are in flight together
+        const float hv = h2[lane];
+        const float* wr = w.w3 + (size_t)(16 * wv) * C::K3 + lane;
+        float wq[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) wq[r] = wr[r * C::K3];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float sv = cg::wave_sum(hv * wq[r]);
+            if (lane == 0) {
+                const int o = 16 * wv + r;
+                const float v = cg::act(2, sv + w.b3[o], sl);
+                h3[o] = v;
+                a.h3buf[(size_t)smp * LH + o] = v;
+            }
+        }
+    } else {
         constexpr int KJ = C::K3 / 256, RB = KJ >= 4 ? 4 : 8;
         static_assert(C::K3 % 256 == 0, "K3");
         float4 hv[KJ];
@@ -745,7 +764,20 @@ __global__ __launch_bounds__(NT2) void locnet_bwd2_k(LocBwd a) {
     __syncthreads();
     // (4) Linear(K3 -> 64) backward: gh2[i] = sum_o w3[o][i] g3[o]; a thread owns K3 / 256 consecutive columns (one 16-byte or 4-byte
     // load per row), 16 rows in flight, rows added in order
-    {
+    if constexpr (K3 == 64) {
+        // K3 = 64 (S = 4): wave q sums rows 16q .. 16q + 15 of column `lane` (16 loads in flight), the four partials meet in LDS (gp is
+        // free until (7)) and are added in wave order
+        const float* wc = w.w3 + (size_t)(16 * wv) * K3 + lane;
+        float wq[16];
+#pragma unroll
+        for (int o = 0; o < 16; ++o) wq[o] = wc[o * K3];
+        float s = 0.f;
+#pragma unroll
+        for (int o = 0; o < 16; ++o) s += wq[o] * g3s[16 * wv + o];
+        gp[tid] = s;
+        __syncthreads();
+        if (tid < K3) gh2[tid] = ((gp[tid] + gp[64 + tid]) + gp[128 + tid]) + gp[192 + tid];
+    } else {
         constexpr int CW = K3 / NT2;      // 1 or 4
         static_assert(CW == 1 || CW == 4, "K3");
         float s4[4] = {0.f, 0.f, 0.f, 0.f};
@@ -778,7 +810,7 @@ __global__ __launch_bounds__(NT2) void locnet_bwd2_k(LocBwd a) {
     }
     __syncthreads();
     // (6) conv 2 data gradient, LeakyReLU backward at conv 1's output -> ga1
-    {
+    if (C::W2 == NW || wv < C::W2) {
         f4 acc[C::NMT2];
         int ab[C::NMT2];
 #pragma unroll
@@ -848,7 +880,18 @@ template <int S, int CIN> int launch_bwd(hipStream_t st, const LocBwd& a, int nb
 // (16, 64) - the branch transformers of D32_st3 at 64x64 (config #5) - was parity-clean in round 4 but is NOT instantiated: it needs
 // 131 / 118 KB of LDS and 260 VGPRs, i.e. one workgroup per CU for 192 samples, and the ten separate (grouped) launches it would
 // replace are faster: config #5 12.67 ms per step without, 12.81 with (profiles/r04_sweeps.txt).
-inline bool has(int S, int Cin) { return (S == 16 && Cin == 3) || (S == 8 && Cin == 64); }
+// (4, 64) - the branch transformers of D32_st3 at 16x16 - is one M tile per sample: conv 1 (K over the waves) and conv 1's data gradient
+// (N over the waves) need only MT tiles per wave; conv 2 and its data gradient, 36 dependent MFMAs (~1.5k cycles), run on wave 0 alone.
+// A K split over the waves would cut that chain to 9 but pay two barriers and an LDS round trip of the partials, about what it saves; several
+// samples per workgroup would leave a partial workgroup to guard in every phase.  14 / 10 KB of LDS, 102 / 142 VGPRs: four / three samples
+// share a CU, the 384 workgroups of the three branches at batch 128 are one round (profiles/scale16_locnet.txt).
+inline bool has(int S, int Cin) { return (S == 16 && Cin == 3) || (S == 8 && Cin == 64) || (S == 4 && Cin == 64); }
+inline int fwd(hipStream_t st, const LocFwd& a, int nb) {
+    return a.S == 4 ? launch_fwd<4, 64>(st, a, nb) : a.S == 8 ? launch_fwd<8, 64>(st, a, nb) : launch_fwd<16, 3>(st, a, nb);
+}
+inline int bwd(hipStream_t st, const LocBwd& a, int nb) {
+    return a.S == 4 ? launch_bwd<4, 64>(st, a, nb) : a.S == 8 ? launch_bwd<8, 64>(st, a, nb) : launch_bwd<16, 3>(st, a, nb);
+}
 inline bool enabled() { return true; }
 
 }  // namespace v2
@@ -860,11 +903,12 @@ size_t bwd_lds_floats(int S, int Cin) { return (size_t)bwd_lds(S, Cin).total; }
 
 extern "C" {
 
-// 1 if the fused launches cover this localisation net: power-of-two pooled size S >= 8 (so that a wave shares its quad of output
-// planes), the activations of one sample within LDS.
+// 1 if the fused launches cover this localisation net: a geometry of the MFMA kernels (v2::has; the only ones with S = 4), or a
+// power-of-two pooled size S >= 8 (so that a wave shares its quad of output planes) with the activations of one sample within LDS.
 int cg_locnet_supported(int S, int Cin, int P) {
-    if (S < 8 || (S & (S - 1)) || Cin < 1 || P < 1 || P > 4) return 0;
+    if (S < 4 || (S & (S - 1)) || Cin < 1 || P < 1 || P > 4) return 0;
     if (v2::enabled() && v2::has(S, Cin)) return 1;     // the MFMA kernels bring their own (smaller) LDS plan
+    if (S < 8) return 0;
     const size_t lim = 160 * 1024 - 1024;   // the kernels' few static __shared__ words come out of the same 160 KB
     return fwd_lds_floats(S, Cin) * 4 <= lim && bwd_lds_floats(S, Cin) * 4 <= lim ? 1 : 0;
 }
@@ -887,7 +931,7 @@ int cg_locnet_forward(void* stream, int ngroups, int n_per_group, const float* x
     a.pbuf = pooled; a.h1buf = h1; a.m2buf = m2; a.h2buf = h2; a.h3buf = h3; a.params = params; a.grid = grid;
     if (v2::enabled() && v2::has(S, Cin)) {   // the MFMA kernels (round 4)
         const int nb = ngroups * n_per_group;
-        const int rc = S == 8 ? v2::launch_fwd<8, 64>(cg::S(stream), a, nb) : v2::launch_fwd<16, 3>(cg::S(stream), a, nb);
+        const int rc = v2::fwd(cg::S(stream), a, nb);
         if (rc) return rc;
         CG_LAUNCH_CHECK();
         return 0;
@@ -918,7 +962,7 @@ int cg_locnet_backward(void* stream, int ngroups, int n_per_group, const float* 
     a.ga1 = ga1; a.ga2 = ga2; a.g3 = g3; a.g4 = g4; a.gx = gx;
     if (v2::enabled() && v2::has(S, Cin)) {
         const int nb = ngroups * n_per_group;
-        const int rc = S == 8 ? v2::launch_bwd<8, 64>(cg::S(stream), a, nb) : v2::launch_bwd<16, 3>(cg::S(stream), a, nb);
+        const int rc = v2::bwd(cg::S(stream), a, nb);
         if (rc) return rc;
         CG_LAUNCH_CHECK();
         return 0;

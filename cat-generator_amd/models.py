@@ -1,7 +1,8 @@
 """models.lua's generator / discriminator factories, translated line for line onto the engine's nn layer.
 
-Only the definitions on the hot path are here: G32up-c (models.lua:196-228, the default
-via create_G :234-240), G32up (:138-160), D32_st3 (:640-711, the only D create_D returns, :276) and the
+Only the definitions the front ends reach are here: G32up-c (models.lua:196-228, the default
+via create_G :234-240), G32up (:138-160) and its 16x16 form G16up (:108-132, what create_G returns at --scale 16),
+D32_st3 (:640-711, the only D create_D returns, :276; it builds at 16, 32 and 64 px) and the
 spatial-transformer factory (:814-906), the validator V (:716-804) that train_v.py trains, and G's encoder / auto-encoder form
 (:50-83, :246-262) that pretrain_g.py trains.  `create_G32up_c_64` is the builder-defined 64x64 extension of
 BASELINE.json config #5.
@@ -11,11 +12,11 @@ from .tensor import Tensor
 from .weight_init import w_init
 
 
-def create_G_decoder_upsampling32(dimensions, noiseDim):
-    """models.lua:138-160."""
+def create_G_decoder_upsampling32(dimensions, noiseDim, base=8):
+    """models.lua:138-160.  `base` is the side of the first map: 8 in the reference (8x8 -> 32x32); base=4 is models.lua:108-132."""
     model = nn.Sequential()
-    model.add(nn.Linear(noiseDim, 128 * 8 * 8))
-    model.add(nn.View(128, 8, 8))
+    model.add(nn.Linear(noiseDim, 128 * base * base))
+    model.add(nn.View(128, base, base))
     model.add(nn.PReLU(None, None, True))
 
     model.add(nn.SpatialUpSamplingNearest(2))
@@ -33,6 +34,11 @@ def create_G_decoder_upsampling32(dimensions, noiseDim):
 
     model = w_init(model, "heuristic")
     return model
+
+
+def create_G_decoder_upsampling16(dimensions, noiseDim):
+    """models.lua:108-132 (G16up): create_G_decoder_upsampling32 from a 4x4 map, 4x4 -> 8x8 -> 16x16."""
+    return create_G_decoder_upsampling32(dimensions, noiseDim, base=4)
 
 
 def create_G_decoder_upsampling32c(dimensions, noiseDim, base=4):
@@ -74,9 +80,9 @@ def create_G32up_c_64(dimensions, noiseDim):
 
 
 def create_G(dimensions, noiseDim):
-    """models.lua:234-240 (the 16px generator is an unused variant, out of scope)."""
+    """models.lua:234-240: G16up at 16 px, G32up-c otherwise (and its 64x64 extension)."""
     if dimensions[1] == 16:
-        raise NotImplementedError("create_G_decoder_upsampling16 is not on the hot path (SURVEY.md §2.1 row 2)")
+        return create_G_decoder_upsampling16(dimensions, noiseDim)
     if dimensions[1] == 64:
         return create_G32up_c_64(dimensions, noiseDim)
     return create_G_decoder_upsampling32c(dimensions, noiseDim)
@@ -120,11 +126,14 @@ def create_G_encoder32(dimensions, noiseDim):
 
 def create_G_autoencoder(dimensions, noiseDim):
     """models.lua:246-262: nn.Sequential{encoder, decoder}.  The decoder is what create_G returns for these dimensions (G32up-c, its
-    64x64 extension when dimensions[1] == 64), so the half pretrain_g.py saves is the net train.py trains.  The tree holds modules
+    64x64 extension when dimensions[1] == 64), so the half pretrain_g.py saves is the net train.py trains.  At 16 px the reference
+    pairs create_G_encoder16 with G16up (:248-250); that encoder is not written here (pre-training is the optional step, and
+    tests/test_pretrain_host.py pins this refusal), so 16 px raises.  The tree holds modules
     the planned executor has no entry for (nn.BatchNormalization): it runs on the per-module walk, encoder and decoder alike."""
     model = nn.Sequential()
     if dimensions[1] == 16:
-        raise NotImplementedError("create_G_encoder16 / create_G_decoder_upsampling16 are not on the hot path (SURVEY.md §2.1 row 2)")
+        raise NotImplementedError("create_G_encoder16 (models.lua:14) is not implemented: G can be trained and sampled at 16 px "
+                                  "(create_G), but not pre-trained as an auto-encoder")
     model.add(create_G_encoder32(dimensions, noiseDim))
     model.add(create_G(dimensions, noiseDim))
     return model

@@ -622,7 +622,7 @@ int cg_bilinear_sampler_backward_shared(void* stream, int ngroups, const float* 
  * Linear(16 (S/2)^2 -> 64) -> LeakyReLU -> Linear(64 -> P), then models.lua:877-878: AffineTransformMatrixGenerator ->
  * AffineGridGeneratorBHWD.  One workgroup per sample keeps the chain's activations in LDS; per element the arithmetic is that of
  * the separate entry points up to fp32 re-association of the convolution / linear sums.  S = spatial size after the first
- * pooling (the transformer's input is [.., 2S, 2S, Cin] NHWC), a power of two >= 8; cg_locnet_supported() == 0: use the modules.
+ * pooling (the transformer's input is [.., 2S, 2S, Cin] NHWC), a power of two >= 8, or 4 with Cin = 64; cg_locnet_supported() == 0: use the modules.
  * `ngroups` (<= 4) networks of identical shape run in one launch, group g on samples [g*n, (g+1)*n) (x_shared != 0: every group
  * reads the SAME n input samples - D32_st3's three branches all look at the trunk's output, models.lua:653-678).
  * weights: host array of 12 device pointers per group: canonical Torch7 tensors conv1 weight [16][Cin][3][3], conv1 bias,
