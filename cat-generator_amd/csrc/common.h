@@ -453,6 +453,20 @@ __device__ __forceinline__ float bn_norm(float x, float m, float s, float g, flo
 __device__ __forceinline__ float bn_dx(float x, float dy, float g, float m, float s, float m1, float m2) {
     return g * s * (dy - m1 - bn_xhat(x, m, s) * m2);
 }
+// the augmentation's noise value of one source sample (ops.hip's on-the-fly kernels, faces.hip's offline variants): Irwin-Hall sum
+// of the twelve 16-bit fields of three splitmix64 outputs (exact in fp32)
+__device__ __forceinline__ float augment_noise(uint64_t seed, uint64_t ctr) {
+    unsigned S = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        uint64_t z = seed + (ctr + k + 1) * 0x9E3779B97F4A7C15ull;   // common.h u01's generator, all 64 bits of it
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        z = z ^ (z >> 31);
+        S += (unsigned)(z & 0xFFFF) + (unsigned)((z >> 16) & 0xFFFF) + (unsigned)((z >> 32) & 0xFFFF) + (unsigned)(z >> 48);
+    }
+    return (float)((int)S - 393210) * (1.0f / 65536.0f);   // |S - 393210| < 2^24 and a power of two: both steps exact
+}
 // tf.warp(order 1, mode="nearest") as the augmentation kernels (ops.hip) and the face extraction (faces.hip) restate it in fp32:
 // one axis of the warp's source position: clamped to [0, L-1] (NaN -> 0), split into the two taps and the fraction
 __device__ __forceinline__ void warp_taps(float s, int L, int* i0, int* i1, float* f) {

@@ -384,19 +384,7 @@ __global__ void images_u8_gather_scale_k(const unsigned char* __restrict__ set, 
 // Phase 1 leaves the pixel stage p (flip, brightness, noise, clip) of the whole source image in the LDS as fp32, [Hs][Ws][3], so that a
 // noise value is hashed once and not once per bilinear tap of every box-filter sample that touches it.  Phase 2 is
 // images_u8_scale_k's walk, one lane per output element, whose source samples are the four warp taps out of the LDS.
-// noise value of one source sample: Irwin-Hall sum of the twelve 16-bit fields of three splitmix64 outputs (exact in fp32)
-__device__ __forceinline__ float augment_noise(uint64_t seed, uint64_t ctr) {
-    unsigned S = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        uint64_t z = seed + (ctr + k + 1) * 0x9E3779B97F4A7C15ull;   // common.h u01's generator, all 64 bits of it
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z = z ^ (z >> 31);
-        S += (unsigned)(z & 0xFFFF) + (unsigned)((z >> 16) & 0xFFFF) + (unsigned)((z >> 32) & 0xFFFF) + (unsigned)(z >> 48);
-    }
-    return (float)((int)S - 393210) * (1.0f / 65536.0f);   // |S - 393210| < 2^24 and a power of two: both steps exact
-}
+using cg::augment_noise;
 using cg::warp_taps;
 // image n of the pool (this workgroup's) from the one source image `im`: both augmentation kernels' whole arithmetic.  n, not the
 // image's place in its set, numbers the noise counters

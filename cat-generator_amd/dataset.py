@@ -262,7 +262,9 @@ def setAugmentation(on=True, **ranges):
     Deliberate differences from the offline tool: no re-quantisation to 8 bits between the stages; the warp acts on the dataset's
     64 x 64 files, which have none of the tool's 30 px padding left, so rotated / shifted borders show replicated edge pixels;
     numpy's seeded generator (dataset.seed) instead of Python's `random`; the noise is a bit-reproducible Irwin-Hall normal
-    (augment_noise), not numpy's."""
+    (augment_noise), not numpy's.  The tool's own variants - warped from the padded full-resolution crop and re-quantised between the
+    stages - are written offline by generate_dataset.py --variantsFrom crop (faces.variants_np); this on-the-fly form warps finished
+    faces whichever way the set was made."""
     global augmentation
     if not on:
         augmentation = None

@@ -18,6 +18,26 @@ extract_face(pad=30)'s padding (the median np.pad, :191-230) and unpad(30) (:145
 extract_faces_np the whole pipeline: it is the yardstick of the device form, cg_faces_u8_extract (csrc/faces.hip), which
 extract_faces_device calls.  Host decisions are fp64 (Python floats); only pixels are computed in fp32 and integers.
 
+For the tool's AUGMENTED variants (generate_dataset.py:62-73, Image.augment, dataset.py:284-308) the padding does not cancel: the
+reference keeps `pad` pixels of real image around the rectangle "for the augmentation" (:62-64), warps at full resolution and only
+then unpads and resizes, so its rotated, shifted and zoomed-out variants show fur and background at their borders.  Four stages
+between 3 and 4, per accepted face (generate_dataset.py --variantsFrom crop; the default, face, warps the finished face instead):
+
+  a. padded crop P, [Hr + 2 pad, Wr + 2 pad, 3] (extract_rectangle, :191-230): the rectangle enlarged by `pad` and clipped to the image
+     (:196-204) out of stage 2's warp, then np.pad(mode="median") for the sides that left it (:206-228)        padded_crop_np, median_pad_np
+  b. pixel stage on the flipped crop (:284-304): brightness, noise, clip - and the re-quantisation to 8 bits that the tool performs
+     between its stages and that the on-the-fly form (dataset.augment_images) deliberately leaves out             variant_pixels_np
+  c. warp (:306-307) by the inverse of ImageAugmenter's matrix (ImageAugmenter.py:111-112, 179-190) with the shifts int(Wp / 2),
+     int(Hp / 2) of the PADDED crop, clamped to the padded crop, re-quantised by truncation; evaluated on the window
+     [pad, pad + Hr) x [pad, pad + Wr) only - the warp is pointwise, so this equals warping all of it and unpad(pad) (:145-150)
+                                                                                                                  variant_warp_np
+  d. resize, stage 4 unchanged.
+variants_np chains a-d and is the yardstick of cg_faces_u8_extract_variants, which extract_variants_device calls.  The draws are
+dataset.augment_draw's (numpy's seeded generator, not the reference's `random` stream), the noise dataset.augment_noise at the counters
+base + 3 j, j = (y Wp + x) 3 + c on the array the warp reads, `base` one 64-bit number per (face, variant) that the caller passes as
+data.  Three exact consequences (tests/test_faces_variants_host.py): the identity draw returns the _000 rectangle; a whole-pixel shift
+alone returns stage 2's warp of the rectangle shifted the other way - real neighbouring pixels; a flip alone returns the mirror.
+
 The keypoint move is written as a closed search instead of a warp of a whole image per point: a white pixel at p reaches output pixel q
 with the weight max(0, 1 - |sx - px|) max(0, 1 - |sy - py|), (sx, sy) = F^-1(q), which is zero outside the rotated unit square around
 F(p); that square lies within 1.92 pixels per axis of round(F(p)), so a 5 x 5 window holds every non-zero weight.  The first maximum
@@ -33,6 +53,10 @@ Era- and library-dependent assumptions (in the sense of the table at the top of 
   * the resize is the 8-bit resampling of the Pillow that is installed today (Resample.c: coefficients normalised in double, taps
     int(0.5 + w 2^22), a horizontal pass into 8 bits and then a vertical one, each clip8((2^21 + sum pixel k) >> 22)); the reference's
     Pillow of 2016 may have rounded differently.  Held by tests/test_faces_host.py::test_resize_stage_equals_pillow_bit_for_bit.
+  * np.pad(mode="median") is written out (median_pad_np): axis 0 first, then axis 1 over all rows, the median of an even number of bytes
+    being the mean of the two middle ones rounded half to even.  That is the numpy installed today (2.2: np.median's mean in double,
+    then ndarray.round); the numpy of 2016 is recalled to behave the same.  Held by
+    tests/test_faces_variants_host.py::test_median_fill_equals_numpy_pad.
 """
 import math
 
@@ -307,6 +331,132 @@ def extract_faces_device(images, geoms, out=64):
     tensor.lib().faces_u8_extract(tensor.stream(), src.data_ptr(), src.numel(), src_off.data_ptr(), geom.data_ptr(), inv.data_ptr(),
                                   taps.data_ptr(), d["taps"].size, tap_off.data_ptr(), dst.data_ptr(), N, out, ws.data_ptr(), wsb)
     return dst.cpu().numpy()
+
+
+# ---------------------------------------------------------------- the variants out of the padded crop
+def _median_u8(a, axis):
+    """The median of 8-bit samples along `axis`, kept as a dimension of 1: the middle one, or the mean of the two middle ones rounded
+    half to even, in integers."""
+    srt = np.sort(np.asarray(a, np.uint8), axis=axis).astype(np.int32)
+    L = srt.shape[axis]
+    t = np.take(srt, [(L - 1) // 2], axis=axis) + np.take(srt, [L // 2], axis=axis)
+    m = t >> 1
+    return (m + ((t & 1) & (m & 1))).astype(np.uint8)
+
+
+def median_pad_np(win, top, left, bottom, right):
+    """np.pad(win, ((top, bottom), (left, right), (0, 0)), mode="median") for an 8-bit [H, W, 3] array, written out (dataset.py:228):
+    axis 0 first - every column gets, per channel, the median of that column over win's rows - then axis 1 over ALL rows of the
+    result, the rows just filled included, which is how the corners get their values."""
+    win = np.asarray(win, np.uint8)
+    H, W, _ = win.shape
+    P = np.empty((H + top + bottom, W + left + right, 3), np.uint8)
+    P[top:top + H, left:left + W] = win
+    if top or bottom:
+        m = _median_u8(win, 0)                                          # [1, W, 3]
+        P[:top, left:left + W] = m
+        P[top + H:, left:left + W] = m
+    if left or right:
+        m = _median_u8(P[:, left:left + W], 1)                          # [Hp, 1, 3]
+        P[:, :left] = m
+        P[:, left + W:] = m
+    return P
+
+
+def crop_pads(Hs, Ws, rect, pad):
+    """(top, left, bottom, right): how far the rectangle enlarged by `pad` leaves its Hs x Ws image on each side (dataset.py:206-226)."""
+    y0, x0, Hr, Wr = rect
+    return (max(0, pad - y0), max(0, pad - x0), max(0, y0 + Hr - 1 + pad - (Hs - 1)), max(0, x0 + Wr - 1 + pad - (Ws - 1)))
+
+
+def padded_crop_np(img, inv, rect, pad):
+    """Stage a: extract_rectangle(pad) (dataset.py:191-230) out of the de-rotated image, uint8 [Hr + 2 pad, Wr + 2 pad, 3] - warp_rect_np
+    over the enlarged rectangle clipped to the image, then the median fill of the sides that left it."""
+    Hs, Ws = np.asarray(img).shape[:2]
+    y0, x0, Hr, Wr = rect
+    top, left, bottom, right = crop_pads(Hs, Ws, rect, pad)
+    win = warp_rect_np(img, inv, (y0 - pad + top, x0 - pad + left, Hr + 2 * pad - top - bottom, Wr + 2 * pad - left - right))
+    return median_pad_np(win, top, left, bottom, right)
+
+
+def noise_scale(noise_std):
+    """s of the pixel stage: 255 noise_std, rounded to fp32 once."""
+    return np.float32(255.0 * float(noise_std))
+
+
+def variant_pixels_np(P, brightness, flip, scale, seed, base):
+    """Stage b on the whole padded crop: q = (u8) clip(fl(fl(P[y][flip ? Wp-1-x : x][c] brightness) + fl(scale z)), 0, 255) truncated
+    (NaN -> 0), z = dataset.augment_noise(seed, base, j), j = (y Wp + x) 3 + c on the flipped array; the noise term is left out for
+    scale == 0."""
+    from .dataset import augment_noise
+    f32 = np.float32
+    P = np.asarray(P, np.uint8)
+    v = (P[:, ::-1] if flip != 0 else P).astype(f32) * f32(brightness)
+    if f32(scale) != 0:
+        v = v + f32(scale) * augment_noise(seed, base, np.arange(P.size, dtype=np.uint64).reshape(P.shape))
+    with np.errstate(invalid="ignore"):
+        v = np.where(~(v >= f32(0)), f32(0), np.where(v > f32(255), f32(255), v)).astype(f32)
+    return v.astype(np.int32).astype(np.uint8)
+
+
+def variant_warp_np(q, m, pad):
+    """Stage c: warp_rect_np's arithmetic on the pixel stage q [Hp, Wp, 3] with the inverse entries m [6], over the window
+    [pad, pad + Hr) x [pad, pad + Wr): uint8 [Hr, Wr, 3]."""
+    Hp, Wp, _ = q.shape
+    return warp_rect_np(q, m, (pad, pad, Hp - 2 * pad, Wp - 2 * pad))
+
+
+def variants_np(img, inv, rect, pad, desc, bases, scale, seed, out=64):
+    """The variants of one face, uint8 [A, out, out, 3]: stages a-d for the descriptors desc [A, 8] (m00 .. m12 of the inverse for the
+    PADDED crop's size, brightness, flip: dataset.augment_descriptors(A, Hp, Wp, draw)) and the counter bases [A].  The yardstick of
+    cg_faces_u8_extract_variants."""
+    P = padded_crop_np(img, inv, rect, pad)
+    desc = np.asarray(desc, np.float32)
+    res = np.empty((len(desc), out, out, 3), np.uint8)
+    for a, d in enumerate(desc):
+        q = variant_pixels_np(P, d[6], d[7], scale, seed, int(bases[a]))
+        res[a] = resize_np(variant_warp_np(q, d[:6], pad), out)
+    return res
+
+
+def variant_bytes(rect, pad, A, out):
+    """Device bytes that one face's variants take beside its source: the padded crop, the horizontal passes' results and the output."""
+    _, _, Hr, Wr = rect
+    return -(-(3 * (Hr + 2 * pad) * (Wr + 2 * pad)) // 16) * 16 + 3 * A * out * (Hr + out)
+
+
+def variants_workspace_bytes(rects, pad, A, out):
+    """cg_faces_u8_extract_variants' workspace for faces with the rectangles `rects` (catgan.h)."""
+    return 48 * len(rects) + 256 + sum(variant_bytes(r, pad, A, out) - 3 * A * out * out for r in rects)
+
+
+def extract_variants_device(images, geoms, pad, desc, bases, scale, seed, out=64, with_faces=False):
+    """cg_faces_u8_extract_variants over one batch: desc float32 [N, A, 8], bases uint64 [N, A] -> uint8 [N, A, out, out, 3] on the
+    host.  with_faces also runs cg_faces_u8_extract over the same upload and returns (faces [N, out, out, 3], variants)."""
+    import torch
+    from . import tensor
+    d = pack_descriptors([im.shape[:2] for im in images], geoms, out)
+    desc, bases = np.ascontiguousarray(desc, np.float32), np.ascontiguousarray(bases, np.uint64)
+    N, A = bases.shape
+    assert N == len(images) and desc.shape == (N, A, 8)
+    dev, lib, s = tensor.device(), tensor.lib(), tensor.stream()
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+    src = up(np.concatenate([np.ascontiguousarray(im, dtype=np.uint8).reshape(-1) for im in images]))
+    src_off, geom, inv, taps, tap_off, ddesc, dbases = (up(a) for a in (d["src_off"], d["geom"], d["inv"], d["taps"], d["tap_off"], desc, bases))
+    wsb = max(variants_workspace_bytes([g["rect"] for g in geoms], pad, A, out), workspace_bytes(N, out, d["rows"]))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    faces = None
+    if with_faces:
+        fdst = torch.empty((N, out, out, 3), dtype=torch.uint8, device=dev)
+        lib.faces_u8_extract(s, src.data_ptr(), src.numel(), src_off.data_ptr(), geom.data_ptr(), inv.data_ptr(), taps.data_ptr(),
+                             d["taps"].size, tap_off.data_ptr(), fdst.data_ptr(), N, out, ws.data_ptr(), wsb)
+        faces = fdst.cpu().numpy()
+    dst = torch.empty((N, A, out, out, 3), dtype=torch.uint8, device=dev)
+    lib.faces_u8_extract_variants(s, src.data_ptr(), src.numel(), src_off.data_ptr(), geom.data_ptr(), inv.data_ptr(), taps.data_ptr(),
+                                  d["taps"].size, tap_off.data_ptr(), pad, A, ddesc.data_ptr(), dbases.data_ptr(), float(scale), int(seed),
+                                  dst.data_ptr(), N, out, ws.data_ptr(), wsb)
+    v = dst.cpu().numpy()
+    return (faces, v) if with_faces else v
 
 
 # ---------------------------------------------------------------- a synthetic raw tree (tests, scripts/faces_bench.py)

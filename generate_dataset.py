@@ -10,11 +10,18 @@ with one warning line - and consumes no index - when it has no .cat file, its .c
 pixel, or its rectangle is degenerate (no rectangle the reference would accept, or a side under 8 pixels).  Two runs over the same input
 write byte-identical files.
 
-out_aug_SxS also gets --augmentations variants NNNNNN_001 ... per face.  They are the project's own augmentation
-(dataset.augment_descriptors and cg_images_u8_augment_to_f32 at equal source and target size, colour space rgb, re-quantised by
-(u8)(v 255 + 0.5), draws seeded by --seed) and differ from the reference's nine in that they are warped from the finished S x S face with
-edge replication, not from the padded full-resolution crop.  The recommended use is --augmentations 0 together with the trainers'
---augment, which draws fresh variants for every epoch pool.
+out_aug_SxS also gets --augmentations variants NNNNNN_001 ... per face, their draws seeded by --seed, made in one of two ways:
+  --variantsFrom face (the default)  the project's own augmentation of the finished face (dataset.augment_descriptors and
+      cg_images_u8_augment_to_f32 at equal source and target size, colour space rgb, re-quantised by (u8)(v 255 + 0.5)): warped from
+      the S x S face with edge replication, so rotated and shifted borders show smeared edge pixels; refused where S S 12 bytes
+      exceed the augmentation kernel's LDS (S of about 117 and up);
+  --variantsFrom crop  the reference's way (faces.py, stages a-d; cg_faces_u8_extract_variants): the rectangle is cut out with
+      --padding (30) pixels of real image around it, median-filled where that leaves the image, the pixel stage and the warp run at
+      full resolution, then the padding comes off and the result is resized - the borders show real fur and background.  Every
+      --scale works.  The draws are dataset.augment_draw's, not the reference's `random` stream.
+The _000 faces and out_unaug_SxS do not depend on the mode.  The trainers' --augment still warps finished faces whichever way the set was
+made; serving it from padded faces is a later step.  --augmentations 0 together with --augment, which draws fresh variants for every
+epoch pool, remains the cheapest use.
 
     python generate_dataset.py --path /data/10k_cats --augmentations 0 --pack
 """
@@ -34,6 +41,7 @@ sys.path.insert(0, ROOT)
 BATCH_BYTES = 256 << 20      # decoded source bytes per device call: batches are bounded by bytes, the images differ in size
 MAX_THREADS = 16
 LOOKAHEAD = 64               # files being decoded, or decoded and waiting for their batch
+VARIANT_BYTES = 256 << 20    # sources, crops, horizontal passes and variants per device call with --variantsFrom crop: all but the first grow with --augmentations
 MIN_SIDE = 8                 # cg_faces_u8_extract's smallest rectangle side
 
 
@@ -45,11 +53,16 @@ def parse(argv=None):
     ap.add_argument("--augmentations", type=int, default=9, help="variants per face in out_aug_SxS, beside _000")
     ap.add_argument("--threads", type=int, default=8, help="decoding threads (at most 16); the files do not depend on their number")
     ap.add_argument("--seed", type=int, default=42, help="seed of the variants' draws")
+    ap.add_argument("--variantsFrom", choices=("face", "crop"), default="face",
+                    help="what the variants are warped from: the finished face (edge replication) or the padded full-resolution crop (the reference's way)")
+    ap.add_argument("--padding", type=int, default=30, help="pixels kept around the face rectangle for --variantsFrom crop (0..64)")
     ap.add_argument("--host", action="store_true", help="compute the faces with the numpy restatement: no GPU, no library")
     ap.add_argument("--pack", action="store_true", help="finish with dataset.buildPack on out_aug_SxS (pack_dataset.py)")
     o = ap.parse_args(argv)
     if o.threads < 1 or not 8 <= o.scale <= 128 or not 0 <= o.augmentations <= 999:
         ap.error("--threads must be positive, --scale in 8..128, --augmentations in 0..999")
+    if not 0 <= o.padding <= 64:
+        ap.error("--padding must be in 0..64")
     return o
 
 
@@ -112,14 +125,48 @@ def _variants(face, index, n, noise_seed, host):
     return (v * np.float32(255.0) + np.float32(0.5)).astype(np.int32).astype(np.uint8)
 
 
+def _crop_variants(batch, index0, A, pad, S, noise_seed, host):
+    """--variantsFrom crop for the faces of one flush, (fp, image, geometry) each, the first of them face `index0` of the set:
+    (faces [n, S, S, 3] or None on the host, variants [n, A, S, S, 3]).  Every face draws as _variants draws; the counter base of
+    variant a of face i is (i A + a) 2^32, so nothing depends on how the faces were batched.  The device calls are bounded by
+    VARIANT_BYTES."""
+    F = importlib.import_module("cat-generator_amd.faces")
+    ds = importlib.import_module("cat-generator_amd.dataset")
+    n = len(batch)
+    desc, bases = np.empty((n, A, 8), np.float32), np.empty((n, A), np.uint64)
+    scale = None
+    for i, (_, _, g) in enumerate(batch):
+        draw = ds.augment_draw(A)
+        desc[i] = ds.augment_descriptors(A, g["rect"][2] + 2 * pad, g["rect"][3] + 2 * pad, draw)
+        bases[i] = [((index0 + i) * A + a) << 32 for a in range(A)]
+        scale = F.noise_scale(draw["noise_std"])
+    if host:
+        return None, np.stack([F.variants_np(im, g["inv"], g["rect"], pad, desc[i], bases[i], scale, noise_seed, S)
+                               for i, (_, im, g) in enumerate(batch)])
+    cost = [im.nbytes + F.variant_bytes(g["rect"], pad, A, S) for _, im, g in batch]
+    faces, variants, lo = [], [], 0
+    while lo < n:
+        hi, nbytes = lo + 1, cost[lo]
+        while hi < n and nbytes + cost[hi] <= VARIANT_BYTES:
+            nbytes += cost[hi]
+            hi += 1
+        f, v = F.extract_variants_device([b[1] for b in batch[lo:hi]], [b[2] for b in batch[lo:hi]], pad, desc[lo:hi], bases[lo:hi], scale,
+                                         noise_seed, S, with_faces=True)
+        faces.append(f)
+        variants.append(v)
+        lo = hi
+    return np.concatenate(faces), np.concatenate(variants)
+
+
 def main(argv=None):
     o = parse(argv)
     from PIL import Image
     F = importlib.import_module("cat-generator_amd.faces")
     ds = importlib.import_module("cat-generator_amd.dataset")
     S, A = o.scale, o.augmentations
-    if A and S * S * 12 > ds.AUG_LDS_BYTES:
-        raise SystemExit(f"generate_dataset: variants of {S} x {S} faces do not fit the augmentation kernel's LDS; use --augmentations 0")
+    crop = A > 0 and o.variantsFrom == "crop"
+    if A and not crop and S * S * 12 > ds.AUG_LDS_BYTES:
+        raise SystemExit(f"generate_dataset: variants of {S} x {S} faces do not fit the augmentation kernel's LDS; use --variantsFrom crop or --augmentations 0")
     files = list_raw(o.path)
     if not files:
         raise SystemExit(f"generate_dataset: no CAT_*/*.jpg under {o.path}")
@@ -136,16 +183,19 @@ def main(argv=None):
         if not batch:
             return
         imgs, geoms = [b[1] for b in batch], [b[2] for b in batch]
-        if o.host:
+        faces = variants = None
+        if crop:
+            faces, variants = _crop_variants(batch, written, A, o.padding, S, noise_seed, o.host)
+        if faces is None and o.host:
             faces = np.stack([F.resize_np(F.warp_rect_np(im, g["inv"], g["rect"]), S) for im, g in zip(imgs, geoms)])
-        else:
+        elif faces is None:
             faces = F.extract_faces_device(imgs, geoms, S)
-        for face in faces:
+        for i, face in enumerate(faces):
             name = "{:0>6}_{:0>3}.jpg".format(written, 0)
             Image.fromarray(face).save(os.path.join(unaug, name))
             Image.fromarray(face).save(os.path.join(aug, name))
             if A:
-                for a, v in enumerate(_variants(face, written, A, noise_seed, o.host)):
+                for a, v in enumerate(variants[i] if crop else _variants(face, written, A, noise_seed, o.host)):
                     Image.fromarray(v).save(os.path.join(aug, "{:0>6}_{:0>3}.jpg".format(written, a + 1)))
             written += 1
 

@@ -176,6 +176,35 @@ int cg_images_u8_gather_augment_to_f32(void* stream, const unsigned char* set, l
 int cg_faces_u8_extract(void* stream, const unsigned char* src, size_t src_bytes, const uint64_t* src_off, const int32_t* geom,
                         const float* inv, const int32_t* taps, size_t ntaps, const uint64_t* tap_off, unsigned char* dst, int N, int out,
                         void* workspace, size_t workspace_bytes);
+/* The tool's AUGMENTED variants of the same faces (dataset/generate_dataset.py:62-73), warped as the reference warps them: out of the
+ * padded full-resolution crop, so that a rotated, shifted or zoomed-out variant shows the real image around the face rectangle and not
+ * replicated edge pixels.  src .. tap_off, N and out are cg_faces_u8_extract's and are checked as it checks them; dst is
+ * [N][A][out][out][3], variant a of face f from desc[f][a] and bases[f][a].  Per face (faces.variants_np is the numpy restatement):
+ *   a. padded crop P, 8 bits, [Hp = Hr + 2 pad][Wp = Wr + 2 pad][3] (extract_rectangle, dataset.py:191-230): cell (cy, cx) is the warp
+ *      above at the image position (y0 - pad + cy, x0 - pad + cx) where that lies inside the image.  The sides that leave it - top =
+ *      max(0, pad - y0), left = max(0, pad - x0), bottom = max(0, y0 + Hr - 1 + pad - (Hs - 1)), right likewise - are filled as
+ *      np.pad(mode="median") fills them: axis 0 first (per column of the in-image window and per channel, the median over the window's
+ *      rows), then axis 1 over ALL rows, those just filled included, which is where the corners get their values.  The median of L
+ *      bytes is the middle one for odd L and otherwise the mean of the two middle ones rounded half to even (t = a + b, m = t >> 1,
+ *      m += (t & 1) & (m & 1)); it comes from a histogram of integer counts, so no order of additions can change it;
+ *   b. pixel stage of variant a (dataset.py:284-304, re-quantised as the tool re-quantises):
+ *      v = fl(fl((float)P[y][flip ? Wp-1-x : x][c] * brightness) + fl(noise_scale * z)), z the noise of cg_images_u8_augment_to_f32 for
+ *      `seed` at the counters bases[f][a] + 3 j + {1, 2, 3}, j = (y Wp + x) 3 + c (the position on the array the warp reads; the term is
+ *      left out for noise_scale == 0); q = (u8) of v clipped to [0, 255] (NaN -> 0), truncated.  noise_scale is 255 noise_std, rounded
+ *      to fp32 once by the caller;
+ *   c. warp (dataset.py:306-307): the fp32 warp above on p = q / 255 with (m00 .. m12) = desc[f][a][0..5], the inverse of
+ *      ImageAugmenter's matrix for the PADDED crop's size, clamped to the padded crop; r = (u8)(w * 255), truncated; evaluated on the
+ *      window [pad, pad + Hr) x [pad, pad + Wr) only - the warp is pointwise, so this is unpad(pad) (:145-150) of the whole;
+ *   d. the resize above, r -> out x out.
+ * desc [N][A][8] float: m00 m01 m02 m10 m11 m12 brightness flip (cg_images_u8_augment_to_f32's layout); bases [N][A] uint64.
+ * workspace: at least 48 N + 256 + sum_f ceil16(3 Hp Wp) + 3 A out sum_f Hr bytes - the launch maps, the padded crops and the
+ * horizontal passes' results.  Like cg_faces_u8_extract it reads its descriptors back, synchronises the stream and cannot be captured.
+ * Errors, all before any launch: cg_faces_u8_extract's; a null desc or bases; pad outside 0..64; A outside 1..999; a padded side beyond
+ * 4096 + 2 * 64; noise_scale negative or not finite; N A too large for one launch; a workspace too small.  dst is untouched on error. */
+int cg_faces_u8_extract_variants(void* stream, const unsigned char* src, size_t src_bytes, const uint64_t* src_off, const int32_t* geom,
+                                 const float* inv, const int32_t* taps, size_t ntaps, const uint64_t* tap_off, int pad, int A,
+                                 const float* desc, const uint64_t* bases, float noise_scale, uint64_t seed, unsigned char* dst, int N, int out,
+                                 void* workspace, size_t workspace_bytes);
 /* NN_UTILS.rgbToColorSpace / NN_UTILS.toRgb (utils/nn_utils.lua:188-249) on fp32 NHWC pixels that are already on the device: three
  * floats in per pixel, three out (one for to == 1).  from / to are the colorspace codes above; the pairs are rgb -> y | yuv | hsl and
  * yuv | hsl -> rgb, anything else is an error.  src == dst is allowed when three planes come out.  Per pixel, every operation a single
