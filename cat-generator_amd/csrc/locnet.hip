@@ -950,6 +950,9 @@ int cg_locnet_backward(void* stream, int ngroups, int n_per_group, const float* 
     CG_REQUIRE(weights && h1 && m2 && h3 && params && ggrid && ga1 && ga2 && g3 && g4 && gx, "cg_locnet_backward: null pointer");
     CG_REQUIRE(ngroups >= 1 && ngroups <= 4 && n_per_group > 0, "cg_locnet_backward: %d groups of %d samples", ngroups, n_per_group);
     CG_REQUIRE(cg_locnet_supported(S, Cin, P), "cg_locnet_backward: S %d Cin %d P %d not supported", S, Cin, P);
+    CG_REQUIRE(P == (use_rot ? 1 : 0) + (use_scale ? 1 : 0) + (use_trans ? 2 : 0), "cg_locnet_backward: P does not match the transform");
+    // the kernels decide LeakyReLU's side on the stored activations h1, m2, h3; only a positive slope keeps the sign of the layer's input
+    CG_REQUIRE(slope > 0.f, "cg_locnet_backward: slope %g: the backward takes slope > 0 (use the modules)", (double)slope);
     LocBwd a;
     for (int g = 0; g < ngroups; ++g) {
         const float* const* w = weights + 12 * g;

@@ -1264,6 +1264,7 @@ struct Compiler {
         if (M(L.kids[6]).ia[7] != 1 || M(L.kids[6]).ia[0] != K3 || d.lin1->ia[0] != K3 || d.lin1->ia[1] != 64 || d.lin2->ia[0] != 64) return false;
         d.slope = M(L.kids[2]).fa[0];
         if (M(L.kids[4]).fa[0] != d.slope || M(L.kids[8]).fa[0] != d.slope) return false;
+        if (!(d.slope > 0.f)) return false;   // cg_locnet_backward reads LeakyReLU's side off the stored activations: slope > 0 only
         const Mod &am = M(q.kids[1]), &ag = M(q.kids[2]);
         d.ur = (int)am.ia[0]; d.us = (int)am.ia[1]; d.ut = (int)am.ia[2]; d.Hg = (int)ag.ia[0]; d.Wg = (int)ag.ia[1];
         if (d.P != d.ur + d.us + 2 * d.ut) return false;

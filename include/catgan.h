@@ -662,7 +662,9 @@ int cg_bilinear_sampler_backward_shared(void* stream, int ngroups, const float* 
  * h2 = its 2x2 average in (c, y, x) order [G n][16 (S/2)^2], h3 = LeakyReLU(linear1) [G n][64], params [G n][P].
  * backward: ggrid -> gx [G n][2S][2S][Cin] (gradient w.r.t. the transformer's input through the localisation branch) and the
  * gradients w.r.t. the pre-activations: g4 [G n][P], g3 [G n][64], ga2 / ga1 [G n][S][S][16] - the weight gradients are
- * cg_conv2d_wgrad(pooled, ga1), (h1, ga2), (h2, g3) and (h3, g4) with the layers' geometries. */
+ * cg_conv2d_wgrad(pooled, ga1), (h1, ga2), (h2, g3) and (h3, g4) with the layers' geometries.  The backward decides LeakyReLU's
+ * side on the stored activations (h1, m2, h3 >= 0), which is the side of the layer's input only for slope > 0: it refuses any
+ * other slope, and the planner walks the ten modules then.  The forward takes any slope. */
 int cg_locnet_supported(int S, int Cin, int P);
 int cg_locnet_forward(void* stream, int ngroups, int n_per_group, const float* x, int x_shared, const float* const* weights, int S, int Cin,
                       int P, int use_rot, int use_scale, int use_trans, float slope, int Hg, int Wg, float* pooled, float* h1, float* m2,
