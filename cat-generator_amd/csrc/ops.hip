@@ -380,25 +380,33 @@ __global__ void images_u8_gather_scale_k(const unsigned char* __restrict__ set, 
 }
 
 // The same with the reference's augmentation in front (dataset/dataset.py:284-306 with the matrices of ImageAugmenter.py:160-190;
-// semantics under cg_images_u8_augment_to_f32 in catgan.h, numpy restatement dataset.augment_images).  One workgroup per image.
-// Phase 1 leaves the pixel stage p (flip, brightness, noise, clip) of the whole source image in the LDS as fp32, [Hs][Ws][3], so that a
-// noise value is hashed once and not once per bilinear tap of every box-filter sample that touches it.  Phase 2 is
-// images_u8_scale_k's walk, one lane per output element, whose source samples are the four warp taps out of the LDS.
+// semantics under cg_images_u8_augment_to_f32 and cg_images_u8_augment_window_to_f32 in catgan.h, numpy restatement
+// dataset.augment_images).  One workgroup per image.  Phase 1 leaves the pixel stage p (flip, brightness, noise, clip) of the whole
+// padded source image in the LDS as fp32, [Hp][Wp][3], so that a noise value is hashed once and not once per bilinear tap of every
+// box-filter sample that touches it.  Phase 2 is images_u8_scale_k's walk over the window [margin, margin + Hs) x [margin, margin + Ws),
+// one lane per output element, whose source samples are the four warp taps out of the LDS; the margin is what a tap may reach before
+// it is clamped.  margin == 0: the window is the image, the form without a margin.
 using cg::augment_noise;
 using cg::warp_taps;
 // image n of the pool (this workgroup's) from the one source image `im`: both augmentation kernels' whole arithmetic.  n, not the
-// image's place in its set, numbers the noise counters
-__device__ __forceinline__ void augment_image(const unsigned char* __restrict__ im, long n, float* __restrict__ dst, int Hs, int Ws, int Hd, int Wd,
-                                              int cs, const float* __restrict__ desc, float sigma, uint64_t seed, uint64_t offset) {
+// image's place in its set, numbers the noise counters.  desc == nullptr: the identity draw (1 0 0 0 1 0 1 0) for every image
+__device__ __forceinline__ void augment_image(const unsigned char* __restrict__ im, long n, float* __restrict__ dst, int Hp, int Wp, int margin,
+                                              int Hd, int Wd, int cs, const float* __restrict__ desc, float sigma, uint64_t seed,
+                                              uint64_t offset) {
 #pragma clang fp contract(off)
-    extern __shared__ float aug_p[];   // [Hs][Ws][3]
-    const float* d = desc + n * 8;
-    const float m00 = d[0], m01 = d[1], m02 = d[2], m10 = d[3], m11 = d[4], m12 = d[5], bright = d[6];
-    const bool flip = d[7] != 0.f;
-    const int row3 = Ws * 3, nsrc = Hs * row3;
+    extern __shared__ float aug_p[];   // [Hp][Wp][3]
+    float m00 = 1.f, m01 = 0.f, m02 = 0.f, m10 = 0.f, m11 = 1.f, m12 = 0.f, bright = 1.f;
+    bool flip = false;
+    if (desc) {
+        const float* d = desc + n * 8;
+        m00 = d[0]; m01 = d[1]; m02 = d[2]; m10 = d[3]; m11 = d[4]; m12 = d[5]; bright = d[6];
+        flip = d[7] != 0.f;
+    }
+    const int Hs = Hp - 2 * margin, Ws = Wp - 2 * margin;
+    const int row3 = Wp * 3, nsrc = Hp * row3;
     for (int k = threadIdx.x; k < nsrc; k += 256) {
         const int y = k / row3, r = k - y * row3, x = r / 3, c = r - x * 3;
-        const int xf = flip ? Ws - 1 - x : x;
+        const int xf = flip ? Wp - 1 - x : x;
         float v = __fdiv_rn((float)im[y * row3 + xf * 3 + c], 255.f) * bright;
         if (sigma != 0.f) {
             const float t = sigma * augment_noise(seed, offset + 3ull * (uint64_t)(n * nsrc + k));
@@ -434,11 +442,12 @@ __device__ __forceinline__ void augment_image(const unsigned char* __restrict__ 
         for (int y = y0; y <= y1 && y - y0 < 8; ++y) {
             float row[3][8];
             for (int x = x0; x <= x1 && x - x0 < 8; ++x) {
-                const float ax = m00 * (float)x, bx = m01 * (float)y, ay = m10 * (float)x, by = m11 * (float)y;
+                const float X = (float)(x + margin), Y = (float)(y + margin);      // window sample (x, y) at its padded position
+                const float ax = m00 * X, bx = m01 * Y, ay = m10 * X, by = m11 * Y;
                 int tx0, tx1, ty0, ty1;
                 float fx, fy;
-                warp_taps((ax + bx) + m02, Ws, &tx0, &tx1, &fx);
-                warp_taps((ay + by) + m12, Hs, &ty0, &ty1, &fy);
+                warp_taps((ax + bx) + m02, Wp, &tx0, &tx1, &fx);
+                warp_taps((ay + by) + m12, Hp, &ty0, &ty1, &fy);
                 const float gx = 1.f - fx, gy = 1.f - fy;
                 const float *p00 = aug_p + ty0 * row3 + tx0 * 3, *p01 = aug_p + ty0 * row3 + tx1 * 3;
                 const float *p10 = aug_p + ty1 * row3 + tx0 * 3, *p11 = aug_p + ty1 * row3 + tx1 * 3;
@@ -459,15 +468,15 @@ __device__ __forceinline__ void augment_image(const unsigned char* __restrict__ 
         store_colorspace(dst, n * (long)Hd * Wd + e, rgb[0], rgb[1], rgb[2], cs);
     }
 }
-__global__ void __launch_bounds__(256) images_u8_augment_k(const unsigned char* __restrict__ src, float* __restrict__ dst, int Hs, int Ws,
-                                                            int Hd, int Wd, int cs, const float* __restrict__ desc, float sigma,
+__global__ void __launch_bounds__(256) images_u8_augment_k(const unsigned char* __restrict__ src, float* __restrict__ dst, int Hp, int Wp,
+                                                            int margin, int Hd, int Wd, int cs, const float* __restrict__ desc, float sigma,
                                                             uint64_t seed, uint64_t offset) {
     const long n = blockIdx.x;
-    augment_image(src + n * (long)Hs * Ws * 3, n, dst, Hs, Ws, Hd, Wd, cs, desc, sigma, seed, offset);
+    augment_image(src + n * (long)Hp * Wp * 3, n, dst, Hp, Wp, margin, Hd, Wd, cs, desc, sigma, seed, offset);
 }
 // the gather form (images_u8_gather_scale_k's addressing): the whole workgroup takes the same branch, so the barrier inside stays uniform
 __global__ void __launch_bounds__(256) images_u8_gather_augment_k(const unsigned char* __restrict__ set, long M, const int32_t* __restrict__ idx,
-                                                                   float* __restrict__ dst, int Hs, int Ws, int Hd, int Wd, int cs,
+                                                                   float* __restrict__ dst, int Hp, int Wp, int margin, int Hd, int Wd, int cs,
                                                                    const float* __restrict__ desc, float sigma, uint64_t seed, uint64_t offset) {
     const long n = blockIdx.x;
     const long m = idx[n];
@@ -475,7 +484,7 @@ __global__ void __launch_bounds__(256) images_u8_gather_augment_k(const unsigned
         for (int e = threadIdx.x; e < Hd * Wd; e += 256) store_zero_pixel(dst, n * (long)Hd * Wd + e, cs);
         return;
     }
-    augment_image(set + m * ((long)Hs * Ws * 3), n, dst, Hs, Ws, Hd, Wd, cs, desc, sigma, seed, offset);
+    augment_image(set + m * ((long)Hp * Wp * 3), n, dst, Hp, Wp, margin, Hd, Wd, cs, desc, sigma, seed, offset);
 }
 
 // ---------------------------------------------------------------- activations
@@ -1542,7 +1551,7 @@ int cg_images_u8_scale_to_f32(void* stream, const unsigned char* src, float* dst
 
 // the pixel stage of one image in the LDS: 64 x 64 sources take 48 KB (three workgroups per CU); above 64 KB a kernel has to ask.  Both
 // augmentation kernels ask together, so one record per thread serves them
-static int augment_lds(const char* who, int Hs, int Ws, long* lds_out) {
+static int augment_lds(const char* who, int Hp, int Wp, long* lds_out) {
     static thread_local int lds_dev = -1, lds_max = 0, lds_asked = 0;
     int dev = 0;
     CG_HIP(hipGetDevice(&dev));
@@ -1550,8 +1559,8 @@ static int augment_lds(const char* who, int Hs, int Ws, long* lds_out) {
         CG_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
         lds_dev = dev; lds_asked = 0;
     }
-    const long lds = (long)Hs * Ws * 3 * sizeof(float);
-    CG_REQUIRE(lds <= lds_max, "%s: a %d x %d source needs %ld bytes of LDS, the device has %d per workgroup", who, Ws, Hs, lds, lds_max);
+    const long lds = (long)Hp * Wp * 3 * sizeof(float);
+    CG_REQUIRE(lds <= lds_max, "%s: a %d x %d source needs %ld bytes of LDS, the device has %d per workgroup", who, Wp, Hp, lds, lds_max);
     if (lds > 65536 && lds > lds_asked) {
         CG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(images_u8_augment_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
         CG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(images_u8_gather_augment_k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max));
@@ -1560,16 +1569,34 @@ static int augment_lds(const char* who, int Hs, int Ws, long* lds_out) {
     *lds_out = lds;
     return 0;
 }
+// the four augmentation entry points' checks beyond their pointers, and the LDS: the shrink limit is the window's, the LDS the padded
+// array's.  The forms without a margin pass 0 and insist on a descriptor buffer themselves
+static int augment_check(const char* who, int N, int Hp, int Wp, int margin, int Hd, int Wd, int colorspace, float noise_std, long* lds_out) {
+    CG_REQUIRE(N > 0 && Hp > 0 && Wp > 0 && Hd > 0 && Wd > 0 && colorspace >= CS_RGB && colorspace <= CS_HSL && noise_std >= 0.f,
+               "%s: bad arguments", who);
+    CG_REQUIRE(margin >= 0 && margin <= (std::min(Hp, Wp) - 1) / 2, "%s: a margin of %d leaves no window in a %d x %d padded image", who,
+               margin, Wp, Hp);
+    CG_REQUIRE(Hp - 2 * margin <= 6 * Hd && Wp - 2 * margin <= 6 * Wd, "%s: down-scaling by more than 6 is not supported", who);
+    return augment_lds(who, Hp, Wp, lds_out);
+}
 
+int cg_images_u8_augment_window_to_f32(void* stream, const unsigned char* src, float* dst, int N, int Hp, int Wp, int margin, int Hd, int Wd,
+                                       int colorspace, const float* desc, float noise_std, uint64_t seed, uint64_t offset) {
+    CG_REQUIRE(src && dst, "cg_images_u8_augment_window_to_f32: bad arguments");
+    long lds = 0;
+    if (int rc = augment_check("cg_images_u8_augment_window_to_f32", N, Hp, Wp, margin, Hd, Wd, colorspace, noise_std, &lds)) return rc;
+    hipLaunchKernelGGL(images_u8_augment_k, dim3(N), dim3(256), (size_t)lds, cg::S(stream), src, dst, Hp, Wp, margin, Hd, Wd, colorspace, desc,
+                       noise_std, seed, offset);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
 int cg_images_u8_augment_to_f32(void* stream, const unsigned char* src, float* dst, int N, int Hs, int Ws, int Hd, int Wd, int colorspace,
                                 const float* desc, float noise_std, uint64_t seed, uint64_t offset) {
-    CG_REQUIRE(src && dst && desc && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && colorspace >= CS_RGB && colorspace <= CS_HSL &&
-               noise_std >= 0.f, "cg_images_u8_augment_to_f32: bad arguments");
-    CG_REQUIRE(Hs <= 6 * Hd && Ws <= 6 * Wd, "cg_images_u8_augment_to_f32: down-scaling by more than 6 is not supported");
+    CG_REQUIRE(src && dst && desc, "cg_images_u8_augment_to_f32: bad arguments");
     long lds = 0;
-    if (int rc = augment_lds("cg_images_u8_augment_to_f32", Hs, Ws, &lds)) return rc;
-    hipLaunchKernelGGL(images_u8_augment_k, dim3(N), dim3(256), (size_t)lds, cg::S(stream), src, dst, Hs, Ws, Hd, Wd, colorspace, desc, noise_std,
-                       seed, offset);
+    if (int rc = augment_check("cg_images_u8_augment_to_f32", N, Hs, Ws, 0, Hd, Wd, colorspace, noise_std, &lds)) return rc;
+    hipLaunchKernelGGL(images_u8_augment_k, dim3(N), dim3(256), (size_t)lds, cg::S(stream), src, dst, Hs, Ws, 0, Hd, Wd, colorspace, desc,
+                       noise_std, seed, offset);
     CG_LAUNCH_CHECK();
     return 0;
 }
@@ -1583,15 +1610,24 @@ int cg_images_u8_gather_scale_to_f32(void* stream, const unsigned char* set, lon
     EW_LAUNCH(images_u8_gather_scale_k, total, set, M, idx, dst, N, Hs, Ws, Hd, Wd, colorspace); return 0;
 }
 
+int cg_images_u8_gather_augment_window_to_f32(void* stream, const unsigned char* set, long M, const int32_t* idx, float* dst, int N, int Hp,
+                                              int Wp, int margin, int Hd, int Wd, int colorspace, const float* desc, float noise_std,
+                                              uint64_t seed, uint64_t offset) {
+    CG_REQUIRE(set && idx && dst && M > 0, "cg_images_u8_gather_augment_window_to_f32: bad arguments");
+    long lds = 0;
+    if (int rc = augment_check("cg_images_u8_gather_augment_window_to_f32", N, Hp, Wp, margin, Hd, Wd, colorspace, noise_std, &lds)) return rc;
+    hipLaunchKernelGGL(images_u8_gather_augment_k, dim3(N), dim3(256), (size_t)lds, cg::S(stream), set, M, idx, dst, Hp, Wp, margin, Hd, Wd,
+                       colorspace, desc, noise_std, seed, offset);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
 int cg_images_u8_gather_augment_to_f32(void* stream, const unsigned char* set, long M, const int32_t* idx, float* dst, int N, int Hs, int Ws,
                                        int Hd, int Wd, int colorspace, const float* desc, float noise_std, uint64_t seed, uint64_t offset) {
-    CG_REQUIRE(set && idx && dst && desc && M > 0 && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && colorspace >= CS_RGB &&
-               colorspace <= CS_HSL && noise_std >= 0.f, "cg_images_u8_gather_augment_to_f32: bad arguments");
-    CG_REQUIRE(Hs <= 6 * Hd && Ws <= 6 * Wd, "cg_images_u8_gather_augment_to_f32: down-scaling by more than 6 is not supported");
+    CG_REQUIRE(set && idx && dst && desc && M > 0, "cg_images_u8_gather_augment_to_f32: bad arguments");
     long lds = 0;
-    if (int rc = augment_lds("cg_images_u8_gather_augment_to_f32", Hs, Ws, &lds)) return rc;
-    hipLaunchKernelGGL(images_u8_gather_augment_k, dim3(N), dim3(256), (size_t)lds, cg::S(stream), set, M, idx, dst, Hs, Ws, Hd, Wd, colorspace,
-                       desc, noise_std, seed, offset);
+    if (int rc = augment_check("cg_images_u8_gather_augment_to_f32", N, Hs, Ws, 0, Hd, Wd, colorspace, noise_std, &lds)) return rc;
+    hipLaunchKernelGGL(images_u8_gather_augment_k, dim3(N), dim3(256), (size_t)lds, cg::S(stream), set, M, idx, dst, Hs, Ws, 0, Hd, Wd,
+                       colorspace, desc, noise_std, seed, offset);
     CG_LAUNCH_CHECK();
     return 0;
 }

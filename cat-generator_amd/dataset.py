@@ -21,6 +21,13 @@ search of sample.py --neighbours (nn_utils.findClosestNeighboursOnDevice), which
 setAugmentation turns on the augmentation the reference only has as an offline tool (dataset/generate_dataset.py): both loaders then
 draw fresh variants for every epoch pool (augment_images on the host, cg_images_u8_augment_to_f32 on the device, bit-equal).
 
+A directory of PADDED faces (generate_dataset.py --margin M: files of side S + 2 M, and a margin.json that says so) keeps M pixels of
+real image around every face.  setDirs reads the margin (dataset.margin; setMargin sets it by hand); every loader then shows the centre
+window of a file - the S x S face, byte for byte what a directory of the cropped windows gives - and the augmentation warps it out of the
+whole padded file, so that rotated, shifted and zoomed-out variants show real neighbours at their borders instead of replicated edge
+pixels (cg_images_u8_augment_window_to_f32 and its gather form serve augmented and un-augmented pools alike).  Margin 0, the default,
+changes nothing anywhere.
+
 A pack (buildPack / openPack, written by pack_dataset.py) holds a directory's files decoded once, as 8-bit RGB.  ResidentSet keeps a
 pack's pixels in device memory for the whole run and ResidentLoader makes every epoch pool a gather out of it
 (cg_images_u8_gather_scale_to_f32 / cg_images_u8_gather_augment_to_f32) on the training stream: the generator's draws and the pixel
@@ -35,6 +42,7 @@ The pack file images_u8.cgpack, all integers little endian:
           48   the freshness table: per file, in loadPaths()' sorted order, uint16 length of the base name, the base name (UTF-8), uint64
                size of the file in bytes, int64 st_mtime_ns - what openPack compares with the directory as it is now
           ...  zeros up to the pixel block: uint8 [M][Hs][Ws][3], image i = _decode(paths[i]); the file ends with it"""
+import json
 import os
 import struct
 import threading
@@ -54,11 +62,49 @@ _prefetch_state = None   # AsyncLoader: the generator's state BEFORE the pick of
 AUG_DEFAULTS = dict(hflip=True, scale=(0.93, 1.08), rotation=8, translation=4, brightness=0.15, noise_std=0.02)
 augmentation = None      # None = off, else a dict with AUG_DEFAULTS' keys
 AUG_LDS_BYTES = 160 * 1024   # gfx950's LDS per workgroup: cg_images_u8_augment_to_f32 keeps one source image there as fp32
+MARGIN_NAME = "margin.json"  # {"margin": M, "side": S} in a directory of padded faces (generate_dataset.py --margin)
+margin = 0                   # pixels of real image around the window that every file of the directories carries
+
+
+def _read_margin(d):
+    """The margin directory d declares in its margin.json; 0 without the file."""
+    path = os.path.join(d, MARGIN_NAME)
+    if not os.path.isfile(path):
+        return 0
+    try:
+        with open(path) as f:
+            m = json.load(f)["margin"]
+    except (ValueError, KeyError, TypeError) as e:
+        raise ValueError(f"{path}: not a margin file ({type(e).__name__}: {e})") from e
+    if isinstance(m, bool) or not isinstance(m, int) or m < 0:
+        raise ValueError(f"{path}: margin = {m!r}, expected a whole number >= 0")
+    return m
 
 
 def setDirs(d):
-    global dirs, paths
-    dirs, paths = list(d), None
+    """The directories of the set; their margin.json files (absent = 0) must agree and give dataset.margin."""
+    global dirs, paths, margin
+    d = list(d)
+    found = {x: _read_margin(x) for x in d}
+    if len(set(found.values())) > 1:
+        raise ValueError(f"setDirs: the directories disagree about the margin: {found}")
+    dirs, paths, margin = d, None, (next(iter(found.values())) if found else 0)
+
+
+def setMargin(m):
+    """The margin by hand (library users whose padded files come without a margin.json); setDirs overwrites it."""
+    global margin
+    if int(m) < 0:
+        raise ValueError(f"setMargin: {m}")
+    margin = int(m)
+
+
+def _window(Hp, Wp, m=None):
+    """The window's size inside an Hp x Wp padded image for the margin m (the module's unless given)."""
+    m = margin if m is None else int(m)
+    if m < 0 or 2 * m >= min(Hp, Wp):
+        raise ValueError(f"a margin of {m} leaves no window in a {Wp}x{Hp} image")
+    return Hp - 2 * m, Wp - 2 * m
 
 
 def setFileExtension(ext):
@@ -260,11 +306,13 @@ def setAugmentation(on=True, **ranges):
     device form.
 
     Deliberate differences from the offline tool: no re-quantisation to 8 bits between the stages; the warp acts on the dataset's
-    64 x 64 files, which have none of the tool's 30 px padding left, so rotated / shifted borders show replicated edge pixels;
-    numpy's seeded generator (dataset.seed) instead of Python's `random`; the noise is a bit-reproducible Irwin-Hall normal
-    (augment_noise), not numpy's.  The tool's own variants - warped from the padded full-resolution crop and re-quantised between the
-    stages - are written offline by generate_dataset.py --variantsFrom crop (faces.variants_np); this on-the-fly form warps finished
-    faces whichever way the set was made."""
+    files at the dataset's resolution, not on the full-resolution crop; numpy's seeded generator (dataset.seed) instead of Python's
+    `random`; the noise is a bit-reproducible Irwin-Hall normal (augment_noise), not numpy's.  What the warp finds beyond the face
+    depends on the set: plain S x S files (margin 0) have none of the tool's padding left, so rotated / shifted borders show replicated
+    edge pixels; a padded set (generate_dataset.py --margin M, dataset.margin) keeps M pixels of real image around every face, resized
+    with it, and the warp reads those - with AUG_DEFAULTS and S = 64 a margin of 12 is never left (tests/test_augment_margin_host.py),
+    a smaller one clamps at its own edge.  The tool's own variants - warped from the padded full-resolution crop and re-quantised
+    between the stages - are written offline by generate_dataset.py --variantsFrom crop (faces.variants_np)."""
     global augmentation
     if not on:
         augmentation = None
@@ -353,7 +401,7 @@ def _warp_taps(s, L):
     return i0, np.minimum(i0 + 1, L - 1), (s - i0.astype(f32)).astype(f32)
 
 
-def augment_images(u8_batch, desc, noise_std, seed, offset, index0=0):
+def augment_images(u8_batch, desc, noise_std, seed, offset, index0=0, margin=0):
     """The pixel stage and the warp for 8-bit RGB images [N, Hs, Ws, 3] with their descriptors [N, 8] -> float32 [N, 3, Hs, Ws], still
     on the source grid, ready for image_scale / rgbToColorSpace.  Every step is one fp32 operation in this order (the device kernel
     images_u8_augment_k performs the same sequence, so the two agree bit for bit):
@@ -362,13 +410,17 @@ def augment_images(u8_batch, desc, noise_std, seed, offset, index0=0):
       sx = (m00 x + m01 y) + m02, sy = (m10 x + m11 y) + m12, clamped to the image (edge replication); x0 = floor(sx), fx = sx - x0,
       x1 = min(x0 + 1, Ws-1), likewise y; top = (1-fx) p[y0][x0] + fx p[y0][x1], bot likewise on y1; w[y][x] = (1-fy) top + fy bot.
     An image of another size than its pool's (the loaders' host path) is passed on its own with index0 = its pool index and so
-    evaluates j with its OWN Hs, Ws: its counters may overlap a neighbour's, which is accepted - the pool is what either loader gives."""
+    evaluates j with its OWN Hs, Ws: its counters may overlap a neighbour's, which is accepted - the pool is what either loader gives.
+    With margin > 0 the batch holds PADDED images [N, Hp, Wp, 3] and everything above runs on them with Hp, Wp in place of Hs, Ws (the
+    flip, the counters j, the clamp, the descriptors' matrix) - but w is evaluated on the window only, at x = margin .. Wp-1-margin,
+    y = margin .. Hp-1-margin: float32 [N, 3, Hp - 2 margin, Wp - 2 margin], whose borders show the padding where the warp reaches it."""
     f32 = np.float32
     u8_batch, desc = np.asarray(u8_batch), np.asarray(desc, dtype=f32)
-    N, Hs, Ws, _ = u8_batch.shape
+    N, Hs, Ws, _ = u8_batch.shape      # the size the pixel stage and the taps see: the padded one
+    Hw, Ww = _window(Hs, Ws, margin)
     sigma = f32(noise_std)
-    out = np.empty((N, 3, Hs, Ws), f32)
-    xs, ys = np.arange(Ws, dtype=f32)[None, :], np.arange(Hs, dtype=f32)[:, None]
+    out = np.empty((N, 3, Hw, Ww), f32)
+    xs, ys = np.arange(margin, margin + Ww, dtype=f32)[None, :], np.arange(margin, margin + Hw, dtype=f32)[:, None]
     per = Hs * Ws * 3
     for n in range(N):
         m00, m01, m02, m10, m11, m12, bright, flip = desc[n]
@@ -391,12 +443,15 @@ def augment_images(u8_batch, desc, noise_std, seed, offset, index0=0):
 
 def _load_scaled(u8, draw=None, i=0):
     """One decoded image -> float32 [3, height, width] in rgb: image.load's floats (or, with a draw, image i of the pool augmented),
-    image.scale."""
+    image.scale.  Of a padded image (dataset.margin) it is the window that is loaded, or warped out of the whole."""
     if draw is None:
+        if margin:
+            Hw, Ww = _window(u8.shape[0], u8.shape[1])
+            u8 = u8[margin:margin + Hw, margin:margin + Ww]
         img = u8.astype(np.float32).transpose(2, 0, 1) / np.float32(255.0)      # image.load(path, 3, 'float')
     else:
         desc = augment_descriptor(draw, i, u8.shape[0], u8.shape[1])
-        img = augment_images(u8[None], desc[None], draw["noise_std"], draw["seed"], 0, index0=i)[0]
+        img = augment_images(u8[None], desc[None], draw["noise_std"], draw["seed"], 0, index0=i, margin=margin)[0]
     return image_scale(img, width, height)
 
 
@@ -422,7 +477,10 @@ class AsyncLoader:
     cg_memcpy_h2d on the copy stream -> cg_images_u8_to_f32 -> event.  The image choice and the pixel values are exactly
     loadRandomImages' (same generator, same decode, same fp32 operations), so switching loaders does not change a run.  With
     setAugmentation on (read when the loader is built) the pool's draws follow its pick on the caller's thread, the descriptors travel
-    with the 8-bit images and cg_images_u8_augment_to_f32 takes the place of the scaling kernel."""
+    with the 8-bit images and cg_images_u8_augment_to_f32 takes the place of the scaling kernel.  With dataset.margin > 0 (read when the
+    loader is built, too) the staged images are the padded ones and cg_images_u8_augment_window_to_f32 serves every pool, augmented
+    (the descriptors are built for the padded size) or not (no descriptors: its identity form, the scaling kernel's bits for the
+    windows)."""
 
     def __init__(self, count, depth=2):
         if paths is None:
@@ -446,12 +504,15 @@ class AsyncLoader:
         # The device kernel scales a batch of ONE source size, and at most 6x down (images_u8_scale_k's box loop).  The reference
         # (dataset.lua:129-131) scales every image on its own: an image of another size - or all of them, if the source is more than
         # 6x the target - takes the blocking loader's host path (image_scale, same arithmetic) and is patched into the pool.
-        self.host_all = self.Hs > 6 * height or self.Ws > 6 * width
+        # With a margin, Hs x Ws is the padded size: the 6x limit is the window's, the LDS limit below the padded image's.
+        self.margin = margin
+        Hw, Ww = _window(self.Hs, self.Ws)
+        self.host_all = Hw > 6 * height or Ww > 6 * width
         if self.host_all:
             import warnings
-            warnings.warn(f"{type(self).__name__}: {self.Ws}x{self.Hs} sources are more than 6x the {width}x{height} target: scaling on the host")
+            warnings.warn(f"{type(self).__name__}: {Ww}x{Hw} sources are more than 6x the {width}x{height} target: scaling on the host")
         self.aug = aug
-        if self.aug and not self.host_all and self.Hs * self.Ws * 12 > AUG_LDS_BYTES:      # the kernel keeps one source image in the LDS
+        if (self.aug or self.margin) and not self.host_all and self.Hs * self.Ws * 12 > AUG_LDS_BYTES:      # the kernel keeps one source image in the LDS
             import warnings
             warnings.warn(f"{type(self).__name__}: {self.Ws}x{self.Hs} sources do not fit the augmentation kernel's LDS: augmenting on the host")
             self.host_all = True
@@ -534,8 +595,13 @@ class AsyncLoader:
             L.memcpy_h2d(cs, slot["dev_u8"], slot["host"], n * self.Hs * self.Ws * 3)
             if self.aug:
                 L.memcpy_h2d(cs, slot["dev_desc"], slot["host_desc"], n * 32)
+            noise_std, nseed = (slot["draw"]["noise_std"], slot["draw"]["seed"]) if self.aug else (0.0, 0)
+            if self.margin:
+                L.images_u8_augment_window_to_f32(cs, slot["dev_u8"], slot["pool"].ptr, n, self.Hs, self.Ws, self.margin, height, width,
+                                                  self.cs_code, slot["dev_desc"] if self.aug else None, noise_std, nseed, 0)
+            elif self.aug:
                 L.images_u8_augment_to_f32(cs, slot["dev_u8"], slot["pool"].ptr, n, self.Hs, self.Ws, height, width, self.cs_code,
-                                           slot["dev_desc"], slot["draw"]["noise_std"], slot["draw"]["seed"], 0)
+                                           slot["dev_desc"], noise_std, nseed, 0)
             else:
                 L.images_u8_scale_to_f32(cs, slot["dev_u8"], slot["pool"].ptr, n, self.Hs, self.Ws, height, width, self.cs_code)
             for i in slot["patches"]:     # images scaled on the host (another source size): over the rows the kernel produced from zeros
@@ -736,9 +802,11 @@ def openPack(d):
 
 
 def _check_resident(who, Hs, Ws, aug):
-    if Hs > 6 * height or Ws > 6 * width:
-        raise ValueError(f"{who}: {Ws}x{Hs} sources are more than 6x the {width}x{height} target (the kernels' limit)")
-    if aug and Hs * Ws * 12 > AUG_LDS_BYTES:
+    """The kernels' limits for a set of Hs x Ws images (padded ones, with dataset.margin): 6x from the window, the LDS from the whole."""
+    Hw, Ww = _window(Hs, Ws)
+    if Hw > 6 * height or Ww > 6 * width:
+        raise ValueError(f"{who}: {Ww}x{Hw} sources are more than 6x the {width}x{height} target (the kernels' limit)")
+    if (aug or margin) and Hs * Ws * 12 > AUG_LDS_BYTES:
         raise ValueError(f"{who}: {Ws}x{Hs} sources do not fit the augmentation kernel's LDS")
 
 
@@ -787,15 +855,15 @@ class ResidentSet:
 
 
 class _ResidentChunks:
-    """cg_images_u8_scale_to_f32 on consecutive slices of a ResidentSet, on the caller's stream, alternating two pools: a pool stays
-    valid until the next-but-one next()."""
+    """cg_images_u8_scale_to_f32 (of a padded set, dataset.margin: cg_images_u8_augment_window_to_f32's identity form) on consecutive
+    slices of a ResidentSet, on the caller's stream, alternating two pools: a pool stays valid until the next-but-one next()."""
 
     def __init__(self, rset, chunk):
         from .tensor import Tensor
         if int(chunk) < 1:
             raise ValueError(f"ResidentSet.chunks: chunk = {chunk}")
         _check_resident("ResidentSet.chunks", rset.Hs, rset.Ws, False)
-        self.set, self.files, self.count = rset, rset.paths, min(int(chunk), rset.M)
+        self.set, self.files, self.count, self.margin = rset, rset.paths, min(int(chunk), rset.M), margin
         self.C = 1 if colorSpace == "y" else 3
         self.cs_code = COLOR_SPACES[colorSpace]
         self.pools = [Tensor.empty((self.count, self.C, height, width), "nhwc") for _ in range(2)]
@@ -808,7 +876,11 @@ class _ResidentChunks:
             return None
         index0, n = self._pos, min(self.count, s.M - self._pos)
         pool = self.pools[self.k]
-        s.L.images_u8_scale_to_f32(stream(), s.ptr + index0 * s.per, pool.ptr, n, s.Hs, s.Ws, height, width, self.cs_code)
+        if self.margin:
+            s.L.images_u8_augment_window_to_f32(stream(), s.ptr + index0 * s.per, pool.ptr, n, s.Hs, s.Ws, self.margin, height, width,
+                                                self.cs_code, None, 0.0, 0, 0)
+        else:
+            s.L.images_u8_scale_to_f32(stream(), s.ptr + index0 * s.per, pool.ptr, n, s.Hs, s.Ws, height, width, self.cs_code)
         self._pos += n
         self.k ^= 1
         return (pool if n == self.count else pool.rows(1, n)), index0, n
@@ -834,13 +906,15 @@ class ResidentLoader:
     synchronisation - no copy stream, no thread, no prefetch.  So there is never a pick in flight and checkpoint_state() is the blocking
     loader's.  The staging is rewritten one epoch later, after the event recorded behind its copies; two pools alternate, each valid
     until the next-but-one next().  A set the kernels cannot serve (more than 6x larger than the target; with augmentation, beyond the
-    LDS) is a ValueError here, and the paths of the set must be the module's."""
+    LDS) is a ValueError here, and the paths of the set must be the module's.  A padded set (dataset.margin when the loader is built; the
+    pack stores the padded size as it always stored the files') goes through cg_images_u8_gather_augment_window_to_f32, augmented or
+    not."""
 
     def __init__(self, count, resident_set):
         import ctypes
         from .tensor import Tensor, lib
         s = self.set = resident_set
-        self.aug = augmentation is not None
+        self.aug, self.margin = augmentation is not None, margin
         _check_resident(type(self).__name__, s.Hs, s.Ws, self.aug)
         if (paths if paths is not None else loadPaths()) != s.paths:
             raise ValueError(f"{type(self).__name__}: the resident set does not hold the files of {dirs}")
@@ -877,9 +951,14 @@ class ResidentLoader:
         self.used = True
         pool = self.pools[self.k]
         self.k ^= 1
-        if self.aug:
+        dev_desc = self.dev.value + len(self.idx) * 4
+        if self.margin:
+            noise_std, nseed = (draw["noise_std"], draw["seed"]) if self.aug else (0.0, 0)
+            L.images_u8_gather_augment_window_to_f32(st, s.ptr, s.M, self.dev.value, pool.ptr, n, s.Hs, s.Ws, self.margin, height, width,
+                                                     self.cs_code, dev_desc if self.aug else None, noise_std, nseed, 0)
+        elif self.aug:
             L.images_u8_gather_augment_to_f32(st, s.ptr, s.M, self.dev.value, pool.ptr, n, s.Hs, s.Ws, height, width, self.cs_code,
-                                              self.dev.value + len(self.idx) * 4, draw["noise_std"], draw["seed"], 0)
+                                              dev_desc, draw["noise_std"], draw["seed"], 0)
         else:
             L.images_u8_gather_scale_to_f32(st, s.ptr, s.M, self.dev.value, pool.ptr, n, s.Hs, s.Ws, height, width, self.cs_code)
         return pool if n == pool.shape[0] else pool.rows(1, n)

@@ -379,6 +379,20 @@ def padded_crop_np(img, inv, rect, pad):
     return median_pad_np(win, top, left, bottom, right)
 
 
+def margin_pad(Hr, margin, out):
+    """The full-resolution pad of a face whose rectangle has the side Hr and whose out x out form keeps `margin` pixels around it:
+    margin Hr / out rounded half up, in integers.  Rectangles are square, so one value serves both axes."""
+    return (2 * margin * Hr + out) // (2 * out)
+
+
+def padded_face_np(img, inv, rect, margin, out=64):
+    """The padded face of generate_dataset.py --margin, uint8 [out + 2 margin, out + 2 margin, 3]: stage a with the pad
+    margin_pad(Hr, margin, out) - real image around the rectangle, median-filled where that leaves the image - through stage 4's
+    unchanged resize.  The pad is rounded to whole source pixels, so the centre window is the _000 face exactly only at unit scale
+    (Hr == out); elsewhere the two differ by that rounding's fraction of a face pixel."""
+    return resize_np(padded_crop_np(img, inv, rect, margin_pad(rect[2], margin, out)), out + 2 * margin)
+
+
 def noise_scale(noise_std):
     """s of the pixel stage: 255 noise_std, rounded to fp32 once."""
     return np.float32(255.0 * float(noise_std))

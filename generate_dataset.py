@@ -19,15 +19,26 @@ out_aug_SxS also gets --augmentations variants NNNNNN_001 ... per face, their dr
       --padding (30) pixels of real image around it, median-filled where that leaves the image, the pixel stage and the warp run at
       full resolution, then the padding comes off and the result is resized - the borders show real fur and background.  Every
       --scale works.  The draws are dataset.augment_draw's, not the reference's `random` stream.
-The _000 faces and out_unaug_SxS do not depend on the mode.  The trainers' --augment still warps finished faces whichever way the set was
-made; serving it from padded faces is a later step.  --augmentations 0 together with --augment, which draws fresh variants for every
-epoch pool, remains the cheapest use.
+The _000 faces and out_unaug_SxS do not depend on the mode.
 
-    python generate_dataset.py --path /data/10k_cats --augmentations 0 --pack
+--margin M (default 0: nothing new is written) adds a third directory, <out>/out_padded_SxS_mM: NNNNNN_000.jpg of side S + 2 M for
+every accepted face - the face with M pixels of real image around it (faces.padded_face_np: the rectangle enlarged by
+faces.margin_pad(Hr, M, S) full-resolution pixels, median-filled where that leaves the image, then the same resize) - and margin.json,
+{"margin": M, "side": S}.  The trainers' --augment, pointed at it (--dataDir <out>/out_padded_SxS_mM), warps every epoch pool's fresh
+variants out of the padded faces, so their borders show real image, and everything un-augmented sees the S x S centre window
+(dataset.setDirs reads margin.json).  With the default ranges and S = 64 a margin of 12 is never left.  An M whose padded face does not
+fit the augmentation kernel's LDS is refused.  The padded faces are computed on the decoding threads by the numpy form in the device
+mode too: a device form needs a pad per face, beyond cg_faces_u8_extract_variants' single pad <= 64, and is deliberately not part of
+this tool yet (profiles/augment_margin_bench.txt has what the host form costs).  --augmentations 0 --margin 12 together with --augment
+is the cheapest use that has real borders.
+
+    python generate_dataset.py --path /data/10k_cats --augmentations 0 --margin 12 --pack
 """
 import argparse
 import glob
 import importlib
+import json
+import math
 import os
 import sys
 from collections import deque
@@ -56,13 +67,17 @@ def parse(argv=None):
     ap.add_argument("--variantsFrom", choices=("face", "crop"), default="face",
                     help="what the variants are warped from: the finished face (edge replication) or the padded full-resolution crop (the reference's way)")
     ap.add_argument("--padding", type=int, default=30, help="pixels kept around the face rectangle for --variantsFrom crop (0..64)")
+    ap.add_argument("--margin", type=int, default=0,
+                    help="M: also write out_padded_SxS_mM, the faces with M pixels of real image around them, for the trainers' --augment (0 = off)")
     ap.add_argument("--host", action="store_true", help="compute the faces with the numpy restatement: no GPU, no library")
-    ap.add_argument("--pack", action="store_true", help="finish with dataset.buildPack on out_aug_SxS (pack_dataset.py)")
+    ap.add_argument("--pack", action="store_true", help="finish with dataset.buildPack on out_aug_SxS, and on the --margin directory (pack_dataset.py)")
     o = ap.parse_args(argv)
     if o.threads < 1 or not 8 <= o.scale <= 128 or not 0 <= o.augmentations <= 999:
         ap.error("--threads must be positive, --scale in 8..128, --augmentations in 0..999")
     if not 0 <= o.padding <= 64:
         ap.error("--padding must be in 0..64")
+    if o.margin < 0:
+        ap.error("--margin must not be negative")
     return o
 
 
@@ -75,8 +90,9 @@ def list_raw(path):
     return files
 
 
-def _load(fp):
-    """One raw file -> (fp, decoded image, geometry) or (fp, None, why it is skipped).  Runs on the decoding threads."""
+def _load(fp, margin=0, S=64):
+    """One raw file -> (fp, decoded image, geometry) or (fp, None, why it is skipped); with a margin the geometry also carries the padded
+    face, g["padded"].  Runs on the decoding threads."""
     F = importlib.import_module("cat-generator_amd.faces")
     ds = importlib.import_module("cat-generator_amd.dataset")
     if not os.path.isfile(fp + ".cat"):
@@ -89,15 +105,19 @@ def _load(fp):
     g = F.face_geometry(kp, img.shape[0], img.shape[1])
     if not isinstance(g, str) and min(g["rect"][2:]) < MIN_SIDE:
         g = "its face rectangle is degenerate"
-    return (fp, None, g) if isinstance(g, str) else (fp, img, g)
+    if isinstance(g, str):
+        return fp, None, g
+    if margin:
+        g["padded"] = F.padded_face_np(img, g["inv"], g["rect"], margin, S)
+    return fp, img, g
 
 
-def _loaded(ex, files):
+def _loaded(ex, files, margin=0, S=64):
     """_load over the files, in their order whatever the threads do, with a bounded look-ahead: decoded sources wait here, never the
     whole set."""
     ahead = deque()
     for fp in files:
-        ahead.append(ex.submit(_load, fp))
+        ahead.append(ex.submit(_load, fp, margin, S))
         if len(ahead) >= LOOKAHEAD:
             yield ahead.popleft().result()
     while ahead:
@@ -167,12 +187,21 @@ def main(argv=None):
     crop = A > 0 and o.variantsFrom == "crop"
     if A and not crop and S * S * 12 > ds.AUG_LDS_BYTES:
         raise SystemExit(f"generate_dataset: variants of {S} x {S} faces do not fit the augmentation kernel's LDS; use --variantsFrom crop or --augmentations 0")
+    if o.margin and (S + 2 * o.margin) ** 2 * 12 > ds.AUG_LDS_BYTES:
+        most = (math.isqrt(ds.AUG_LDS_BYTES // 12) - S) // 2
+        raise SystemExit(f"generate_dataset: --margin {o.margin}: {S + 2 * o.margin} x {S + 2 * o.margin} padded faces do not fit the augmentation "
+                         f"kernel's LDS; " + (f"the largest margin that fits {S} x {S} faces is {most}" if most >= 0 else f"no {S} x {S} face fits at all"))
     files = list_raw(o.path)
     if not files:
         raise SystemExit(f"generate_dataset: no CAT_*/*.jpg under {o.path}")
     unaug, aug = (os.path.join(o.out, f"out_{k}_{S}x{S}") for k in ("unaug", "aug"))
     os.makedirs(unaug, exist_ok=True)
     os.makedirs(aug, exist_ok=True)
+    padded = os.path.join(o.out, f"out_padded_{S}x{S}_m{o.margin}") if o.margin else None
+    if padded:
+        os.makedirs(padded, exist_ok=True)
+        with open(os.path.join(padded, ds.MARGIN_NAME), "w") as f:
+            json.dump({"margin": o.margin, "side": S}, f)
     ds.seed(o.seed)
     ds.setAugmentation(True)
     noise_seed = int(ds.augment_draw(1)["seed"])
@@ -194,6 +223,8 @@ def main(argv=None):
             name = "{:0>6}_{:0>3}.jpg".format(written, 0)
             Image.fromarray(face).save(os.path.join(unaug, name))
             Image.fromarray(face).save(os.path.join(aug, name))
+            if padded:
+                Image.fromarray(geoms[i]["padded"]).save(os.path.join(padded, name))
             if A:
                 for a, v in enumerate(variants[i] if crop else _variants(face, written, A, noise_seed, o.host)):
                     Image.fromarray(v).save(os.path.join(aug, "{:0>6}_{:0>3}.jpg".format(written, a + 1)))
@@ -201,7 +232,7 @@ def main(argv=None):
 
     batch, nbytes = [], 0
     with ThreadPoolExecutor(max_workers=min(o.threads, MAX_THREADS)) as ex:
-        for fp, img, g in _loaded(ex, files):
+        for fp, img, g in _loaded(ex, files, o.margin, S):
             if img is None:
                 print(f"<dataset> warning: {fp} skipped: {g}")
                 skipped += 1
@@ -213,11 +244,13 @@ def main(argv=None):
             nbytes += img.nbytes
         flush(batch)
     ds.setAugmentation(False)
-    print(f"<dataset> {written} faces of {S}x{S} ({skipped} images skipped) -> {unaug}, {aug} (+{A} variants each)")
+    print(f"<dataset> {written} faces of {S}x{S} ({skipped} images skipped) -> {unaug}, {aug} (+{A} variants each)"
+          + (f", {padded} (margin {o.margin})" if padded else ""))
     if o.pack:
         ds.setFileExtension("jpg")
-        path, M = ds.buildPack(aug, o.threads)
-        print(f"<dataset> {M} images -> {path}")
+        for d in (aug, padded) if padded else (aug,):
+            path, M = ds.buildPack(d, o.threads)
+            print(f"<dataset> {M} images -> {path}")
     return written, skipped
 
 

@@ -145,6 +145,27 @@ int cg_images_u8_gather_scale_to_f32(void* stream, const unsigned char* set, lon
                                      int Hd, int Wd, int colorspace);
 int cg_images_u8_gather_augment_to_f32(void* stream, const unsigned char* set, long M, const int32_t* idx, float* dst, int N, int Hs, int Ws,
                                        int Hd, int Wd, int colorspace, const float* desc, float noise_std, uint64_t seed, uint64_t offset);
+/* The two augmentation entry points above for sources that keep `margin` pixels of real image around the part that is shown (the padded
+ * faces of generate_dataset.py --margin): src / set hold [Hp][Wp][3] images, the window is Hs = Hp - 2 margin by Ws = Wp - 2 margin at
+ * offset (margin, margin), and a rotated, shifted or zoomed-out variant reads real neighbours where the forms above replicate the edge.
+ *   pixel stage over the WHOLE padded array, [Hp][Wp][3] fp32 in the LDS: the flip mirrors the padded array (Wp-1-x), the noise counter
+ *     is j = ((n Hp + y) Wp + x) 3 + c;
+ *   image.scale walks the WINDOW: cg_images_u8_scale_to_f32's footprints for Hs, Ws -> Hd, Wd, and window sample (x, y) is the warp
+ *     evaluated at its padded position, X = x + margin, Y = y + margin (exact floats):
+ *     sx = (m00 X + m01 Y) + m02, sy = (m10 X + m11 Y) + m12, clamped to [0, Wp-1] x [0, Hp-1] (NaN -> 0), the taps and the blend as above
+ *     on the padded array.  desc holds the inverse of the matrix built for the PADDED size (dataset.augment_descriptor(draw, i, Hp, Wp)),
+ *     whose centre int(Wp / 2) is the window's centre.
+ * Every operation is a single correctly rounded fp32 one in that order (dataset.augment_images(..., margin) restates it).  margin == 0
+ * gives the forms above bit for bit - the four entry points launch the same two kernels.  desc == NULL is allowed HERE (not above) and
+ * means the identity draw (1 0 0 0 1 0 1 0) for every image: with noise_std == 0 the result is then, bit for bit,
+ * cg_images_u8_scale_to_f32 / cg_images_u8_gather_scale_to_f32 of the cropped windows - how a padded set serves un-augmented pools.
+ * Errors, all before any launch: those of the forms above; margin < 0 or 2 margin >= min(Hp, Wp); a shrink factor of the WINDOW above 6;
+ * a PADDED array beyond the LDS (Hp Wp 12 bytes).  A gathered index outside [0, M) gives an all-zero image. */
+int cg_images_u8_augment_window_to_f32(void* stream, const unsigned char* src, float* dst, int N, int Hp, int Wp, int margin, int Hd, int Wd,
+                                       int colorspace, const float* desc, float noise_std, uint64_t seed, uint64_t offset);
+int cg_images_u8_gather_augment_window_to_f32(void* stream, const unsigned char* set, long M, const int32_t* idx, float* dst, int N, int Hp,
+                                              int Wp, int margin, int Hd, int Wd, int colorspace, const float* desc, float noise_std,
+                                              uint64_t seed, uint64_t offset);
 /* The reference's offline dataset tool for its un-augmented variant (dataset/generate_dataset.py:53-91: remove_rotation,
  * dataset/dataset.py:152-181; extract_face with method-4's rectangle, :191-239, 602-676, whose 30 px padding unpad(30) takes off again;
  * resize, :127-139): N faces, each cut out of its own decoded source image (8-bit RGB, [Hs][Ws][3], sizes differ per face) and
