@@ -59,12 +59,13 @@ constexpr int kEwWgsPerCU = 4, kColReduceWgsPerCU = 1;
 enum Opt {
     OPT_SKINNY, OPT_GEMM_BK32, OPT_WINO_BK, OPT_NN_TILE, OPT_TN_TILE, OPT_NN_SPLITS, OPT_TN_SPLITS,
     OPT_XCD_SWIZZLE, OPT_NN_GLDS, OPT_TN_GLDS, OPT_WINO_GLDS, OPT_PAD_SKIP, OPT_WINO3, OPT_WINO_DGRAD_FUSE, OPT_WINO_DGRAD_FUSE_LAUNCHES,
-    OPT_WINO3_LAUNCHES, OPT_PACK_WIDE, OPT_COUNT
+    OPT_WINO3_LAUNCHES, OPT_PACK_WIDE, OPT_SAMPLER_ATOMIC_LAUNCHES, OPT_COUNT
 };
 long opt(Opt o);
 // CG_WINO_DGRAD_FUSE_LAUNCHES and CG_WINO3_LAUNCHES are not tunables but counters kept in the same table (cg_get_option reads them,
 // cg_set_option resets them): the launches of wino_dgrad_fused_kernel (winograd.hip) and of wino3_fused_k (wino3.hip), so that a test can
-// tell that the fused path ran and not its fallback.
+// tell that the fused path ran and not its fallback.  CG_SAMPLER_ATOMIC_LAUNCHES counts the other way round: the launches of
+// bilinear_bwd_k (ops.hip), the float-atomic fallback of the sampler's deterministic gather backward.
 // CG_PACK_WIDE: 1 = the weight re-packing after every parameter update runs in its wide launches (pack_weight_ups2_wide_kernel and
 // pack_weight_batch_wide_kernel in pack.hip, the both-operand Winograd filter transforms in winograd.hip), 0 = the kernels they replace.
 // The bytes written are the same.

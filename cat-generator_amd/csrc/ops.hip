@@ -27,6 +27,7 @@ const OptDef kOptDefs[OPT_COUNT] = {
     {"CG_SKINNY", 1}, {"CG_GEMM_BK32", 1}, {"CG_WINO_BK", 0}, {"CG_NN_TILE", 0}, {"CG_TN_TILE", 0}, {"CG_NN_SPLITS", 0}, {"CG_TN_SPLITS", 0},
     {"CG_XCD_SWIZZLE", 7}, {"CG_NN_GLDS", 1}, {"CG_TN_GLDS", 1}, {"CG_WINO_GLDS", 1}, {"CG_PAD_SKIP", 20}, {"CG_WINO3", 1},
     {"CG_WINO_DGRAD_FUSE", 1}, {"CG_WINO_DGRAD_FUSE_LAUNCHES", 0}, {"CG_WINO3_LAUNCHES", 0}, {"CG_PACK_WIDE", 1},
+    {"CG_SAMPLER_ATOMIC_LAUNCHES", 0},
 };
 long g_opt_val[OPT_COUNT];
 int g_opt_state[OPT_COUNT];   // 0 = not read yet, 1 = default / environment, 2 = set through the ABI
@@ -1980,6 +1981,7 @@ int sampler_backward(void* stream, const float* img, const float* grid, const fl
         CG_LAUNCH_CHECK();
         return 0;
     }
+    cg::opt_count(cg::OPT_SAMPLER_ATOMIC_LAUNCHES);
     CG_HIP(hipMemsetAsync(gimg, 0, sizeof(float) * (size_t)N * Hi * Wi * C, cg::S(stream)));
     const long npix = (long)N * Ho * Wo;
     int G = 4;

@@ -44,7 +44,7 @@ extern "C" {
  * utils/nn_utils.lua:638-643). */
 int         cg_abi_version(void);
 const char* cg_last_error(void);
-/* Tunables of the kernel dispatch, named like the environment variables that set their defaults (15 names and two counters; value == -1 restores the
+/* Tunables of the kernel dispatch, named like the environment variables that set their defaults (15 names and three counters; value == -1 restores the
  * default).  Results never depend on them beyond fp32 re-association; the parity tests use them to run every compiled kernel variant
  * against the oracle.
  *   CG_NN_TILE / CG_TN_TILE (bm*1000+bn), CG_NN_SPLITS / CG_TN_SPLITS : block tile and split count of the forward (data-gradient) /
@@ -71,6 +71,7 @@ const char* cg_last_error(void);
  *   CG_PACK_WIDE : 1 = cg_pack_conv_weight_ups2 (k = 3, 5) packs one phase of a 32 x 16 channel block per workgroup from LDS-staged,
  *       coalesced reads, and cg_conv2d_ups2_wino_pack / _wino22_pack transform both operands in one launch; 0 = the kernels these
  *       replace.  Both settings write the same bytes.
+ *   CG_SAMPLER_ATOMIC_LAUNCHES : a counter like the two above: the backward calls of cg_bilinear_sampler_* that took the float-atomic fallback.
  * (CG_SPLIT_TARGET / _MINK, CG_TN_SMAX / _TARGET, CG_EPILOGUE_STATS, CG_COLREDUCE_WGS_PER_CU, CG_EW_WGS_PER_CU became constants in round 6.) */
 int cg_set_option(const char* name, long value);
 int cg_get_option(const char* name, long* value);

@@ -1,7 +1,7 @@
 """What several test modules share (a plain module, imported as tests/plan_trace.py is): the two measures of the parity tests, the
 `options` context that forces dispatch tunables, `counter` that reads a launch counter, the per-tensor gradient rule, the JPEG directory
-of the loader tests, the torch fp64 twin of an engine nn.Sequential, and the measures, launch arithmetic and inputs of the memory-bound
-edge sweeps."""
+of the loader tests, the torch fp64 twin of an engine nn.Sequential, and the measures, launch arithmetic, inputs and guarded device
+buffers of the memory-bound edge sweeps."""
 import ctypes
 import os
 
@@ -36,7 +36,7 @@ class options:
 
 
 def counter(cg, name):
-    """A launch counter kept among the options (CG_WINO3_LAUNCHES, CG_WINO_DGRAD_FUSE_LAUNCHES): how a test tells which kernel ran."""
+    """A launch counter kept among the options (CG_WINO3_LAUNCHES, CG_WINO_DGRAD_FUSE_LAUNCHES, CG_SAMPLER_ATOMIC_LAUNCHES): how a test tells which kernel ran."""
     v = ctypes.c_long(-1)
     assert cg.lib().get_option(name.encode(), ctypes.byref(v)) == 0
     return v.value
@@ -161,16 +161,20 @@ def bits_equal(a, b, what=""):
 
 def rounding_close(a, ref, terms, r, what="", slack=0.0):
     """|a - ref| <= r (U24 terms + TINY) + slack per element (per column for a reduction): ref the fp64 value, terms the sum of the
-    magnitudes of the addends of that element, r the number of fp32 roundings on the longest chain of the kernel's expression plus 2,
-    slack an error propagated from an input that is checked on its own.  Nothing here is scaled by a tensor's maximum."""
+    magnitudes of the addends of that element, r the number of fp32 roundings on the longest chain of the kernel's expression plus 2
+    (a number, or an array that broadcasts against ref where the chain's length depends on the element), slack an error propagated from
+    an input that is checked on its own.  Nothing here is scaled by a tensor's maximum."""
     a, ref = np.asarray(a, dtype=np.float64), np.asarray(ref, dtype=np.float64)
     assert a.shape == ref.shape, f"{what}: shape {a.shape} vs {ref.shape}"
     assert np.isfinite(a).all(), f"{what}: non-finite values"
-    bound = r * (U24 * np.broadcast_to(np.abs(terms), ref.shape) + TINY) + slack
+    rr = np.broadcast_to(np.asarray(r, dtype=np.float64), ref.shape)
+    bound = rr * (U24 * np.broadcast_to(np.abs(terms), ref.shape) + TINY) + slack
     d = np.abs(a - ref)
     worst = float((d / bound).max()) if d.size else 0.0
-    print(f"{what}: worst |d| / bound = {worst:.3f} (r = {r})")
-    assert worst <= 1.0, f"{what}: |d| = {worst:.3f} x the bound of {r} roundings at flat index {int(np.argmax(d / bound))}"
+    rs = f"{r}" if np.ndim(r) == 0 else f"{int(rr.min())}..{int(rr.max())}"
+    print(f"{what}: worst |d| / bound = {worst:.3f} (r = {rs})")
+    k = int(np.argmax(d / bound)) if d.size else 0
+    assert worst <= 1.0, f"{what}: |d| = {worst:.3f} x the bound of {rr.ravel()[k] if d.size else r:g} roundings at flat index {k}"
     return worst
 
 
@@ -234,3 +238,32 @@ def duplicate_in_windows(rng, x, frac=0.2):
         sel = pick & (rng.random(pick.shape) < 0.6)
         w[:, :, iy, :, ix, :] = np.where(sel, src, w[:, :, iy, :, ix, :])
     return x
+
+
+# ------------------------------------------------------------------------------ guarded device buffers of the edge sweeps
+def dev(a, misaligned=False):
+    """A flat device copy of a; misaligned: a view one float into a larger tensor (4 bytes off a 16-byte boundary).  The tensor it
+    lives in has four guard floats on either side, which host() checks."""
+    a = np.ascontiguousarray(a)
+    if a.dtype != np.float32:
+        return torch.from_numpy(a.reshape(-1)).cuda()
+    big = torch.full((a.size + 9,), 777.0, dtype=torch.float32, device="cuda")
+    o = 5 if misaligned else 4
+    v = big[o:o + a.size]
+    v.copy_(torch.from_numpy(a.reshape(-1)))
+    assert v.data_ptr() % 16 == (4 if misaligned else 0)
+    v.guard = (big, o, a.size)
+    return v
+
+
+def out_like(n, misaligned=False, fill=555.0):
+    """A guarded output buffer of n floats, prefilled (with NaN an element the kernel leaves unwritten fails every measure here)."""
+    return dev(np.full(int(n), fill, np.float32), misaligned)
+
+
+def host(t, shape=None):
+    big, o, n = t.guard
+    g = big.cpu().numpy()
+    assert (g[:o] == 777.0).all() and (g[o + n:] == 777.0).all(), "a kernel wrote outside its tensor"
+    a = g[o:o + n].copy()
+    return a if shape is None else a.reshape(shape)

@@ -23,8 +23,8 @@ import pytest
 import torch
 
 import test_gpu_membound_edges as E
-from helpers import duplicate_in_windows, edge_normal, options
-from test_gpu_membound_edges import dev, host, out_like, ptrs, scalar
+from helpers import dev, duplicate_in_windows, edge_normal, host, options, out_like
+from test_gpu_membound_edges import ptrs, scalar
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32

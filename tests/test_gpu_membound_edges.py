@@ -18,7 +18,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import U24, bits_equal, col_launch, col_tree, duplicate_in_windows, edge_normal, fixed_channel_grid, rounding_close
+from helpers import (U24, bits_equal, col_launch, col_tree, dev, duplicate_in_windows, edge_normal, fixed_channel_grid, host, out_like,
+                     rounding_close)
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -178,33 +179,6 @@ def bn_near_kink(x, mean, invstd, gamma, beta):
 
 
 # ------------------------------------------------------------------------------ device plumbing
-def dev(a, misaligned=False, pad=0.0):
-    """A flat device copy of a; misaligned: a view one float into a larger tensor (4 bytes off a 16-byte boundary).  The tensor it
-    lives in has four guard floats on either side, see guards_intact()."""
-    a = np.ascontiguousarray(a)
-    if a.dtype != np.float32:
-        return torch.from_numpy(a.reshape(-1)).cuda()
-    big = torch.full((a.size + 9,), 777.0, dtype=torch.float32, device="cuda")
-    o = 5 if misaligned else 4
-    v = big[o:o + a.size]
-    v.copy_(torch.from_numpy(a.reshape(-1)))
-    assert v.data_ptr() % 16 == (4 if misaligned else 0)
-    v.guard = (big, o, a.size)
-    return v
-
-
-def out_like(n, misaligned=False):
-    return dev(np.full(int(n), 555.0, f32), misaligned)
-
-
-def host(t, shape=None):
-    big, o, n = t.guard
-    g = big.cpu().numpy()
-    assert (g[:o] == 777.0).all() and (g[o + n:] == 777.0).all(), "a kernel wrote outside its tensor"
-    a = g[o:o + n].copy()
-    return a if shape is None else a.reshape(shape)
-
-
 def ptrs(ts):
     return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
