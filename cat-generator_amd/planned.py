@@ -231,7 +231,10 @@ class PlannedNet:
 
     # ---- passes
     def _wrap(self, ptr, nd, dims, fmt):
+        """A result descriptor (ptr, nd, dims, fmt + 2 * ups) as a Tensor; in trace mode, where nothing was computed, the shape and layout alone."""
         shape = tuple(int(dims[i]) for i in range(nd))
+        if self.trace:
+            return Tensor(torch.empty(0), shape, "nhwc" if fmt & 1 else "plain")
         ups = fmt >> 1
         n = 1
         for d in shape:
@@ -253,8 +256,6 @@ class PlannedNet:
         r.offset += draws.value
         self.last_draws = int(draws.value)      # static per plan: a host may reserve the stream positions behind this pass ahead of time
         self._x = x
-        if self.trace:
-            return Tensor(torch.empty(0), tuple(int(ydims[i]) for i in range(ynd.value)), "nhwc" if yfmt.value & 1 else "plain")
         return self._wrap(y.value, ynd.value, ydims, yfmt.value)
 
     def forward_pair(self, x, x2):
@@ -285,8 +286,6 @@ class PlannedNet:
         gdims = (ctypes.c_long * 4)()
         self.L.net_backward(self.h, stream(), x.ptr, gy.ptr, 1 if gy.fmt == "nhwc" else 0, int(bool(acc)), float(scale), ctypes.byref(gx),
                             ctypes.byref(gnd), gdims, ctypes.byref(gfmt))
-        if self.trace:
-            return Tensor(torch.empty(0), tuple(int(gdims[i]) for i in range(gnd.value)), "nhwc" if gfmt.value & 1 else "plain")
         return self._wrap(gx.value, gnd.value, gdims, gfmt.value)
 
     def set_defer_running(self, on):

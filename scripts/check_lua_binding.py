@@ -166,15 +166,17 @@ def check_brackets(path, raw, src):
 
 def check_net_builder():
     """4. the planned executor's builder: lua/catgan/net.lua describes a module with the same (kind, iargs, fargs) as the executable
-    twin cat-generator_amd/planned.py, and both use the kind numbers of csrc/net.hip's enum (the header documents them)."""
+    twin cat-generator_amd/planned.py, and both use the kind numbers of csrc/net_plan.h's enum (the header documents them)."""
     errs = []
-    hip = open(os.path.join(ROOT, "cat-generator_amd", "csrc", "net.hip")).read()
+    hip = open(os.path.join(ROOT, "cat-generator_amd", "csrc", "net_plan.h")).read()
     enum = dict((n, int(v)) for n, v in re.findall(r"K_([A-Z]+) = (\d+)", hip))
     names = {"SEQ": "Sequential", "CONCAT": "Concat", "CONCATTABLE": "ConcatTable", "LINEAR": "Linear", "CONV": "SpatialConvolution", "PRELU": "PReLU",
              "LRELU": "LeakyReLU", "SIGMOID": "Sigmoid", "BN": "SpatialBatchNormalization", "VIEW": "View", "COPY": "Copy", "TRANSPOSE": "Transpose",
              "UPS": "SpatialUpSamplingNearest", "AVGPOOL": "SpatialAveragePooling", "MAXPOOL": "SpatialMaxPooling", "SDROP": "SpatialDropout",
              "DROP": "Dropout", "AFFMAT": "AffineTransformMatrixGenerator", "AFFGRID": "AffineGridGeneratorBHWD", "SAMPLER": "BilinearSamplerBHWD"}
     want = {names[k]: v for k, v in enum.items() if k in names}
+    if len(want) != len(names):
+        errs.append("csrc/net_plan.h: the module-kind enum (K_<NAME> = <number>) does not name all %d kinds" % len(names))
     py = open(os.path.join(ROOT, "cat-generator_amd", "planned.py")).read()
     py_kind = dict((n, int(v)) for n, v in re.findall(r"(\w+)=(\d+)", py[py.index("KIND = dict("):py.index(")", py.index("KIND = dict("))]))
     lua = open(os.path.join(ROOT, "lua", "catgan", "net.lua")).read()
@@ -182,9 +184,9 @@ def check_net_builder():
     hdr = open(os.path.join(ROOT, "include", "catgan.h")).read()
     for cls, k in want.items():
         if py_kind.get(cls) != k:
-            errs.append(f"planned.py: KIND[{cls}] = {py_kind.get(cls)}, csrc/net.hip says {k}")
+            errs.append(f"planned.py: KIND[{cls}] = {py_kind.get(cls)}, csrc/net_plan.h says {k}")
         if lua_kind.get(cls) != k:
-            errs.append(f"lua/catgan/net.lua: KIND[nn.{cls}] = {lua_kind.get(cls)}, csrc/net.hip says {k}")
+            errs.append(f"lua/catgan/net.lua: KIND[nn.{cls}] = {lua_kind.get(cls)}, csrc/net_plan.h says {k}")
         if not re.search(r"\b%d (?:nn|nn\|cudnn)\.%s" % (k, cls), hdr):
             errs.append(f"include/catgan.h: cg_net_add's comment does not list kind {k} as {cls}")
     # argument lists: the fields each describe() reads, per kind, must be the same fields in the same order

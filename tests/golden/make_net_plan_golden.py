@@ -9,6 +9,7 @@ The variant matrix (VARIANTS below) pins the shipped default configuration and e
 takes: three cases as full text (net_plan_variant_*.txt), all the others as a SHA-1 of that text (net_plan_variants.json).
 
     python tests/golden/make_net_plan_golden.py --variants             # rewrite the variant fixtures
+    python tests/golden/make_net_plan_golden.py --add                  # record the digests of the cases net_plan_variants.json lacks
     python tests/golden/make_net_plan_golden.py --print <variant id>   # one case's text on stdout, to diff two builds of the library
     python tests/golden/make_net_plan_golden.py --dump <directory>     # every case's text, one file per variant
     python tests/golden/make_net_plan_golden.py --list                 # the variant ids
@@ -49,24 +50,42 @@ FULL_TEXT = ["D32_st3-N8-default", "G32up-c-N8-default", "D32_st3-N8-grouped=0"]
 DIGESTS = os.path.join(HERE, "net_plan_variants.json")
 
 
-def variant_id(which, N, options=(), dp=None):
+def variant_id(which, N, options=(), dp=None, mode=None):
     tag = "+".join(f"{k}={v}" for k, v in options) or "default"
     if dp:
-        tag = "world%d-%s" % (dp["world"], "buckets" if dp["buckets"] else "nobuckets")
+        tag = "world%d-%s" % (dp["world"], "buckets" if dp["buckets"] else "nobuckets") + ("+" + tag if options else "")
+    if mode:
+        tag = mode + ("+" + tag if options else "")
     return f"{which}-N{N}-{tag}"
 
 
-VARIANTS = {variant_id(w, n, o): (w, n, o, None) for w, n in VARIANT_NETS for o in VARIANT_OPTIONS}
-VARIANTS.update({variant_id(w, n, (), dp): (w, n, (), dp) for w, n, dp in VARIANT_DP})
+# id -> (network, batch, options, dp, keywords of plan_trace.trace that choose another kind of pass)
+VARIANTS = {variant_id(w, n, o): (w, n, o, None, {}) for w, n in VARIANT_NETS for o in VARIANT_OPTIONS}
+VARIANTS.update({variant_id(w, n, (), dp): (w, n, (), dp, {}) for w, n, dp in VARIANT_DP})
+
+# ---- recorded on the parent commit of the change that split csrc/net.hip in three: the paths no case above reaches
+NOFUSION = (("fusion", 0),)
+OPTIONS_16 = [(), NOFUSION, (("stacking", 0),), (("wgrad_stream", 0),)]
+OPTIONS_D16 = OPTIONS_16 + [(("grouped", 0),), (("fuse_locnet", 0),), (("fuse_locnet", 2),)]
+VARIANTS.update({variant_id(w, n, o): (w, n, o, None, {})                      # the 16 px networks
+                 for w, opts in (("D32_st3@16", OPTIONS_D16), ("G16up", OPTIONS_16)) for n in (8, 128) for o in opts})
+DP2 = dict(world=2, buckets=True)                                              # world 2 off the fused path (G: the unfused sync-BN exchanges)
+VARIANTS.update({variant_id(w, 8, NOFUSION, DP2): (w, 8, NOFUSION, DP2, {}) for w in ("G32up-c", "D32_st3")})
+# after net:evaluate(): D whole (dropout as a scaling, the head module by module), the generators forward only (their batch-norm backward is refused)
+VARIANTS.update({variant_id("D32_st3", 8, o, mode="evaluate"): ("D32_st3", 8, o, None, dict(evaluate=True)) for o in ((), NOFUSION)})
+VARIANTS.update({variant_id(w, n, mode="evaluate-forward"): (w, n, (), None, dict(evaluate=True, backward=False)) for w, n in (("G32up-c", 8), ("G32up", 16))})
+# forward_pair on 4 and 8 rows + pair_join, the backward continuing the second pass
+VARIANTS[variant_id("G32up-c", 8, mode="pair4")] = ("G32up-c", 8, (), None, dict(pair=4))
 
 
 def variant_text(vid):
-    which, N, options, dp = VARIANTS[vid]
-    r = T.trace(which, N, options=list(options), dp=dp)
+    which, N, options, dp, mode = VARIANTS[vid]
+    r = T.trace(which, N, options=list(options), dp=dp, **mode)
     out = [f"# {vid}: draws {r['draws']}", "# stats " + " ".join(f"{k}={v}" for k, v in sorted(r["stats"].items()))]
     for phase in ("first_forward", "forward", "backward", "updateGradInput"):
-        out.append(f"## {phase}")
-        out += T.canon(r[phase])
+        if phase in r:
+            out.append(f"## {phase}")
+            out += T.canon(r[phase])
     return "\n".join(out) + "\n"
 
 
@@ -87,6 +106,12 @@ if __name__ == "__main__":
         os.makedirs(sys.argv[2], exist_ok=True)
         for vid in VARIANTS:
             open(os.path.join(sys.argv[2], vid + ".txt"), "w").write(variant_text(vid))
+    elif sys.argv[1:2] == ["--add"]:           # the recorded digests stay as they are
+        sums = json.load(open(DIGESTS))
+        new = [vid for vid in VARIANTS if vid not in sums and vid not in FULL_TEXT]
+        sums.update({vid: digest(variant_text(vid)) for vid in new})
+        json.dump(sums, open(DIGESTS, "w"), indent=0, sort_keys=True)
+        print(DIGESTS, len(new), "digests added")
     elif sys.argv[1:2] == ["--variants"]:
         sums = {}
         for vid in VARIANTS:

@@ -24,15 +24,23 @@ def build(which, seed=3):
         return cg.models.create_D((3, 32, 32)), (3, 32, 32), "nhwc"
     if which == "D32_st3@64":
         return cg.models.create_D((3, 64, 64)), (3, 64, 64), "nhwc"
+    if which == "D32_st3@16":
+        return cg.models.create_D((3, 16, 16)), (3, 16, 16), "nhwc"
+    if which == "G16up":
+        return cg.models.create_G((3, 16, 16), 100), (100,), "plain"
     raise KeyError(which)
 
 
-def trace(which, N, options=(), dp=None, rng_offset=1000):
-    """-> dict(forward=[lines], backward=[...], updateGradInput=[...], draws=int, out_shape=..., net=PlannedNet)."""
+def trace(which, N, options=(), dp=None, rng_offset=1000, evaluate=False, backward=True, pair=None):
+    """-> dict(forward=[lines], backward=[...], updateGradInput=[...], draws=int, out_shape=..., net=PlannedNet).
+    evaluate: after net:evaluate(); backward False: the forward passes alone; pair = N1: every forward is forward_pair on N1 and N rows
+    followed by pair_join (the backward continues the N-row pass)."""
     cg = cg_pkg()
     P = importlib.import_module("cat-generator_amd.planned")
     net, ishape, fmt = build(which)
     net.getParameters()
+    if evaluate:
+        net.evaluate()
     x = cg.Tensor(torch.zeros(N * int(np.prod(ishape))), (N,) + ishape, fmt)
     pn = P.PlannedNet(net, trace=True)
     L = cg.lib()
@@ -43,14 +51,28 @@ def trace(which, N, options=(), dp=None, rng_offset=1000):
         cg.parallel.attach(dp["world"], 0)
     try:
         L.net_trace_region(pn.h, x.ptr, x.t.numel() * 4)
+        if pair:
+            x1 = cg.Tensor(torch.zeros(pair * int(np.prod(ishape))), (pair,) + ishape, fmt)
+            L.net_trace_region(pn.h, x1.ptr, x1.t.numel() * 4)
+
+        def forward():
+            if not pair:
+                return pn.forward(x)
+            pn.forward_pair(x1, x)
+            return pn.pair_join()
+
         r = cg.tensor.rng()
         r.offset = rng_offset
-        pn.forward(x)
+        forward()
         first = pn.take_trace().strip().split("\n")   # first pass: weight packing included
         r.offset = rng_offset
-        y = pn.forward(x)
+        y = forward()
         res = dict(first_forward=first, forward=pn.take_trace().strip().split("\n"), draws=r.offset - rng_offset, out_shape=y.shape,
                    out_fmt=y.fmt)
+        res["stats"] = pn.stats()
+        res["net"], res["module"] = pn, net
+        if not backward:
+            return res
         gy = cg.Tensor(torch.zeros(int(np.prod(y.shape))), y.shape, y.fmt)
         L.net_trace_region(pn.h, gy.ptr, max(gy.t.numel() * 4, 4))
         gi = pn.backward(x, gy, True)

@@ -44,7 +44,9 @@ def test_plan_variants_equal_the_recorded_sequences(vid, tmp_path):
     draw count and the plan's statistics.  The fixtures were recorded on the parent commit of the change that made a lone module a
     lockstep group of one (one tree walker in csrc/net.hip instead of two) and are not regenerated: that walker must emit exactly
     what the single-branch walker emitted.  Three cases are kept as text, the others as a SHA-1 of it;
-    `make_net_plan_golden.py --print <id>` writes a case's text for a diff between two builds."""
+    `make_net_plan_golden.py --print <id>` writes a case's text for a diff between two builds.
+    The 16 px networks, the passes after evaluate(), world 2 with fusion off and the forward_pair / pair_join entry points were
+    recorded (`--add`) on the parent commit of the change that wrote each layer's launch sequence once and split csrc/net.hip in three."""
     got = G.variant_text(vid)
     if vid in G.FULL_TEXT:
         want = open(G.variant_file(vid)).read()
@@ -57,6 +59,14 @@ def test_plan_variants_equal_the_recorded_sequences(vid, tmp_path):
         fn = tmp_path / (vid + ".txt")
         fn.write_text(got)
         pytest.fail(f"{vid}: the plan's text (written to {fn}) has SHA-1 {G.digest(got)}, recorded {want}")
+
+
+@pytest.mark.parametrize("which,N", [("G32up-c", 8), ("G32up", 16)])
+def test_batch_norm_backward_after_evaluate_is_refused(which, N):
+    """The generators' forward after evaluate() is recorded above; their backward has no launch for a batch-norm on its running
+    statistics and says so instead of planning one."""
+    with pytest.raises(T.cg_pkg()._abi.CatganError, match=r"batch-norm backward in evaluate\(\) mode is not on the path"):
+        T.trace(which, N, evaluate=True)
 
 
 def test_segments_and_lockstep_branches_of_the_discriminator():
