@@ -31,7 +31,12 @@
 //     geometry allows (round 2: the ablation builds below located the loop's loss in the register -> LDS staging).
 // What the two staging families of a GEMM have in common is written once: the blockIdx.z decode and operand selection (nn_tile / tn_tile),
 // the NN epilogue (nn_epilogue: bias, activation, statistics, the lean and the generic stores), the TN partial store (tn_store_partials) and
-// the host's packing of the four-pointer argument fields (set4).  The skinny 3x3 layers (<= 3 output planes) have their kernels, MFMA and
+// the host's packing of the four-pointer argument fields (set4) here; in gemm_tile.h everything in front of and inside the K loop - the
+// XCD tile orders (nn_tile_order / tn_tile_order), the FAST gather state of the NN pair (NNGather: row decode, tap masks, the tap walk
+// with its position-major variant, weight offsets, descriptors), the lean addressing of the TN pair (tn_col_decode, tn_lean_geom - the
+// rule the host's tng_ok states too -, tn_lean_a / tn_lean_b, tn_tile_bases), the two-buffer loop driver (k_loop2) and the K-major
+// fragment loop (mfma_k_major; igemm_nng_kernel's quad fragments are its own).  The host picks the compiled block tile in one place
+// (with_block_tile).  The skinny 3x3 layers (<= 3 output planes) have their kernels, MFMA and
 // VALU, in skinny.hip; this file only decides which of them runs (cg::skinny_ok, CG_SKINNY).  What follows a weight-gradient launch - the
 // reduction of its partials into the canonical gradients, now or deferred - is cg::wgrad_finish (wgrad_finish.hip); the re-packing of the
 // canonical weights into this file's operands is pack.hip.
@@ -232,6 +237,8 @@ __device__ __forceinline__ int pm_valid_taps(const Geom& g, int pos) {
 template <int BKT>
 __device__ __forceinline__ int a_swizzle(int kv) { return BKT == 32 ? ((kv & 7) << 2) : ((kv & 3) << 3); }
 
+#include "gemm_tile.h"   // tile order, NN gather state, TN addressing, the K loop: shared by the staging families below
+
 // Lean epilogue of the NN kernels for a FULL tile whose output rows are consecutive ([row][Cout], i.e. stride-1 layers and split
 // partials): one buffer store per value at (per-lane byte offset) + (row offset in an SGPR).  The generic loop below it - bounds checks,
 // 64-bit addresses and an output-row decode per row - is ~2000 instructions per wave; with all workgroups of a launch reaching their
@@ -394,13 +401,9 @@ __global__ __launch_bounds__(256, BK == 16 ? 4 : 2) void igemm_nn_kernel(NNArgs 
     // at fixed k) stays a permutation of the 32 banks.  No padding.
     constexpr int LDA = BM, LDB = BN;
     constexpr int A_TILE = BK * LDA, B_TILE = BK * LDB;
-    constexpr int KV = BK / 4;        // float4 per A row
-    constexpr int ARPP = 256 / KV;    // A rows per pass
-    constexpr int AROWS = BM / ARPP;  // float4 per thread per tile (A)
-    static_assert(BM % ARPP == 0 && AROWS >= 1, "BM multiple of rows-per-pass");
-    constexpr int NVEC = BN / 4;
-    constexpr int BRPP = 256 / NVEC;  // B rows per pass
-    constexpr int BPASS = (BK + BRPP - 1) / BRPP;
+    using Gather = NNGather<BM, BN, BK, false>;
+    constexpr int KV = Gather::KV, ARPP = Gather::ARPP, AROWS = Gather::AROWS;       // float4 per A row, A rows per pass, float4 per thread per tile
+    constexpr int NVEC = Gather::NVEC, BRPP = Gather::BRPP, BPASS = Gather::BPASS;   // B rows per pass
 
     __shared__ __attribute__((aligned(16))) float smem[2 * A_TILE + 2 * B_TILE];
     float* As = smem;
@@ -414,114 +417,43 @@ __global__ __launch_bounds__(256, BK == 16 ? 4 : 2) void igemm_nn_kernel(NNArgs 
     const int wm0 = (wave / WN) * (BM / WM);
     const int wn0 = (wave % WN) * (BN / WN);
 
-    const int ntn = (g.Cout + BN - 1) / BN;
-    // XCD-aware tile order: workgroup b is dispatched to XCD b % 8 (each XCD has its own L2), so hand every XCD a CONTIGUOUS
-    // range of tiles - neighbours then share their A rows / B columns through one L2 instead of eight
-    int bid = blockIdx.x;
-    if ((a.xcd_swizzle & 1) && (gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
-    const int tn = ntn == 1 ? 0 : bid % ntn, tm = ntn == 1 ? bid : bid / ntn;
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int split = blockIdx.y;
+    const TileIdx ti = nn_tile_order<false, false>((g.Cout + BN - 1) / BN, a.xcd_swizzle);
+    const int tm = ti.tm, split = ti.split;
+    const int m0 = tm * BM, n0 = ti.tn * BN;
     const int zz = blockIdx.z;
     const NNTile z = nn_tile(a, zz);
-    const int phase = z.phase, pa = z.pa, pb = z.pb;
+    const int pa = z.pa, pb = z.pb;
     const float* gx = z.x;
     const float* wph = z.w;
     const int ks = split * a.kchunk;
     const int kend = min(g.Ktot, ks + a.kchunk);
-    const int T = CG_PROBE_HALF(1, (kend - ks + BK - 1) / BK);
+    int T = CG_PROBE_HALF(1, (kend - ks + BK - 1) / BK);
 
     // ---- A staging: thread owns k-vector a_kv (4 consecutive k) of rows a_r + 64p
     const int a_kv = tid % KV, a_r = tid / KV;
     int rowb[AROWS], r_oy[AROWS], r_ox[AROWS];
     bool r_ok[AROWS];
 #pragma unroll
-    for (int p = 0; p < AROWS; ++p) {
-        const int m = m0 + a_r + ARPP * p;
-        r_ok[p] = m < g.M;
-        int n, oy, ox;
-        pix_decode(g, r_ok[p] ? m : 0, n, oy, ox);
-        r_oy[p] = oy; r_ox[p] = ox;
-        rowb[p] = ((n * g.Hs + oy * g.td.ss) * g.Ws + ox * g.td.ss) * g.Cin;
-    }
+    for (int p = 0; p < AROWS; ++p) Gather::decode_row(g, m0 + a_r + ARPP * p, 0, rowb[p], r_oy[p], r_ox[p], r_ok[p]);
     const int b_nv = tid % NVEC, b_kr = tid / NVEC;
 
     float4 areg[AROWS];
     float4 breg[BPASS];
 
-    // ---- FAST-path state -------------------------------------------------------------------------------
-    unsigned long long cur[AROWS];     // tap-validity mask of each row, shifted so bit 0 = next tile's tap
-    unsigned rowbytes[AROWS];
-    unsigned bvoff[BPASS];
-    int tapi = 0, ci0 = 0, toff = 0, minoff = 0;
-    __amdgpu_buffer_rsrc_t rsx, rsw;
-    if (FAST) {
-        const TapDesc& d = g.td;
-        const int kh = d.kk / d.kw;
-#pragma unroll
-        for (int p = 0; p < AROWS; ++p) cur[p] = 0ull;
-        for (int grp = 0; grp < d.ngroups; ++grp) {
-            int ga = pa, gb = pb;
-            if (d.ngroups > 1) { ga = grp >> 1; gb = grp & 1; }
-            unsigned xb[AROWS];
-#pragma unroll
-            for (int p = 0; p < AROWS; ++p) xb[p] = 0u;
-            for (int rx = 0; rx < d.kw; ++rx) {
-                const int tx = d.sgn * ((gb ? d.r0x1 : d.r0x0) + rx);
-#pragma unroll
-                for (int p = 0; p < AROWS; ++p)
-                    xb[p] |= ((unsigned)(r_ox[p] + tx) < (unsigned)g.Wv ? 1u : 0u) << rx;
-            }
-            for (int ry = 0; ry < kh; ++ry) {
-                const int ty = d.sgn * ((ga ? d.r0y1 : d.r0y0) + ry);
-                const int sh = grp * d.kk + ry * d.kw;
-#pragma unroll
-                for (int p = 0; p < AROWS; ++p)
-                    if (r_ok[p] && (unsigned)(r_oy[p] + ty) < (unsigned)g.Hv) cur[p] |= (unsigned long long)xb[p] << sh;
-            }
-        }
-        minoff = sel4(phase, g.minoff0, g.minoff1, g.minoff2, g.minoff3);   // host-computed (finish_geom)
-        tapi = ks == 0 ? 0 : ks / g.Cin;
-        ci0 = ks - tapi * g.Cin;
-        { int ty, tx; tap_decode(g, tapi, pa, pb, ty, tx, toff); }
-#pragma unroll
-        for (int p = 0; p < AROWS; ++p) {
-            cur[p] >>= tapi;
-            rowbytes[p] = (unsigned)(rowb[p] + 4 * a_kv) * 4u;
-        }
-        // base shifted down by the most negative tap offset so that the SGPR offset stays non-negative
-        rsx = __builtin_amdgcn_make_buffer_rsrc((void*)(gx + minoff), 0, 0x7fffffff, 0x00020000);
-        rsw = __builtin_amdgcn_make_buffer_rsrc((void*)wph, 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-        for (int q = 0; q < BPASS; ++q) {
-            const int kr = b_kr + q * BRPP;
-            const int n = n0 + 4 * b_nv;
-            bvoff[q] = (kr < BK && n < g.Cout) ? (unsigned)(kr * g.Cout + n) * 4u : OOB;
-        }
-    }
+    Gather gs;     // FAST-path state
+    if (FAST) gs.start(g, z, gx, wph, a.kchunk, ks, split, T, a_kv, n0, b_nv, b_kr, rowb, r_oy, r_ox, r_ok);
 
     auto load_tile = [&](int k0) {
         if (FAST) {
-            // (tapi, ci0, toff) describe this tile; all SGPR arithmetic
-            const int soff = (toff - minoff + ci0) * 4;
+            const int soff = gs.soff();
 #pragma unroll
-            for (int p = 0; p < AROWS; ++p) {
-                const unsigned voff = ((unsigned)cur[p] & 1u) ? rowbytes[p] : OOB;
-                areg[p] = bufld4(rsx, voff, soff);
-            }
+            for (int p = 0; p < AROWS; ++p) areg[p] = bufld4(gs.rsx, gs.avoff(p), soff);
             if (VECB) {
                 const int sb = k0 * g.Cout * 4;
 #pragma unroll
-                for (int q = 0; q < BPASS; ++q) breg[q] = bufld4(rsw, bvoff[q], sb);
+                for (int q = 0; q < BPASS; ++q) breg[q] = bufld4(gs.rsw, gs.bvoff[q], sb);
             }
-            ci0 += BK;
-            if (ci0 >= g.Cin) {
-                ci0 = 0;
-                ++tapi;
-#pragma unroll
-                for (int p = 0; p < AROWS; ++p) cur[p] >>= 1;
-                if (tapi < g.ntaps) { int ty, tx; tap_decode(g, tapi, pa, pb, ty, tx, toff); }
-            }
+            gs.advance(g, pa, pb);
         } else {
             float tmp[AROWS][4];
 #pragma unroll
@@ -569,9 +501,7 @@ __global__ __launch_bounds__(256, BK == 16 ? 4 : 2) void igemm_nn_kernel(NNArgs 
         }
     };
 
-    // the LDS double-buffer index is a compile-time constant everywhere (the K loop is unrolled by two), so that every
-    // ds_read / ds_write address is a loop-invariant register plus an immediate offset - no address VALU in the loop
-    auto store_tile = [&](auto bufc) {
+    auto store_tile = [&](auto bufc) {   // compile-time buffer index: k_loop2
         constexpr int buf = decltype(bufc)::value;
         float* A = As + buf * A_TILE;
         float* B = Bs + buf * B_TILE;
@@ -590,13 +520,7 @@ __global__ __launch_bounds__(256, BK == 16 ? 4 : 2) void igemm_nn_kernel(NNArgs 
         }
     };
 
-    f32x16 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc[MI][NI] = {};
 
     CG_STAMP(6);   // trace builds: end of the integer set-up (tile origin, tap-validity masks, descriptors)
     if (T > 0) {
@@ -609,23 +533,13 @@ __global__ __launch_bounds__(256, BK == 16 ? 4 : 2) void igemm_nn_kernel(NNArgs 
     auto k_tile = [&](auto bufc, int t) {
         constexpr int buf = decltype(bufc)::value;
         if (t + 1 < T) load_tile(ks + (t + 1) * BK);   // tile t + 1 into the staging registers, stored to LDS behind this tile's MFMAs
-        const float* A = As + buf * A_TILE + wm0;
-        const float* B = Bs + buf * B_TILE + wn0 + l31;
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            float av[MI], bv[NI];
-#pragma unroll
-            for (int i = 0; i < MI; ++i) av[i] = A[(kk + h) * LDA + i * 32 + (l31 ^ a_swizzle<BK>(kk >> 2))];
-#pragma unroll
-            for (int j = 0; j < NI; ++j) bv[j] = B[(kk + h) * LDB + j * 32];
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-        }
+        mfma_k_major<MI, NI, LDA, LDB, BK, true>(acc, As + buf * A_TILE + wm0, Bs + buf * B_TILE + wn0 + l31, h, l31);
         if (t + 1 < T) store_tile(std::integral_constant<int, buf ^ 1>{});
         __syncthreads();
     };
+    // (k_loop2's loop, spelled out: through the shared driver this kernel's short launches - nn.Linear 100 -> 8192 forward, 7 K tiles - ran
+    // 17.8 us against the parent's 17.5 in every alternating run, with the same instructions in the loop, and no other form of the driver
+    // brought them back: profiles/gemm_prologue_refactor.txt, section 3)
     for (int t = 0; t < T; t += 2) {
         k_tile(std::integral_constant<int, 0>{}, t);
         if (t + 1 < T) k_tile(std::integral_constant<int, 1>{}, t + 1);
@@ -656,15 +570,11 @@ __global__ __launch_bounds__(256, 2) void igemm_nng_kernel(NNArgs a) {
     constexpr int MI = BM / WM / 32;
     constexpr int NI = BN / WN / 32;
     constexpr int A_TILE = BK * BM, B_TILE = BK * BN;
-    constexpr int KV = BK / 4;        // quads per A row
+    using Gather = NNGather<BM, BN, BK, PM>;
+    constexpr int KV = Gather::KV, ARPP = Gather::ARPP, AROWS = Gather::AROWS;       // quads per A row, A rows per pass of the workgroup
+    constexpr int NVEC = Gather::NVEC, BRPP = Gather::BRPP, BPASS = Gather::BPASS;   // B rows per pass
     constexpr int RPW = 64 / KV;      // A rows per wave instruction
-    constexpr int ARPP = 256 / KV;    // A rows per pass of the workgroup
-    constexpr int AROWS = BM / ARPP;
-    static_assert(BM % ARPP == 0 && AROWS >= 1, "BM multiple of rows-per-pass");
-    constexpr int NVEC = BN / 4;
     constexpr int BRPW = 64 / NVEC;   // B rows per wave instruction
-    constexpr int BRPP = 256 / NVEC;  // B rows per pass
-    constexpr int BPASS = (BK + BRPP - 1) / BRPP;
     constexpr int G2 = KV / 2;
 
     // separate arrays per buffer: the compiler can then tell the buffer the DMA writes from the one the fragments are read from
@@ -681,32 +591,15 @@ __global__ __launch_bounds__(256, 2) void igemm_nng_kernel(NNArgs a) {
     const int wm0 = (wave / WN) * (BM / WM);
     const int wn0 = (wave % WN) * (BN / WN);
 
-    const int ntn = (g.Cout + BN - 1) / BN;
-    int bid = blockIdx.x;
-    // (PM: the natural order - consecutive tiles on consecutive XCDs - spreads the short border positions and the long centre ones
-    // evenly over the XCDs; contiguous ranges would give one XCD the top row of the image and another the middle)
-    int tn, tm;
-    const int tiles_m = (int)gridDim.x / ntn, xg = ntn <= 8 ? 8 / ntn : 0;       // xg: XCDs per column tile
-    if (!PM && (a.xcd_swizzle & 4) && (ntn == 2 || ntn == 4 || ntn == 8) && (gridDim.x & 7) == 0 && tiles_m % xg == 0) {
-        // WEIGHTS-stationary XCDs (round 5): XCD k = bid % 8 owns column tile k % ntn and one of 8 / ntn row ranges, so its
-        // L2 holds ONE [Ktot x BN] slice of the (phase) kernel - 1 MB for conv1's forward, where the row-range order below made all eight
-        // XCDs fetch all four column slices: 8 x 16.8 MB of kernels per launch against 4 x 4.2 MB of input now (r x c XCD grid over
-        // rows x columns: traffic = c * |x| + r * |w|)
-        const int k = bid & 7, j = bid >> 3;
-        tn = k % ntn;
-        tm = (k / ntn) * (tiles_m / xg) + j;
-    } else {
-        if (!PM && (a.xcd_swizzle & 1) && (gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
-        tn = ntn == 1 ? 0 : bid % ntn; tm = ntn == 1 ? bid : bid / ntn;
-    }
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int split = blockIdx.y;
+    const TileIdx ti = nn_tile_order<true, PM>((g.Cout + BN - 1) / BN, a.xcd_swizzle);
+    const int tm = ti.tm, split = ti.split;
+    const int m0 = tm * BM, n0 = ti.tn * BN;
     const int zz = blockIdx.z;
     const NNTile z = nn_tile(a, zz);
-    const int phase = z.phase, pa = z.pa, pb = z.pb;
+    const int pa = z.pa, pb = z.pb;
     const float* gx = z.x;
     const float* wph = z.w;
-    int ks = split * a.kchunk;
+    const int ks = split * a.kchunk;
     const int kend = min(g.Ktot, ks + a.kchunk);
     int T = (kend - ks + BK - 1) / BK;
     const int pos_u = PM ? (m0 >> g.pm_lg) : 0;      // PM: the tile's pixel position (wave-uniform; N is a multiple of BM)
@@ -717,129 +610,31 @@ __global__ __launch_bounds__(256, 2) void igemm_nng_kernel(NNArgs a) {
     int rowb[AROWS], r_oy[AROWS], r_ox[AROWS];
     bool r_ok[AROWS];
 #pragma unroll
-    for (int p = 0; p < AROWS; ++p) {
-        const int m = m0 + a_r + ARPP * p;
-        r_ok[p] = m < g.M;
-        int n, oy, ox;
-        if (PM) {
-            n = m & (g.pmn - 1);
-            oy = g.lgW >= 0 ? pos_u >> g.lgW : pos_u / g.Wg;
-            ox = pos_u - oy * g.Wg;
-        } else pix_decode(g, r_ok[p] ? m : 0, n, oy, ox);
-        r_oy[p] = oy; r_ox[p] = ox;
-        rowb[p] = ((n * g.Hs + oy * g.td.ss) * g.Ws + ox * g.td.ss) * g.Cin;
-    }
+    for (int p = 0; p < AROWS; ++p) Gather::decode_row(g, m0 + a_r + ARPP * p, pos_u, rowb[p], r_oy[p], r_ox[p], r_ok[p]);
     const int b_nv = tid % NVEC, b_kr = tid / NVEC;
-
-    unsigned long long cur[AROWS];     // tap-validity mask of each row, shifted so bit 0 = next tile's tap
-    unsigned long long um = 0ull;      // PM: the tile's tap-validity mask (unshifted, wave-uniform)
-    unsigned rowbytes[AROWS];
-    unsigned bvoff[BPASS];
-    int tapi = 0, ci0 = 0, toff = 0, minoff = 0;
-    {
-        const TapDesc& d = g.td;
-        const int kh = d.kk / d.kw;
-#pragma unroll
-        for (int p = 0; p < AROWS; ++p) cur[p] = 0ull;
-        for (int grp = 0; grp < d.ngroups; ++grp) {
-            int ga = pa, gb = pb;
-            if (d.ngroups > 1) { ga = grp >> 1; gb = grp & 1; }
-            unsigned xb[AROWS];
-#pragma unroll
-            for (int p = 0; p < AROWS; ++p) xb[p] = 0u;
-            for (int rx = 0; rx < d.kw; ++rx) {
-                const int tx = d.sgn * ((gb ? d.r0x1 : d.r0x0) + rx);
-#pragma unroll
-                for (int p = 0; p < AROWS; ++p)
-                    xb[p] |= ((unsigned)(r_ox[p] + tx) < (unsigned)g.Wv ? 1u : 0u) << rx;
-            }
-            for (int ry = 0; ry < kh; ++ry) {
-                const int ty = d.sgn * ((ga ? d.r0y1 : d.r0y0) + ry);
-                const int sh = grp * d.kk + ry * d.kw;
-#pragma unroll
-                for (int p = 0; p < AROWS; ++p)
-                    if (r_ok[p] && (unsigned)(r_oy[p] + ty) < (unsigned)g.Hv) cur[p] |= (unsigned long long)xb[p] << sh;
-            }
-        }
-        minoff = sel4(phase, g.minoff0, g.minoff1, g.minoff2, g.minoff3);   // host-computed (finish_geom)
-        if (PM) {
-            // every row of the tile has the mask of row 0; the tile's VALID taps (16 .. 49 of the 7x7 kernel at 8x8) are walked in tap
-            // order, in as many equal K units as their length asks for (a.kchunk = the unit the host aims at), one workgroup each
-            um = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(cur[0] >> 32)) << 32) |
-                 (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)cur[0]);   // (the builtin returns int: no sign extension)
-            const int kv = __builtin_popcountll(um) * g.Cin;
-            const int nunits = (kv + a.kchunk - 1) / a.kchunk;        // <= gridDim.y; a workgroup past them has nothing to do:
-            if (split >= nunits) return;                              // the reduce adds this tile's nunits partials only
-            const int kch = ((kv / BK + nunits - 1) / nunits) * BK;
-            const int ksv = split * kch, kev = min(kv, ksv + kch);
-            T = kev > ksv ? (kev - ksv) / BK : 0;
-            const int vi = ksv / g.Cin;
-            ci0 = ksv - vi * g.Cin;
-            unsigned long long r = um;
-            for (int c = 0; c < vi; ++c) r &= r - 1;
-            tapi = r ? __builtin_ctzll(r) : g.ntaps;
-        } else {
-        tapi = ks == 0 ? 0 : ks / g.Cin;
-        ci0 = ks - tapi * g.Cin;
-        }
-        { int ty, tx; tap_decode(g, tapi, pa, pb, ty, tx, toff); }
-#pragma unroll
-        for (int p = 0; p < AROWS; ++p) {
-            cur[p] >>= tapi;
-            rowbytes[p] = (unsigned)(rowb[p] + 4 * (a_kv ^ a_sw)) * 4u;
-        }
-#pragma unroll
-        for (int q = 0; q < BPASS; ++q) {
-            const int kr = b_kr + q * BRPP;
-            const int n = n0 + 4 * b_nv;
-            bvoff[q] = (kr < BK && n < g.Cout) ? (unsigned)(kr * g.Cout + n) * 4u : OOB;
-        }
-    }
-    // base shifted down by the most negative tap offset so that the SGPR offset stays non-negative
-    __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)(gx + minoff), 0, 0x7fffffff, 0x00020000);
-    __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)wph, 0, 0x7fffffff, 0x00020000);
+    Gather gs;
+    if (!gs.start(g, z, gx, wph, a.kchunk, ks, split, T, a_kv ^ a_sw, n0, b_nv, b_kr, rowb, r_oy, r_ox, r_ok)) return;
 
     // request tile k0 (the FAST-path state describes it) into buffer `buf`; the wave's own 1 KB pieces
     auto dma_tile = [&](int k0, auto bufc) {
         constexpr int buf = decltype(bufc)::value;
         float* A = buf ? As1 : As0;
         float* B = buf ? Bs1 : Bs0;
-        const int soff = (toff - minoff + ci0) * 4;
-        if (PM) k0 = tapi * g.Cin + ci0;       // the weight rows of the tap the walk is at
+        const int soff = gs.soff();
+        if (PM) k0 = gs.tapi * g.Cin + gs.ci0;       // the weight rows of the tap the walk is at
 #pragma unroll
-        for (int p = 0; p < AROWS; ++p) {
-            const unsigned voff = (PM || ((unsigned)cur[p] & 1u)) ? rowbytes[p] : OOB;   // PM: only valid taps are visited
-            glds16(rsx, A + (ARPP * p + wave * RPW) * BK, voff, soff);
-        }
+        for (int p = 0; p < AROWS; ++p) glds16(gs.rsx, A + (ARPP * p + wave * RPW) * BK, gs.avoff(p), soff);
         const int sb = k0 * g.Cout * 4;
 #pragma unroll
         for (int q = 0; q < BPASS; ++q) {
             const int row0 = q * BRPP + wave * BRPW;   // wave-uniform
             if (BPASS * BRPP == BK || row0 < BK)
-                glds16(rsw, B + row0 * BN, bvoff[q], sb);
+                glds16(gs.rsw, B + row0 * BN, gs.bvoff[q], sb);
         }
-        ci0 += BK;
-        if (ci0 >= g.Cin) {
-            ci0 = 0;
-            if (PM) {
-                const unsigned long long rest = um >> (tapi + 1);      // tapi + 1 <= 64 taps - 1 (finish_geom caps a launch at 64 taps ...)
-                tapi = rest ? tapi + 1 + __builtin_ctzll(rest) : g.ntaps;
-            } else {
-            ++tapi;
-#pragma unroll
-            for (int p = 0; p < AROWS; ++p) cur[p] >>= 1;
-            }
-            if (tapi < g.ntaps) { int ty, tx; tap_decode(g, tapi, pa, pb, ty, tx, toff); }
-        }
+        gs.advance(g, pa, pb);
     };
 
-    f32x16 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc[MI][NI] = {};
 
     T = CG_PROBE_HALF(1, T);
     if (T > 0) dma_tile(ks, std::integral_constant<int, 0>{});
@@ -879,10 +674,7 @@ __global__ __launch_bounds__(256, 2) void igemm_nng_kernel(NNArgs a) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of tile t + 1 are in LDS
         __syncthreads();
     };
-    for (int t = 0; t < T; t += 2) {
-        k_tile(std::integral_constant<int, 0>{}, t);
-        if (t + 1 < T) k_tile(std::integral_constant<int, 1>{}, t + 1);
-    }
+    k_loop2(T, k_tile);
 
     CG_STAMP(2);
     nn_epilogue<BM, BN, WM, WN, true, PM>(acc, a, z, m0, n0, wm0, wn0, l31, h, wave, tm, zz, split, pos_u);
@@ -1023,23 +815,12 @@ __global__ __launch_bounds__(256, 4) void igemm_tn_kernel(TNArgs a) {
     const int wm0 = (wave / WN) * (BM / WM);
     const int wn0 = (wave % WN) * (BN / WN);
 
-    const int ntn = (g.Cout + BN - 1) / BN;
-    int bid = blockIdx.x, split = blockIdx.y;
-    if ((a.xcd_swizzle & 2) && (gridDim.y & 7) == 0) {
-        // XCD = pixel chunk: workgroup L of the dispatch order (x fastest, then y) runs on XCD L % 8; give every XCD the splits
-        // congruent to its number, for all tiles - it then reads one eighth of x and dy (each pixel chunk is wanted by every
-        // tile), instead of every XCD reading all of dy for its few tiles
-        const int L = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x, s8 = (int)gridDim.y >> 3;
-        split = (L & 7) + 8 * ((L >> 3) % s8);
-        bid = (L >> 3) / s8;
-    } else if ((a.xcd_swizzle & 1) && (gridDim.x & 7) == 0) {
-        bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);   // see igemm_nn_kernel
-    }
-    const int tn = ntn == 1 ? 0 : bid % ntn, tm = ntn == 1 ? bid : bid / ntn;
+    const TileIdx ti = tn_tile_order((g.Cout + BN - 1) / BN, a.xcd_swizzle);
+    const int tm = ti.tm, tn = ti.tn, split = ti.split;
     const int m0 = tm * BM, n0 = tn * BN;  // m0: row of dW (tap,ci)
     const int zz = blockIdx.z;
     const TNTile z = tn_tile(a, zz);
-    const int phase = z.phase, pa = z.pa, pb = z.pb;
+    const int pa = z.pa, pb = z.pb;
     const float* gx = z.x;
     const float* gdy = z.dy;
     const int ps = split * a.pchunk;
@@ -1051,19 +832,11 @@ __global__ __launch_bounds__(256, 4) void igemm_tn_kernel(TNArgs a) {
     int c_off[NJ], c_ty[NJ], c_tx[NJ];
     bool c_ok[NJ];
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int mm = m0 + 4 * a_mv + j;
-        c_ok[j] = mm < g.Ktot;
-        const int mc = c_ok[j] ? mm : 0;
-        const int tap = mc / g.Cin;
-        int off;
-        tap_decode(g, tap, pa, pb, c_ty[j], c_tx[j], off);
-        c_off[j] = off + (mc - tap * g.Cin);
-    }
+    for (int j = 0; j < NJ; ++j) tn_col_decode(g, m0 + 4 * a_mv + j, pa, pb, c_ok[j], c_ty[j], c_tx[j], c_off[j]);
     const int b_nv = tid % BVEC, b_kr = tid / BVEC;
     const bool b_nok = n0 + 4 * b_nv < g.Cout;
-    __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)gx, 0, 0x7fffffff, 0x00020000);
-    __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc((void*)gdy, 0, 0x7fffffff, 0x00020000);
+    __amdgpu_buffer_rsrc_t rsx = buf_rsrc(gx);
+    __amdgpu_buffer_rsrc_t rsd = buf_rsrc(gdy);
 
     float4 areg[APASS];
     float4 breg[BPASS];
@@ -1071,59 +844,27 @@ __global__ __launch_bounds__(256, 4) void igemm_tn_kernel(TNArgs a) {
     const bool do_bias = a.bias_part != nullptr && tm == 0;
     float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
 
-    // Lean per-tile address math (every VALU op here costs MFMA issue slots): 32-bit offsets, the pixel decoded
-    // once per row and shared by both operands when their row mappings coincide, source base = pix*Cin when the
-    // grid and the source tensor have the same geometry (always true for "same"-padded layers).
-    const bool lin_src = g.td.ss == 1 && g.Hs == g.Hg && g.Ws == g.Wg;
-    const bool lin_out = g.so == 1 && g.nphase == 1;
+    // The generic gather below decodes the pixel once per row and shares it between both operands when their row mappings coincide; the
+    // lean arm (tn_lean_geom; vector loads, whole K tiles, whole passes) keeps every per-tile VALU op out of the loop.
+    const bool lin_src = tn_lin_src(g), lin_out = tn_lin_out(g);
     constexpr bool SAME_ROWS = (AVEC == BVEC);
-
-    // ---- lean tile addressing for power-of-two grids (all layers of the models): a K tile is 16 consecutive grid pixels
-    // starting at a multiple of 16, so the image and the tile's first row / column are wave-uniform (SALU), while a
-    // thread's own row / column offset inside the tile, its tap and its byte offsets are loop invariants.  Per tile and
-    // operand row that leaves two adds, two compares and a select instead of ~25 VALU of pixel decoding.
-    const int HWg = g.Hg * g.Wg;
-    const bool lean = VECA && VECB && g.lgW >= 0 && g.lgHW >= 0 && HWg >= BK && lin_src && (lin_out || g.so == 2) &&
-                      (ps % BK) == 0 && (pend % BK) == 0 && APASS * ARPP == BK && BPASS * BRPP == BK;
+    const bool lean = VECA && VECB && tn_lean_geom(g) && (ps % BK) == 0 && (pend % BK) == 0 && APASS * ARPP == BK && BPASS * BRPP == BK;
     int l_ay[APASS], l_ax[APASS];
     unsigned l_avoff[APASS], l_bvoff[BPASS];
     int l_minoff = 0;
     __amdgpu_buffer_rsrc_t rsx_l = rsx;
     if (lean) {
-        l_minoff = sel4(phase, g.minoff0, g.minoff1, g.minoff2, g.minoff3);   // host-computed (finish_geom)
-        rsx_l = __builtin_amdgcn_make_buffer_rsrc((void*)(gx + l_minoff), 0, 0x7fffffff, 0x00020000);
-#pragma unroll
-        for (int q = 0; q < APASS; ++q) {
-            const int kr = a_kr + q * ARPP;
-            const int kyo = g.Wg >= BK ? 0 : (kr >> g.lgW), kxo = g.Wg >= BK ? kr : (kr & (g.Wg - 1));
-            l_ay[q] = kyo + c_ty[0];
-            l_ax[q] = kxo + c_tx[0];
-            l_avoff[q] = c_ok[0] ? (unsigned)(kr * g.Cin + c_off[0] - l_minoff) * 4u : OOB;
-        }
-#pragma unroll
-        for (int q = 0; q < BPASS; ++q) {
-            const int kr = b_kr + q * BRPP;
-            const int kyo = g.Wg >= BK ? 0 : (kr >> g.lgW), kxo = g.Wg >= BK ? kr : (kr & (g.Wg - 1));
-            const int rel = lin_out ? kr * g.Cout : (kyo * g.so * g.Wout + kxo * g.so) * g.Cout;
-            l_bvoff[q] = b_nok ? (unsigned)(rel + n0 + 4 * b_nv) * 4u : OOB;
-        }
+        l_minoff = sel4(z.phase, g.minoff0, g.minoff1, g.minoff2, g.minoff3);   // host-computed (finish_geom)
+        rsx_l = buf_rsrc(gx + l_minoff);
+        tn_lean_a<APASS, ARPP>(g, 0, a_kr, c_ok[0], c_ty[0], c_tx[0], c_off[0], l_minoff, l_ay, l_ax, l_avoff);
+        tn_lean_b<BPASS, BRPP>(g, 0, b_kr, b_nok, n0, b_nv, l_bvoff);
     }
     auto load_tile = [&](int p0) {
         if (lean) {
-            const int r0 = p0 & (HWg - 1);
-            const int oyb = r0 >> g.lgW, oxb = r0 & (g.Wg - 1);
-            const int soa = p0 * g.Cin * 4;
+            int oyb, oxb, soa, sob;
+            tn_tile_bases(g, false, p0, pa, pb, oyb, oxb, soa, sob);
 #pragma unroll
-            for (int q = 0; q < APASS; ++q) {
-                const bool ok = (unsigned)(oyb + l_ay[q]) < (unsigned)g.Hv && (unsigned)(oxb + l_ax[q]) < (unsigned)g.Wv;
-                areg[q] = bufld4(rsx_l, ok ? l_avoff[q] : OOB, soa);
-            }
-            int sob;
-            if (lin_out) sob = p0 * g.Cout * 4;
-            else {
-                const int nimg = p0 >> g.lgHW;
-                sob = (((nimg * g.Hout + oyb * g.so + pa) * g.Wout + oxb * g.so + pb) * g.Cout) * 4;
-            }
+            for (int q = 0; q < APASS; ++q) areg[q] = bufld4(rsx_l, tn_row_ok(g, oyb + l_ay[q], oxb + l_ax[q]) ? l_avoff[q] : OOB, soa);
 #pragma unroll
             for (int q = 0; q < BPASS; ++q) breg[q] = bufld4(rsd, l_bvoff[q], sob);
             return;
@@ -1191,7 +932,7 @@ __global__ __launch_bounds__(256, 4) void igemm_tn_kernel(TNArgs a) {
         }
     };
 
-    auto store_tile = [&](auto bufc) {   // compile-time buffer index, as in igemm_nn_kernel
+    auto store_tile = [&](auto bufc) {   // compile-time buffer index: k_loop2
         constexpr int buf = decltype(bufc)::value;
         float* A = As + buf * A_TILE;
         float* B = Bs + buf * B_TILE;
@@ -1210,13 +951,7 @@ __global__ __launch_bounds__(256, 4) void igemm_tn_kernel(TNArgs a) {
         }
     };
 
-    f32x16 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc[MI][NI] = {};
 
     if (T > 0) {
         load_tile(ps);
@@ -1229,26 +964,11 @@ __global__ __launch_bounds__(256, 4) void igemm_tn_kernel(TNArgs a) {
         if (t + 1 < T) load_tile(ps + (t + 1) * BK);
         const float* A = As + buf * A_TILE + wm0 + l31;
         const float* B = Bs + buf * B_TILE + wn0 + l31;
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            float av[MI], bv[NI];
-#pragma unroll
-            for (int i = 0; i < MI; ++i) av[i] = A[(kk + h) * LDA + i * 32];
-#pragma unroll
-            for (int j = 0; j < NI; ++j) bv[j] = B[(kk + h) * LDB + j * 32];
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-        }
+        mfma_k_major<MI, NI, LDA, LDB, BK, false>(acc, A, B, h, l31);
         if (t + 1 < T) store_tile(std::integral_constant<int, buf ^ 1>{});
         __syncthreads();
     };
-    for (int t = 0; t < T; t += 2) {
-        k_tile(std::integral_constant<int, 0>{}, t);
-        if (t + 1 < T) k_tile(std::integral_constant<int, 1>{}, t + 1);
-    }
+    k_loop2(T, k_tile);
 
     if (do_bias) {  // all waves are past the loop's final barrier: reuse the A tile as scratch
         float* red = smem;
@@ -1307,20 +1027,12 @@ __global__ __launch_bounds__(256, 2) void igemm_tng_kernel(TNArgs a, int mode) {
     const int wm0 = (wave / WN) * (BM / WM);
     const int wn0 = (wave % WN) * (BN / WN);
 
-    const int ntn = (g.Cout + BN - 1) / BN;
-    int bid = blockIdx.x, split = blockIdx.y;
-    if ((a.xcd_swizzle & 2) && (gridDim.y & 7) == 0) {   // XCD = pixel chunk, see igemm_tn_kernel
-        const int L = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x, s8 = (int)gridDim.y >> 3;
-        split = (L & 7) + 8 * ((L >> 3) % s8);
-        bid = (L >> 3) / s8;
-    } else if ((a.xcd_swizzle & 1) && (gridDim.x & 7) == 0) {
-        bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
-    }
-    const int tn = ntn == 1 ? 0 : bid % ntn, tm = ntn == 1 ? bid : bid / ntn;
+    const TileIdx ti = tn_tile_order((g.Cout + BN - 1) / BN, a.xcd_swizzle);
+    const int tm = ti.tm, tn = ti.tn, split = ti.split;
     const int m0 = tm * BM, n0 = tn * BN;
     const int zz = blockIdx.z;
     const TNTile z = tn_tile(a, zz);
-    const int phase = z.phase, pa = z.pa, pb = z.pb;
+    const int pa = z.pa, pb = z.pb;
     const float* gx = z.x;
     const float* gdy = z.dy;
     const int ps = split * a.pchunk;
@@ -1351,41 +1063,16 @@ __global__ __launch_bounds__(256, 2) void igemm_tng_kernel(TNArgs a, int mode) {
 
     const int a_mv = tid % AVEC, a_kr = tid / AVEC;
     const int b_nv = tid % BVEC, b_kr = tid / BVEC;
-    const bool lin_out = g.so == 1 && g.nphase == 1;
-    const int HWg = g.Hg * g.Wg;
-    int l_minoff = 0, c_ty = 0, c_tx = 0, c_off = 0;
+    int c_ty, c_tx, c_off;
     bool c_ok;
-    {
-        const int mm = m0 + 4 * a_mv;
-        c_ok = mm < g.Ktot;
-        const int mc = c_ok ? mm : 0;
-        const int tap = mc / g.Cin;
-        int off;
-        tap_decode(g, tap, pa, pb, c_ty, c_tx, off);
-        c_off = off + (mc - tap * g.Cin);
-        l_minoff = sel4(phase, g.minoff0, g.minoff1, g.minoff2, g.minoff3);   // host-computed (finish_geom)
-    }
-    __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc((void*)(gx + l_minoff), 0, 0x7fffffff, 0x00020000);
-    __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc((void*)gdy, 0, 0x7fffffff, 0x00020000);
-    const bool b_nok = n0 + 4 * b_nv < g.Cout;
+    tn_col_decode(g, m0 + 4 * a_mv, pa, pb, c_ok, c_ty, c_tx, c_off);
+    const int l_minoff = sel4(z.phase, g.minoff0, g.minoff1, g.minoff2, g.minoff3);   // host-computed (finish_geom)
+    __amdgpu_buffer_rsrc_t rsx = buf_rsrc(gx + l_minoff);
+    __amdgpu_buffer_rsrc_t rsd = buf_rsrc(gdy);
     int l_ay[APASS], l_ax[APASS];
     unsigned l_avoff[APASS], l_bvoff[BPASS];
-    const bool wide = flat || g.Wg >= BK;
-#pragma unroll
-    for (int q = 0; q < APASS; ++q) {
-        const int kr = a_kr + q * ARPP;
-        const int kyo = (wide || pm) ? 0 : (kr >> g.lgW), kxo = (flat || pm) ? 0 : (wide ? kr : (kr & (g.Wg - 1)));
-        l_ay[q] = kyo + c_ty;
-        l_ax[q] = kxo + c_tx;
-        l_avoff[q] = (c_ok && kr < BK) ? (unsigned)(kr * (pm ? g.Hs * g.Ws : 1) * g.Cin + c_off - l_minoff) * 4u : OOB;
-    }
-#pragma unroll
-    for (int q = 0; q < BPASS; ++q) {
-        const int kr = b_kr + q * BRPP;
-        const int byo = wide ? 0 : (kr >> g.lgW), bxo = wide ? kr : (kr & (g.Wg - 1));
-        const int rel = pm ? kr * g.Hout * g.Wout * g.Cout : (lin_out ? kr * g.Cout : (byo * g.so * g.Wout + bxo * g.so) * g.Cout);
-        l_bvoff[q] = (b_nok && kr < BK) ? (unsigned)(rel + n0 + 4 * b_nv) * 4u : OOB;
-    }
+    tn_lean_a<APASS, ARPP>(g, mode, a_kr, c_ok, c_ty, c_tx, c_off, l_minoff, l_ay, l_ax, l_avoff);
+    tn_lean_b<BPASS, BRPP>(g, mode, b_kr, n0 + 4 * b_nv < g.Cout, n0, b_nv, l_bvoff);
     // gradBias rides along on the row-tile 0 workgroups (mode 2: the tile of the tap at offset (0, 0), which visits every position):
     // column sums of the dy rows, read back from the LDS tile
     const int tm_bias = pm ? ((-g.td.r0y0) * g.td.kw + (-g.td.r0x0)) * g.Cin / BM : 0;
@@ -1405,23 +1092,11 @@ __global__ __launch_bounds__(256, 2) void igemm_tng_kernel(TNArgs a, int mode) {
                 q_c = 0;
                 if (++q_x == q_x1) { q_x = q_x0; ++q_y; }
             }
-        } else {
-            const int r0 = flat ? 0 : (p0 & (HWg - 1));
-            oyb = flat ? 0 : (r0 >> g.lgW); oxb = flat ? 0 : (r0 & (g.Wg - 1));
-            soa = p0 * g.Cin * 4;
-            if (lin_out) sob = p0 * g.Cout * 4;
-            else {
-                const int nimg = p0 >> g.lgHW;
-                sob = (((nimg * g.Hout + oyb * g.so + pa) * g.Wout + oxb * g.so + pb) * g.Cout) * 4;
-            }
-        }
+        } else tn_tile_bases(g, flat, p0, pa, pb, oyb, oxb, soa, sob);
 #pragma unroll
         for (int q = 0; q < APASS; ++q) {
             const int row0 = q * ARPP + wave * ARPW;   // wave-uniform
-            if (APASS * ARPP == BK || row0 < BK) {
-                const bool ok = (unsigned)(oyb + l_ay[q]) < (unsigned)g.Hv && (unsigned)(oxb + l_ax[q]) < (unsigned)g.Wv;
-                glds16(rsx, A + row0 * LDA, ok ? l_avoff[q] : OOB, soa);
-            }
+            if (APASS * ARPP == BK || row0 < BK) glds16(rsx, A + row0 * LDA, tn_row_ok(g, oyb + l_ay[q], oxb + l_ax[q]) ? l_avoff[q] : OOB, soa);
         }
 #pragma unroll
         for (int q = 0; q < BPASS; ++q) {
@@ -1430,13 +1105,7 @@ __global__ __launch_bounds__(256, 2) void igemm_tng_kernel(TNArgs a, int mode) {
         }
     };
 
-    f32x16 acc[MI][NI];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NI; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc[MI][NI] = {};
 
     if (T > 0) dma_tile(ps, std::integral_constant<int, 0>{});
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1451,26 +1120,11 @@ __global__ __launch_bounds__(256, 2) void igemm_tng_kernel(TNArgs a, int mode) {
 #pragma unroll
             for (int kk = 0; kk < BK; ++kk) bsum += (buf ? Bs1 : Bs0)[kk * LDB + tid];
         }
-#pragma unroll
-        for (int kk = 0; kk < BK; kk += 2) {
-            float av[MI], bv[NI];
-#pragma unroll
-            for (int i = 0; i < MI; ++i) av[i] = A[(kk + h) * LDA + i * 32];
-#pragma unroll
-            for (int j = 0; j < NI; ++j) bv[j] = B[(kk + h) * LDB + j * 32];
-#pragma unroll
-            for (int i = 0; i < MI; ++i)
-#pragma unroll
-                for (int j = 0; j < NI; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-        }
+        mfma_k_major<MI, NI, LDA, LDB, BK, false>(acc, A, B, h, l31);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
     };
-    for (int t = 0; t < T; t += 2) {
-        k_tile(std::integral_constant<int, 0>{}, t);
-        if (t + 1 < T) k_tile(std::integral_constant<int, 1>{}, t + 1);
-    }
+    k_loop2(T, k_tile);
 
     if (do_bias && tid < BN && n0 + tid < g.Cout)
         a.bias_part[tn_plane(a, split, zz) * g.Cout + n0 + tid] = bsum;
@@ -1499,6 +1153,16 @@ __global__ __launch_bounds__(256, 2) void igemm_tng_kernel(TNArgs a, int mode) {
 
 // ---- host-side dispatch -----------------------------------------------------
 struct TileCfg { int bm, bn; };
+// the compiled block tiles (BM x BN, WM x WN waves) of all four GEMM kernels: launch(BlockTile<...>{}) for the one the plan chose
+template <int BM_, int BN_, int WM_, int WN_> struct BlockTile { static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_; };
+template <class Launch>
+static void with_block_tile(const TileCfg& tc, Launch&& launch) {
+    if (tc.bm == 128 && tc.bn == 128) launch(BlockTile<128, 128, 2, 2>{});
+    else if (tc.bm == 64 && tc.bn == 128) launch(BlockTile<64, 128, 2, 2>{});
+    else if (tc.bm == 128 && tc.bn == 64) launch(BlockTile<128, 64, 2, 2>{});
+    else if (tc.bm == 64 && tc.bn == 64) launch(BlockTile<64, 64, 2, 2>{});
+    else launch(BlockTile<128, 32, 4, 1>{});
+}
 // swept in rounds 2-5 (profiles/r0N_sweeps.txt: flat or worse around these), constants since round 6
 constexpr int kSplitTarget = 1, kSplitMinK = 8;      // forward / data gradient: split K until one workgroup per CU, >= 8 K iterations per split
 constexpr int kTnSplitMax = 256, kTnTarget = 3;      // weight gradients: pixel splits up to 256, three workgroups per CU
@@ -1579,16 +1243,12 @@ static void launch_tn(const TNArgs& a, dim3 grid, hipStream_t st, bool veca, boo
     else hipLaunchKernelGGL((igemm_tn_kernel<BM, BN, WM, WN, false, false>), grid, dim3(256), 0, st, a);
 }
 
-// LDS-direct weight-gradient kernel (igemm_tng_kernel, K step 16): lean addressing only
+// LDS-direct weight-gradient kernel (igemm_tng_kernel, K step 16): lean addressing only - whole K tiles of a flat or a lean geometry
+static bool tng_flat(const Geom& g) { return g.ntaps == 1 && g.td.r0y0 == 0 && g.td.r0x0 == 0 && tn_lin_out(g); }
 static bool tng_ok(const Geom& g, int pchunk, bool veca, bool vecb) {
-    if (!cg::opt(cg::OPT_TN_GLDS) || !veca || !vecb) return false;
-    const bool lin_src = g.td.ss == 1 && g.Hs == g.Hg && g.Ws == g.Wg;
-    const bool lin_out = g.so == 1 && g.nphase == 1;
-    if (!lin_src || g.M % 16 || pchunk % 16) return false;
-    const bool flat = g.ntaps == 1 && g.td.r0y0 == 0 && g.td.r0x0 == 0 && lin_out;
-    return flat || (g.lgW >= 0 && g.lgHW >= 0 && g.Hg * g.Wg >= 16 && (lin_out || g.so == 2));
+    if (!cg::opt(cg::OPT_TN_GLDS) || !veca || !vecb || g.M % BK || pchunk % BK) return false;
+    return (tn_lin_src(g) && tng_flat(g)) || tn_lean_geom(g);
 }
-static bool tng_flat(const Geom& g) { return g.ntaps == 1 && g.td.r0y0 == 0 && g.td.r0x0 == 0 && g.so == 1 && g.nphase == 1; }
 
 // Position-major K tiles (igemm_tng_kernel mode 2): the share of the layer's MACs that multiply zero padding in per cent, -1 = not this
 // geometry (a plain stride-1 convolution with a tap at offset (0, 0) that is valid at every position, whole K tiles of images).
@@ -1743,9 +1403,6 @@ static size_t nn_ws_bytes(const Geom& g, const NNPlan& p, int ngroups) {
 }
 
 struct TNPlan { TileCfg tc; int splits; int pchunk; bool pm; };
-static bool tn_pm_use(const Geom& g, bool image_major_ok);
-static bool tng_ok(const Geom& g, int pchunk, bool veca, bool vecb);
-static int tn_pm_share(const Geom& g);
 static TNPlan plan_tn(const Geom& g, int ngroups, bool allow_pm = true) {
     TNPlan p;
     int bn = g.Cout > 64 ? 128 : (g.Cout > 32 ? 64 : 32);
@@ -1863,11 +1520,10 @@ static int run_nn(hipStream_t st, const Geom& g, int ngroups, const float* const
         a.g.pm_lg = ilog2_exact(a.g.pmn);
     }
     dim3 grid(cg::cdiv(g.M, p.tc.bm) * cg::cdiv(g.Cout, p.tc.bn), p.splits, g.nphase * ngroups);
-    if (p.tc.bm == 128 && p.tc.bn == 128) launch_nn<128, 128, 2, 2>(a, grid, st, fast, vecb, bk32);
-    else if (p.tc.bm == 64 && p.tc.bn == 128) launch_nn<64, 128, 2, 2>(a, grid, st, fast, vecb, bk32);
-    else if (p.tc.bm == 128 && p.tc.bn == 64) launch_nn<128, 64, 2, 2>(a, grid, st, fast, vecb, bk32);
-    else if (p.tc.bm == 64 && p.tc.bn == 64) launch_nn<64, 64, 2, 2>(a, grid, st, fast, vecb, bk32);
-    else launch_nn<128, 32, 4, 1>(a, grid, st, fast, vecb, bk32);
+    with_block_tile(p.tc, [&](auto t) {
+        using T = decltype(t);
+        launch_nn<T::BM, T::BN, T::WM, T::WN>(a, grid, st, fast, vecb, bk32);
+    });
     CG_LAUNCH_CHECK();
     if (p.splits > 1) {
         const long PMN = (long)ngroups * g.nphase * g.M * g.Cout;
@@ -2048,20 +1704,13 @@ int cg_conv2d_wgrad_gemm(void* stream, const float* x, const float* dy, int N, i
 }
 
 namespace {
-// the compiled block tiles of the two staging families (tng: LDS-direct loads)
+// the two staging families of the weight gradient (tng: LDS-direct loads)
 void launch_tn_tile(const TNArgs& a, const TileCfg& tc, bool tng, dim3 grid, hipStream_t st, bool veca, bool vecb) {
-    if (tng) {
-        if (tc.bm == 128 && tc.bn == 128) launch_tng<128, 128, 2, 2>(a, grid, st);
-        else if (tc.bm == 64 && tc.bn == 128) launch_tng<64, 128, 2, 2>(a, grid, st);
-        else if (tc.bm == 128 && tc.bn == 64) launch_tng<128, 64, 2, 2>(a, grid, st);
-        else if (tc.bm == 64 && tc.bn == 64) launch_tng<64, 64, 2, 2>(a, grid, st);
-        else launch_tng<128, 32, 4, 1>(a, grid, st);
-    }
-    else if (tc.bm == 128 && tc.bn == 128) launch_tn<128, 128, 2, 2>(a, grid, st, veca, vecb);
-    else if (tc.bm == 64 && tc.bn == 128) launch_tn<64, 128, 2, 2>(a, grid, st, veca, vecb);
-    else if (tc.bm == 128 && tc.bn == 64) launch_tn<128, 64, 2, 2>(a, grid, st, veca, vecb);
-    else if (tc.bm == 64 && tc.bn == 64) launch_tn<64, 64, 2, 2>(a, grid, st, veca, vecb);
-    else launch_tn<128, 32, 4, 1>(a, grid, st, veca, vecb);
+    with_block_tile(tc, [&](auto t) {
+        using T = decltype(t);
+        if (tng) launch_tng<T::BM, T::BN, T::WM, T::WN>(a, grid, st);
+        else launch_tn<T::BM, T::BN, T::WM, T::WN>(a, grid, st, veca, vecb);
+    });
 }
 
 int wgrad_impl(void* stream, int ngroups, const float* const* x, const float* const* dy, float* const* gw, float* const* gb, int N,

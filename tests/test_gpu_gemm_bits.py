@@ -59,9 +59,10 @@ def check(golden, case, *arrays):
     print(f"{case}: sha256 {digest}")
     if RECORD:
         _recorded[case] = digest
-        return
+        return digest
     assert case in golden, f"{case}: no digest in {GOLDEN}"
     assert digest == golden[case], f"{case}: output / gradInput / gradWeight / gradBias differ from the recorded bits"
+    return digest
 
 
 # the two staging families (register staging / LDS-direct loads) of the NN and TN kernels
@@ -110,6 +111,57 @@ def test_store_tails(cg, golden, tail, family, splits):
     epilogue adds the bias and stores the output itself; with three forced splits it stores partials and the reduce kernels finish."""
     with options(cg, CG_NN_SPLITS=splits, CG_TN_SPLITS=splits, **FAMILIES[family], **NO_OTHER):
         check(golden, f"{tail} / {family} / splits {splits}", *conv_bits(cg, *TAILS[tail], seed=len(tail)))
+
+
+# The branches of the kernels' SET-UP (tile order, row / column decode, tap masks and walk, lean addressing, K step, rows per pass): what
+# the two staging families share in front of and inside the K loop (csrc/gemm_tile.h).
+LEAN = TAILS["lean consecutive tail"]
+
+
+def test_no_vector_path(cg, golden):
+    """(2, 5, 6, 5, 7, 3, 0): M = 2 * 6 * 5 = 60 rows of a 6 x 5 grid (no power of two: lgW = -1, the pixel decode divides), Cin = 5 and
+    Cout = 7, so Cin % 16 != 0 (FAST off: igemm_nn_kernel's per-element gather), Cout % 4 != 0 forward and Cin % 4 != 0 in the data
+    gradient (VECB off: scalar weight loads) -> igemm_nn_kernel<128, 32, 4, 1, false, false, 16> both ways; the weight gradient has
+    Cin % 4 != 0 and Cout % 4 != 0 -> igemm_tn_kernel<..., false, false> (four columns decoded per thread, scalar dy loads, never lean)."""
+    with options(cg, **NO_OTHER):
+        check(golden, "no vector path", *conv_bits(cg, 2, 5, 6, 5, 7, 3, 0, seed=19))
+
+
+@pytest.mark.parametrize("family", list(FAMILIES))
+def test_k_step_16(cg, golden, family):
+    """CG_GEMM_BK32 = 0 on (4, 64, 16, 16, 128, 3, 0): the plan picks 64-row tiles (M = 1024: 8 x 1 tiles of 128 rows < 2 x 256 CUs), which
+    run K step 32 by default; with the option off igemm_nn_kernel<64, 128, 2, 2, true, true, 16> (regs) and igemm_nng_kernel<64, 128, 2, 2, 16>
+    (glds: CG_NN_GLDS = 3 allows its K step 16) - KV = 4 quads per row, the two-bit swizzles, ARPP = 64 rows per pass."""
+    with options(cg, CG_GEMM_BK32=0, **FAMILIES[family], **NO_OTHER):
+        check(golden, f"k step 16 / {family}", *conv_bits(cg, *LEAN, seed=23))
+
+
+@pytest.mark.parametrize("bk32", [1, 0])
+@pytest.mark.parametrize("family", list(FAMILIES))
+def test_128_row_tiles(cg, golden, family, bk32):
+    """CG_NN_TILE = CG_TN_TILE = 128128 on the same shape.  NN: MI = 2 accumulator rows per wave; K step 32 only in the LDS-direct family
+    (igemm_nng_kernel<128, 128, 2, 2, 32>: ARPP = 32, AROWS = 4), the register kernel keeps K step 16 for 128-row tiles (ARPP = 64,
+    AROWS = 2) and so does LDS-direct with CG_GEMM_BK32 = 0.  TN: AVEC = 32 quads per row, ARPP = 8, APASS = 2 passes per K tile for both
+    operands (the 64-row tiles: one A pass of 16 rows); Ktot = 576 = 4.5 row tiles, so the last tile is half empty (c_ok, generic store)."""
+    with options(cg, CG_NN_TILE=128128, CG_TN_TILE=128128, CG_GEMM_BK32=bk32, **FAMILIES[family], **NO_OTHER):
+        check(golden, f"128-row tiles / {family} / bk32 {bk32}", *conv_bits(cg, *LEAN, seed=29))
+
+
+@pytest.mark.parametrize("family", list(FAMILIES))
+def test_tile_orders(cg, golden, family):
+    """(8, 256, 8, 8, 256, 3, 0), CG_NN_SPLITS = 1, CG_TN_SPLITS = 8, at CG_XCD_SWIZZLE 0 (natural order), 1 and 7.
+    NN (forward and data gradient alike, Cin = Cout): M = 8 * 64 = 512, Cout = 256 -> BN = 128, and 4 x 2 tiles of 128 rows < 2 x 256 CUs
+    -> BM = 64: gridDim.x = 8 row tiles x 2 column tiles = 16, a multiple of 8, so bit 1 hands every XCD a row range; ntn = 2, xg = 4 XCDs
+    per column tile, 8 row tiles % 4 == 0 and ntn * xb + (8 / ntn) * wb < xb + 8 * wb (xb = 8 * 64 * 256 * 4 = 0.5 MB < 4 wb,
+    wb = 2304 * 256 * 4 = 2.4 MB), so bit 4 makes the LDS-direct kernel weights-stationary (the register kernel has bit 1 only).
+    TN: Ktot = 2304 -> 18 x 2 tiles of 128 x 128, 512 / 16 = 32 K tiles in 8 splits of 64 pixels: gridDim.y & 7 == 0, so bit 2 gives every
+    XCD its pixel chunks (gridDim.x = 36 is no multiple of 8: bit 1 alone leaves the natural order).
+    The order decides only which workgroup computes which tile: the three digests are equal, and pinned."""
+    digests = []
+    for swz in (0, 1, 7):
+        with options(cg, CG_XCD_SWIZZLE=swz, CG_NN_SPLITS=1, CG_TN_SPLITS=8, **FAMILIES[family], **NO_OTHER):
+            digests.append(check(golden, f"tile order / {family} / swizzle {swz}", *conv_bits(cg, 8, 256, 8, 8, 256, 3, 0, seed=31)))
+    assert digests[0] == digests[1] == digests[2], f"the tile order changed the bits: {digests}"
 
 
 def planned_bits(cg, build, x, fusion, seed):
