@@ -19,6 +19,13 @@
 //   faces_variant_hpass_k  one workgroup per (band of window rows, variant): the second warp, whose taps read the pixel stage
 //                       (flip, brightness, noise, clip, truncation) evaluated on the fly out of the crop - the noise is keyed by the
 //                       source position, so a tap shared by two outputs agrees - then the horizontal pass out of the LDS.
+//
+// cg_faces_u8_extract_padded makes the padded faces of generate_dataset.py --margin: the whole padded crop of each face, its pad its
+// own (faces_crop_k and faces_median_k read a pad per face; the variants pass their one scalar), resized.  The numpy restatement is
+// faces.padded_face_np.  One kernel between the crops and the same vertical pass:
+//   faces_crop_hpass_k  one workgroup per band of crop rows: the finished rows are copied into the LDS byte for byte (no warp - an
+//                       identity warp would re-quantise through (u8)((v / 255) 255), which is not v for every byte), then the
+//                       horizontal pass out of the LDS against the tables of the PADDED sides.
 #include <vector>
 #include "common.h"
 
@@ -100,6 +107,15 @@ __device__ __forceinline__ int owner(const int32_t* __restrict__ start, int N, i
     }
     return f;
 }
+// the band of rows that block b works on: its face, its first row and its rows, for faces whose geometry rows hold (H, W) at [4], [5]
+struct Band {
+    int f, r0, nr;
+};
+__device__ __forceinline__ Band band_of(const int32_t* __restrict__ band_start, const int32_t* __restrict__ geom, int N, int b) {
+    const int f = owner(band_start, N, b);
+    const int H = geom[(long)f * kGeom + 4], R = band_rows(geom[(long)f * kGeom + 5]), r0 = (b - band_start[f]) * R;
+    return {f, r0, min(R, H - r0)};
+}
 // the horizontal pass of nr warped rows [nr][Wr][3] out of the LDS against one table (tb: [out][2] (xmin, count), then [out][kx] taps)
 __device__ __forceinline__ void hpass_band(const unsigned char* band, int nr, int Wr, const int32_t* __restrict__ tb, int kx, int out,
                                            unsigned char* __restrict__ trow) {
@@ -126,10 +142,9 @@ __global__ void __launch_bounds__(256) faces_warp_hpass_k(const unsigned char* _
     __shared__ float unit[256];
     fill_unit(unit);
     __syncthreads();
-    const int b = blockIdx.x, f = owner(band_start, N, b);
+    const auto [f, r0, nr] = band_of(band_start, geom, N, blockIdx.x);
     const int32_t* g = geom + (long)f * kGeom;
-    const int Hs = g[0], Ws = g[1], y0 = g[2], x0 = g[3], Hr = g[4], Wr = g[5], kx = g[6];
-    const int R = band_rows(Wr), r0 = (b - band_start[f]) * R, nr = min(R, Hr - r0);
+    const int Hs = g[0], Ws = g[1], y0 = g[2], x0 = g[3], Wr = g[5], kx = g[6];
     const ImagePx px{src + src_off[f], Ws * 3};
     const float* m = inv + (long)f * 6;
     for (int e = threadIdx.x; e < nr * Wr; e += 256) {
@@ -140,18 +155,20 @@ __global__ void __launch_bounds__(256) faces_warp_hpass_k(const unsigned char* _
     hpass_band(band, nr, Wr, taps + tap_off[2 * f], kx, out, tmp + tmp_off[f] + (long)r0 * out * 3);
 }
 
-// the padded crop's in-image window (extract_rectangle, dataset.py:191-230, before its np.pad): kCropPixels pixels per workgroup
+// the padded crop's in-image window (extract_rectangle, dataset.py:191-230, before its np.pad): kCropPixels pixels per workgroup.
+// Face f's pad is pads[f], or pad_all for every face where pads is null
 constexpr int kCropPixels = 1024;
 __global__ void __launch_bounds__(256) faces_crop_k(const unsigned char* __restrict__ src, const uint64_t* __restrict__ src_off,
                                                     const int32_t* __restrict__ geom, const float* __restrict__ inv,
                                                     const int32_t* __restrict__ cblk_start, const uint64_t* __restrict__ crop_off,
-                                                    unsigned char* __restrict__ crops, int N, int pad) {
+                                                    unsigned char* __restrict__ crops, int N, const int32_t* __restrict__ pads,
+                                                    int pad_all) {
     __shared__ float unit[256];
     fill_unit(unit);
     __syncthreads();
     const int b = blockIdx.x, f = owner(cblk_start, N, b);
     const int32_t* g = geom + (long)f * kGeom;
-    const int Hs = g[0], Ws = g[1], y0 = g[2], x0 = g[3], Hr = g[4], Wr = g[5];
+    const int Hs = g[0], Ws = g[1], y0 = g[2], x0 = g[3], Hr = g[4], Wr = g[5], pad = pads ? pads[f] : pad_all;
     const int Wp = Wr + 2 * pad, top = max(0, pad - y0), left = max(0, pad - x0);
     const int Hwin = min(Hs - 1, y0 + Hr - 1 + pad) - (y0 - pad + top) + 1, Wwin = min(Ws - 1, x0 + Wr - 1 + pad) - (x0 - pad + left) + 1;
     const ImagePx px{src + src_off[f], Ws * 3};
@@ -166,15 +183,17 @@ __global__ void __launch_bounds__(256) faces_crop_k(const unsigned char* __restr
 
 // np.pad(mode="median") of one line, one wave per line.  axis 0: line = a column of the window, the median over the window's rows goes
 // into that column's cells above and below; axis 1: line = a row of the whole crop, the median over the window's columns goes into the
-// cells left and right.  The median of L bytes: the middle one, or the mean of the two middle ones rounded half to even.
+// cells left and right.  The median of L bytes: the middle one, or the mean of the two middle ones rounded half to even.  The pad is
+// faces_crop_k's.
 __global__ void __launch_bounds__(64) faces_median_k(const int32_t* __restrict__ geom, const int32_t* __restrict__ line_face,
                                                      const int32_t* __restrict__ line_start, int nfaces, const uint64_t* __restrict__ crop_off,
-                                                     unsigned char* __restrict__ crops, int pad, int axis) {
+                                                     unsigned char* __restrict__ crops, const int32_t* __restrict__ pads, int pad_all,
+                                                     int axis) {
     __shared__ int hist[3][256];
     __shared__ int med[3];
     const int b = blockIdx.x, k = owner(line_start, nfaces, b), f = line_face[k], line = b - line_start[k];
     const int32_t* g = geom + (long)f * kGeom;
-    const int Hs = g[0], Ws = g[1], y0 = g[2], x0 = g[3], Hr = g[4], Wr = g[5];
+    const int Hs = g[0], Ws = g[1], y0 = g[2], x0 = g[3], Hr = g[4], Wr = g[5], pad = pads ? pads[f] : pad_all;
     const int Hp = Hr + 2 * pad, Wp = Wr + 2 * pad;
     const int top = max(0, pad - y0), left = max(0, pad - x0);
     const int bottom = max(0, y0 + Hr - 1 + pad - (Hs - 1)), right = max(0, x0 + Wr - 1 + pad - (Ws - 1));
@@ -220,10 +239,10 @@ __global__ void __launch_bounds__(256) faces_variant_hpass_k(const unsigned char
     __shared__ float unit[256];
     fill_unit(unit);
     __syncthreads();
-    const int b = blockIdx.x, a = blockIdx.y, f = owner(band_start, N, b);
+    const auto [f, r0, nr] = band_of(band_start, geom, N, blockIdx.x);
+    const int a = blockIdx.y;
     const int32_t* g = geom + (long)f * kGeom;
     const int Hr = g[4], Wr = g[5], kx = g[6], Hp = Hr + 2 * pad, Wp = Wr + 2 * pad;
-    const int R = band_rows(Wr), r0 = (b - band_start[f]) * R, nr = min(R, Hr - r0);
     const long item = (long)f * A + a;
     const float* d = desc + item * 8;
     const VariantPx px{crops + crop_off[f], Wp, d[6], sigma, d[7] != 0.f, seed, bases[item]};
@@ -233,6 +252,28 @@ __global__ void __launch_bounds__(256) faces_variant_hpass_k(const unsigned char
     }
     __syncthreads();
     hpass_band(band, nr, Wr, taps + tap_off[2 * f], kx, out, tmp + tmp_off[f] + ((long)a * Hr + r0) * out * 3);
+}
+
+// A band of rows of a finished crop through the horizontal pass.  pgeom holds the PADDED sides (Hp, Wp) and their ksizes where geom
+// holds the rectangle's, so a band is nr Wp 3 contiguous bytes of the crop.  They are copied as they are, 16 bytes per lane between
+// a head and a tail of single bytes; the LDS copy starts at the source's offset within 16 bytes, which aligns both sides alike.
+__global__ void __launch_bounds__(256) faces_crop_hpass_k(const unsigned char* __restrict__ crops, const uint64_t* __restrict__ crop_off,
+                                                          const int32_t* __restrict__ pgeom, const int32_t* __restrict__ taps,
+                                                          const uint64_t* __restrict__ tap_off, const int32_t* __restrict__ band_start,
+                                                          const uint64_t* __restrict__ tmp_off, unsigned char* __restrict__ tmp, int N, int out) {
+    __shared__ __align__(16) unsigned char lds[kBandBytes + 16];   // [rows][Wp][3] from lds + (the source address & 15)
+    const auto [f, r0, nr] = band_of(band_start, pgeom, N, blockIdx.x);
+    const int Wp = pgeom[(long)f * kGeom + 5], kx = pgeom[(long)f * kGeom + 6], n = nr * Wp * 3;
+    const unsigned char* p = crops + crop_off[f] + (long)r0 * Wp * 3;
+    const int shift = (int)(reinterpret_cast<uintptr_t>(p) & 15), head = min((16 - shift) & 15, n), body = (n - head) >> 4;
+    unsigned char* band = lds + shift;
+    if ((int)threadIdx.x < head) band[threadIdx.x] = p[threadIdx.x];
+    const uint4* p16 = reinterpret_cast<const uint4*>(p + head);
+    uint4* b16 = reinterpret_cast<uint4*>(band + head);
+    for (int i = threadIdx.x; i < body; i += 256) b16[i] = p16[i];
+    for (int i = head + (body << 4) + threadIdx.x; i < n; i += 256) band[i] = p[i];
+    __syncthreads();
+    hpass_band(band, nr, Wp, taps + tap_off[2 * f], kx, out, tmp + tmp_off[f] + (long)r0 * out * 3);
 }
 
 // the vertical pass over N per_face items: item i belongs to face i / per_face, its rows follow its face's earlier items in tmp
@@ -268,14 +309,18 @@ int check_table(const char* who, const std::vector<int32_t>& taps, uint64_t off,
     return 0;
 }
 
-// What both entry points take and check alike.  The descriptors are device arrays: they come back once, so that every limit is checked
-// before anything is launched
+constexpr int kPadMax = 2048, kPaddedSideMax = 8192;   // band_rows(8192) is still 1; beyond 10922 it would be 0
+
+// What the entry points take and check alike.  The descriptors are device arrays: they come back once, so that every limit is checked
+// before anything is launched.  With `padded`, dpads [N] comes back too and the resampled sides - what ksize and the tap tables belong
+// to - are the rectangle's enlarged by 2 pads[f]; without it pads stays empty and they are the rectangle's own
 struct Faces {
-    std::vector<int32_t> geom, taps;
+    std::vector<int32_t> geom, taps, pads;
     std::vector<uint64_t> src_off, tap_off;
     int read(const char* who, hipStream_t s, const unsigned char* src, size_t src_bytes, const uint64_t* dsrc_off, const int32_t* dgeom,
-             const float* inv, const int32_t* dtaps, size_t ntaps, const uint64_t* dtap_off, unsigned char* dst, int N, int out, void* workspace) {
-        CG_REQUIRE(src && dsrc_off && dgeom && inv && dtaps && dtap_off && dst && workspace, "%s: null pointer", who);
+             const float* inv, const int32_t* dtaps, size_t ntaps, const uint64_t* dtap_off, unsigned char* dst, int N, int out, void* workspace,
+             const int32_t* dpads = nullptr, bool padded = false) {
+        CG_REQUIRE(src && dsrc_off && dgeom && inv && dtaps && dtap_off && dst && workspace && (dpads || !padded), "%s: null pointer", who);
         CG_REQUIRE(N > 0 && N <= (1 << 20), "%s: N = %d is outside 1..2^20", who, N);
         CG_REQUIRE(out >= 8 && out <= 128, "%s: out = %d is outside 8..128", who, out);
         CG_REQUIRE(src_bytes > 0 && ntaps > 0 && ntaps <= (size_t)1 << 28, "%s: bad array lengths (%zu source bytes, %zu taps)", who, src_bytes, ntaps);
@@ -284,21 +329,30 @@ struct Faces {
         CG_HIP(hipMemcpyAsync(taps.data(), dtaps, taps.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         CG_HIP(hipMemcpyAsync(src_off.data(), dsrc_off, src_off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
         CG_HIP(hipMemcpyAsync(tap_off.data(), dtap_off, tap_off.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        if (padded) {
+            pads.resize(N);
+            CG_HIP(hipMemcpyAsync(pads.data(), dpads, pads.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        }
         CG_HIP(hipStreamSynchronize(s));
         for (int f = 0; f < N; ++f) {
             const int32_t* g = geom.data() + (size_t)f * kGeom;
-            const int Hs = g[0], Ws = g[1], y0 = g[2], x0 = g[3], Hr = g[4], Wr = g[5], kx = g[6], ky = g[7];
+            const int Hs = g[0], Ws = g[1], y0 = g[2], x0 = g[3], Hr = g[4], Wr = g[5], kx = g[6], ky = g[7], pad = padded ? pads[f] : 0;
             CG_REQUIRE(Hs >= 8 && Hs <= 8192 && Ws >= 8 && Ws <= 8192, "%s: face %d: a %d x %d source is outside 8..8192", who, f, Ws, Hs);
+            CG_REQUIRE(pad >= 0 && pad <= kPadMax, "%s: face %d: pad = %d is outside 0..%d", who, f, pad, kPadMax);
+            // ahead of the rectangle's own limit, which with pad <= 2048 implies this one: the kernels' limit is the padded side
+            CG_REQUIRE(!padded || ((long)Hr + 2 * pad <= kPaddedSideMax && (long)Wr + 2 * pad <= kPaddedSideMax),
+                       "%s: face %d: a padded crop of %ld x %ld is beyond %d", who, f, (long)Wr + 2 * pad, (long)Hr + 2 * pad, kPaddedSideMax);
             CG_REQUIRE(Hr >= 8 && Hr <= 4096 && Wr >= 8 && Wr <= 4096, "%s: face %d: a %d x %d rectangle is outside 8..4096", who, f, Wr, Hr);
             CG_REQUIRE(y0 >= 0 && x0 >= 0 && (long)y0 + Hr <= Hs && (long)x0 + Wr <= Ws,
                        "%s: face %d: the rectangle (%d, %d) + %d x %d is not inside its %d x %d source", who, f, x0, y0, Wr, Hr, Ws, Hs);
             CG_REQUIRE(src_off[f] <= src_bytes && (uint64_t)Hs * Ws * 3 <= src_bytes - src_off[f],
                        "%s: face %d: its source at %llu does not fit the %zu bytes given", who, f, (unsigned long long)src_off[f], src_bytes);
-            CG_REQUIRE(kx == resample_ksize(Wr, out) && ky == resample_ksize(Hr, out),
-                       "%s: face %d: ksize (%d, %d) disagrees with the sides %d x %d -> %d, which need (%d, %d)", who, f, kx, ky, Wr, Hr, out,
-                       resample_ksize(Wr, out), resample_ksize(Hr, out));
-            if (int rc = check_table(who, taps, tap_off[2 * f], Wr, out, kx, f, "horizontal")) return rc;
-            if (int rc = check_table(who, taps, tap_off[2 * f + 1], Hr, out, ky, f, "vertical")) return rc;
+            const int Hp = Hr + 2 * pad, Wp = Wr + 2 * pad;
+            CG_REQUIRE(kx == resample_ksize(Wp, out) && ky == resample_ksize(Hp, out),
+                       "%s: face %d: ksize (%d, %d) disagrees with the sides %d x %d -> %d, which need (%d, %d)", who, f, kx, ky, Wp, Hp, out,
+                       resample_ksize(Wp, out), resample_ksize(Hp, out));
+            if (int rc = check_table(who, taps, tap_off[2 * f], Wp, out, kx, f, "horizontal")) return rc;
+            if (int rc = check_table(who, taps, tap_off[2 * f + 1], Hp, out, ky, f, "vertical")) return rc;
         }
         return 0;
     }
@@ -312,6 +366,88 @@ struct Layout {
         bytes = (bytes + n + 15) / 16 * 16;
         return at;
     }
+};
+
+// The padded crops of a batch, face f's pad being pad_of(f): where each lies behind the workspace head, the crop kernel's block map and
+// the lines of the two median launches.  reserve() takes their places in the head, plan() fills them, launch() enqueues the crop
+// kernel and the median fills of the faces and axes that need one
+struct Crops {
+    size_t off_cblk = 0, off_ls[2] = {0, 0}, off_lf[2] = {0, 0}, off_cropoff = 0;
+    long cblks = 0, lines[2] = {0, 0};
+    int nlf[2] = {0, 0};
+    uint64_t bytes = 0;   // every crop [Hp][Wp][3] from a multiple of 16
+    void reserve(Layout& lay, int N) {
+        off_cblk = lay.take((size_t)(N + 1) * 4);
+        for (int a = 0; a < 2; ++a) off_ls[a] = lay.take((size_t)(N + 1) * 4);
+        for (int a = 0; a < 2; ++a) off_lf[a] = lay.take((size_t)N * 4);
+        off_cropoff = lay.take((size_t)N * 8);
+    }
+    template <class Pad>
+    void plan(unsigned char* head, const int32_t* geom, int N, const Pad& pad_of) {
+        auto i32 = [&](size_t off) { return reinterpret_cast<int32_t*>(head + off); };
+        int32_t *cblk_start = i32(off_cblk), *line_start[2] = {i32(off_ls[0]), i32(off_ls[1])}, *line_face[2] = {i32(off_lf[0]), i32(off_lf[1])};
+        uint64_t* crop_off = reinterpret_cast<uint64_t*>(head + off_cropoff);
+        for (int f = 0; f < N; ++f) {
+            const int32_t* g = geom + (size_t)f * kGeom;
+            const int Hs = g[0], Ws = g[1], y0 = g[2], x0 = g[3], Hr = g[4], Wr = g[5], pad = pad_of(f);
+            const int Hp = Hr + 2 * pad, Wp = Wr + 2 * pad;
+            const int top = std::max(0, pad - y0), left = std::max(0, pad - x0);
+            const int bottom = std::max(0, y0 + Hr - 1 + pad - (Hs - 1)), right = std::max(0, x0 + Wr - 1 + pad - (Ws - 1));
+            const int Hwin = Hp - top - bottom, Wwin = Wp - left - right;
+            cblk_start[f] = (int32_t)cblks;
+            crop_off[f] = bytes;
+            cblks += cdiv((long)Hwin * Wwin, kCropPixels);
+            bytes += ((uint64_t)Hp * Wp * 3 + 15) / 16 * 16;
+            if (top || bottom) {   // axis 0: one line per column of the window
+                line_face[0][nlf[0]] = f, line_start[0][nlf[0]++] = (int32_t)lines[0];
+                lines[0] += Wwin;
+            }
+            if (left || right) {   // axis 1: one line per row of the crop, the rows axis 0 filled included
+                line_face[1][nlf[1]] = f, line_start[1][nlf[1]++] = (int32_t)lines[1];
+                lines[1] += Hp;
+            }
+        }
+        cblk_start[N] = (int32_t)cblks;
+        line_start[0][nlf[0]] = (int32_t)lines[0], line_start[1][nlf[1]] = (int32_t)lines[1];
+    }
+    bool fit_one_launch() const { return cblks <= INT32_MAX && lines[0] <= INT32_MAX && lines[1] <= INT32_MAX; }
+    // ws: the workspace with the head in place, the crops from ws + off_crops; pads [N] on the device, or null and pad_all
+    int launch(hipStream_t s, const unsigned char* src, const uint64_t* src_off, const int32_t* geom, const float* inv, unsigned char* ws,
+               size_t off_crops, int N, const int32_t* pads, int pad_all) const {
+        auto di32 = [&](size_t off) { return reinterpret_cast<const int32_t*>(ws + off); };
+        const uint64_t* crop_off = reinterpret_cast<const uint64_t*>(ws + off_cropoff);
+        hipLaunchKernelGGL(faces_crop_k, dim3((unsigned)cblks), dim3(256), 0, s, src, src_off, geom, inv, di32(off_cblk), crop_off, ws + off_crops, N,
+                           pads, pad_all);
+        CG_LAUNCH_CHECK();
+        for (int axis = 0; axis < 2; ++axis) {
+            if (!lines[axis]) continue;
+            hipLaunchKernelGGL(faces_median_k, dim3((unsigned)lines[axis]), dim3(64), 0, s, geom, di32(off_lf[axis]), di32(off_ls[axis]), nlf[axis],
+                               crop_off, ws + off_crops, pads, pad_all, axis);
+            CG_LAUNCH_CHECK();
+        }
+        return 0;
+    }
+};
+
+// The bands of rows of a horizontal pass and where each face's result lies in tmp: face f has hw(f) = (H, W) rows and columns going
+// in, and per_row bytes of tmp per row
+struct Bands {
+    long bands = 0;
+    uint64_t rows = 0;
+    template <class HW>
+    void plan(int32_t* band_start, uint64_t* tmp_off, int N, uint64_t per_row, const HW& hw) {
+        for (int f = 0; f < N; ++f) {
+            const auto [H, W] = hw(f);
+            band_start[f] = (int32_t)bands;
+            tmp_off[f] = rows * per_row;
+            bands += cdiv(H, band_rows(W));
+            rows += (uint64_t)H;
+        }
+        band_start[N] = (int32_t)bands;
+    }
+};
+struct Side2 {
+    int H, W;
 };
 
 }  // namespace
@@ -330,25 +466,16 @@ int cg_faces_u8_extract(void* stream, const unsigned char* src, size_t src_bytes
     Layout lay;
     const size_t off_band = lay.take((size_t)(N + 1) * 4), off_tmpoff = lay.take((size_t)N * 8), off_tmp = lay.bytes;
     std::vector<unsigned char> head(off_tmp, 0);
-    int32_t* band_start = reinterpret_cast<int32_t*>(head.data() + off_band);
-    uint64_t* tmp_off = reinterpret_cast<uint64_t*>(head.data() + off_tmpoff);
-    long bands = 0;
-    uint64_t rows = 0;
-    for (int f = 0; f < N; ++f) {
-        const int Hr = h.geom[(size_t)f * kGeom + 4], Wr = h.geom[(size_t)f * kGeom + 5];
-        band_start[f] = (int32_t)bands;
-        tmp_off[f] = rows * (uint64_t)out * 3;
-        bands += cdiv(Hr, band_rows(Wr));
-        rows += (uint64_t)Hr;
-    }
-    band_start[N] = (int32_t)bands;
-    CG_REQUIRE(bands <= INT32_MAX, "%s: %ld bands of rows do not fit one launch", who, bands);
-    const size_t need = off_tmp + rows * (size_t)out * 3;
+    Bands b;
+    b.plan(reinterpret_cast<int32_t*>(head.data() + off_band), reinterpret_cast<uint64_t*>(head.data() + off_tmpoff), N, (uint64_t)out * 3,
+           [&](int f) { return Side2{h.geom[(size_t)f * kGeom + 4], h.geom[(size_t)f * kGeom + 5]}; });
+    CG_REQUIRE(b.bands <= INT32_MAX, "%s: %ld bands of rows do not fit one launch", who, b.bands);
+    const size_t need = off_tmp + b.rows * (size_t)out * 3;
     CG_REQUIRE(workspace_bytes >= need, "%s: the workspace has %zu bytes, %zu are needed", who, workspace_bytes, need);
     unsigned char* ws = static_cast<unsigned char*>(workspace);
     CG_HIP(hipMemcpyAsync(ws, head.data(), head.size(), hipMemcpyHostToDevice, s));
     CG_HIP(hipStreamSynchronize(s));   // `head` is pageable and ends with this call
-    hipLaunchKernelGGL(faces_warp_hpass_k, dim3((unsigned)bands), dim3(256), 0, s, src, src_off, geom, inv, taps, tap_off,
+    hipLaunchKernelGGL(faces_warp_hpass_k, dim3((unsigned)b.bands), dim3(256), 0, s, src, src_off, geom, inv, taps, tap_off,
                        reinterpret_cast<const int32_t*>(ws + off_band), reinterpret_cast<const uint64_t*>(ws + off_tmpoff), ws + off_tmp, N, out);
     CG_LAUNCH_CHECK();
     const int bpf = cdiv((long)out * out * 3, 256);
@@ -370,73 +497,83 @@ int cg_faces_u8_extract_variants(void* stream, const unsigned char* src, size_t 
     hipStream_t s = S(stream);
     Faces h;
     if (int rc = h.read(who, s, src, src_bytes, src_off, geom, inv, taps, ntaps, tap_off, dst, N, out, workspace)) return rc;
-    // workspace: band_start, cblk_start [N + 1] int32 | the two median launches' line_start [N + 1], line_face [N] int32 |
-    //            tmp_off, crop_off [N] uint64 | the padded crops, each [Hp][Wp][3] from a multiple of 16 | tmp bytes
-    Layout lay;
-    const size_t off_band = lay.take((size_t)(N + 1) * 4), off_cblk = lay.take((size_t)(N + 1) * 4);
-    const size_t off_ls[2] = {lay.take((size_t)(N + 1) * 4), lay.take((size_t)(N + 1) * 4)};
-    const size_t off_lf[2] = {lay.take((size_t)N * 4), lay.take((size_t)N * 4)};
-    const size_t off_tmpoff = lay.take((size_t)N * 8), off_cropoff = lay.take((size_t)N * 8), off_crops = lay.bytes;
-    std::vector<unsigned char> head(off_crops, 0);
-    auto i32 = [&](size_t off) { return reinterpret_cast<int32_t*>(head.data() + off); };
-    auto u64 = [&](size_t off) { return reinterpret_cast<uint64_t*>(head.data() + off); };
-    int32_t *band_start = i32(off_band), *cblk_start = i32(off_cblk);
-    int32_t *line_start[2] = {i32(off_ls[0]), i32(off_ls[1])}, *line_face[2] = {i32(off_lf[0]), i32(off_lf[1])};
-    uint64_t *tmp_off = u64(off_tmpoff), *crop_off = u64(off_cropoff);
-    long bands = 0, cblks = 0, lines[2] = {0, 0};
-    int nlf[2] = {0, 0};
-    uint64_t rows = 0, crop_bytes = 0;
     for (int f = 0; f < N; ++f) {
-        const int32_t* g = h.geom.data() + (size_t)f * kGeom;
-        const int Hs = g[0], Ws = g[1], y0 = g[2], x0 = g[3], Hr = g[4], Wr = g[5];
-        const int Hp = Hr + 2 * pad, Wp = Wr + 2 * pad;
+        const int Hp = h.geom[(size_t)f * kGeom + 4] + 2 * pad, Wp = h.geom[(size_t)f * kGeom + 5] + 2 * pad;
         CG_REQUIRE(Hp <= 4096 + 2 * 64 && Wp <= 4096 + 2 * 64, "%s: face %d: a padded crop of %d x %d is beyond %d", who, f, Wp, Hp, 4096 + 2 * 64);
-        const int top = std::max(0, pad - y0), left = std::max(0, pad - x0);
-        const int bottom = std::max(0, y0 + Hr - 1 + pad - (Hs - 1)), right = std::max(0, x0 + Wr - 1 + pad - (Ws - 1));
-        const int Hwin = Hp - top - bottom, Wwin = Wp - left - right;
-        band_start[f] = (int32_t)bands;
-        cblk_start[f] = (int32_t)cblks;
-        tmp_off[f] = rows * (uint64_t)A * out * 3;
-        crop_off[f] = crop_bytes;
-        bands += cdiv(Hr, band_rows(Wr));
-        cblks += cdiv((long)Hwin * Wwin, kCropPixels);
-        rows += (uint64_t)Hr;
-        crop_bytes += ((uint64_t)Hp * Wp * 3 + 15) / 16 * 16;
-        if (top || bottom) {   // axis 0: one line per column of the window
-            line_face[0][nlf[0]] = f, line_start[0][nlf[0]++] = (int32_t)lines[0];
-            lines[0] += Wwin;
-        }
-        if (left || right) {   // axis 1: one line per row of the crop, the rows axis 0 filled included
-            line_face[1][nlf[1]] = f, line_start[1][nlf[1]++] = (int32_t)lines[1];
-            lines[1] += Hp;
-        }
     }
-    band_start[N] = (int32_t)bands, cblk_start[N] = (int32_t)cblks;
-    line_start[0][nlf[0]] = (int32_t)lines[0], line_start[1][nlf[1]] = (int32_t)lines[1];
+    // workspace: band_start [N + 1] int32 | Crops' maps: cblk_start [N + 1], the two median launches' line_start [N + 1] and
+    //            line_face [N] int32, crop_off [N] uint64 | tmp_off [N] uint64 | the padded crops | tmp bytes
+    Layout lay;
+    const size_t off_band = lay.take((size_t)(N + 1) * 4);
+    Crops c;
+    c.reserve(lay, N);
+    const size_t off_tmpoff = lay.take((size_t)N * 8), off_crops = lay.bytes;
+    std::vector<unsigned char> head(off_crops, 0);
+    Bands b;
+    b.plan(reinterpret_cast<int32_t*>(head.data() + off_band), reinterpret_cast<uint64_t*>(head.data() + off_tmpoff), N, (uint64_t)A * out * 3,
+           [&](int f) { return Side2{h.geom[(size_t)f * kGeom + 4], h.geom[(size_t)f * kGeom + 5]}; });
+    c.plan(head.data(), h.geom.data(), N, [&](int) { return pad; });
     const int bpf = cdiv((long)out * out * 3, 256);
-    CG_REQUIRE(bands <= INT32_MAX && cblks <= INT32_MAX && lines[0] <= INT32_MAX && lines[1] <= INT32_MAX && (long)N * A * bpf <= INT32_MAX,
-               "%s: %d faces with %d variants (%ld bands of rows, %ld crop blocks) do not fit one launch", who, N, A, bands, cblks);
-    const size_t off_tmp = off_crops + crop_bytes, need = off_tmp + rows * (size_t)A * out * 3;
+    CG_REQUIRE(b.bands <= INT32_MAX && c.fit_one_launch() && (long)N * A * bpf <= INT32_MAX,
+               "%s: %d faces with %d variants (%ld bands of rows, %ld crop blocks) do not fit one launch", who, N, A, b.bands, c.cblks);
+    const size_t off_tmp = off_crops + c.bytes, need = off_tmp + b.rows * (size_t)A * out * 3;
     CG_REQUIRE(workspace_bytes >= need, "%s: the workspace has %zu bytes, %zu are needed", who, workspace_bytes, need);
     unsigned char* ws = static_cast<unsigned char*>(workspace);
     CG_HIP(hipMemcpyAsync(ws, head.data(), head.size(), hipMemcpyHostToDevice, s));
     CG_HIP(hipStreamSynchronize(s));   // `head` is pageable and ends with this call
     auto di32 = [&](size_t off) { return reinterpret_cast<const int32_t*>(ws + off); };
     auto du64 = [&](size_t off) { return reinterpret_cast<const uint64_t*>(ws + off); };
-    hipLaunchKernelGGL(faces_crop_k, dim3((unsigned)cblks), dim3(256), 0, s, src, src_off, geom, inv, di32(off_cblk), du64(off_cropoff),
-                       ws + off_crops, N, pad);
-    CG_LAUNCH_CHECK();
-    for (int axis = 0; axis < 2; ++axis) {
-        if (!lines[axis]) continue;
-        hipLaunchKernelGGL(faces_median_k, dim3((unsigned)lines[axis]), dim3(64), 0, s, geom, di32(off_lf[axis]), di32(off_ls[axis]), nlf[axis],
-                           du64(off_cropoff), ws + off_crops, pad, axis);
-        CG_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(faces_variant_hpass_k, dim3((unsigned)bands, (unsigned)A), dim3(256), 0, s, ws + off_crops, du64(off_cropoff), geom, desc,
-                       bases, taps, tap_off, di32(off_band), du64(off_tmpoff), ws + off_tmp, N, A, pad, out, noise_scale, seed);
+    if (int rc = c.launch(s, src, src_off, geom, inv, ws, off_crops, N, nullptr, pad)) return rc;
+    hipLaunchKernelGGL(faces_variant_hpass_k, dim3((unsigned)b.bands, (unsigned)A), dim3(256), 0, s, ws + off_crops, du64(c.off_cropoff), geom,
+                       desc, bases, taps, tap_off, di32(off_band), du64(off_tmpoff), ws + off_tmp, N, A, pad, out, noise_scale, seed);
     CG_LAUNCH_CHECK();
     hipLaunchKernelGGL(faces_vpass_k, dim3((unsigned)((long)N * A * bpf)), dim3(256), 0, s, ws + off_tmp, du64(off_tmpoff), geom, taps, tap_off,
                        dst, out, bpf, A);
     CG_LAUNCH_CHECK();
     return 0;
 }
+
+int cg_faces_u8_extract_padded(void* stream, const unsigned char* src, size_t src_bytes, const uint64_t* src_off, const int32_t* geom,
+                               const float* inv, const int32_t* taps, size_t ntaps, const uint64_t* tap_off, const int32_t* pads,
+                               unsigned char* dst, int N, int out, void* workspace, size_t workspace_bytes) {
+    static const char who[] = "cg_faces_u8_extract_padded";
+    hipStream_t s = S(stream);
+    Faces h;
+    if (int rc = h.read(who, s, src, src_bytes, src_off, geom, inv, taps, ntaps, tap_off, dst, N, out, workspace, pads, true)) return rc;
+    // workspace: band_start [N + 1] int32 | Crops' maps (as the variants') | tmp_off [N] uint64 | pgeom [N][8] int32, geom with the
+    //            padded sides in place of the rectangle's | the padded crops | tmp bytes
+    Layout lay;
+    const size_t off_band = lay.take((size_t)(N + 1) * 4);
+    Crops c;
+    c.reserve(lay, N);
+    const size_t off_tmpoff = lay.take((size_t)N * 8), off_pgeom = lay.take((size_t)N * kGeom * 4), off_crops = lay.bytes;
+    std::vector<unsigned char> head(off_crops, 0);
+    int32_t* pgeom = reinterpret_cast<int32_t*>(head.data() + off_pgeom);
+    for (int f = 0; f < N; ++f) {
+        std::copy_n(h.geom.data() + (size_t)f * kGeom, kGeom, pgeom + (size_t)f * kGeom);
+        pgeom[(size_t)f * kGeom + 4] += 2 * h.pads[f], pgeom[(size_t)f * kGeom + 5] += 2 * h.pads[f];
+    }
+    Bands b;
+    b.plan(reinterpret_cast<int32_t*>(head.data() + off_band), reinterpret_cast<uint64_t*>(head.data() + off_tmpoff), N, (uint64_t)out * 3,
+           [&](int f) { return Side2{pgeom[(size_t)f * kGeom + 4], pgeom[(size_t)f * kGeom + 5]}; });
+    c.plan(head.data(), h.geom.data(), N, [&](int f) { return h.pads[f]; });
+    const int bpf = cdiv((long)out * out * 3, 256);
+    CG_REQUIRE(b.bands <= INT32_MAX && c.fit_one_launch() && (long)N * bpf <= INT32_MAX,
+               "%s: %d faces (%ld bands of rows, %ld crop blocks) do not fit one launch", who, N, b.bands, c.cblks);
+    const size_t off_tmp = off_crops + c.bytes, need = off_tmp + b.rows * (size_t)out * 3;
+    CG_REQUIRE(workspace_bytes >= need, "%s: the workspace has %zu bytes, %zu are needed", who, workspace_bytes, need);
+    unsigned char* ws = static_cast<unsigned char*>(workspace);
+    CG_HIP(hipMemcpyAsync(ws, head.data(), head.size(), hipMemcpyHostToDevice, s));
+    CG_HIP(hipStreamSynchronize(s));   // `head` is pageable and ends with this call
+    auto di32 = [&](size_t off) { return reinterpret_cast<const int32_t*>(ws + off); };
+    auto du64 = [&](size_t off) { return reinterpret_cast<const uint64_t*>(ws + off); };
+    if (int rc = c.launch(s, src, src_off, geom, inv, ws, off_crops, N, pads, 0)) return rc;
+    hipLaunchKernelGGL(faces_crop_hpass_k, dim3((unsigned)b.bands), dim3(256), 0, s, ws + off_crops, du64(c.off_cropoff), di32(off_pgeom), taps,
+                       tap_off, di32(off_band), du64(off_tmpoff), ws + off_tmp, N, out);
+    CG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(faces_vpass_k, dim3((unsigned)((long)N * bpf)), dim3(256), 0, s, ws + off_tmp, du64(off_tmpoff), di32(off_pgeom), taps,
+                       tap_off, dst, out, bpf, 1);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+

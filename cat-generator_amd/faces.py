@@ -38,6 +38,9 @@ base + 3 j, j = (y Wp + x) 3 + c on the array the warp reads, `base` one 64-bit 
 data.  Three exact consequences (tests/test_faces_variants_host.py): the identity draw returns the _000 rectangle; a whole-pixel shift
 alone returns stage 2's warp of the rectangle shifted the other way - real neighbouring pixels; a flip alone returns the mirror.
 
+The PADDED face of generate_dataset.py --margin is stage a with a pad of the face's own (margin_pad) through stage 4 as a whole, with
+nothing in between: padded_face_np, the yardstick of cg_faces_u8_extract_padded, which extract_padded_device calls.
+
 The keypoint move is written as a closed search instead of a warp of a whole image per point: a white pixel at p reaches output pixel q
 with the weight max(0, 1 - |sx - px|) max(0, 1 - |sy - py|), (sx, sy) = F^-1(q), which is zero outside the rotated unit square around
 F(p); that square lies within 1.92 pixels per axis of round(F(p)), so a 5 x 5 window holds every non-zero weight.  The first maximum
@@ -283,30 +286,43 @@ def extract_faces_np(images, keypoints, out=64):
     return res
 
 
-def pack_descriptors(shapes, geoms, out):
-    """The arrays cg_faces_u8_extract reads (catgan.h) for faces with the source sizes `shapes` [(Hs, Ws)] and the geometries `geoms`
-    (dict(inv, rect), as face_geometry's) -> dict(src_off uint64 [N], geom int32 [N, 8], inv float32 [N, 6], taps int32 [ntaps],
-    tap_off uint64 [N, 2], rows = sum of Hr).  Faces of one side share a tap table; source f is expected at src_off[f] of the
-    concatenated bytes."""
+def pack_padded_descriptors(shapes, geoms, pads, out):
+    """The arrays cg_faces_u8_extract_padded reads (catgan.h) for faces with the source sizes `shapes` [(Hs, Ws)], the geometries
+    `geoms` (dict(inv, rect), as face_geometry's) and the pads `pads` -> dict(src_off uint64 [N], geom int32 [N, 8], inv float32
+    [N, 6], taps int32 [ntaps], tap_off uint64 [N, 2], pads int32 [N], rows = sum of Hr + 2 pad).  geom keeps the un-padded rectangle;
+    its two ksizes and the tap tables belong to the padded sides, and faces of one padded side share a table.  Source f is expected at
+    src_off[f] of the concatenated bytes."""
     N = len(shapes)
     src_off, geom = np.zeros(N, np.uint64), np.zeros((N, 8), np.int32)
     inv, tap_off = np.zeros((N, 6), np.float32), np.zeros((N, 2), np.uint64)
+    pads = np.asarray(pads, np.int32).reshape(N)
     tables, where, ntaps, off = [], {}, 0, 0
     for f, ((Hs, Ws), g) in enumerate(zip(shapes, geoms)):
         y0, x0, Hr, Wr = g["rect"]
+        Hp, Wp = Hr + 2 * int(pads[f]), Wr + 2 * int(pads[f])
         src_off[f] = off
         off += Hs * Ws * 3
-        geom[f] = (Hs, Ws, y0, x0, Hr, Wr, resample_ksize(Wr, out), resample_ksize(Hr, out))
+        geom[f] = (Hs, Ws, y0, x0, Hr, Wr, resample_ksize(Wp, out), resample_ksize(Hp, out))
         inv[f] = g["inv"]
-        for a, side in enumerate((Wr, Hr)):
+        for a, side in enumerate((Wp, Hp)):
             if side not in where:
                 b, k = _cached_taps(side, out)
                 where[side] = ntaps
                 tables += [b.reshape(-1), k.reshape(-1)]
                 ntaps += b.size + k.size
             tap_off[f, a] = where[side]
-    return dict(src_off=src_off, geom=geom, inv=inv, taps=np.concatenate(tables).astype(np.int32), tap_off=tap_off,
-                rows=int(geom[:, 4].astype(np.int64).sum()))
+    return dict(src_off=src_off, geom=geom, inv=inv, taps=np.concatenate(tables).astype(np.int32), tap_off=tap_off, pads=pads,
+                rows=int((geom[:, 4].astype(np.int64) + 2 * pads.astype(np.int64)).sum()))
+
+
+def pack_descriptors(shapes, geoms, out):
+    """The arrays cg_faces_u8_extract reads (catgan.h) for faces with the source sizes `shapes` [(Hs, Ws)] and the geometries `geoms`
+    (dict(inv, rect), as face_geometry's) -> dict(src_off uint64 [N], geom int32 [N, 8], inv float32 [N, 6], taps int32 [ntaps],
+    tap_off uint64 [N, 2], rows = sum of Hr).  Faces of one side share a tap table; source f is expected at src_off[f] of the
+    concatenated bytes.  It is pack_padded_descriptors without a pad."""
+    d = pack_padded_descriptors(shapes, geoms, np.zeros(len(shapes), np.int32), out)
+    del d["pads"]
+    return d
 
 
 def workspace_bytes(N, out, rows):
@@ -471,6 +487,60 @@ def extract_variants_device(images, geoms, pad, desc, bases, scale, seed, out=64
                                   dst.data_ptr(), N, out, ws.data_ptr(), wsb)
     v = dst.cpu().numpy()
     return (faces, v) if with_faces else v
+
+
+# ---------------------------------------------------------------- the padded faces on the device
+PADDED_SIDE_MAX = 8192   # cg_faces_u8_extract_padded's largest padded side, Hr + 2 pad: one row of it still fits a band of the horizontal pass
+PADDED_PAD_MAX = 2048    # and its largest pad
+
+
+def padded_fits_device(rect, pad):
+    """Whether cg_faces_u8_extract_padded takes a face with this rectangle and pad; padded_face_np takes every one."""
+    return 0 <= pad <= PADDED_PAD_MAX and max(rect[2], rect[3]) + 2 * pad <= PADDED_SIDE_MAX
+
+
+def padded_bytes(rect, pad, out):
+    """Device bytes that one padded face takes beside its source: the padded crop, the horizontal pass' result and the out x out face."""
+    _, _, Hr, Wr = rect
+    return -(-(3 * (Hr + 2 * pad) * (Wr + 2 * pad)) // 16) * 16 + 3 * out * (Hr + 2 * pad + out)
+
+
+def padded_workspace_bytes(rects, pads, out):
+    """cg_faces_u8_extract_padded's workspace for faces with the rectangles `rects` and the pads `pads` (catgan.h)."""
+    return 80 * len(rects) + 256 + sum(padded_bytes(r, int(p), out) - 3 * out * out for r, p in zip(rects, pads))
+
+
+def extract_padded_device(images, geoms, margin, out=64, with_faces=False):
+    """cg_faces_u8_extract_padded over one batch: the padded faces of generate_dataset.py --margin, uint8
+    [N, out + 2 margin, out + 2 margin, 3] on the host - padded_face_np's bytes, face f's pad being margin_pad(Hr, margin, out).  One
+    upload of the concatenated sources and of the descriptors.  with_faces also runs cg_faces_u8_extract over the same upload (its
+    own geometry and tap tables beside the padded ones) and returns (faces [N, out, out, 3], padded)."""
+    import torch
+    from . import tensor
+    shapes, rects, N, side = [im.shape[:2] for im in images], [g["rect"] for g in geoms], len(images), out + 2 * margin
+    pads = [margin_pad(r[2], margin, out) for r in rects]
+    d = pack_padded_descriptors(shapes, geoms, pads, side)
+    dev, lib, s = tensor.device(), tensor.lib(), tensor.stream()
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+    src = up(np.concatenate([np.ascontiguousarray(im, dtype=np.uint8).reshape(-1) for im in images]))
+    src_off, geom, inv, taps, tap_off, dpads = (up(d[k]) for k in ("src_off", "geom", "inv", "taps", "tap_off", "pads"))
+    wsb = padded_workspace_bytes(rects, pads, side)
+    fd = pack_descriptors(shapes, geoms, out) if with_faces else None
+    if with_faces:
+        wsb = max(wsb, workspace_bytes(N, out, fd["rows"]))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    faces = None
+    if with_faces:
+        fgeom, ftaps, ftap_off = (up(fd[k]) for k in ("geom", "taps", "tap_off"))
+        fdst = torch.empty((N, out, out, 3), dtype=torch.uint8, device=dev)
+        lib.faces_u8_extract(s, src.data_ptr(), src.numel(), src_off.data_ptr(), fgeom.data_ptr(), inv.data_ptr(), ftaps.data_ptr(),
+                             fd["taps"].size, ftap_off.data_ptr(), fdst.data_ptr(), N, out, ws.data_ptr(), wsb)
+        faces = fdst.cpu().numpy()
+    dst = torch.empty((N, side, side, 3), dtype=torch.uint8, device=dev)
+    lib.faces_u8_extract_padded(s, src.data_ptr(), src.numel(), src_off.data_ptr(), geom.data_ptr(), inv.data_ptr(), taps.data_ptr(),
+                                d["taps"].size, tap_off.data_ptr(), dpads.data_ptr(), dst.data_ptr(), N, side, ws.data_ptr(), wsb)
+    p = dst.cpu().numpy()
+    return (faces, p) if with_faces else p
 
 
 # ---------------------------------------------------------------- a synthetic raw tree (tests, scripts/faces_bench.py)

@@ -27,10 +27,13 @@ faces.margin_pad(Hr, M, S) full-resolution pixels, median-filled where that leav
 {"margin": M, "side": S}.  The trainers' --augment, pointed at it (--dataDir <out>/out_padded_SxS_mM), warps every epoch pool's fresh
 variants out of the padded faces, so their borders show real image, and everything un-augmented sees the S x S centre window
 (dataset.setDirs reads margin.json).  With the default ranges and S = 64 a margin of 12 is never left.  An M whose padded face does not
-fit the augmentation kernel's LDS is refused.  The padded faces are computed on the decoding threads by the numpy form in the device
-mode too: a device form needs a pad per face, beyond cg_faces_u8_extract_variants' single pad <= 64, and is deliberately not part of
-this tool yet (profiles/augment_margin_bench.txt has what the host form costs).  --augmentations 0 --margin 12 together with --augment
-is the cheapest use that has real borders.
+fit the augmentation kernel's LDS is refused.  The padded faces are pixel work like the faces and run on the device
+(cg_faces_u8_extract_padded, a pad per face; faces.extract_padded_device), in calls bounded by PADDED_BYTES that share the faces'
+upload; with --variantsFrom crop the variants' calls have made the faces already and the padded faces take a second upload of the
+sources.  A face whose padded side or pad exceeds the entry point's limits (faces.padded_fits_device) is computed by
+faces.padded_face_np instead - rare, and the bytes are the same.  With --host the numpy form runs on the decoding threads
+(profiles/augment_margin_bench.txt has what either costs).  --augmentations 0 --margin 12 together with --augment is the cheapest
+use that has real borders.
 
     python generate_dataset.py --path /data/10k_cats --augmentations 0 --margin 12 --pack
 """
@@ -53,6 +56,7 @@ BATCH_BYTES = 256 << 20      # decoded source bytes per device call: batches are
 MAX_THREADS = 16
 LOOKAHEAD = 64               # files being decoded, or decoded and waiting for their batch
 VARIANT_BYTES = 256 << 20    # sources, crops, horizontal passes and variants per device call with --variantsFrom crop: all but the first grow with --augmentations
+PADDED_BYTES = 256 << 20     # sources, padded crops, horizontal passes and padded faces per device call with --margin
 MIN_SIDE = 8                 # cg_faces_u8_extract's smallest rectangle side
 
 
@@ -90,9 +94,9 @@ def list_raw(path):
     return files
 
 
-def _load(fp, margin=0, S=64):
-    """One raw file -> (fp, decoded image, geometry) or (fp, None, why it is skipped); with a margin the geometry also carries the padded
-    face, g["padded"].  Runs on the decoding threads."""
+def _load(fp, margin=0, S=64, host=False):
+    """One raw file -> (fp, decoded image, geometry) or (fp, None, why it is skipped); with a margin and --host the geometry also carries
+    the padded face, g["padded"] (without --host the flush makes it on the device).  Runs on the decoding threads."""
     F = importlib.import_module("cat-generator_amd.faces")
     ds = importlib.import_module("cat-generator_amd.dataset")
     if not os.path.isfile(fp + ".cat"):
@@ -107,17 +111,17 @@ def _load(fp, margin=0, S=64):
         g = "its face rectangle is degenerate"
     if isinstance(g, str):
         return fp, None, g
-    if margin:
+    if margin and host:
         g["padded"] = F.padded_face_np(img, g["inv"], g["rect"], margin, S)
     return fp, img, g
 
 
-def _loaded(ex, files, margin=0, S=64):
+def _loaded(ex, files, margin=0, S=64, host=False):
     """_load over the files, in their order whatever the threads do, with a bounded look-ahead: decoded sources wait here, never the
     whole set."""
     ahead = deque()
     for fp in files:
-        ahead.append(ex.submit(_load, fp, margin, S))
+        ahead.append(ex.submit(_load, fp, margin, S, host))
         if len(ahead) >= LOOKAHEAD:
             yield ahead.popleft().result()
     while ahead:
@@ -178,6 +182,41 @@ def _crop_variants(batch, index0, A, pad, S, noise_seed, host):
     return np.concatenate(faces), np.concatenate(variants)
 
 
+def _padded_faces(batch, margin, S, with_faces):
+    """--margin on the device for the faces of one flush, (fp, image, geometry) each: (faces [n, S, S, 3] or None, the padded faces
+    [n, S + 2 margin, S + 2 margin, 3]).  The device calls are bounded by PADDED_BYTES; with_faces makes them return the S x S faces
+    over the same upload.  A face that cg_faces_u8_extract_padded would refuse for its size goes through faces.padded_face_np (and,
+    with_faces, a call of cg_faces_u8_extract of its own), which writes the same bytes."""
+    F = importlib.import_module("cat-generator_amd.faces")
+    n, side = len(batch), S + 2 * margin
+    padded = np.empty((n, side, side, 3), np.uint8)
+    faces = np.empty((n, S, S, 3), np.uint8) if with_faces else None
+    dev, cost = [], []
+    for i, (_, im, g) in enumerate(batch):
+        pad = F.margin_pad(g["rect"][2], margin, S)
+        if F.padded_fits_device(g["rect"], pad):
+            dev.append(i)
+            cost.append(im.nbytes + F.padded_bytes(g["rect"], pad, side) + (3 * S * (g["rect"][2] + S) if with_faces else 0))
+            continue
+        padded[i] = F.padded_face_np(im, g["inv"], g["rect"], margin, S)
+        if with_faces:
+            faces[i] = F.extract_faces_device([im], [g], S)[0]
+    lo = 0
+    while lo < len(dev):
+        hi, nbytes = lo + 1, cost[lo]
+        while hi < len(dev) and nbytes + cost[hi] <= PADDED_BYTES:
+            nbytes += cost[hi]
+            hi += 1
+        ix = dev[lo:hi]
+        got = F.extract_padded_device([batch[i][1] for i in ix], [batch[i][2] for i in ix], margin, S, with_faces=with_faces)
+        if with_faces:
+            faces[ix], padded[ix] = got
+        else:
+            padded[ix] = got
+        lo = hi
+    return faces, padded
+
+
 def main(argv=None):
     o = parse(argv)
     from PIL import Image
@@ -212,9 +251,14 @@ def main(argv=None):
         if not batch:
             return
         imgs, geoms = [b[1] for b in batch], [b[2] for b in batch]
-        faces = variants = None
+        faces = variants = pfaces = None
         if crop:
             faces, variants = _crop_variants(batch, written, A, o.padding, S, noise_seed, o.host)
+        if padded and o.host:
+            pfaces = [g["padded"] for g in geoms]
+        elif padded:
+            f, pfaces = _padded_faces(batch, o.margin, S, with_faces=faces is None)
+            faces = f if faces is None else faces
         if faces is None and o.host:
             faces = np.stack([F.resize_np(F.warp_rect_np(im, g["inv"], g["rect"]), S) for im, g in zip(imgs, geoms)])
         elif faces is None:
@@ -224,7 +268,7 @@ def main(argv=None):
             Image.fromarray(face).save(os.path.join(unaug, name))
             Image.fromarray(face).save(os.path.join(aug, name))
             if padded:
-                Image.fromarray(geoms[i]["padded"]).save(os.path.join(padded, name))
+                Image.fromarray(pfaces[i]).save(os.path.join(padded, name))
             if A:
                 for a, v in enumerate(variants[i] if crop else _variants(face, written, A, noise_seed, o.host)):
                     Image.fromarray(v).save(os.path.join(aug, "{:0>6}_{:0>3}.jpg".format(written, a + 1)))
@@ -232,7 +276,7 @@ def main(argv=None):
 
     batch, nbytes = [], 0
     with ThreadPoolExecutor(max_workers=min(o.threads, MAX_THREADS)) as ex:
-        for fp, img, g in _loaded(ex, files, o.margin, S):
+        for fp, img, g in _loaded(ex, files, o.margin, S, o.host):
             if img is None:
                 print(f"<dataset> warning: {fp} skipped: {g}")
                 skipped += 1

@@ -227,6 +227,27 @@ int cg_faces_u8_extract_variants(void* stream, const unsigned char* src, size_t 
                                  const float* inv, const int32_t* taps, size_t ntaps, const uint64_t* tap_off, int pad, int A,
                                  const float* desc, const uint64_t* bases, float noise_scale, uint64_t seed, unsigned char* dst, int N, int out,
                                  void* workspace, size_t workspace_bytes);
+/* The PADDED faces of the same batch (generate_dataset.py --margin; faces.padded_face_np is the numpy restatement): face f with pads[f]
+ * full-resolution pixels of real image around its rectangle, resized as a whole.  src .. tap_off, N and out are cg_faces_u8_extract's
+ * with two differences: geom rows are  Hs Ws y0 x0 Hr Wr kx ky  with the rectangle UN-padded, while kx, ky and the two tap tables of
+ * face f belong to the padded sides, Wp = Wr + 2 pads[f] -> out and Hp = Hr + 2 pads[f] -> out; and the caller passes the side of the
+ * padded face as `out` (S + 2 M for S x S faces with a margin of M).  pads [N] int32 in device memory, one pad per face - the caller
+ * is free in it; faces.margin_pad is what the tool uses.  dst [N][out][out][3].  Per face:
+ *   a. the padded crop P [Hp][Wp][3] of cg_faces_u8_extract_variants' stage a with pad = pads[f], its median fill included;
+ *   b. cg_faces_u8_extract's resize of all of P to out x out.  The crop's bytes go into the resampling as they are - no second warp
+ *      and no float: an identity warp would re-quantise through (u8)((v / 255) 255), which is not v for every byte.
+ * With every pad 0 this is cg_faces_u8_extract bit for bit.
+ * workspace: at least 80 N + 256 + sum_f ceil16(3 Hp Wp) + 3 out sum_f Hp bytes, laid out as: band_start [N + 1] int32 | cblk_start
+ * [N + 1] int32 | line_start [2][N + 1] int32 | line_face [2][N] int32 | crop_off [N] uint64 | tmp_off [N] uint64 | the padded
+ * geometry [N][8] int32 (geom with Hp, Wp in place of Hr, Wr), each piece from a multiple of 16 | the padded crops, each from a
+ * multiple of 16 | the horizontal pass' result, [Hp][out][3] per face.  Like its siblings it reads its descriptors back, synchronises
+ * the stream and cannot be captured.  Errors, all before any launch: cg_faces_u8_extract's, with ksize and the tap tables checked
+ * against the padded sides; a null pads; a pad outside 0..2048; a padded side beyond 8192 (the widest row that still fits a band of
+ * the horizontal pass; with the limits on the pad and the rectangle it cannot be exceeded alone); a batch too large for one launch; a
+ * workspace too small.  dst is untouched on error. */
+int cg_faces_u8_extract_padded(void* stream, const unsigned char* src, size_t src_bytes, const uint64_t* src_off, const int32_t* geom,
+                               const float* inv, const int32_t* taps, size_t ntaps, const uint64_t* tap_off, const int32_t* pads,
+                               unsigned char* dst, int N, int out, void* workspace, size_t workspace_bytes);
 /* NN_UTILS.rgbToColorSpace / NN_UTILS.toRgb (utils/nn_utils.lua:188-249) on fp32 NHWC pixels that are already on the device: three
  * floats in per pixel, three out (one for to == 1).  from / to are the colorspace codes above; the pairs are rgb -> y | yuv | hsl and
  * yuv | hsl -> rgb, anything else is an error.  src == dst is allowed when three planes come out.  Per pixel, every operation a single

@@ -8,12 +8,17 @@ No thresholds: every figure is printed with the spread of its blocks or runs.
            process, --blocks alternating blocks of --reps back-to-back launches each between device events; per side the median block
            and the fastest and slowest one.  The first pool of the two forms of this commit is compared with the host restatement.
   tool     generate_dataset.py --augmentations 0 end to end on the device path over faces_bench.py's synthetic tree (--images files of
-           375 x 500), without --margin and with --margin 12, alternating, --repeats times each; padded_face_np alone over the same
-           files on the tool's threads.
+           375 x 500), without --margin and with --margin 12, and - with --parent-tree, a checkout of the parent commit with its
+           library built - the parent's library and front end with --margin 12, whose files are then compared with this commit's;
+           alternating, --repeats times each.  Then padded_face_np alone over the same files on the tool's threads, and one
+           cg_faces_u8_extract_padded call over the front end's first device call, between device events (--reps calls).  Its
+           kernels are not separable with events from outside the call; their durations come from a kernel trace, taken in a run of
+           its own, of    python scripts/augment_margin_bench.py --worker --do call --images 400 --reps 5
 
-The measurements run in ONE child process under a time limit; the parent never touches the GPU.
+The kernel stage runs in ONE child process, the tool stage in one worker process per tree that the parent feeds commands; all under a
+time limit, and the parent never touches the GPU.
 
-    python scripts/augment_margin_bench.py [--stages kernel,tool] [--parent-lib FILE.so] [--out FILE.txt] [--timeout 900]"""
+    python scripts/augment_margin_bench.py [--stages kernel,tool] [--parent-lib FILE.so] [--parent-tree DIR] [--out FILE.txt] [--timeout 900]"""
 import argparse
 import os
 import statistics
@@ -85,46 +90,164 @@ def kernel_stage(o, lines):
         lines.append(f"  {name:72s} median {statistics.median(v):8.2f}  ({min(v):.2f} - {max(v):.2f})")
 
 
-def tool_stage(o, lines):
+def padded_call(o, F, G, files, reply):
+    """cg_faces_u8_extract_padded over the front end's first device call at --margin 12 (what fits PADDED_BYTES of sources, crops and
+    passes): device events around the whole call - the descriptors' round trip, the head's upload and the four or five kernels."""
     import importlib
+    import numpy as np
+    import torch
+    cg = importlib.import_module("cat-generator_amd")
+    M, S, side = 12, 64, 88
+    batch, nb = [], 0
+    for fp in files:
+        _, img, g = G._load(fp)
+        pad = F.margin_pad(g["rect"][2], M, S)
+        cost = img.nbytes + F.padded_bytes(g["rect"], pad, side)
+        if batch and nb + cost > G.PADDED_BYTES:
+            break
+        batch.append((img, g, pad))
+        nb += cost
+    imgs, geoms, pads = [b[0] for b in batch], [b[1] for b in batch], [b[2] for b in batch]
+    d = F.pack_padded_descriptors([im.shape[:2] for im in imgs], geoms, pads, side)
+    N, dev = len(imgs), cg.tensor.device()
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
+    src = up(np.concatenate([im.reshape(-1) for im in imgs]))
+    arrs = [up(d[k]) for k in ("src_off", "geom", "inv", "taps", "tap_off", "pads")]
+    wsb = F.padded_workspace_bytes([g["rect"] for g in geoms], pads, side)
+    ws, dst = torch.empty(wsb, dtype=torch.uint8, device=dev), torch.empty((N, side, side, 3), dtype=torch.uint8, device=dev)
+    call = lambda: cg.lib().faces_u8_extract_padded(cg.tensor.stream(), src.data_ptr(), src.numel(), arrs[0].data_ptr(), arrs[1].data_ptr(),
+                                                    arrs[2].data_ptr(), arrs[3].data_ptr(), d["taps"].size, arrs[4].data_ptr(), arrs[5].data_ptr(),
+                                                    dst.data_ptr(), N, side, ws.data_ptr(), wsb)
+    ms = []
+    for k in range(3 + o.reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        call()
+        b.record()
+        torch.cuda.synchronize()
+        if k >= 3:
+            ms.append(a.elapsed_time(b))
+    want = np.stack([F.padded_face_np(im, g["inv"], g["rect"], M, S) for im, g in zip(imgs[:8], geoms[:8])])
+    assert np.array_equal(dst[:8].cpu().numpy(), want), "the timed call's padded faces differ from the host restatement's"
+    filled = sum(max(F.crop_pads(im.shape[0], im.shape[1], g["rect"], p)) > 0 for im, g, p in zip(imgs, geoms, pads))
+    reply.update(N=N, src_mb=src.numel() / 1e6, ws_mb=wsb / 1e6, pads=[min(pads), max(pads)], filled=int(filled), med=statistics.median(ms),
+                 lo=min(ms), hi=max(ms), reps=o.reps)
+
+
+def worker(o):
+    """One process that serves one tree (this one, or --tree: a checkout of another commit with its library built): a JSON command per
+    line of stdin - or the one command of --do - answered by a line `@ {...}`."""
+    import importlib
+    import json
     from concurrent.futures import ThreadPoolExecutor
     import torch
-    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.abspath(o.tree or ROOT))
     F = importlib.import_module("cat-generator_amd.faces")
     G = importlib.import_module("generate_dataset")
-    with tempfile.TemporaryDirectory() as tmp:
-        files = F.write_raw_tree(os.path.join(tmp, "raw"), [(375, 500)] * o.images, folders=tuple(f"CAT_{k:02d}" for k in range(7)))
-        F.write_raw_tree(os.path.join(tmp, "small"), [(375, 500)] * 12)
-        lines.append(f"generate_dataset.py --augmentations 0 on the device path; {o.images} images of 375 x 500; {o.threads} threads; faces of 64 x 64")
-        G.main(["--path", os.path.join(tmp, "small"), "--out", os.path.join(tmp, "warm"), "--augmentations", "0"])      # code objects, allocator
-        for r in range(o.repeats):
-            for name, extra in (("without --margin", []), ("--margin 12", ["--margin", "12"])):
+    files = []
+    for line in ([json.dumps(dict(cmd=o.do, path=None))] if o.do else sys.stdin):
+        c = json.loads(line)
+        reply = {}
+        with tempfile.TemporaryDirectory() as own:
+            if c["cmd"] == "tree":                                 # the synthetic raw trees; no GPU work
+                F.write_raw_tree(os.path.join(c["path"], "raw"), [(375, 500)] * o.images, folders=tuple(f"CAT_{k:02d}" for k in range(7)))
+                F.write_raw_tree(os.path.join(c["path"], "small"), [(375, 500)] * 12)
+            elif c["cmd"] == "run":                                # generate_dataset.py end to end
                 t0 = time.time()
-                n, _ = G.main(["--path", os.path.join(tmp, "raw"), "--out", os.path.join(tmp, f"o{r}{len(extra)}"), "--augmentations", "0",
-                               "--threads", str(o.threads)] + extra)
+                n, _ = G.main(c["argv"])
                 torch.cuda.synchronize()
-                dt = time.time() - t0
-                lines.append(f"  {name:17s} end to end {dt:8.2f} s   {n / dt:8.0f} faces/s   (run {r})")
-        loaded = [G._load(fp) for fp in files[:200]]
-        t0 = time.time()
-        with ThreadPoolExecutor(max_workers=o.threads) as ex:
-            list(ex.map(lambda x: F.padded_face_np(x[1], x[2]["inv"], x[2]["rect"], 12, 64), loaded))
-        dt = time.time() - t0
-        lines.append(f"  padded_face_np alone, 200 decoded images on {o.threads} threads: {dt:.2f} s   {200 / dt:.0f} faces/s")
+                reply.update(dt=time.time() - t0, n=n, device=torch.cuda.get_device_name(0))
+            else:
+                raw = os.path.join(c["path"] or own, "raw")
+                files = G.list_raw(raw) if c["path"] else F.write_raw_tree(raw, [(375, 500)] * o.images)
+                if c["cmd"] == "padded_np":                        # the host form alone, on the tool's threads
+                    loaded = [G._load(fp) for fp in files[:200]]
+                    t0 = time.time()
+                    with ThreadPoolExecutor(max_workers=o.threads) as ex:
+                        list(ex.map(lambda x: F.padded_face_np(x[1], x[2]["inv"], x[2]["rect"], 12, 64), loaded))
+                    reply.update(dt=time.time() - t0)
+                elif c["cmd"] == "call":
+                    padded_call(o, F, G, files, reply)
+        print("@ " + json.dumps(reply), flush=True)
+
+
+class Worker:
+    def __init__(self, o, tree):
+        cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--images", str(o.images), "--threads", str(o.threads), "--reps", str(o.reps)]
+        self.p = subprocess.Popen(cmd + (["--tree", tree] if tree else []), stdin=subprocess.PIPE, stdout=subprocess.PIPE, text=True)
+
+    def ask(self, **c):
+        import json
+        self.p.stdin.write(json.dumps(c) + "\n")
+        self.p.stdin.flush()
+        for line in self.p.stdout:
+            if line.startswith("@ "):
+                return json.loads(line[2:])
+        sys.exit(f"augment_margin_bench: a worker ended (or ran into the time limit) during {c}")
+
+    def close(self):
+        self.p.stdin.close()
+        self.p.wait()
+
+
+def tool_stage(o, lines):
+    """Runs in the parent process, which never touches the GPU: every measurement is made by a worker process, one per tree, and the
+    configurations alternate between them within one run."""
+    import filecmp
+    import threading
+    here, old = Worker(o, None), (Worker(o, os.path.abspath(o.parent_tree)) if o.parent_tree else None)
+    workers = [w for w in (here, old) if w]
+    limit = threading.Timer(o.timeout, lambda: [w.p.kill() for w in workers])
+    limit.start()
+    try:
+        with tempfile.TemporaryDirectory() as tmp:
+            here.ask(cmd="tree", path=tmp)
+            argv = lambda tree, out, extra: ["--path", os.path.join(tmp, tree), "--out", os.path.join(tmp, out), "--augmentations", "0",
+                                             "--threads", str(o.threads)] + extra
+            configs = [("without --margin", here, []), ("--margin 12", here, ["--margin", "12"])]
+            if old:
+                configs.append(("--margin 12, parent", old, ["--margin", "12"]))
+            for k, w in enumerate(workers):                        # code objects, allocator
+                dev = w.ask(cmd="run", argv=argv("small", f"warm{k}", ["--margin", "12"]))["device"]
+            lines.append(f"device {dev}")
+            lines.append(f"generate_dataset.py --augmentations 0 on the device path; {o.images} images of 375 x 500; {o.threads} threads; faces of 64 x 64"
+                         + ("; `parent`: the parent commit's library and front end, alternating with this commit's in the same run" if old else ""))
+            for r in range(o.repeats):
+                for k, (name, w, extra) in enumerate(configs):
+                    a = w.ask(cmd="run", argv=argv("raw", f"o{r}_{k}", extra))
+                    lines.append(f"  {name:20s} end to end {a['dt']:8.2f} s   {a['n'] / a['dt']:8.0f} faces/s   (run {r})")
+            if old:
+                for d in ("out_padded_64x64_m12", "out_unaug_64x64"):
+                    a, b = os.path.join(tmp, "o0_1", d), os.path.join(tmp, "o0_2", d)
+                    names = sorted(os.listdir(a))
+                    _, mismatch, errors = filecmp.cmpfiles(a, b, names, shallow=False)
+                    assert names == sorted(os.listdir(b)) and not mismatch and not errors, f"{d}: this commit's files differ from the parent's"
+                lines.append(f"  this commit's out_padded_64x64_m12 and out_unaug_64x64 ({len(names)} faces each) are the parent's byte for byte")
+            dt = here.ask(cmd="padded_np", path=tmp)["dt"]
+            lines.append(f"  padded_face_np alone, 200 decoded images on {o.threads} threads: {dt:.2f} s   {200 / dt:.0f} faces/s")
+            c = here.ask(cmd="call", path=tmp)
+            lines.append(f"  cg_faces_u8_extract_padded over the first device call at --margin 12: {c['N']} faces, {c['src_mb']:.0f} MB of sources, pads "
+                         f"{c['pads'][0]}..{c['pads'][1]}, {c['filled']} of them median-filled, {c['ws_mb']:.1f} MB workspace")
+            lines.append(f"    call (read-back + its kernels)  median {c['med']:8.3f} ms of {c['reps']}  ({c['lo']:.3f} - {c['hi']:.3f})   "
+                         f"{c['N'] / c['med'] * 1e3:10.0f} faces/s; its first 8 padded faces equal the host restatement's")
+    finally:
+        limit.cancel()
+        for w in workers:
+            w.close()
 
 
 def child(o):
     import torch
     lines = [f"device {torch.cuda.get_device_name(0)}"]
-    for stage in o.stages.split(","):
-        {"kernel": kernel_stage, "tool": tool_stage}[stage](o, lines)
+    kernel_stage(o, lines)
     print("\n".join(lines))
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stages", default="kernel,tool")
-    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--parent-lib", default=None, help="kernel stage: the parent commit's libcatgan_hip.so")
+    ap.add_argument("--parent-tree", default=None, help="tool stage: a checkout of the parent commit with its library built")
     ap.add_argument("--set", type=int, default=8000)
     ap.add_argument("--blocks", type=int, default=7)
     ap.add_argument("--reps", type=int, default=50)
@@ -134,14 +257,24 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--timeout", type=int, default=900)
     ap.add_argument("--child", action="store_true")
+    ap.add_argument("--worker", action="store_true")
+    ap.add_argument("--tree", default=None)
+    ap.add_argument("--do", default=None, help="with --worker: one command (call, padded_np) over a tree of its own, e.g. under a kernel trace")
     o = ap.parse_args()
     if o.child:
         return child(o)
-    cmd = [sys.executable, os.path.abspath(__file__), "--child"] + [a for a in sys.argv[1:] if a != "--child"]
-    out = subprocess.run(cmd, capture_output=True, text=True, timeout=o.timeout)
-    if out.returncode != 0:
-        sys.exit(out.stdout[-4000:] + out.stderr[-4000:])
-    report = "\n".join(ln for ln in out.stdout.splitlines() if not ln.startswith("<dataset>"))
+    if o.worker:
+        return worker(o)
+    stages, lines = o.stages.split(","), []
+    if "kernel" in stages:
+        cmd = [sys.executable, os.path.abspath(__file__), "--child"] + [a for a in sys.argv[1:] if a != "--child"]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=o.timeout)
+        if out.returncode != 0:
+            sys.exit(out.stdout[-4000:] + out.stderr[-4000:])
+        lines += [ln for ln in out.stdout.splitlines() if not ln.startswith("<dataset>")]
+    if "tool" in stages:
+        tool_stage(o, lines)
+    report = "\n".join(lines)
     print(report)
     if o.out:
         with open(o.out, "w") as f:
