@@ -75,6 +75,52 @@ class State:
         self.keep_outputs = False  # tests: snapshot D's output before the G-step reuses the buffer
         self.device_rng = False    # draw the real-batch indices on the device (required under hipGraph replay)
         self._d_draws = {}         # batch -> counter-stream draws of MODEL_D:forward (learned in the first iteration)
+        self.EMA = None            # --G_ema D (not in the reference): the running average of PARAMETERS_G, kept inside G's update
+        D = float(self.OPT.get("G_ema", 0) or 0)      # read, never defaulted into OPT: a checkpoint of a run without it stores the same OPT
+        if D != 0:
+            if not 0 < D < 1:
+                raise ValueError(f"G_ema = {D}: the decay of the generator's running average must lie in (0, 1)")
+            self._build_ema(D)
+
+    def _build_ema(self, D):
+        """MODEL_G_EMA: a second tree shaped like MODEL_G whose getParameters() vector IS e - the update kernel writes straight into a net
+        that can run.  Always in evaluate mode; its batch-norm running statistics are not averaged (six more small launches per
+        iteration) but copied from the live G whenever the net is about to be used (sync_ema_stats)."""
+        import io
+        from . import t7, t7_nn
+        r, off = rng(), rng().offset
+        buf = io.BytesIO()                          # the tree MODEL_G has (create_G's, or a pre-trained decoder's), through torch.save's format
+        t7.Writer(buf).write(t7_nn.to_t7(self.MODEL_G))
+        buf.seek(0)
+        self.MODEL_G_EMA = t7_nn.from_t7(t7.Reader(buf).read())
+        r.offset = off                              # rebuilding modules draws initial weights; the training streams stay where they were
+        self.MODEL_G_EMA.evaluate()
+        e, _ = self.MODEL_G_EMA.getParameters()
+        assert e.nElement() == self.PARAMETERS_G.nElement()
+        self.PARAMETERS_G_EMA = e
+        self.EMA = {"e": e, "decay": D, "n": 0}
+        self.reset_ema()
+
+    def reset_ema(self, n=0):
+        """e <- PARAMETERS_G, n applied updates behind it: when the state is built, and after a load that brings no average."""
+        self.PARAMETERS_G_EMA.copy(self.PARAMETERS_G)
+        self.set_ema_n(n)
+
+    def set_ema_n(self, n):
+        self.EMA["n"] = int(n)
+        if "n_dev" in self.EMA:
+            self.EMA["n_dev"].fill_(int(n))
+
+    def ema_n(self):
+        """Applied updates the average has seen; in replay mode the device counter is the truth, as for Adam's t."""
+        return int(self.EMA["n_dev"].item()) if "n_dev" in self.EMA else int(self.EMA["n"])
+
+    def sync_ema_stats(self):
+        """The live G's batch-norm running statistics into MODEL_G_EMA, which is then ready to run."""
+        bn = lambda net: [m for m in net.listModules() if isinstance(m, nn.SpatialBatchNormalization)]
+        for a, b in zip(bn(self.MODEL_G_EMA), bn(self.MODEL_G)):
+            a.running_mean.copy(b.running_mean); a.running_var.copy(b.running_var)
+        return self.MODEL_G_EMA
 
 
 def mean(t):
@@ -264,7 +310,8 @@ def iteration(S, trainData, thisBatchSize=None, maxAccuracyD=1.01, accsInterval=
                      clamp=OPT["G_clamp"]) if OPT["fused_update"] else None
         m = OPT["G_optmethod"]  # adversarial.lua:257-265
         assert m in ("sgd", "adagrad", "adam"), "[Warning] Unknown optimizer method chosen for G."
-        getattr(optim, m)(fevalG_on_D, S.PARAMETERS_G, S.OPTSTATE[m]["G"], fused=fused)
+        # S.EMA (--G_ema, else None): the average moves inside Adam's pass, or right behind the step of sgd / adagrad
+        getattr(optim, m)(fevalG_on_D, S.PARAMETERS_G, S.OPTSTATE[m]["G"], fused=fused, ema=S.EMA)
         if S.keep_outputs:
             S._last["gG"] = S.GRAD_PARAMETERS_G.clone()
     return st["doTrainD"]
@@ -313,6 +360,8 @@ class GraphedIteration:
         S.device_rng = True
         for k in ("D", "G"):
             S.OPTSTATE["adam"][k]["device_step"] = True
+        if S.EMA is not None:                 # the average's update count beside Adam's: in device memory under replay
+            S.EMA["device_step"] = True
         r = rng()
         self.base = r.enable_device_base()
         self.off0 = r.offset
@@ -324,6 +373,7 @@ class GraphedIteration:
                 self._eager()
         torch.cuda.synchronize()
         ts = {k: S.OPTSTATE["adam"][k]["t"] for k in ("D", "G")}
+        n_ema = S.EMA["n"] if S.EMA is not None else None
         self.exec = ctypes.c_void_p()
         # The capture goes through hipStreamBeginCapture directly (not torch.cuda.graph, which would give it a private memory pool):
         # an allocation made while capturing would have its address baked into the graph while torch's caching allocator stays free
@@ -346,6 +396,8 @@ class GraphedIteration:
                                f"may reuse.  Run more warm-up iterations or find the late allocation.")
         for k in ("D", "G"):   # capture launched nothing: the host step count must not move (it is what a checkpoint stores)
             S.OPTSTATE["adam"][k]["t"] = ts[k]
+        if S.EMA is not None:
+            S.EMA["n"] = n_ema
         self.replays = 0
 
     @staticmethod
@@ -373,6 +425,8 @@ class GraphedIteration:
         self.replays += 1
         for k in ("D", "G"):
             self.S.OPTSTATE["adam"][k]["t"] += 1
+        if self.S.EMA is not None:
+            self.S.EMA["n"] += 1
 
     def __del__(self):
         try:

@@ -56,6 +56,9 @@ def save(path, S):
                     if k == "t" and "t_dev" in st:   # replay mode: the device counter is the step count that was applied
                         v = int(st["t_dev"].item())
                     out[key] = np.array(v)
+    if getattr(S, "EMA", None) is not None:   # --G_ema: the averaged vector and the updates it has seen (replay mode: the device count)
+        out["PARAMETERS_G_ema"] = S.PARAMETERS_G_EMA.numpy()
+        out["G_ema_n"] = np.int64(S.ema_n())
     np.savez(path, **out)
     return path
 
@@ -87,6 +90,13 @@ def load(path, S):
             st[k] = v.item()
         else:
             st[k] = Tensor.from_numpy(v, fmt="plain")
+    if getattr(S, "EMA", None) is not None:   # with the flag off a stored average is ignored
+        if "PARAMETERS_G_ema" in z.files:
+            S.PARAMETERS_G_EMA.copy(z["PARAMETERS_G_ema"])
+            S.set_ema_n(int(z["G_ema_n"]))
+        else:
+            print(f"<checkpoint> {path} holds no averaged generator: --G_ema starts its average from the loaded G, n = 0")
+            S.reset_ema()
     return S
 
 
@@ -110,6 +120,9 @@ def export_t7(path, S, plot_data=None, cuda=False, normalize_mean=None, normaliz
             optstate[method][net] = d
     obj = {"D": t7_nn.to_t7(S.MODEL_D, cuda), "G": t7_nn.to_t7(S.MODEL_G, cuda), "opt": opt,
            "plot_data": [list(r) for r in (plot_data or [])], "epoch": int(S.EPOCH), "optstate": optstate}
+    if getattr(S, "EMA", None) is not None:   # --G_ema: the averaged generator as a net of its own, with the live G's BN statistics
+        obj["G_ema"] = t7_nn.to_t7(S.sync_ema_stats(), cuda)
+        obj["G_ema_n"] = S.ema_n()
     if normalize_mean is not None:
         obj["normalize_mean"], obj["normalize_std"] = normalize_mean, normalize_std
     return t7.save(path, obj)
@@ -120,8 +133,8 @@ def import_t7(path):
     rebuilt as engine modules (G, D), and opt / epoch / plot_data / optstate as plain Python values."""
     from . import t7, t7_nn
     z = t7.load(path)
-    out = {k: v for k, v in z.items() if k not in ("D", "G")}
-    for k in ("D", "G"):
+    out = {k: v for k, v in z.items() if k not in ("D", "G", "G_ema")}
+    for k in ("D", "G", "G_ema"):
         if z.get(k) is not None:
             out[k] = t7_nn.from_t7(z[k])
     if isinstance(out.get("plot_data"), dict):
@@ -146,4 +159,11 @@ def load_t7(path, S):
             dst = S.OPTSTATE.setdefault(method, {}).setdefault(net, {})
             for k, v in st.items():
                 dst[k] = Tensor.from_numpy(v, fmt="plain") if isinstance(v, np.ndarray) else v
+    if getattr(S, "EMA", None) is not None:
+        if z.get("G_ema") is not None:
+            S.PARAMETERS_G_EMA.copy(z["G_ema"].getParameters()[0].numpy())
+            S.set_ema_n(int(z.get("G_ema_n", 0)))
+        else:
+            print(f"<checkpoint> {path} holds no averaged generator: --G_ema starts its average from the loaded G, n = 0")
+            S.reset_ema()
     return S

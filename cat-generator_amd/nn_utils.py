@@ -50,21 +50,23 @@ def stepNoiseInputsAt(S, N, offset):
     return _fill_noise(t, offset)
 
 
-def createImagesFromNoise(S, noiseInputs, outputAsList=False, *_):
+def createImagesFromNoise(S, noiseInputs, outputAsList=False, *_, model=None):
     """G forward in chunks of OPT.batchSize (nn_utils.lua:48-58).  Note MODEL_G stays in training mode
     (train-mode BN on the chunk), exactly as upstream.  The reference's :clone() of each chunk is kept only when
-    there is more than one chunk (the G output buffer is reused by the next forward)."""
+    there is more than one chunk (the G output buffer is reused by the next forward).  `model`: another generator than
+    S.MODEL_G (the averaged one of --G_ema)."""
+    G = model if model is not None else S.MODEL_G
     noiseInputs = nn.to_device(noiseInputs)
     N = noiseInputs.size(1)
     bs = S.OPT["batchSize"]
     nBatches = -(-N // bs)
     if nBatches == 1:
-        images = S.MODEL_G.forward(noiseInputs)
+        images = G.forward(noiseInputs)
     else:
         images = None
         for i in range(1, nBatches + 1):
             a, b = 1 + (i - 1) * bs, min(i * bs, N)
-            generated = nn.as_nhwc(S.MODEL_G.forward(noiseInputs.rows(a, b)))
+            generated = nn.as_nhwc(G.forward(noiseInputs.rows(a, b)))
             if images is None:
                 images = Tensor.empty((N,) + generated.shape[1:], "nhwc")
             images.rows(a, b).copy(generated)
@@ -312,6 +314,16 @@ def visualizeProgress(S, noiseInputs, trainImages, save_dir, start_time=0, plot_
             if verbose:
                 print("<nnutils viz> [V] semiRandom: %.4f, goodImages: %.4f, badImages: %.4f" % tuple(ratings))
         out["ratings"] = ratings
+        if getattr(S, "EMA", None) is not None:
+            # --G_ema: the same fixed noise through the averaged generator (evaluate mode, the live G's running statistics), after
+            # everything above so that the three grids and every draw are what they are without the flag
+            ema = nn.as_nhwc(createImagesFromNoise(S, noiseInputs, model=S.sync_ema_stats())).numpy()
+            path = os.path.join(save_dir, "images_ema", "%d_%05d.png" % (start_time, ep))
+            saveImagesAsGrid(path, toRgb(ema, cs), 10, 10, ep)
+            out["images_ema"] = path
+            out["rating_ema"] = rateWithV(S, ema)
+            if out["rating_ema"] is not None and verbose:
+                print("<nnutils viz> [V] averaged G (--G_ema): %.4f" % out["rating_ema"])
         return out
     finally:
         switchToTrainingMode(S)

@@ -4,13 +4,52 @@ adam follows torch/optim's form [upstream]: m = b1 m + (1-b1) g; v = b2 v + (1-b
 x -= lr sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps)  — eps is added to sqrt(v) without bias-correcting v.
 One fused kernel (cg_adam_step) instead of ~8 elementwise passes; optionally it also applies the L1/L2
 penalty and the clamp of adversarial.lua:92-98,110-112 in its prologue (`fused=`).
+
+`ema=` (not in the reference; train.py --G_ema) keeps a running average of x beside the update: a dict {"e": flat Tensor shaped like
+x, "decay": D, "n": applied updates so far}.  adam folds it into its own pass (cg_adam_step_ema), sgd and adagrad run cg_ema_update
+right behind their step.  The decay of the n-th update is ema_decay(D, n).
 """
+import numpy as np
 import torch
 
 from .tensor import Tensor, lib, stream
 
 
-def adam(opfunc, x, config=None, state=None, fused=None):
+def ema_decay(D, n):
+    """d_n = (float) min((double)(float)D, (1 + n) / (10 + n)) of the n-th applied update (n from 1), as a Python float holding the fp32
+    value: the average's window grows with the run until D caps it (at D = 0.999 from n = 8991 on)."""
+    return float(np.float32(min(float(np.float32(D)), (1.0 + n) / (10.0 + n))))
+
+
+def ema_np(e, p, d):
+    """The element update of cg_ema_update restated in fp64: d e + (1 - d) p for the fp32 decay d."""
+    d = float(np.float32(d))
+    return d * np.asarray(e, np.float64) + (1.0 - d) * np.asarray(p, np.float64)
+
+
+def _ema_advance(ema, device):
+    """Count one more applied update; under device_step the count the kernel reads lives in device memory (hipGraph replay)."""
+    ema["n"] = ema.get("n", 0) + 1
+    if ema.get("device_step"):
+        if "n_dev" not in ema:
+            ema["n_dev"] = torch.full((1,), ema["n"] - 1, dtype=torch.int64, device=device)
+        lib().counter_add(stream(), ema["n_dev"].data_ptr(), 1)
+        return True
+    return False
+
+
+def _ema_after_step(ema, x):
+    """sgd / adagrad: the stand-alone kernel right behind their step."""
+    if ema is None:
+        return
+    if _ema_advance(ema, x.t.device):
+        lib().ema_update_dev(stream(), ema["e"].ptr, x.ptr, x.nElement(), float(np.float32(ema["decay"])), ema["n_dev"].data_ptr())
+    else:
+        lib().ema_update(stream(), ema["e"].ptr, x.ptr, x.nElement(), ema_decay(ema["decay"], ema["n"]))
+    ema["e"].epoch.bump()
+
+
+def adam(opfunc, x, config=None, state=None, fused=None, ema=None):
     config = config if config is not None else {}
     state = state if state is not None else config
     lr = config.get("learningRate", 0.001)
@@ -29,17 +68,33 @@ def adam(opfunc, x, config=None, state=None, fused=None):
     state["t"] += 1
     l1, l2, clamp = (fused.get("l1", 0.0), fused.get("l2", 0.0), fused.get("clamp", 0.0)) if fused else (0.0, 0.0, 0.0)
     wb = 1 if fused and fused.get("write_back", True) else 0
-    if config.get("device_step"):
+    dev = bool(config.get("device_step"))
+    if dev:
         # hipGraph replay mode: the step count lives in device memory (kernel arguments are frozen under replay)
         if "t_dev" not in state:
             state["t_dev"] = torch.full((1,), state["t"] - 1, dtype=torch.int64, device=x.t.device)
         lib().counter_add(stream(), state["t_dev"].data_ptr(), 1)
+    if ema is not None:
+        ema["device_step"] = dev          # both counters on the device or neither
+    if ema is not None and fused:         # the average inside Adam's own pass; without `fused` (the separate passes) it follows the step
+        _ema_advance(ema, x.t.device)
+        if dev:
+            lib().adam_step_ema_dev(stream(), x.ptr, dfdx.ptr, state["m"].ptr, state["v"].ptr, ema["e"].ptr, x.nElement(), lr, beta1,
+                                    beta2, epsilon, state["t_dev"].data_ptr(), l1, l2, clamp, wb, float(np.float32(ema["decay"])),
+                                    ema["n_dev"].data_ptr())
+        else:
+            lib().adam_step_ema(stream(), x.ptr, dfdx.ptr, state["m"].ptr, state["v"].ptr, ema["e"].ptr, x.nElement(), lr, beta1,
+                                beta2, epsilon, state["t"], l1, l2, clamp, wb, ema_decay(ema["decay"], ema["n"]))
+        ema["e"].epoch.bump()
+    elif dev:
         lib().adam_step_dev(stream(), x.ptr, dfdx.ptr, state["m"].ptr, state["v"].ptr, x.nElement(), lr, beta1, beta2,
                             epsilon, state["t_dev"].data_ptr(), l1, l2, clamp, wb)
     else:
         lib().adam_step(stream(), x.ptr, dfdx.ptr, state["m"].ptr, state["v"].ptr, x.nElement(), lr, beta1, beta2,
                         epsilon, state["t"], l1, l2, clamp, wb)
     x.epoch.bump()
+    if not fused:
+        _ema_after_step(ema, x)
     return x, [fx]
 
 
@@ -48,7 +103,7 @@ def _fused(fused):
             if fused else (0.0, 0.0, 0.0, 0))
 
 
-def sgd(opfunc, x, config=None, state=None, fused=None):
+def sgd(opfunc, x, config=None, state=None, fused=None, ema=None):
     """optim.sgd as train.lua:201-204 configures it (learningRate, momentum; Torch7 defaults: dampening = momentum,
     no Nesterov, no weight decay, no lr decay).  First step with momentum: v = g [upstream: dfdx:clone()]."""
     config = config if config is not None else {}
@@ -67,10 +122,11 @@ def sgd(opfunc, x, config=None, state=None, fused=None):
     lib().sgd_step(stream(), x.ptr, dfdx.ptr, state["dfdx"].ptr if mom != 0 else None, x.nElement(), lr, mom,
                    0.0 if (mom != 0 and first) else damp, l1, l2, clamp, wb)
     x.epoch.bump()
+    _ema_after_step(ema, x)
     return x, [fx]
 
 
-def adagrad(opfunc, x, config=None, state=None, fused=None):
+def adagrad(opfunc, x, config=None, state=None, fused=None, ema=None):
     """optim.adagrad (train.lua:193-196): paramVariance += g^2; x -= lr * g / (sqrt(paramVariance) + 1e-10)."""
     config = config if config is not None else {}
     state = state if state is not None else config
@@ -84,6 +140,7 @@ def adagrad(opfunc, x, config=None, state=None, fused=None):
     state["evalCounter"] = state.get("evalCounter", 0) + 1
     lib().adagrad_step(stream(), x.ptr, dfdx.ptr, state["paramVariance"].ptr, x.nElement(), lr, l1, l2, clamp, wb)
     x.epoch.bump()
+    _ema_after_step(ema, x)
     return x, [fx]
 
 

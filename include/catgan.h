@@ -867,7 +867,30 @@ int cg_adam_step_dev(void* stream, float* p, float* g, float* m, float* v, long 
                      float lr, float beta1, float beta2, float eps, const uint64_t* t_dev,
                      float l1, float l2, float clamp, int write_back_grad);
 
-/* optim.sgd (adversarial.lua:240,257; train.lua:201-204: learningRate, momentum; Torch7 form, no Nesterov, no
+/* ---- running average of a parameter vector (train.py --G_ema D; not in the reference) --------------------------------
+ * e is a flat fp32 vector shaped like p.  After the n-th applied update (n counts from 1) that produced p':
+ *   d_n = (float) min((double)(float)D, (1 + n) / (10 + n))      warm-up: the window grows with the run, then D caps it
+ *   e   = fmaf(d_n, e, (1.f - d_n) * p')                         the product rounded on its own, then one fma
+ * Every entry below evaluates that one expression, 16 bytes per lane when every pointer is 16-byte aligned (any n), else a
+ * scalar twin with the same bits.  decay (or decay_cap) outside (0, 1) and null pointers are refused.
+ * cg_ema_update: decay = d_n, formed by the host (optim.ema_decay). */
+int cg_ema_update(void* stream, float* e, const float* p, long n, float decay);
+/* The same with d_n formed in the kernel, in double as written above, from decay_cap = (float)D and n = *n_dev: a counter of
+ * applied updates in device memory that the host advances with cg_counter_add before the call (hipGraph replay freezes the
+ * kernel arguments, as for cg_adam_step_dev). */
+int cg_ema_update_dev(void* stream, float* e, const float* p, long n, float decay_cap, const uint64_t* n_dev);
+/* cg_adam_step followed by cg_ema_update on its p' in one pass over the vectors: p, g, m, v come out with cg_adam_step's bits,
+ * e with cg_ema_update's, and p' is not read back from memory in between.  t >= 1. */
+int cg_adam_step_ema(void* stream, float* p, float* g, float* m, float* v, float* e, long n,
+                     float lr, float beta1, float beta2, float eps, int t,
+                     float l1, float l2, float clamp, int write_back_grad, float decay);
+/* cg_adam_step_dev and cg_ema_update_dev in one pass: t = *t_dev and n = *n_dev are both read from device memory. */
+int cg_adam_step_ema_dev(void* stream, float* p, float* g, float* m, float* v, float* e, long n,
+                         float lr, float beta1, float beta2, float eps, const uint64_t* t_dev,
+                         float l1, float l2, float clamp, int write_back_grad,
+                         float decay_cap, const uint64_t* n_dev);
+
+/* optim.sgd(adversarial.lua:240,257; train.lua:201-204: learningRate, momentum; Torch7 form, no Nesterov, no
  * dampening change: v = mom*v + (1-damp)*g with damp = mom on the first call semantics folded by the host):
  *   g' = penalty/clamp as in cg_adam_step;  v = momentum*v + (1-dampening)*g' (momentum != 0);  p -= lr * (v or g').
  * optim.adagrad (train.lua:193-196):  var += g'^2 ;  p -= lr * g' / (sqrt(var) + 1e-10). */

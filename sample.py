@@ -3,7 +3,9 @@
 engine's .npz), switch both to evaluate mode, and per run write the grids sample.lua:69-128 writes: 64 training images, 256 and
 1024 of 1024 fresh samples, the 64 best / worst (by D) / random ones, optionally the nearest training-set neighbours of the 16
 best (--neighbours: searched on the device while the set streams through it; --neighboursHost keeps the reference's host loop).  Same
-flags as sample.lua:11-25, plus --neighboursOf / --neighbourChunk.
+flags as sample.lua:11-25, plus --neighboursOf / --neighbourChunk, and --G_ema: sample from the averaged generator a `train.py --G_ema D`
+run saved (the G_ema field of a .net, PARAMETERS_G_ema of an .npz) instead of the generator of its last mini-batch.  The flag is parsed
+but, like train.py's, not listed by --help: the recorded command lines (tests/golden/cli_flags.json) pin the help text and the defaults.
 
     python sample.py --save logs --writeto samples --runs 1 --dataDir dataset/out_aug_64x64
 """
@@ -31,6 +33,7 @@ def parse():
     a("--neighboursHost", action="store_true", help="--neighbours (implied) with the reference's host loop over the whole set held in memory")
     a("--neighboursOf", type=int, default=16, help="how many of the best images are searched (1..64; sample.lua: 16)")
     a("--neighbourChunk", type=int, default=4096, help="training images per device pool of the search")
+    a("--G_ema", action="store_true", default=argparse.SUPPRESS, help=argparse.SUPPRESS)     # see the module docstring
     o = ap.parse_args()
     if not 1 <= o.neighboursOf <= 64:
         ap.error("--neighboursOf must be in 1..64")
@@ -41,16 +44,30 @@ def parse():
     return o
 
 
+NO_G_EMA = "%s holds no averaged generator: --G_ema needs a checkpoint of a `train.py --G_ema D` run"
+
+
 def load_models(cg, o, dims):
-    """sample.lua:213-227: G from --G_base, D from --D_base, both in evaluate mode."""
+    """sample.lua:213-227: G from --G_base, D from --D_base, both in evaluate mode.  With --G_ema, G is the averaged generator of the file
+    (its weights the running average, its batch-norm statistics the live G's at the time of the save); ValueError(NO_G_EMA) without one."""
     nets = {}
+    ema = bool(getattr(o, "G_ema", False))
     for key, name in (("G", o.G_base), ("D", o.D_base)):
         path = os.path.join(o.save, name)
         if path.endswith(".npz"):
             G, D = cg.models.create_G(dims, o.noiseDim), cg.models.create_D(dims)
             S = cg.adversarial.State(dict(batchSize=o.batchSize, noiseDim=o.noiseDim), G, D)
             cg.checkpoint.load(path, S)
+            if key == "G" and ema:
+                z = np.load(path, allow_pickle=False)
+                if "PARAMETERS_G_ema" not in z.files:
+                    raise ValueError(NO_G_EMA % path)
+                S.PARAMETERS_G.copy(z["PARAMETERS_G_ema"])
             nets[key] = {"G": G, "D": D}[key]
+        elif key == "G" and ema:
+            nets[key] = cg.checkpoint.import_t7(path).get("G_ema")
+            if nets[key] is None:
+                raise ValueError(NO_G_EMA % path)
         else:
             nets[key] = cg.checkpoint.import_t7(path)[key]
         nets[key].evaluate()
@@ -68,7 +85,10 @@ def main():
     rs = np.random.RandomState(o.seed)                       # torch.manualSeed: the generator behind torch.randperm
     dims = fe.img_dimensions(o)
     ds = fe.configure_dataset(o)                             # sample.py has no --augment: the augmentation stays off
-    G, D = load_models(cg, o, dims)
+    try:
+        G, D = load_models(cg, o, dims)
+    except ValueError as e:
+        sys.exit(str(e))
     S = cg.adversarial.State(dict(batchSize=o.batchSize, noiseDim=o.noiseDim, colorSpace=o.colorSpace), G, D)
     G.evaluate(); D.evaluate()
     os.makedirs(o.writeto, exist_ok=True)

@@ -8,7 +8,14 @@ is what it was before.  The recalled upstream behaviour V relies on is tabulated
 and <G_pretrained_dir>/g_pretrained_CxHxW_ndN.net exists (train.lua:20,152-158; pretrain_g.py writes it) G starts from that decoder
 instead of create_G; without the file nothing changes.
 
+Not in the reference: --G_ema D (0 < D < 1; off without it) keeps a running average of G's weights inside G's optimiser step, with the
+warm-up d_n = min(D, (1 + n) / (10 + n)) over the applied updates n; every epoch's visualisation also writes images_ema/ from the
+averaged generator and the checkpoints carry it (sample.py --G_ema samples from it).  The flag is parsed but not listed by --help and
+absent from the parsed options unless given: the recorded command lines (tests/golden/cli_flags.json) pin both, and a run without it
+stores the OPT it always stored.
+
     python train.py --batchSize 128 --N_epoch 1000 --epochs 3 --synthetic          # no dataset needed
+    python train.py --batchSize 128 --synthetic --epochs 30 --G_ema 0.999
     python train.py --dataDir dataset/out_aug_64x64 --colorSpace y --saveFreq 30
 """
 import argparse
@@ -44,7 +51,14 @@ def parse(argv=None):
     a("--V_dir", default="logs", help="train.lua:19 - directory of the validator network v_CxHxW.net that train_v.py writes")
     a("--G_pretrained_dir", default="logs", help="train.lua:20 - directory of the pre-trained generator g_pretrained_CxHxW_ndN.net that "
       "pretrain_g.py writes")
-    return ap.parse_args(argv)
+    a("--G_ema", type=float, default=argparse.SUPPRESS, help=argparse.SUPPRESS)     # see the module docstring
+    o = ap.parse_args(argv)
+    if hasattr(o, "G_ema"):
+        if not 0 <= o.G_ema < 1:
+            ap.error("--G_ema must be in [0, 1): the decay of the generator's running average (0 = off)")
+        if o.G_ema == 0:
+            del o.G_ema          # off: the options are those of a run without the flag
+    return o
 
 
 def load_pretrained_G(cg, G_pretrained_dir, dims, noiseDim):
