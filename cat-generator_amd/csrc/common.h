@@ -65,7 +65,7 @@ long opt(Opt o);
 // CG_WINO_DGRAD_FUSE_LAUNCHES and CG_WINO3_LAUNCHES are not tunables but counters kept in the same table (cg_get_option reads them,
 // cg_set_option resets them): the launches of wino_dgrad_fused_kernel (winograd.hip) and of wino3_fused_k (wino3.hip), so that a test can
 // tell that the fused path ran and not its fallback.  CG_SAMPLER_ATOMIC_LAUNCHES counts the other way round: the launches of
-// bilinear_bwd_k (ops.hip), the float-atomic fallback of the sampler's deterministic gather backward.
+// bilinear_bwd_k (sampler.hip), the float-atomic fallback of the sampler's deterministic gather backward.
 // CG_PACK_WIDE: 1 = the weight re-packing after every parameter update runs in its wide launches (pack_weight_ups2_wide_kernel and
 // pack_weight_batch_wide_kernel in pack.hip, the both-operand Winograd filter transforms in winograd.hip), 0 = the kernels they replace.
 // The bytes written are the same.
@@ -172,6 +172,25 @@ static inline int ew_grid(long n, int per_block = 256) {
 static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 template <class... P>
 static inline bool vec_ok(long n, const P*... p) { return n % 4 == 0 && (al16(p) && ...); }
+// a grid-stride kernel over n lanes on the entry point's `stream`; nothing to launch for n <= 0
+#define CG_EW_LAUNCH(kern, n, ...)                                                                    \
+    do {                                                                                              \
+        if ((n) > 0) {                                                                                \
+            hipLaunchKernelGGL(kern, dim3(cg::ew_grid(n)), dim3(256), 0, cg::S(stream), __VA_ARGS__); \
+            CG_LAUNCH_CHECK();                                                                        \
+        }                                                                                             \
+    } while (0)
+// The float4-or-scalar twins of one kernel template over n floats: where `vec`, V = 4 and n / 4 lanes, else V = 1 and n lanes.  The
+// kernel and its arguments are written once, with V wherever the width enters: as the template argument, and under every length or
+// channel count that the kernel takes in lanes (none where the kernel itself walks the n % 4 floats behind its float4 body)
+#define CG_EW_LAUNCH_V(vec, kern, n, ...)                                                                                   \
+    do {                                                                                                                    \
+        if ((n) > 0) {                                                                                                      \
+            if (vec) { constexpr int V = 4; hipLaunchKernelGGL(kern, dim3(cg::ew_grid((n) / V)), dim3(256), 0, cg::S(stream), __VA_ARGS__); } \
+            else { constexpr int V = 1; hipLaunchKernelGGL(kern, dim3(cg::ew_grid((n) / V)), dim3(256), 0, cg::S(stream), __VA_ARGS__); }    \
+            CG_LAUNCH_CHECK();                                                                                              \
+        }                                                                                                                   \
+    } while (0)
 
 // ---- device-side helpers -------------------------------------------------
 // The fused-transform Winograd kernels (wino3.hip, wino_dgrad_fused_kernel in winograd.hip) read their A operand from an LDS patch with
@@ -364,7 +383,7 @@ __device__ __forceinline__ double block_sum_256(double v, double* sh /*[4]*/) {
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < (n); i += (long)gridDim.x * blockDim.x)
 
 // VW floats of one lane: one 16-byte access at VW == 4 (the pointer must be 16-byte aligned), one dword at VW == 1.  T is the raw lane
-// type with its operations as static functions: bilinear_bwd_det_k (ops.hip) keeps its register arrays in T, and from arrays of a
+// type with its operations as static functions: bilinear_bwd_det_k (sampler.hip) keeps its register arrays in T, and from arrays of a
 // wrapping struct the compiler forms other code - and, where it fuses a product into a sum, other bits (found with the pins of
 // tests/test_gpu_membound_bits.py).  The elementwise kernels hold one Vec and address its lanes with [].  dot() and fma() state their
 // operation order; their arguments are taken by value for the same reason.
@@ -454,7 +473,7 @@ __device__ __forceinline__ float bn_norm(float x, float m, float s, float g, flo
 __device__ __forceinline__ float bn_dx(float x, float dy, float g, float m, float s, float m1, float m2) {
     return g * s * (dy - m1 - bn_xhat(x, m, s) * m2);
 }
-// the augmentation's noise value of one source sample (ops.hip's on-the-fly kernels, faces.hip's offline variants): Irwin-Hall sum
+// the augmentation's noise value of one source sample (images.hip's on-the-fly kernels, faces.hip's offline variants): Irwin-Hall sum
 // of the twelve 16-bit fields of three splitmix64 outputs (exact in fp32)
 __device__ __forceinline__ float augment_noise(uint64_t seed, uint64_t ctr) {
     unsigned S = 0;
@@ -468,7 +487,7 @@ __device__ __forceinline__ float augment_noise(uint64_t seed, uint64_t ctr) {
     }
     return (float)((int)S - 393210) * (1.0f / 65536.0f);   // |S - 393210| < 2^24 and a power of two: both steps exact
 }
-// tf.warp(order 1, mode="nearest") as the augmentation kernels (ops.hip) and the face extraction (faces.hip) restate it in fp32:
+// tf.warp(order 1, mode="nearest") as the augmentation kernels (images.hip) and the face extraction (faces.hip) restate it in fp32:
 // one axis of the warp's source position: clamped to [0, L-1] (NaN -> 0), split into the two taps and the fraction
 __device__ __forceinline__ void warp_taps(float s, int L, int* i0, int* i1, float* f) {
 #pragma clang fp contract(off)

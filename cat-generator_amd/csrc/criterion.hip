@@ -13,6 +13,8 @@
 // result is the correctly rounded fp32 value or its neighbour (relative error of the sum <= n 2^-53).
 // The aligned path (n % 4 == 0, both pointers 16-byte aligned) reads a quad as one 16-byte load, the other path as four scalar
 // loads with an element guard: the same elements in the same accumulators, hence the same bits.
+//
+// nn.BCECriterion, the adversarial loss, follows the MSE kernels: one workgroup sums a batch of sigmoid outputs in fp64.
 #include "common.h"
 
 namespace cg {
@@ -81,10 +83,40 @@ __global__ __launch_bounds__(kThreads) void mse_bwd_k(const float* __restrict__ 
     }
 }
 
+// ------------------------------------------------------------------------ BCE
+__global__ void bce_fwd_k(const float* p, const float* t, float* loss, long n) {
+    // single block: n is the batch size
+    __shared__ double sh[4];
+    double s = 0.0;
+    for (long i = threadIdx.x; i < n; i += blockDim.x) {
+        const float x = p[i], y = t[i];
+        s -= (double)(logf(x + 1e-12f) * y + logf(1.f - x + 1e-12f) * (1.f - y));
+    }
+    const double tot = block_sum_256(s, sh);
+    if (threadIdx.x == 0) *loss = (float)(tot / (double)n);
+}
+__global__ void bce_bwd_k(const float* p, const float* t, float* dp, long n) {
+    const float norm = 1.f / (float)n;
+    CG_GRID_STRIDE(i, n) {
+        const float x = p[i], y = t[i];
+        dp[i] = -norm * (y - x) / ((1.f - x + 1e-12f) * (x + 1e-12f));
+    }
+}
+
 }  // namespace
 }  // namespace cg
 
 extern "C" {
+
+int cg_bce_forward(void* stream, const float* p, const float* t, float* loss, long n) {
+    CG_REQUIRE(p && t && loss && n > 0, "cg_bce_forward: bad args");
+    hipLaunchKernelGGL(cg::bce_fwd_k, dim3(1), dim3(256), 0, cg::S(stream), p, t, loss, n);
+    CG_LAUNCH_CHECK(); return 0;
+}
+int cg_bce_backward(void* stream, const float* p, const float* t, float* dp, long n) {
+    CG_REQUIRE(p && t && dp, "cg_bce_backward: null pointer");
+    CG_EW_LAUNCH(cg::bce_bwd_k, n, p, t, dp, n); return 0;
+}
 
 int cg_mse_forward(void* stream, const float* x, const float* t, float* loss, long n) {
     using namespace cg;
@@ -113,11 +145,7 @@ int cg_mse_backward(void* stream, const float* x, const float* t, float* dx, lon
     using namespace cg;
     CG_REQUIRE(x && t && dx, "cg_mse_backward: null pointer");
     CG_REQUIRE(n > 0, "cg_mse_backward: bad length n = %ld", n);
-    if (vec_ok(n, x, t, dx))
-        hipLaunchKernelGGL(mse_bwd_k<true>, dim3(ew_grid(n / 4, kThreads)), dim3(kThreads), 0, S(stream), x, t, dx, n);
-    else
-        hipLaunchKernelGGL(mse_bwd_k<false>, dim3(ew_grid(n, kThreads)), dim3(kThreads), 0, S(stream), x, t, dx, n);
-    CG_LAUNCH_CHECK();
+    CG_EW_LAUNCH_V(vec_ok(n, x, t, dx), mse_bwd_k<V == 4>, n, x, t, dx, n);   // blocks of 256 = kThreads
     return 0;
 }
 

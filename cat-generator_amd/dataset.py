@@ -168,7 +168,7 @@ def rgb2y(im):
 
 def rgb2yuv(im):
     """image.rgb2yuv [upstream, recalled: the constants and the order of lua/image.lua:152-155] for a float32 [3, H, W] image, every
-    operation a single fp32 one (the device form is store_colorspace in csrc/ops.hip, same sequence).  U and V are signed."""
+    operation a single fp32 one (the device form is store_colorspace in csrc/images.hip, same sequence).  U and V are signed."""
     f = np.float32
     r, g, b = (np.asarray(im[k], dtype=f) for k in range(3))
     return np.stack([(f(0.299) * r + f(0.587) * g) + f(0.114) * b,
@@ -178,7 +178,7 @@ def rgb2yuv(im):
 
 def rgb2hsl(im):
     """image.rgb2hsl [upstream, recalled: lua/image.lua:159-170] for a float32 [3, H, W] image -> planes h, s, l with h in [0, 1);
-    fp32 step by step, the quotients correctly rounded (store_colorspace in csrc/ops.hip is the same sequence)."""
+    fp32 step by step, the quotients correctly rounded (store_colorspace in csrc/images.hip is the same sequence)."""
     f = np.float32
     r, g, b = (np.asarray(im[k], dtype=f) for k in range(3))
     mx, mn = np.maximum(r, np.maximum(g, b)), np.minimum(r, np.minimum(g, b))

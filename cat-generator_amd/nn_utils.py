@@ -155,7 +155,7 @@ def activateCuda(net):
 # ------------------------------------------------------------------ visual grids
 def yuv2rgb(im):
     """image.yuv2rgb [upstream, recalled: the constants and the order of lua/image.lua:156-158] for a float32 [3, H, W] image, every
-    operation a single fp32 one (the device form is colorspace_to_rgb in csrc/ops.hip, same sequence).  The two matrices are five-digit
+    operation a single fp32 one (the device form is colorspace_to_rgb in csrc/images.hip, same sequence).  The two matrices are five-digit
     constants, no exact inverses: a round trip leaves the unit cube by a few 1e-5, which _png_bytes clamps as image.save does."""
     f = np.float32
     y, u, v = (np.asarray(im[k], dtype=f) for k in range(3))
@@ -174,7 +174,7 @@ def _hue(p, q, t):
 
 def hsl2rgb(im):
     """image.hsl2rgb [upstream, recalled: lua/image.lua:179-186] for a float32 [3, H, W] image with planes h, s, l; fp32 step by step
-    (colorspace_to_rgb in csrc/ops.hip is the same sequence)."""
+    (colorspace_to_rgb in csrc/images.hip is the same sequence)."""
     f = np.float32
     h, s, l = (np.asarray(im[k], dtype=f) for k in range(3))
     q = np.where(l < f(0.5), l * (f(1) + s), (l + s) - l * s)

@@ -59,7 +59,7 @@ def lib():
 
 
 class SplitMix:
-    """Counter-based generator, host twin of cg_rng_* (csrc/ops.hip u01): parameters are initialised on
+    """Counter-based generator, host twin of cg_rng_* (csrc/common.h u01): parameters are initialised on
     the host (as Torch7 does before :cuda()) from the same stream the device kernels use for masks/noise."""
 
     def __init__(self, seed=1):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""nn.BilinearSamplerBHWD backward (deterministic gather form, csrc/ops.hip) under degenerate sampling grids: a localisation net that
+"""nn.BilinearSamplerBHWD backward (deterministic gather form, csrc/sampler.hip) under degenerate sampling grids: a localisation net that
 collapses (scale -> 0) maps every output pixel into ONE source cell.  Times the backward for scales 1, 0.5, 0.1, 0.01, 0 at the step's two
 geometries and checks the gradient against a float64 scatter on the host for the collapsed grid.
 python scripts/sampler_worstcase.py"""

@@ -1,4 +1,4 @@
-"""The bilinear sampler of csrc/ops.hip (bilinear_fwd_k, bilinear_bwd_det_k, bilinear_bwd_k) restated in fp64 numpy, with the
+"""The bilinear sampler of csrc/sampler.hip (bilinear_fwd_k, bilinear_bwd_det_k, bilinear_bwd_k) restated in fp64 numpy, with the
 magnitude sums the per-element rounding bounds of tests/test_gpu_sampler_edges.py need, and its host dispatch (sampler_forward /
 sampler_backward) restated as sampler_plan().  A plain module, imported as tests/locnet_ref.py is.
 
@@ -15,7 +15,7 @@ import numpy as np
 
 f32, f64 = np.float32, np.float64
 
-# the constants of the host dispatch; tests/test_sampler_ref_host.py reads every one of them out of common.h / ops.hip
+# the constants of the host dispatch; tests/test_sampler_ref_host.py reads every one of them out of common.h / sampler.hip
 NUM_CU = 256                 # common.h kNumCU
 EW_WGS_PER_CU = 4            # common.h kEwWgsPerCU (cg::ew_grid's cap)
 DET_LDS_LIMIT = 140 * 1024   # sampler_backward: `shb <= 140 * 1024`
@@ -130,7 +130,7 @@ def _ew(n):
 
 
 def sampler_plan(N, Nimg, Hi, Wi, C, Ho, Wo, aligned, grid_aligned=None):
-    """ops.hip sampler_forward / sampler_backward for N samples on Nimg images.  aligned: img, out, gout and gimg sit on 16-byte
+    """sampler.hip sampler_forward / sampler_backward for N samples on Nimg images.  aligned: img, out, gout and gimg sit on 16-byte
     boundaries; grid_aligned: the grid on an 8-byte one (default: as the tensors).  -> dict(forward=..., backward=...)."""
     grid_aligned = aligned if grid_aligned is None else grid_aligned
     P, Q = Ho * Wo, Hi * Wi

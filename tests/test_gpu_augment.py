@@ -17,7 +17,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CODE = {"rgb": 0, "y": 1, "yuv": 2, "hsl": 3}
 IDENTITY = np.array([1, 0, 0, 0, 1, 0, 1, 0], np.float32)
-GEOMETRIES = [(64, 64, 32, 32), (64, 64, 64, 64), (32, 32, 64, 64), (96, 60, 32, 24)]      # Hs, Ws, h, w
+# Hs, Ws, h, w.  The last three: image.scale's two axes in different branches of its footprint rule (down / up, equal / down, up / equal)
+GEOMETRIES = [(64, 64, 32, 32), (64, 64, 64, 64), (32, 32, 64, 64), (96, 60, 32, 24), (13, 4, 5, 9), (7, 11, 7, 4), (5, 11, 13, 11)]
 
 
 @pytest.fixture(scope="module")

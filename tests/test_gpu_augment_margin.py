@@ -16,8 +16,9 @@ CODE = {"rgb": 0, "y": 1, "yuv": 2, "hsl": 3}
 IDENTITY = np.array([1, 0, 0, 0, 1, 0, 1, 0], np.float32)
 SEED, OFFSET = 0x5DEECE66D1234567, 987654321
 # Hp, Wp, margin, Hd, Wd, N: equal sizes, a shrink by 2, a non-integer shrink of a window that is not square, an enlargement, and the
-# padded 64 x 64 face (93 KB of LDS: the dynamic size has to be asked for)
-SHAPES = [(12, 12, 2, 8, 8, None), (20, 20, 2, 8, 8, None), (17, 19, 2, 8, 8, None), (12, 12, 2, 12, 12, None), (88, 88, 12, 32, 32, 2)]
+# padded 64 x 64 face (93 KB of LDS: the dynamic size has to be asked for); a 13 x 4 window shrunk down its height and stretched along its width
+SHAPES = [(12, 12, 2, 8, 8, None), (20, 20, 2, 8, 8, None), (17, 19, 2, 8, 8, None), (12, 12, 2, 12, 12, None), (88, 88, 12, 32, 32, 2),
+          (17, 8, 2, 5, 9, None)]
 
 
 @pytest.fixture(scope="module")

@@ -36,7 +36,8 @@ def test_loader_kernels_equal_the_host_loader_bit_for_bit(cg, ds, cs):
     from oracle import oracle as O
     C = 1 if cs == "y" else 3
     rs = np.random.RandomState(3)
-    for (Hs, Ws, h, w) in ((64, 64, 32, 32), (64, 64, 64, 64), (32, 32, 64, 64), (96, 60, 32, 24), (80, 80, 32, 32)):
+    for (Hs, Ws, h, w) in ((64, 64, 32, 32), (64, 64, 64, 64), (32, 32, 64, 64), (96, 60, 32, 24), (80, 80, 32, 32),
+                           (13, 4, 5, 9), (7, 11, 7, 4), (5, 11, 13, 11)):      # the two axes in different branches of the footprint rule
         u8 = rs.randint(0, 256, size=(2, Hs, Ws, 3)).astype(np.uint8)
         if cs == "hsl":      # grey pixels and ties between channels inside a scaled image too
             u8[0, : Hs // 4] = u8[0, : Hs // 4, :, :1]

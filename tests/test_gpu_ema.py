@@ -1,6 +1,6 @@
 """--G_ema on the device: the running average of G's weights kept inside its optimiser step.
 
-Kernels (csrc/ops.hip adam_ema_k / ema_k) through the C ABI over their dispatch edges - a float4 body with a live scalar tail, the
+Kernels (csrc/optim.hip adam_ema_k / ema_k) through the C ABI over their dispatch edges - a float4 body with a live scalar tail, the
 all-scalar twin behind any pointer 4 bytes off a 16-byte boundary, the grid-stride wrap behind cg::ew_grid's cap - with two measures:
   bits_equal      the fused entry against cg_adam_step (p, g, m, v) and against cg_ema_update on its p' (e); the device-counter forms
                   against the host-count forms

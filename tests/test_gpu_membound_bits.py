@@ -1,4 +1,4 @@
-"""Bit-for-bit pins of the memory-bound kernels of csrc/ops.hip and csrc/fused.hip, and of the two other users of the shared activation
+"""Bit-for-bit pins of the memory-bound kernels of csrc/ops.hip (with csrc/optim.hip's Adam) and csrc/fused.hip, and of the two other users of the shared activation
 (the GEMM epilogue of csrc/gemm.hip, the localisation launch of csrc/locnet.hip).
 
 The element arithmetic of these kernels is written once, in csrc/common.h, and every scalar / float4 twin is one template: a restructuring

@@ -1,4 +1,4 @@
-"""The memory-bound kernels of csrc/ops.hip and csrc/fused.hip over their dispatch edges, through the C ABI, against fp64 numpy on the
+"""The memory-bound kernels of csrc/ops.hip (with csrc/optim.hip's Adam) and csrc/fused.hip over their dispatch edges, through the C ABI, against fp64 numpy on the
 same fp32 inputs: scalar twins (n % 4, C % 4, a pointer off its 16-byte boundary), the grid-stride wrap behind cg::ew_grid's cap with
 channel counts that do not divide 256, every regime of the column reductions' chunk / ColTree arithmetic, stacked groups, and the value
 edges the oracle defines (+-0.0 at the kink, ties in the max pool).

@@ -352,7 +352,7 @@ def test_shared_image_sampler_equals_one_launch_per_branch(cg, C, H):
 @pytest.mark.parametrize("scale", [0.0, 0.01, 0.1])
 def test_sampler_backward_under_a_collapsed_transformer(cg, C, H, scale):
     """A localisation net that collapses (scale -> 0) maps every output pixel into ONE source cell: up to H*W taps in one bucket of the
-    deterministic gather backward (csrc/ops.hip, bilinear_bwd_det_k).  Round 6 found the step 40 % slower for 25 iterations of a long run
+    deterministic gather backward (csrc/sampler.hip, bilinear_bwd_det_k).  Round 6 found the step 40 % slower for 25 iterations of a long run
     because of it (a single thread insertion-sorted the bucket, one lane group summed it: 2-8 ms instead of 11-28 us): buckets are now
     ordered by rank in parallel and pixels with more than 64 taps are summed by the whole workgroup in a fixed order.  Against the oracle's
     scatter, twice (bit-equal: the order is fixed), and bounded in time."""
@@ -645,7 +645,7 @@ def test_graph_replay_matches_eager(cg):
     eG, eD, te = run(False)
     assert tg == te == 3
     # same kernels, same streams, same step counts, and no float atomics anywhere on the path (the sampler's image gradient
-    # is a gather, csrc/ops.hip bilinear_bwd_det_k): replay and eager launches give the same bits
+    # is a gather, csrc/sampler.hip bilinear_bwd_det_k): replay and eager launches give the same bits
     np.testing.assert_array_equal(gG, eG)
     np.testing.assert_array_equal(gD, eD)
 

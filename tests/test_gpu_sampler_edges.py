@@ -1,4 +1,4 @@
-"""The bilinear sampler of csrc/ops.hip - bilinear_fwd_k<1|4>, the deterministic gather backward bilinear_bwd_det_k<G, CACC, VW> with its
+"""The bilinear sampler of csrc/sampler.hip - bilinear_fwd_k<1|4>, the deterministic gather backward bilinear_bwd_det_k<G, CACC, VW> with its
 whole-workgroup path for source pixels that collect more than kHeavy = 64 taps, the float-atomic fallback bilinear_bwd_k<G> and the
 host dispatch behind cg_bilinear_sampler_{forward,backward}[_shared] - over its dispatch and value edges, through the C ABI, against
 the fp64 restatement of tests/sampler_ref.py on the same fp32 inputs.

@@ -90,7 +90,7 @@ def test_fp32_taps_against_fp64_taps():
 
 def test_the_plan_uses_the_constants_of_the_source():
     common = open(os.path.join(ROOT, "cat-generator_amd", "csrc", "common.h")).read()
-    ops = open(os.path.join(ROOT, "cat-generator_amd", "csrc", "ops.hip")).read()
+    ops = open(os.path.join(ROOT, "cat-generator_amd", "csrc", "sampler.hip")).read()
     k = {n: int(re.search(rf"\b{n} = (\d+)", common).group(1)) for n in ("kNumCU", "kEwWgsPerCU")}
     assert (R.NUM_CU, R.EW_WGS_PER_CU) == (k["kNumCU"], k["kEwWgsPerCU"])
     body = ops[ops.index("int sampler_backward("):ops.index("int cg_bilinear_sampler_forward(")]
