@@ -13,6 +13,9 @@ Differences from the reference, all inert on results:
   * the rolling-accuracy gate (:144-166) only reads the confusion counts back when D_maxAcc <= 1 can trigger.
 Under data parallelism the flat gradient is all-reduced (mean) right after backward, i.e. before penalty and
 clamp — the order adversarial.lua:89-112 fixes.
+Not in the reference, and off unless OPT carries the key: G_ema (a running average of G's weights inside its update) and D_diffaug
+(diffaug.py: the same random transform T over every image D sees, in front of MODEL_D.forward in both steps, and T's adjoint behind
+MODEL_D.modules[0].gradInput on the way to G).
 """
 import math
 import time
@@ -22,7 +25,7 @@ import os
 import numpy as np
 import torch
 
-from . import nn, nn_utils, optim, parallel
+from . import diffaug, nn, nn_utils, optim, parallel
 from .tensor import Tensor, has_gpu, lib, rng, stream
 
 DEFAULT_OPT = dict(  # train.lua:15-49
@@ -81,6 +84,10 @@ class State:
             if not 0 < D < 1:
                 raise ValueError(f"G_ema = {D}: the decay of the generator's running average must lie in (0, 1)")
             self._build_ema(D)
+        # --D_diffaug POLICY (not in the reference): the same random transform over every image D sees, G's gradient taken through it.
+        # Read, never defaulted into OPT, like G_ema; a policy by names ("color,translation,cutout") or as its bit mask
+        pol = self.OPT.get("D_diffaug")
+        self.DIFFAUG = diffaug.DiffAugment(pol) if pol not in (None, "", "none", 0) else None
 
     def _build_ema(self, D):
         """MODEL_G_EMA: a second tree shaped like MODEL_G whose getParameters() vector IS e - the update kernel writes straight into a net
@@ -141,6 +148,8 @@ def _buffers(S, thisBatchSize, dims):
             targets_G=Tensor.from_numpy(np.full(thisBatchSize, S.Y_NOT_GENERATOR, np.float32)),
             idx=torch.zeros(half, dtype=torch.int32, device=S.PARAMETERS_D.t.device),
         )
+        if S.DIFFAUG is not None:      # the G-step's augmented samples and the gradient T's adjoint hands to G: persistent, like inputs
+            b.update(aug_G=Tensor.zeros((thisBatchSize,) + tuple(dims), "nhwc"), gaug_G=Tensor.zeros((thisBatchSize,) + tuple(dims), "nhwc"))
         S._cache[key] = b
     return b
 
@@ -157,6 +166,7 @@ def iteration(S, trainData, thisBatchSize=None, maxAccuracyD=1.01, accsInterval=
     inputs, half = buf["inputs"], N // 2
     rowlen = int(np.prod(dims))
     st = {"doTrainD": True}
+    aug = S.DIFFAUG                # --D_diffaug, else None: three more launches per iteration (T on D's batch, T and its adjoint in the G-step)
     # data parallelism: G's gradient travels in per-layer buckets started from inside the planned backward
     S.MODEL_G._bucket_overlap = bool(parallel.world_size() > 1 and OPT.get("overlap_comm", True) and _bucketable(S.MODEL_G) and nn.planned)
     # ... and so does D's (round 6): Linear(20480, 256) is 79 % of D's gradient and the FIRST bucket its backward completes, so it travels
@@ -193,7 +203,7 @@ def iteration(S, trainData, thisBatchSize=None, maxAccuracyD=1.01, accsInterval=
         S.CONFUSION.batchAdd(nn.as_plain(outputs), targets)
         if not OPT["fused_update"] and OPT["D_clamp"] != 0:
             S.GRAD_PARAMETERS_D.clamp(-OPT["D_clamp"], OPT["D_clamp"])
-        S._last = dict(outputs_D=outputs.clone() if S.keep_outputs else outputs, f_D=f)
+        S._last = dict(outputs_D=outputs.clone() if S.keep_outputs else outputs, f_D=f, **st.pop("keep", {}))
         if maxAccuracyD <= 1.0:  # the gate can trigger: read this batch's accuracy back (:115-166)
             o = nn.as_plain(outputs).numpy().reshape(-1)
             t = targets.numpy().reshape(-1)
@@ -225,14 +235,23 @@ def iteration(S, trainData, thisBatchSize=None, maxAccuracyD=1.01, accsInterval=
                 r.take(st["noiseInputs"].nElement())
         if samples is None:
             samples = nn_utils.createImagesFromNoise(S, st["noiseInputs"], False, True)
-        outputs = S.MODEL_D.forward(samples)
+        seen = samples                  # what D is shown: T(samples) with fresh draws, G's own images left as they are
+        if aug is not None:
+            seen = aug.forward(nn.as_nhwc(samples), buf["aug_G"], "G")
+        outputs = S.MODEL_D.forward(seen)
         f = S.CRITERION.forward(outputs, targets)
         df_samples = S.CRITERION.backward(outputs, targets)
         if OPT["exact_reference_backward"]:
-            S.MODEL_D.backward(samples, df_samples)
+            S.MODEL_D.backward(seen, df_samples)
         else:
-            S.MODEL_D.updateGradInput(samples, df_samples)
+            S.MODEL_D.updateGradInput(seen, df_samples)
         df_do = S.MODEL_D.modules[0].gradInput
+        if aug is not None:             # G is trained against D o T: the gradient goes through T's adjoint with the forward's draws
+            if S.keep_outputs:
+                S._last.update(aug_G=seen.clone(), desc_G=aug.desc_np("G", N), gradInput_D=nn.as_nhwc(df_do).clone())
+            df_do = aug.backward(nn.as_nhwc(df_do), buf["gaug_G"], "G")
+            if S.keep_outputs:
+                S._last["df_G"] = df_do.clone()
         if getattr(S.MODEL_G, "_bucket_overlap", False) and S.MODEL_G._planned_last:
             # the plan starts each gradient bucket's all-reduce as soon as its backward is complete (cg_net_set_dp): all but the
             # last bucket (Linear 100 -> 8192) travel under the remaining backward; nothing is ever one step stale
@@ -266,6 +285,9 @@ def iteration(S, trainData, thisBatchSize=None, maxAccuracyD=1.01, accsInterval=
         lib().gather_rows(stream(), trainData.pool.ptr, buf["idx"].data_ptr(), inputs.ptr, half, rowlen)
         # (1.2) sampled data
         noise = nn.to_device(noise_D) if noise_D is not None else nn_utils.stepNoiseInputs(S, half)
+        # T's draws for D's batch are taken HERE, where they lie in the order of calls (behind the fake images' noise, in front of D's
+        # dropout masks): the pair schedule below computes the G-step's noise position from the stream as it stands
+        aug_off = aug.reserve(N) if aug is not None else None
         both = _both_forwards_ok(S, N)
         if both:
             # ONE call below the ABI (cg_net_forward_pair, round 6): the fake-image pass on the step's stream, the G-step's pass on a library
@@ -282,6 +304,12 @@ def iteration(S, trainData, thisBatchSize=None, maxAccuracyD=1.01, accsInterval=
             samples = nn.as_nhwc(nn_utils.createImagesFromNoise(S, noise, False))
         lib().memcpy_d2d(stream(), inputs.ptr + half * rowlen * 4, samples.ptr, half * rowlen * 4)
         S._last_fake = samples.clone() if S.keep_outputs else samples
+        if aug is not None:             # both halves alike, in place: D never sees an un-augmented image
+            if S.keep_outputs:
+                st["keep"] = dict(inputs_D=inputs.clone())
+            aug.forward(inputs, inputs, "D", offset=aug_off)
+            if S.keep_outputs:
+                st["keep"].update(aug_D=inputs.clone(), desc_D=aug.desc_np("D", N))
         fused = dict(l1=OPT["D_L1"], l2=OPT["D_L2"], clamp=OPT["D_clamp"]) if OPT["fused_update"] else None
         m = OPT["D_optmethod"]  # adversarial.lua:240-248
         assert m in ("sgd", "adagrad", "adam"), "[Warning] Unknown optimizer method chosen for D."

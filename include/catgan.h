@@ -890,6 +890,43 @@ int cg_adam_step_ema_dev(void* stream, float* p, float* g, float* m, float* v, f
                          float l1, float l2, float clamp, int write_back_grad,
                          float decay_cap, const uint64_t* n_dev);
 
+/* ---- differentiable augmentation of D's input (train.py --D_diffaug POLICY; csrc/diffaug.hip; Zhao et al. 2020, not in the
+ * reference) ----
+ * x, y: fp32 NHWC [N][H][W][C], C = 1 or 3.  policy is a bit mask: 1 colour, 2 translation, 4 cutout; any non-empty combination
+ * (1..7).  Each image has a descriptor of eight floats in device memory, desc[n] = (b, s, c, tx, ty, cy, cx, 0), drawn from the
+ * engine's counter stream (u01(seed, ctr)): image n always uses counters offset + 8n + k, k = 0..7, whatever the policy, so the
+ * stream position never depends on the policy; the eighth counter is reserved.  With u_k = u01(seed, offset + 8n + k), in fp32:
+ *   b = u0 - 0.5, s = 2 u1, c = u2 + 0.5
+ *   Rw = (int)(W 0.125 + 0.5), Rh likewise from H;  tx = floor(u3 (2Rw+1)) - Rw, ty = floor(u4 (2Rh+1)) - Rh, stored as exact floats
+ *   ch = (int)(H 0.5 + 0.5), cw = (int)(W 0.5 + 0.5);  cy = floor(u5 (H + 1 - ch%2)), cx = floor(u6 (W + 1 - cw%2))
+ * Forward applies each stage only when its bit is set, in this order:
+ *   1. colour, brightness:  x1 = x + b
+ *   2. colour, saturation:  m = (sum over the pixel's channels of x1) / C, x2 = (x1 - m) s + m; skipped for C = 1
+ *   3. colour, contrast:    M = the image's mean of x2, accumulated in fp64 and rounded to fp32 once; x3 = (x2 - M) c + M
+ *   4. translation:         out[y][x] = x3[y - ty][x - tx] where the source lies in the image, otherwise 0
+ *   5. cutout:              zero the rectangle of rows cy - ch/2 ... cy - ch/2 + ch - 1 and columns cx - cw/2 ... cx - cw/2 + cw - 1
+ *                           (integer division), intersected with the image
+ * Backward takes g, the gradient with respect to out, and the same desc:
+ *   1. zero g inside the cutout rectangle
+ *   2. g2[y][x] = g[y + ty][x + tx] where that lies in the image, otherwise 0
+ *   3. contrast:    Gm = the image's mean of g2, in fp64 as above; g3 = (g2 - Gm) c + Gm
+ *   4. saturation:  with m the pixel's channel mean of g3, dx = (g3 - m) s + m
+ *   5. brightness has an identity adjoint
+ * (v - m) k + m is evaluated as fmaf(v - m, k, m), the channel mean as ((v0 + v1) + v2) / 3.
+ * One workgroup per image with the image staged in the LDS, one launch per call: one read of x, one write of y.  y == x (gx == gy)
+ * is allowed and gives the bits of the out-of-place call.  16-byte global accesses where C H W % 4 == 0 and both image pointers are
+ * 16-byte aligned, else a scalar twin with the same bits.  The fp64 sums have a fixed order: an image's result is bit-reproducible
+ * and depends neither on N nor on its position in the batch.  No floating-point atomics.
+ * draw != 0: the kernel draws image n's descriptor at offset (+ *base when base != NULL: cg_rng_*_dev semantics, so that a captured
+ *   iteration replays with fresh draws) + 8n + k, uses it and stores it to desc[n].
+ * draw == 0: the kernel reads desc[n] (seed, offset and base are ignored); integer fields beyond the image are clamped to where
+ *   nothing of it is reached any more.
+ * Refused before any launch: null x / y / desc, N <= 0, H or W <= 0, C not 1 or 3, policy outside 1..7, an image of more than
+ * 64 KB (C H W 4 bytes: it would not fit the workgroup's LDS stage). */
+int cg_diffaug_forward(void* stream, const float* x, float* y, float* desc, int N, int H, int W, int C, int policy,
+                       int draw, uint64_t seed, uint64_t offset, const uint64_t* base);
+int cg_diffaug_backward(void* stream, const float* gy, float* gx, const float* desc, int N, int H, int W, int C, int policy);
+
 /* optim.sgd(adversarial.lua:240,257; train.lua:201-204: learningRate, momentum; Torch7 form, no Nesterov, no
  * dampening change: v = mom*v + (1-damp)*g with damp = mom on the first call semantics folded by the host):
  *   g' = penalty/clamp as in cg_adam_step;  v = momentum*v + (1-dampening)*g' (momentum != 0);  p -= lr * (v or g').

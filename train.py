@@ -14,8 +14,16 @@ averaged generator and the checkpoints carry it (sample.py --G_ema samples from 
 absent from the parsed options unless given: the recorded command lines (tests/golden/cli_flags.json) pin both, and a run without it
 stores the OPT it always stored.
 
+Not in the reference either: --D_diffaug POLICY (a comma list out of color, translation, cutout; off without it, or with an empty value
+or `none`) applies the same random differentiable augmentation T to every image D sees, real and fake, in the D-step and in the G-step,
+and takes G's gradient through T (Zhao et al. 2020; cat-generator_amd/diffaug.py): D never sees an un-augmented image and
+cannot memorise the set, while G's own samples stay un-augmented.  Three more launches per iteration; the draws come from the engine's
+counter stream, so checkpoints resume bit for bit.  `color` needs channels that are colours: with --colorSpace yuv or hsl it is an
+argument error (with y, saturation has nothing to do and is skipped).  Parsed like --G_ema: not listed by --help, absent unless given.
+
     python train.py --batchSize 128 --N_epoch 1000 --epochs 3 --synthetic          # no dataset needed
     python train.py --batchSize 128 --synthetic --epochs 30 --G_ema 0.999
+    python train.py --batchSize 128 --synthetic --epochs 30 --D_diffaug color,translation,cutout
     python train.py --dataDir dataset/out_aug_64x64 --colorSpace y --saveFreq 30
 """
 import argparse
@@ -52,12 +60,24 @@ def parse(argv=None):
     a("--G_pretrained_dir", default="logs", help="train.lua:20 - directory of the pre-trained generator g_pretrained_CxHxW_ndN.net that "
       "pretrain_g.py writes")
     a("--G_ema", type=float, default=argparse.SUPPRESS, help=argparse.SUPPRESS)     # see the module docstring
+    a("--D_diffaug", default=argparse.SUPPRESS, help=argparse.SUPPRESS)             # likewise
     o = ap.parse_args(argv)
     if hasattr(o, "G_ema"):
         if not 0 <= o.G_ema < 1:
             ap.error("--G_ema must be in [0, 1): the decay of the generator's running average (0 = off)")
         if o.G_ema == 0:
             del o.G_ema          # off: the options are those of a run without the flag
+    if hasattr(o, "D_diffaug"):
+        if o.D_diffaug.strip().lower() in ("", "none"):
+            del o.D_diffaug      # off, likewise
+        else:
+            diffaug = importlib.import_module("cat-generator_amd.diffaug")
+            try:
+                policy = diffaug.parse_policy(o.D_diffaug)
+            except ValueError as e:
+                ap.error(f"--D_diffaug: {e}")
+            if policy & diffaug.COLOR and o.colorSpace in ("yuv", "hsl"):
+                ap.error(f"--D_diffaug color with --colorSpace {o.colorSpace}: a per-pixel channel mean means nothing there (rgb and y are fine)")
     return o
 
 
