@@ -497,5 +497,44 @@ __device__ __forceinline__ void warp_taps(float s, int L, int* i0, int* i1, floa
     *f = s - (float)*i0;
     *i1 = min(*i0 + 1, L - 1);
 }
+// ---- the spatial transformer's affine arithmetic: sampler.hip's cg_affine_* kernels and the fused launches of locnet.hip ----------
+// Each expression stands once, with the parenthesisation and operand order the pins of tests/test_gpu_membound_bits.py recorded.
+// coordinate of index i of n in [-1, 1]
+__device__ __forceinline__ float grid_coord(int i, int n) { return n > 1 ? -1.f + 2.f * (float)i / (float)(n - 1) : -1.f; }
+// The transform's parameters as the generator stores them - [theta][scale][tx, ty], each part present by its flag - unpacked, and
+// T = R(theta) * S(s) * Tr(tx,ty); rows: [c*s, -sn*s, c*s*tx - sn*s*ty], [sn*s, c*s, sn*s*tx + c*s*ty].  cs, where given, receives
+// (cos, sin, scale, tx, ty) for affine_param_grad.  Unpacking and T are ONE function on purpose: a caller that wants only cs leaves T
+// unused, and with a separate unpacking the compiler contracts affine_param_grad's sums otherwise (profiles/locnet_stages_resources.txt)
+__device__ __forceinline__ void affine_T(const float* prm, int ur, int us, int ut, float* T, float* cs = nullptr) {
+    int k = 0;
+    float th = 0.f, sc = 1.f, tx = 0.f, ty = 0.f;
+    if (ur) th = prm[k++];
+    if (us) sc = prm[k++];
+    if (ut) { tx = prm[k]; ty = prm[k + 1]; }
+    const float c = cosf(th), s = sinf(th);
+    T[0] = c * sc; T[1] = -s * sc; T[2] = c * sc * tx - s * sc * ty;
+    T[3] = s * sc; T[4] = c * sc;  T[5] = s * sc * tx + c * sc * ty;
+    if (cs) { cs[0] = c; cs[1] = s; cs[2] = sc; cs[3] = tx; cs[4] = ty; }
+}
+// gparams from g = dL/dT
+__device__ __forceinline__ void affine_param_grad(float c, float s, float sc, float tx, float ty, const float* g, int ur, int us, int ut, float* gp) {
+    int k = 0;
+    if (ur) {
+        // d/dtheta: c -> -s, s -> c
+        const float d0 = -s * sc, d1 = -c * sc, d2 = -s * sc * tx - c * sc * ty;
+        const float d3 = c * sc, d4 = -s * sc, d5 = c * sc * tx - s * sc * ty;
+        gp[k++] = g[0] * d0 + g[1] * d1 + g[2] * d2 + g[3] * d3 + g[4] * d4 + g[5] * d5;
+    }
+    if (us) gp[k++] = g[0] * c + g[1] * (-s) + g[2] * (c * tx - s * ty) + g[3] * s + g[4] * c + g[5] * (s * tx + c * ty);
+    if (ut) {
+        gp[k] = g[2] * (c * sc) + g[5] * (s * sc);
+        gp[k + 1] = g[2] * (-s * sc) + g[5] * (c * sc);
+    }
+}
+// one grid point's terms of gT[r][:] = sum_{i,j} ggrid[i,j,r] * (y_i, x_j, 1): fp32 products into fp64 sums
+__device__ __forceinline__ void affine_grid_acc(double (&acc)[6], float g0, float g1, float y, float x) {
+    acc[0] += g0 * y; acc[1] += g0 * x; acc[2] += g0;
+    acc[3] += g1 * y; acc[4] += g1 * x; acc[5] += g1;
+}
 
 }  // namespace cg

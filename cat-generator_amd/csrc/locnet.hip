@@ -28,15 +28,15 @@ constexpr int LH = 64;   // hidden units of the first linear layer (models.lua:8
 
 struct LocW { const float *w1, *b1, *w2, *b2, *w3, *b3, *w4, *b4, *wf1, *wb1, *wf2, *wb2; };   // wf / wb: cg_pack_conv_weight's copies
 
-struct LocFwd {
+struct LocGeo {                                     // what both launches take: the groups' weights, the geometry, the transform, the slope
     LocW g[4];
-    const float* x; int x_shared;                   // [.., 2S, 2S, Cin] NHWC; x_shared: every group reads samples [0, N)
     int G, N, S, Cin, P, Hg, Wg, ur, us, ut; float slope;
+};
+struct LocFwd : LocGeo {
+    const float* x; int x_shared;                   // [.., 2S, 2S, Cin] NHWC; x_shared: every group reads samples [0, N)
     float *pbuf, *h1buf, *m2buf, *h2buf, *h3buf, *params, *grid;
 };
-struct LocBwd {
-    LocW g[4];
-    int G, N, S, Cin, P, Hg, Wg, ur, us, ut; float slope;
+struct LocBwd : LocGeo {
     const float *h1buf, *m2buf, *h3buf, *params, *ggrid;
     float *ga1, *ga2, *g3, *g4, *gx;
 };
@@ -116,18 +116,6 @@ __host__ __device__ inline int conv_part_floats(int S, int OUT) {
     return R == 1 ? 0 : R * items * 16;
 }
 
-__device__ __forceinline__ void affine_T(const float* prm, int ur, int us, int ut, float T[6], float* cs = nullptr) {
-    int k = 0;
-    float th = 0.f, sc = 1.f, tx = 0.f, ty = 0.f;
-    if (ur) th = prm[k++];
-    if (us) sc = prm[k++];
-    if (ut) { tx = prm[k]; ty = prm[k + 1]; }
-    const float c = cosf(th), s = sinf(th);
-    T[0] = c * sc; T[1] = -s * sc; T[2] = c * sc * tx - s * sc * ty;
-    T[3] = s * sc; T[4] = c * sc;  T[5] = s * sc * tx + c * sc * ty;
-    if (cs) { cs[0] = c; cs[1] = s; cs[2] = sc; cs[3] = tx; cs[4] = ty; }
-}
-
 // LDS plan shared by the kernels and the host-side size check (floats)
 struct FwdLds { int p, w1l, h1, w2l, m2, h2, h3, prm, zero, part, total; };
 __host__ __device__ inline FwdLds fwd_lds(int S, int Cin) {
@@ -165,6 +153,112 @@ __host__ __device__ inline BwdLds bwd_lds(int S, int Cin) {
     return L;
 }
 
+// ================================================================================================ the stages both kernel families run
+// The 768-thread VALU kernels below and the 256-thread MFMA kernels of v2 differ in how they run the long sums.  Everything else is the
+// same expression in both and stands here once: NTH = threads of the workgroup; At = where pixel pix of an LDS image lies (Rows: the
+// VALU kernels' [S*S][stride] with an odd stride; Haloed: the MFMA kernels' zero-haloed [(S+2)^2][CP]); GW = floats per access to the
+// grid / its gradient (2: one float2 per point, which the MFMA kernels have always taken; 1: two scalars, the VALU kernels - they ask
+// no alignment of either tensor).
+// NOT here, and not to be merged: both convolutions (taps split over threads with fixed-order partial sums, against MFMA K-steps),
+// Linear(K3 -> 64) forward and backward (lanes striding over k, against 16-byte columns), Linear(64 -> P) forward (one serial chain
+// per output, against a wave's shuffle tree) and the MFMA kernels' float4 pooling.  Their sums associate differently per family; one
+// function for both would change bits that tests/test_gpu_membound_bits.py pins.
+// Nor the one-lane matrix backward: its arithmetic is common.h's (cg::affine_T, cg::affine_param_grad), but the few lines around the
+// two calls stay in each backward kernel.  Which product of a sum like s*tx + c*ty the compiler fuses into an fma there depends on how
+// it pairs the block's operations into packed instructions, and with the block behind one more function (or the MFMA kernel's tile
+// walks behind a lambda, see tiles_each) it pairs them otherwise: g4 moved in its last bit in every backward pin
+// (profiles/locnet_stages_resources.txt).
+struct Rows { int stride; __device__ __forceinline__ int operator()(int pix) const { return pix * stride; } };
+__device__ __forceinline__ int pp(int pix, int S, int SP) { return ((pix / S) + 1) * SP + (pix % S) + 1; }   // S: a power of two
+template <int S, int CP> struct Haloed { __device__ __forceinline__ int operator()(int pix) const { return pp(pix, S, S + 2) * CP; } };
+
+// AvgPool(2,2,2,2) of the sample, one element per lane (cg_avgpool2_forward's order of additions) -> the LDS image and pbuf
+template <int NTH, typename At>
+__device__ __forceinline__ void pool_input(const float* xs, int S, int Cin, float* img, At at, float* pb) {
+    for (int i = threadIdx.x; i < S * S * Cin; i += NTH) {
+        const int c = i % Cin, pix = i / Cin, px = pix % S, py = pix / S;
+        const size_t b = ((size_t)(2 * py) * (2 * S) + 2 * px) * Cin + c;
+        const float v = (xs[b] + xs[b + Cin] + xs[b + (size_t)2 * S * Cin] + xs[b + (size_t)2 * S * Cin + Cin]) * 0.25f;
+        img[at(pix) + c] = v;
+        pb[i] = v;
+    }
+}
+// AvgPool(2) of m2 ([S*S][LC + 1] in both families) -> h2; i = (c, py, px): nn.View(16*h*h) flattens the NCHW map
+template <int NTH>
+__device__ __forceinline__ void pool_flatten(const float* m2, int S, float* h2, float* h2buf) {
+    const int Sh = S / 2;
+    for (int i = threadIdx.x; i < LC * Sh * Sh; i += NTH) {
+        const int px = i % Sh, py = (i / Sh) % Sh, c = i / (Sh * Sh);
+        const float* q = m2 + ((2 * py) * S + 2 * px) * (LC + 1) + c;
+        const float pv = (q[0] + q[LC + 1] + q[S * (LC + 1)] + q[(S + 1) * (LC + 1)]) * 0.25f;
+        h2[i] = pv;
+        h2buf[i] = pv;
+    }
+}
+// AffineTransformMatrixGenerator + AffineGridGeneratorBHWD: the sample's grid from its parameters
+template <int NTH, int GW>
+__device__ __forceinline__ void grid_write(const float* prm, int ur, int us, int ut, int H, int W, float* gr) {
+    float T[6];
+    cg::affine_T(prm, ur, us, ut, T);
+    for (int i = threadIdx.x; i < H * W; i += NTH) {
+        const int ii = i / W, j = i - ii * W;
+        const float y = cg::grid_coord(ii, H), x = cg::grid_coord(j, W);
+        const float gy = T[0] * y + T[1] * x + T[2], gx = T[3] * y + T[4] * x + T[5];
+        if constexpr (GW == 2) reinterpret_cast<float2*>(gr)[i] = make_float2(gy, gx);
+        else { gr[i * 2 + 0] = gy; gr[i * 2 + 1] = gx; }
+    }
+}
+// affine_grid_backward: gT[r][:] = sum_{i,j} ggrid[i,j,r] * (y_i, x_j, 1) in fp64; leaves every wave's sums (fixed shuffle tree) in shd
+template <int NTH, int GW>
+__device__ __forceinline__ void grid_grad_sums(const float* gg, int H, int W, double (*shd)[NTH / 64]) {
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = threadIdx.x; i < H * W; i += NTH) {
+        const int ii = i / W, j = i - ii * W;
+        const float y = cg::grid_coord(ii, H), x = cg::grid_coord(j, W);     // before the loads, as the compiler then keeps them
+        float g0, g1;
+        if constexpr (GW == 2) { const float2 gv = reinterpret_cast<const float2*>(gg)[i]; g0 = gv.x; g1 = gv.y; }
+        else { g0 = gg[i * 2]; g1 = gg[i * 2 + 1]; }
+        cg::affine_grid_acc(acc, g0, g1, y, x);
+    }
+    const int tid = threadIdx.x;
+    for (int k = 0; k < 6; ++k) {
+        const double t = cg::wave_sum(acc[k]);
+        if ((tid & 63) == 0) shd[k][tid >> 6] = t;
+    }
+}
+// Linear(64 -> P) backward + LeakyReLU backward: g3[k] = lrelu'(a3[k]) * sum_p w4[p][k] g4[p]
+__device__ __forceinline__ void linear2_backward(const float* w4, const float* g4s, int P, const float* h3, float sl, float* g3s, float* g3) {
+    const int tid = threadIdx.x;
+    if (tid < LH) {
+        float s = 0.f;
+        for (int q = 0; q < P; ++q) s += w4[q * LH + tid] * g4s[q];
+        const float v = cg::dact(2, h3[tid], s, sl);
+        g3s[tid] = v;
+        g3[tid] = v;
+    }
+}
+// AvgPool backward (x 0.25) + LeakyReLU backward at conv 2's output -> the LDS image of ga2 and the tensor (for the weight gradient)
+template <int NTH, typename At>
+__device__ __forceinline__ void pool_backward(const float* gh2, const float* m2buf, int S, float sl, float* img, At at, float* ga2) {
+    const int Sh = S / 2;
+    for (int i = threadIdx.x; i < S * S * LC; i += NTH) {
+        const int c = i % LC, pix = i / LC, y = pix / S, x = pix % S;
+        const float gv = gh2[c * Sh * Sh + (y >> 1) * Sh + (x >> 1)] * 0.25f;
+        const float v = cg::dact(2, m2buf[i], gv, sl);
+        img[at(pix) + c] = v;
+        ga2[i] = v;
+    }
+}
+// AvgPool backward of gp ([S*S][stride] in both families) to the transformer's input resolution
+template <int NTH>
+__device__ __forceinline__ void unpool_input(const float* gp, int stride, int S, int Cin, float* gx) {
+    for (int i = threadIdx.x; i < 4 * S * S * Cin; i += NTH) {
+        const int c = i % Cin, xx = (i / Cin) % (2 * S), yy = i / (Cin * 2 * S);
+        gx[i] = gp[((yy >> 1) * S + (xx >> 1)) * stride + c] * 0.25f;
+    }
+}
+
+// ================================================================================================ the VALU kernels
 __global__ __launch_bounds__(NT) void locnet_fwd_k(LocFwd a) {
     extern __shared__ float sm[];
     const int S = a.S, Cin = a.Cin, S2 = S * S, CP = Cin | 1, Sh = S / 2, K3 = LC * Sh * Sh, tid = threadIdx.x;
@@ -175,15 +269,7 @@ __global__ __launch_bounds__(NT) void locnet_fwd_k(LocFwd a) {
           *prm = sm + L.prm, *zero = sm + L.zero, *part = sm + L.part;
     const float sl = a.slope;
 
-    // AvgPool(2,2,2,2) of the sample (cg_avgpool2_forward's order of additions)
-    const float* xs = a.x + (size_t)(a.x_shared ? n : smp) * (4 * S2) * Cin;
-    for (int i = tid; i < S2 * Cin; i += NT) {
-        const int c = i % Cin, px = (i / Cin) % S, py = i / (Cin * S);
-        const size_t b = ((size_t)(2 * py) * (2 * S) + 2 * px) * Cin + c;
-        const float v = (xs[b] + xs[b + Cin] + xs[b + (size_t)2 * S * Cin] + xs[b + (size_t)2 * S * Cin + Cin]) * 0.25f;
-        p[(py * S + px) * CP + c] = v;
-        a.pbuf[(size_t)smp * S2 * Cin + i] = v;
-    }
+    pool_input<NT>(a.x + (size_t)(a.x_shared ? n : smp) * (4 * S2) * Cin, S, Cin, p, Rows{CP}, a.pbuf + (size_t)smp * S2 * Cin);
     // kernels as [(tap*C + ci)][co]
     // (cg_pack_conv_weight's forward copies already have this layout: straight, coalesced copies)
     for (int d = tid; d < 9 * Cin * LC; d += NT) w1l[d] = w.wf1[d];
@@ -208,13 +294,7 @@ __global__ __launch_bounds__(NT) void locnet_fwd_k(LocFwd a) {
         a.m2buf[((size_t)smp * S2 + pix) * LC + c] = v;
     }
     __syncthreads();
-    for (int i = tid; i < K3; i += NT) {          // i = (c, py, px): nn.View(16*h*h) flattens the NCHW map
-        const int px = i % Sh, py = (i / Sh) % Sh, c = i / (Sh * Sh);
-        const float* q = m2 + ((2 * py) * S + 2 * px) * (LC + 1) + c;
-        const float pv = (q[0] + q[LC + 1] + q[S * (LC + 1)] + q[(S + 1) * (LC + 1)]) * 0.25f;
-        h2[i] = pv;
-        a.h2buf[(size_t)smp * K3 + i] = pv;
-    }
+    pool_flatten<NT>(m2, S, h2, a.h2buf + (size_t)smp * K3);
     __syncthreads();
     // Linear(K3 -> 64) + LeakyReLU: eight waves take 8 outputs each; a wave's lanes stride over k and keep all 8 running sums, so every
     // step has 8 (x2 unrolled) independent coalesced row loads in flight (the weight matrix streams from L2: latency, not arithmetic,
@@ -257,19 +337,7 @@ __global__ __launch_bounds__(NT) void locnet_fwd_k(LocFwd a) {
         a.params[(size_t)smp * a.P + tid] = s;
     }
     __syncthreads();
-    // AffineTransformMatrixGenerator + AffineGridGeneratorBHWD
-    float T[6];
-    affine_T(prm, a.ur, a.us, a.ut, T);
-    const int H = a.Hg, W = a.Wg;
-    float* gr = a.grid + (size_t)smp * H * W * 2;
-    for (int i = tid; i < H * W; i += NT) {
-        const int ii = i / W, j = i - ii * W;
-        const float y = H > 1 ? -1.f + 2.f * (float)ii / (float)(H - 1) : -1.f;
-        const float x = W > 1 ? -1.f + 2.f * (float)j / (float)(W - 1) : -1.f;
-        gr[i * 2 + 0] = T[0] * y + T[1] * x + T[2];
-        gr[i * 2 + 1] = T[3] * y + T[4] * x + T[5];
-    }
-   
+    grid_write<NT, 1>(prm, a.ur, a.us, a.ut, a.Hg, a.Wg, a.grid + (size_t)smp * a.Hg * a.Wg * 2);
 }
 
 // Backward of the same chain for one sample: ggrid -> gT -> gparams -> ... -> gradient w.r.t. the (un-pooled) input.  Leaves
@@ -287,24 +355,9 @@ __global__ __launch_bounds__(NT) void locnet_bwd_k(LocBwd a) {
           *g4s = sm + L.g4, *zero = sm + L.zero, *part = sm + L.part;
     const float sl = a.slope;
 
-    // affine_grid_backward: gT[r][:] = sum_{i,j} ggrid[i,j,r] * (y_i, x_j, 1)   (fp64 block sums, fixed order)
-    const int H = a.Hg, W = a.Wg;
-    const float* gg = a.ggrid + (size_t)smp * H * W * 2;
-    double acc[6] = {0, 0, 0, 0, 0, 0};
-    for (int i = tid; i < H * W; i += NT) {
-        const int ii = i / W, j = i - ii * W;
-        const float y = H > 1 ? -1.f + 2.f * (float)ii / (float)(H - 1) : -1.f;
-        const float x = W > 1 ? -1.f + 2.f * (float)j / (float)(W - 1) : -1.f;
-        const float g0 = gg[i * 2], g1 = gg[i * 2 + 1];
-        acc[0] += g0 * y; acc[1] += g0 * x; acc[2] += g0;
-        acc[3] += g1 * y; acc[4] += g1 * x; acc[5] += g1;
-    }
-    for (int k = 0; k < 6; ++k) {             // wave sums (fixed shuffle tree), then the waves in order
-        const double t = cg::wave_sum(acc[k]);
-        if ((tid & 63) == 0) shd[k][tid >> 6] = t;
-    }
+    grid_grad_sums<NT, 1>(a.ggrid + (size_t)smp * a.Hg * a.Wg * 2, a.Hg, a.Wg, shd);
     __syncthreads();
-    if (tid < 6) {
+    if (tid < 6) {                            // the waves in order, rounded to fp32
         double t = 0.0;
         for (int wv = 0; wv < NT / 64; ++wv) t += shd[tid][wv];
         gTs[tid] = (float)t;
@@ -324,31 +377,13 @@ __global__ __launch_bounds__(NT) void locnet_bwd_k(LocBwd a) {
         for (int k = 0; k < 6; ++k) gT[k] = gTs[k];
         const float* prm = a.params + (size_t)smp * a.P;
         float T[6], cs[5];
-        affine_T(prm, a.ur, a.us, a.ut, T, cs);
+        cg::affine_T(prm, a.ur, a.us, a.ut, T, cs);
         const float c = cs[0], s = cs[1], sc = cs[2], tx = cs[3], ty = cs[4];
-        int k = 0;
-        if (a.ur) {
-            const float d0 = -s * sc, d1 = -c * sc, d2 = -s * sc * tx - c * sc * ty;
-            const float d3 = c * sc, d4 = -s * sc, d5 = c * sc * tx - s * sc * ty;
-            g4s[k++] = gT[0] * d0 + gT[1] * d1 + gT[2] * d2 + gT[3] * d3 + gT[4] * d4 + gT[5] * d5;
-        }
-        if (a.us) g4s[k++] = gT[0] * c + gT[1] * (-s) + gT[2] * (c * tx - s * ty) + gT[3] * s + gT[4] * c + gT[5] * (s * tx + c * ty);
-        if (a.ut) {
-            g4s[k] = gT[2] * (c * sc) + gT[5] * (s * sc);
-            g4s[k + 1] = gT[2] * (-s * sc) + gT[5] * (c * sc);
-        }
+        cg::affine_param_grad(c, s, sc, tx, ty, gT, a.ur, a.us, a.ut, g4s);
         for (int q = 0; q < a.P; ++q) a.g4[(size_t)smp * a.P + q] = g4s[q];
     }
     __syncthreads();
-    // Linear(64 -> P) backward + LeakyReLU backward: g3[k] = lrelu'(a3[k]) * sum_p w4[p][k] g4[p]
-    if (tid < LH) {
-        float s = 0.f;
-        for (int q = 0; q < a.P; ++q) s += w.w4[q * LH + tid] * g4s[q];
-        const float h = a.h3buf[(size_t)smp * LH + tid];
-        const float v = cg::dact(2, h, s, sl);
-        g3s[tid] = v;
-        a.g3[(size_t)smp * LH + tid] = v;
-    }
+    linear2_backward(w.w4, g4s, a.P, a.h3buf + (size_t)smp * LH, sl, g3s, a.g3 + (size_t)smp * LH);
     __syncthreads();
     // Linear(K3 -> 64) backward: gh2[i] = sum_o w3[o][i] g3[o]   (consecutive lanes, consecutive i: coalesced rows)
     for (int i0 = tid; i0 < K3; i0 += 4 * NT) {            // up to four columns per thread, 16 rows at a time: 64 loads in flight
@@ -370,15 +405,7 @@ __global__ __launch_bounds__(NT) void locnet_bwd_k(LocBwd a) {
         for (int j = 0; j < 4; ++j) if (i0 + NT * j < K3) gh2[i0 + NT * j] = s4[j];
     }
     __syncthreads();
-    // AvgPool backward (x 0.25) + LeakyReLU backward at conv 2's output
-    for (int i = tid; i < S2 * LC; i += NT) {
-        const int c = i % LC, pix = i / LC, y = pix / S, x = pix % S;
-        const float gv = gh2[c * Sh * Sh + (y >> 1) * Sh + (x >> 1)] * 0.25f;
-        const float m = a.m2buf[((size_t)smp * S2 + pix) * LC + c];
-        const float v = cg::dact(2, m, gv, sl);
-        ga2[pix * (LC + 1) + c] = v;
-        a.ga2[((size_t)smp * S2 + pix) * LC + c] = v;
-    }
+    pool_backward<NT>(gh2, a.m2buf + (size_t)smp * S2 * LC, S, sl, ga2, Rows{LC + 1}, a.ga2 + (size_t)smp * S2 * LC);
     __syncthreads();
     // conv 2 data gradient, then LeakyReLU backward at conv 1's output (in place)
     conv3x3_lds(ga2, LC + 1, LC, w2l, LC, zero, S, LC, ga1, LC + 1, part);
@@ -393,16 +420,20 @@ __global__ __launch_bounds__(NT) void locnet_bwd_k(LocBwd a) {
     __syncthreads();
     // conv 1 data gradient (output planes = the layer's input planes, padded to a multiple of 4)
     conv3x3_lds(ga1, LC + 1, LC, w1l, CinQ, zero, S, CinQ, gp, CinQ + 1, part);
-    // AvgPool backward to the transformer's input resolution
-    float* gx = a.gx + (size_t)smp * (4 * S2) * Cin;
-    for (int i = tid; i < 4 * S2 * Cin; i += NT) {
-        const int c = i % Cin, xx = (i / Cin) % (2 * S), yy = i / (Cin * 2 * S);
-        gx[i] = gp[((yy >> 1) * S + (xx >> 1)) * (CinQ + 1) + c] * 0.25f;
-    }
+    unpool_input<NT>(gp, CinQ + 1, S, Cin, a.gx + (size_t)smp * (4 * S2) * Cin);
 }
 
+// A launch with `lds` bytes of dynamic LDS: beyond the default 64 KB the kernel K is granted its size first, once per size reached
+template <auto K, typename A>
+int launch(hipStream_t st, int nblk, int nthreads, size_t lds, const A& a) {
+    static size_t granted = 64 * 1024;
+    if (lds > granted) { CG_HIP(hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); granted = lds; }
+    hipLaunchKernelGGL(K, dim3(nblk), dim3(nthreads), lds, st, a);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
 
-// ================================================================================================ round 4: the same chain on the MFMA
+// ================================================================================================ the MFMA kernels: the same chain as implicit GEMMs
 // The kernels above keep one sample's maps AND kernels in ~100 KB of LDS (one workgroup of 768 threads per CU, the 384 samples of
 // the three branch transformers in 1.5 rounds) and run the two convolutions at VALU + LDS-read rates with the nine taps split over
 // threads whose partial sums meet in LDS: 114 us forward / 116-166 us backward for the three-branch launch at batch 128, ~0.01 of any
@@ -418,7 +449,7 @@ __global__ __launch_bounds__(NT) void locnet_bwd_k(LocBwd a) {
 //     sample (global load -> pool -> conv -> conv -> pool -> 2 linear layers -> grid) hide under the others';
 //   * the 16 K3 x 64 linear layer streams its rows as 16-byte loads, 4-8 rows in flight per wave, against register-held input.
 // Buffers, layouts and entry points are unchanged (the weight gradients stay on the GEMM path); sums re-associate within fp32
-// (K-steps of 4 input planes accumulate in tap order).  The round-3 VALU kernels remain the fallback for the geometries v2::has() does not list.
+// (K-steps of 4 input planes accumulate in tap order).  The VALU kernels remain the fallback for the geometries v2::has() does not list.
 namespace v2 {
 
 constexpr int NW = 4, NT2 = 64 * NW;
@@ -449,8 +480,6 @@ template <int S_, int CIN_> struct Cfg {
     static_assert((NP * CP1) % 4 == 0 && (NP * CP2) % 4 == 0 && (S2 * (LC + 1)) % 4 == 0, "16-byte sections");
 };
 
-__device__ __forceinline__ int pp(int pix, int S, int SP) { return ((pix / S) + 1) * SP + (pix % S) + 1; }   // S: compile-time power of two
-
 // acc[m] += A_m (16 pixels x 4 planes) * B (4 planes x 16) over 9 taps x NCH K-steps.  in: zero-haloed LDS image, pixel stride CP;
 // ab[m]: this lane's element of tile m at tap (0,0), plane kq (+ the wave's plane offset); b: this lane's B elements, [tap][K-step].
 template <int NMT, int NCH, int CP, int SP>
@@ -465,6 +494,28 @@ __device__ __forceinline__ void conv_mfma(const float* in, const int (&ab)[NMT],
                 acc[m] = __builtin_amdgcn_mfma_f32_16x16x4f32(in[ab[m] + toff + 4 * j], b[t * NCH + j], acc[m], 0, 0, 0);
         }
     }
+}
+
+// The scaffold around conv_mfma.  A wave runs the NMT tiles first .. first + NMT - 1 of 16 pixels: first = wv * NMT where the M tiles go
+// over the waves, 0 where every wave runs all tiles (on its own planes).  tiles_begin zeroes acc[m] and sets ab[m] (koff: the lane's
+// plane); tiles_each hands every acc[m][r] to f(pix, n, value): rows 4 kq .. 4 kq + 3 of the tile, column n.  The forward kernel walks
+// its tiles with tiles_each; the backward kernel writes the two loops out, because with lambdas in that kernel the compiler contracts
+// the matrix backward's sums otherwise (the note at the head of the shared stages).
+template <int S, int CP, int NMT>
+__device__ __forceinline__ void tiles_begin(int first, int n, int koff, int (&ab)[NMT], f4 (&acc)[NMT]) {
+#pragma unroll
+    for (int m = 0; m < NMT; ++m) {
+        acc[m] = (f4){0.f, 0.f, 0.f, 0.f};
+        ab[m] = pp((first + m) * 16 + n, S, S + 2) * CP + koff;
+    }
+}
+template <int NMT, typename F>
+__device__ __forceinline__ void tiles_each(int first, int lane, const f4 (&acc)[NMT], F f) {
+    const int n = lane & 15, kq = lane >> 4;
+#pragma unroll
+    for (int m = 0; m < NMT; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) f((first + m) * 16 + kq * 4 + r, n, acc[m][r]);
 }
 
 // B fragments of a 16 -> 16 convolution from a packed copy w[(tap*16 + k)][16]: lane (n = l & 15, kq = l >> 4) takes w[(t*16 + 4j + kq)][n]
@@ -530,13 +581,7 @@ __global__ __launch_bounds__(NT2) void locnet_fwd2_k(LocFwd a) {
                 reinterpret_cast<float4*>(pb)[i] = v;
             }
         } else {
-            for (int i = tid; i < S2 * CIN; i += NT2) {
-                const int c = i % CIN, pix = i / CIN, px = pix % S, py = pix / S;
-                const size_t b = ((size_t)(2 * py) * (2 * S) + 2 * px) * CIN + c;
-                const float v = (xs[b] + xs[b + CIN] + xs[b + (size_t)2 * S * CIN] + xs[b + (size_t)2 * S * CIN + CIN]) * 0.25f;
-                pP[pp(pix, S, SP) * C::CP1 + c] = v;
-                pb[i] = v;
-            }
+            pool_input<NT2>(xs, S, CIN, pP, Haloed<S, C::CP1>(), pb);
         }
     }
     __syncthreads();
@@ -544,19 +589,12 @@ __global__ __launch_bounds__(NT2) void locnet_fwd2_k(LocFwd a) {
     {
         f4 acc[C::NMT1];
         int ab[C::NMT1];
-#pragma unroll
-        for (int m = 0; m < C::NMT1; ++m) {
-            acc[m] = (f4){0.f, 0.f, 0.f, 0.f};
-            const int mt = C::KSPLIT ? m : wv * C::NMT1 + m;
-            ab[m] = pp(mt * 16 + n, S, SP) * C::CP1 + kq + (C::KSPLIT ? (C::CK1 / NW) * wv : 0);
-        }
+        const int first = C::KSPLIT ? 0 : wv * C::NMT1;
+        tiles_begin<S, C::CP1>(first, n, kq + (C::KSPLIT ? (C::CK1 / NW) * wv : 0), ab, acc);
         conv_mfma<C::NMT1, C::NCH1, C::CP1, SP>(pP, ab, b1, acc);
         if (C::KSPLIT) {
             __syncthreads();   // every wave has read its planes of the input image: the partials go on top of it
-#pragma unroll
-            for (int m = 0; m < C::NMT1; ++m)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) red[(wv * S2 + m * 16 + kq * 4 + r) * C::RS + n] = acc[m][r];
+            tiles_each(first, lane, acc, [&](int pix, int n, float v) { red[(wv * S2 + pix) * C::RS + n] = v; });
             __syncthreads();
             for (int e = tid; e < S2 * LC; e += NT2) {
                 const int c = e & (LC - 1), pix = e >> 4;
@@ -569,15 +607,11 @@ __global__ __launch_bounds__(NT2) void locnet_fwd2_k(LocFwd a) {
             }
         } else {
             const float bias = w.b1[n];
-#pragma unroll
-            for (int m = 0; m < C::NMT1; ++m)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int pix = (wv * C::NMT1 + m) * 16 + kq * 4 + r;
-                    const float v = cg::act(2, acc[m][r] + bias, sl);
-                    h1P[pp(pix, S, SP) * C::CP2 + n] = v;
-                    a.h1buf[((size_t)smp * S2 + pix) * LC + n] = v;
-                }
+            tiles_each(first, lane, acc, [&](int pix, int n, float s) {
+                const float v = cg::act(2, s + bias, sl);
+                h1P[pp(pix, S, SP) * C::CP2 + n] = v;
+                a.h1buf[((size_t)smp * S2 + pix) * LC + n] = v;
+            });
         }
     }
     __syncthreads();
@@ -585,32 +619,18 @@ __global__ __launch_bounds__(NT2) void locnet_fwd2_k(LocFwd a) {
     if (C::W2 == NW || wv < C::W2) {
         f4 acc[C::NMT2];
         int ab[C::NMT2];
-#pragma unroll
-        for (int m = 0; m < C::NMT2; ++m) {
-            acc[m] = (f4){0.f, 0.f, 0.f, 0.f};
-            ab[m] = pp((wv * C::NMT2 + m) * 16 + n, S, SP) * C::CP2 + kq;
-        }
+        tiles_begin<S, C::CP2>(wv * C::NMT2, n, kq, ab, acc);
         conv_mfma<C::NMT2, 4, C::CP2, SP>(h1P, ab, b2, acc);
         const float bias = w.b2[n];
-#pragma unroll
-        for (int m = 0; m < C::NMT2; ++m)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int pix = (wv * C::NMT2 + m) * 16 + kq * 4 + r;
-                const float v = cg::act(2, acc[m][r] + bias, sl);
-                m2[pix * (LC + 1) + n] = v;
-                a.m2buf[((size_t)smp * S2 + pix) * LC + n] = v;
-            }
+        tiles_each(wv * C::NMT2, lane, acc, [&](int pix, int n, float s) {
+            const float v = cg::act(2, s + bias, sl);
+            m2[pix * (LC + 1) + n] = v;
+            a.m2buf[((size_t)smp * S2 + pix) * LC + n] = v;
+        });
     }
     __syncthreads();
-    // (5) AvgPool(2); i = (c, py, px): nn.View(16*h*h) flattens the NCHW map
-    for (int i = tid; i < C::K3; i += NT2) {
-        const int px = i % C::Sh, py = (i / C::Sh) % C::Sh, c = i / (C::Sh * C::Sh);
-        const float* q = m2 + ((2 * py) * S + 2 * px) * (LC + 1) + c;
-        const float pv = (q[0] + q[LC + 1] + q[S * (LC + 1)] + q[(S + 1) * (LC + 1)]) * 0.25f;
-        h2[i] = pv;
-        a.h2buf[(size_t)smp * C::K3 + i] = pv;
-    }
+    // (5) AvgPool(2) and nn.View
+    pool_flatten<NT2>(m2, S, h2, a.h2buf + (size_t)smp * C::K3);
     __syncthreads();
     // (6) Linear(K3 -> 64) + LeakyReLU: a wave takes 16 outputs, RB rows at a time; lane l holds input elements 4l + 256j .. +3 and
     // reads the same columns of every row as 16-byte loads (a row = K3 / 256 coalesced 1 KB requests per wave)
@@ -670,17 +690,8 @@ __global__ __launch_bounds__(NT2) void locnet_fwd2_k(LocFwd a) {
         }
     }
     __syncthreads();
-    // (8) AffineTransformMatrixGenerator + AffineGridGeneratorBHWD
-    float T[6];
-    affine_T(prm, a.ur, a.us, a.ut, T);
-    const int H = a.Hg, W = a.Wg;
-    float2* gr = reinterpret_cast<float2*>(a.grid + (size_t)smp * H * W * 2);
-    for (int i = tid; i < H * W; i += NT2) {
-        const int ii = i / W, j = i - ii * W;
-        const float y = H > 1 ? -1.f + 2.f * (float)ii / (float)(H - 1) : -1.f;
-        const float x = W > 1 ? -1.f + 2.f * (float)j / (float)(W - 1) : -1.f;
-        gr[i] = make_float2(T[0] * y + T[1] * x + T[2], T[3] * y + T[4] * x + T[5]);
-    }
+    // (8) the grid
+    grid_write<NT2, 2>(prm, a.ur, a.us, a.ut, a.Hg, a.Wg, a.grid + (size_t)smp * a.Hg * a.Wg * 2);
 }
 
 template <int S, int CIN>
@@ -689,7 +700,6 @@ __global__ __launch_bounds__(NT2) void locnet_bwd2_k(LocBwd a) {
     using C = Cfg<S, CIN>;
     extern __shared__ float sm[];
     __shared__ double shd[6][NW];
-    __shared__ float gTs[6];
     float *ga2P = sm + C::B_GA2, *ga1P = sm + C::B_GA1, *gp = sm + C::B_GP, *gh2 = sm + C::B_GH2, *g3s = sm + C::B_G3, *g4s = sm + C::B_G4;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, n = lane & 15, kq = lane >> 4;
     const int smp = blockIdx.x, g = smp / a.N;
@@ -711,56 +721,21 @@ __global__ __launch_bounds__(NT2) void locnet_bwd2_k(LocBwd a) {
         float4* z = reinterpret_cast<float4*>(sm);
         for (int i = tid; i < C::B_GP / 4; i += NT2) z[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    // (1) affine_grid_backward: gT[r][:] = sum_{i,j} ggrid[i,j,r] * (y_i, x_j, 1)   (fp64 block sums, fixed order)
-    const int H = a.Hg, W = a.Wg;
-    {
-        const float2* gg = reinterpret_cast<const float2*>(a.ggrid + (size_t)smp * H * W * 2);
-        double acc[6] = {0, 0, 0, 0, 0, 0};
-        for (int i = tid; i < H * W; i += NT2) {
-            const int ii = i / W, j = i - ii * W;
-            const float y = H > 1 ? -1.f + 2.f * (float)ii / (float)(H - 1) : -1.f;
-            const float x = W > 1 ? -1.f + 2.f * (float)j / (float)(W - 1) : -1.f;
-            const float2 gv = gg[i];
-            acc[0] += gv.x * y; acc[1] += gv.x * x; acc[2] += gv.x;
-            acc[3] += gv.y * y; acc[4] += gv.y * x; acc[5] += gv.y;
-        }
-        for (int k = 0; k < 6; ++k) {
-            const double t = cg::wave_sum(acc[k]);
-            if (lane == 0) shd[k][wv] = t;
-        }
-    }
+    // (1) - (3) grid gradient sums, affine_matrix_backward on one lane, Linear(64 -> P) backward + LeakyReLU backward
+    grid_grad_sums<NT2, 2>(a.ggrid + (size_t)smp * a.Hg * a.Wg * 2, a.Hg, a.Wg, shd);
     __syncthreads();
-    // (2) affine_matrix_backward (cg_affine_matrix_backward's formulas), one lane
     if (tid == 0) {
         float gT[6];
-        for (int k = 0; k < 6; ++k) { double t = 0.0; for (int q = 0; q < NW; ++q) t += shd[k][q]; gT[k] = (float)t; gTs[k] = gT[k]; }
+        for (int k = 0; k < 6; ++k) { double t = 0.0; for (int q = 0; q < NW; ++q) t += shd[k][q]; gT[k] = (float)t; }
         const float* prm = a.params + (size_t)smp * a.P;
         float T[6], cs[5];
-        affine_T(prm, a.ur, a.us, a.ut, T, cs);
+        cg::affine_T(prm, a.ur, a.us, a.ut, T, cs);
         const float c = cs[0], s = cs[1], sc = cs[2], tx = cs[3], ty = cs[4];
-        int k = 0;
-        if (a.ur) {
-            const float d0 = -s * sc, d1 = -c * sc, d2 = -s * sc * tx - c * sc * ty;
-            const float d3 = c * sc, d4 = -s * sc, d5 = c * sc * tx - s * sc * ty;
-            g4s[k++] = gT[0] * d0 + gT[1] * d1 + gT[2] * d2 + gT[3] * d3 + gT[4] * d4 + gT[5] * d5;
-        }
-        if (a.us) g4s[k++] = gT[0] * c + gT[1] * (-s) + gT[2] * (c * tx - s * ty) + gT[3] * s + gT[4] * c + gT[5] * (s * tx + c * ty);
-        if (a.ut) {
-            g4s[k] = gT[2] * (c * sc) + gT[5] * (s * sc);
-            g4s[k + 1] = gT[2] * (-s * sc) + gT[5] * (c * sc);
-        }
+        cg::affine_param_grad(c, s, sc, tx, ty, gT, a.ur, a.us, a.ut, g4s);
         for (int q = 0; q < a.P; ++q) a.g4[(size_t)smp * a.P + q] = g4s[q];
     }
     __syncthreads();
-    // (3) Linear(64 -> P) backward + LeakyReLU backward
-    if (tid < LH) {
-        float s = 0.f;
-        for (int q = 0; q < a.P; ++q) s += w.w4[q * LH + tid] * g4s[q];
-        const float h = a.h3buf[(size_t)smp * LH + tid];
-        const float v = cg::dact(2, h, s, sl);
-        g3s[tid] = v;
-        a.g3[(size_t)smp * LH + tid] = v;
-    }
+    linear2_backward(w.w4, g4s, a.P, a.h3buf + (size_t)smp * LH, sl, g3s, a.g3 + (size_t)smp * LH);
     __syncthreads();
     // (4) Linear(K3 -> 64) backward: gh2[i] = sum_o w3[o][i] g3[o]; a thread owns K3 / 256 consecutive columns (one 16-byte or 4-byte
     // load per row), 16 rows in flight, rows added in order
@@ -800,24 +775,13 @@ __global__ __launch_bounds__(NT2) void locnet_bwd2_k(LocBwd a) {
     }
     __syncthreads();
     // (5) AvgPool backward (x 0.25) + LeakyReLU backward at conv 2's output -> ga2 (haloed image + global, for the weight gradient)
-    for (int i = tid; i < S2 * LC; i += NT2) {
-        const int c = i & (LC - 1), pix = i >> 4, y = pix / S, x = pix % S;
-        const float gv = gh2[c * Sh * Sh + (y >> 1) * Sh + (x >> 1)] * 0.25f;
-        const float m = a.m2buf[((size_t)smp * S2 + pix) * LC + c];
-        const float v = cg::dact(2, m, gv, sl);
-        ga2P[pp(pix, S, SP) * C::CP2 + c] = v;
-        a.ga2[((size_t)smp * S2 + pix) * LC + c] = v;
-    }
+    pool_backward<NT2>(gh2, a.m2buf + (size_t)smp * S2 * LC, S, sl, ga2P, Haloed<S, C::CP2>(), a.ga2 + (size_t)smp * S2 * LC);
     __syncthreads();
     // (6) conv 2 data gradient, LeakyReLU backward at conv 1's output -> ga1
     if (C::W2 == NW || wv < C::W2) {
         f4 acc[C::NMT2];
         int ab[C::NMT2];
-#pragma unroll
-        for (int m = 0; m < C::NMT2; ++m) {
-            acc[m] = (f4){0.f, 0.f, 0.f, 0.f};
-            ab[m] = pp((wv * C::NMT2 + m) * 16 + n, S, SP) * C::CP2 + kq;
-        }
+        tiles_begin<S, C::CP2>(wv * C::NMT2, n, kq, ab, acc);
         conv_mfma<C::NMT2, 4, C::CP2, SP>(ga2P, ab, b2, acc);
 #pragma unroll
         for (int m = 0; m < C::NMT2; ++m)
@@ -836,48 +800,24 @@ __global__ __launch_bounds__(NT2) void locnet_bwd2_k(LocBwd a) {
         constexpr int NMT = C::NSPLIT ? C::MT : C::MT / NW;
         f4 acc[NMT];
         int ab[NMT];
-#pragma unroll
-        for (int m = 0; m < NMT; ++m) {
-            acc[m] = (f4){0.f, 0.f, 0.f, 0.f};
-            const int mt = C::NSPLIT ? m : wv * NMT + m;
-            ab[m] = pp(mt * 16 + n, S, SP) * C::CP2 + kq;
-        }
+        const int first = C::NSPLIT ? 0 : wv * NMT;
+        tiles_begin<S, C::CP2>(first, n, kq, ab, acc);
         conv_mfma<NMT, 4, C::CP2, SP>(ga1P, ab, b1, acc);
         const int nb = C::NSPLIT ? 16 * wv + n : n;
 #pragma unroll
         for (int m = 0; m < NMT; ++m)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int pix = (C::NSPLIT ? m : wv * NMT + m) * 16 + kq * 4 + r;
+                const int pix = (first + m) * 16 + kq * 4 + r;
                 if (nb < CQ) gp[pix * (CQ + 1) + nb] = acc[m][r];
             }
     }
     __syncthreads();
     // (8) AvgPool backward to the transformer's input resolution
-    float* gx = a.gx + (size_t)smp * (4 * S2) * CIN;
-    for (int i = tid; i < 4 * S2 * CIN; i += NT2) {
-        const int c = i % CIN, xx = (i / CIN) % (2 * S), yy = i / (CIN * 2 * S);
-        gx[i] = gp[((yy >> 1) * S + (xx >> 1)) * (CQ + 1) + c] * 0.25f;
-    }
+    unpool_input<NT2>(gp, CQ + 1, S, CIN, a.gx + (size_t)smp * (4 * S2) * CIN);
 }
 
-template <int S, int CIN> int launch_fwd(hipStream_t st, const LocFwd& a, int nblk) {
-    using C = Cfg<S, CIN>;
-    constexpr size_t lds = (size_t)C::F_TOT * 4;
-    static bool granted = false;
-    if (lds > 64 * 1024 && !granted) { CG_HIP(hipFuncSetAttribute((const void*)locnet_fwd2_k<S, CIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); granted = true; }
-    hipLaunchKernelGGL((locnet_fwd2_k<S, CIN>), dim3(nblk), dim3(NT2), lds, st, a);
-    return 0;
-}
-template <int S, int CIN> int launch_bwd(hipStream_t st, const LocBwd& a, int nblk) {
-    using C = Cfg<S, CIN>;
-    constexpr size_t lds = (size_t)C::B_TOT * 4;
-    static bool granted = false;
-    if (lds > 64 * 1024 && !granted) { CG_HIP(hipFuncSetAttribute((const void*)locnet_bwd2_k<S, CIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); granted = true; }
-    hipLaunchKernelGGL((locnet_bwd2_k<S, CIN>), dim3(nblk), dim3(NT2), lds, st, a);
-    return 0;
-}
-// (16, 64) - the branch transformers of D32_st3 at 64x64 (config #5) - was parity-clean in round 4 but is NOT instantiated: it needs
+// (16, 64) - the branch transformers of D32_st3 at 64x64 (config #5) - was parity-clean when these kernels were written but is NOT instantiated: it needs
 // 131 / 118 KB of LDS and 260 VGPRs, i.e. one workgroup per CU for 192 samples, and the ten separate (grouped) launches it would
 // replace are faster: config #5 12.67 ms per step without, 12.81 with (profiles/r04_sweeps.txt).
 // (4, 64) - the branch transformers of D32_st3 at 16x16 - is one M tile per sample: conv 1 (K over the waves) and conv 1's data gradient
@@ -886,13 +826,10 @@ template <int S, int CIN> int launch_bwd(hipStream_t st, const LocBwd& a, int nb
 // samples per workgroup would leave a partial workgroup to guard in every phase.  14 / 10 KB of LDS, 102 / 142 VGPRs: four / three samples
 // share a CU, the 384 workgroups of the three branches at batch 128 are one round (profiles/scale16_locnet.txt).
 inline bool has(int S, int Cin) { return (S == 16 && Cin == 3) || (S == 8 && Cin == 64) || (S == 4 && Cin == 64); }
-inline int fwd(hipStream_t st, const LocFwd& a, int nb) {
-    return a.S == 4 ? launch_fwd<4, 64>(st, a, nb) : a.S == 8 ? launch_fwd<8, 64>(st, a, nb) : launch_fwd<16, 3>(st, a, nb);
-}
-inline int bwd(hipStream_t st, const LocBwd& a, int nb) {
-    return a.S == 4 ? launch_bwd<4, 64>(st, a, nb) : a.S == 8 ? launch_bwd<8, 64>(st, a, nb) : launch_bwd<16, 3>(st, a, nb);
-}
-inline bool enabled() { return true; }
+template <int S, int CIN> int fwd_at(hipStream_t st, const LocFwd& a, int nb) { return launch<locnet_fwd2_k<S, CIN>>(st, nb, NT2, (size_t)Cfg<S, CIN>::F_TOT * 4, a); }
+template <int S, int CIN> int bwd_at(hipStream_t st, const LocBwd& a, int nb) { return launch<locnet_bwd2_k<S, CIN>>(st, nb, NT2, (size_t)Cfg<S, CIN>::B_TOT * 4, a); }
+inline int fwd(hipStream_t st, const LocFwd& a, int nb) { return a.S == 4 ? fwd_at<4, 64>(st, a, nb) : a.S == 8 ? fwd_at<8, 64>(st, a, nb) : fwd_at<16, 3>(st, a, nb); }
+inline int bwd(hipStream_t st, const LocBwd& a, int nb) { return a.S == 4 ? bwd_at<4, 64>(st, a, nb) : a.S == 8 ? bwd_at<8, 64>(st, a, nb) : bwd_at<16, 3>(st, a, nb); }
 
 }  // namespace v2
 
@@ -907,75 +844,54 @@ extern "C" {
 // power-of-two pooled size S >= 8 (so that a wave shares its quad of output planes) with the activations of one sample within LDS.
 int cg_locnet_supported(int S, int Cin, int P) {
     if (S < 4 || (S & (S - 1)) || Cin < 1 || P < 1 || P > 4) return 0;
-    if (v2::enabled() && v2::has(S, Cin)) return 1;     // the MFMA kernels bring their own (smaller) LDS plan
+    if (v2::has(S, Cin)) return 1;     // the MFMA kernels bring their own (smaller) LDS plan
     if (S < 8) return 0;
     const size_t lim = 160 * 1024 - 1024;   // the kernels' few static __shared__ words come out of the same 160 KB
     return fwd_lds_floats(S, Cin) * 4 <= lim && bwd_lds_floats(S, Cin) * 4 <= lim ? 1 : 0;
+}
+
+// The checks and the fill of what both launches share; fn: the entry point's name, backward: it takes a positive slope only
+static int loc_geo(const char* fn, bool backward, LocGeo& a, int ngroups, int n_per_group, const float* const* weights, int S, int Cin, int P, int use_rot,
+                   int use_scale, int use_trans, float slope, int Hg, int Wg) {
+    CG_REQUIRE(ngroups >= 1 && ngroups <= 4 && n_per_group > 0, "%s: %d groups of %d samples", fn, ngroups, n_per_group);
+    CG_REQUIRE(cg_locnet_supported(S, Cin, P), "%s: S %d Cin %d P %d not supported", fn, S, Cin, P);
+    CG_REQUIRE(P == (use_rot ? 1 : 0) + (use_scale ? 1 : 0) + (use_trans ? 2 : 0), "%s: P does not match the transform", fn);
+    // the backward kernels decide LeakyReLU's side on the stored activations h1, m2, h3; only a positive slope keeps the sign of the layer's input
+    CG_REQUIRE(!backward || slope > 0.f, "%s: slope %g: the backward takes slope > 0 (use the modules)", fn, (double)slope);
+    for (int g = 0; g < ngroups; ++g) {
+        const float* const* w = weights + 12 * g;
+        for (int k = 0; k < 12; ++k) CG_REQUIRE(w[k], "%s: null weight pointer", fn);
+        a.g[g] = LocW{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11]};
+    }
+    a.G = ngroups; a.N = n_per_group; a.S = S; a.Cin = Cin; a.P = P; a.Hg = Hg; a.Wg = Wg;
+    a.ur = use_rot ? 1 : 0; a.us = use_scale ? 1 : 0; a.ut = use_trans ? 1 : 0; a.slope = slope;
+    return 0;
 }
 
 int cg_locnet_forward(void* stream, int ngroups, int n_per_group, const float* x, int x_shared, const float* const* weights, int S, int Cin,
                       int P, int use_rot, int use_scale, int use_trans, float slope, int Hg, int Wg, float* pooled, float* h1, float* m2,
                       float* h2, float* h3, float* params, float* grid) {
     CG_REQUIRE(x && weights && pooled && h1 && m2 && h2 && h3 && params && grid, "cg_locnet_forward: null pointer");
-    CG_REQUIRE(ngroups >= 1 && ngroups <= 4 && n_per_group > 0, "cg_locnet_forward: %d groups of %d samples", ngroups, n_per_group);
-    CG_REQUIRE(cg_locnet_supported(S, Cin, P), "cg_locnet_forward: S %d Cin %d P %d not supported", S, Cin, P);
-    CG_REQUIRE(P == (use_rot ? 1 : 0) + (use_scale ? 1 : 0) + (use_trans ? 2 : 0), "cg_locnet_forward: P does not match the transform");
     LocFwd a;
-    for (int g = 0; g < ngroups; ++g) {
-        const float* const* w = weights + 12 * g;
-        for (int k = 0; k < 12; ++k) CG_REQUIRE(w[k], "cg_locnet_forward: null weight pointer");
-        a.g[g] = LocW{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11]};
-    }
-    a.x = x; a.x_shared = x_shared; a.G = ngroups; a.N = n_per_group; a.S = S; a.Cin = Cin; a.P = P; a.Hg = Hg; a.Wg = Wg;
-    a.ur = use_rot ? 1 : 0; a.us = use_scale ? 1 : 0; a.ut = use_trans ? 1 : 0; a.slope = slope;
+    if (const int rc = loc_geo("cg_locnet_forward", false, a, ngroups, n_per_group, weights, S, Cin, P, use_rot, use_scale, use_trans, slope, Hg, Wg)) return rc;
+    a.x = x; a.x_shared = x_shared;
     a.pbuf = pooled; a.h1buf = h1; a.m2buf = m2; a.h2buf = h2; a.h3buf = h3; a.params = params; a.grid = grid;
-    if (v2::enabled() && v2::has(S, Cin)) {   // the MFMA kernels (round 4)
-        const int nb = ngroups * n_per_group;
-        const int rc = v2::fwd(cg::S(stream), a, nb);
-        if (rc) return rc;
-        CG_LAUNCH_CHECK();
-        return 0;
-    }
-    const size_t lds = fwd_lds_floats(S, Cin) * 4;
-    static size_t granted = 64 * 1024;
-    if (lds > granted) { CG_HIP(hipFuncSetAttribute((const void*)locnet_fwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); granted = lds; }
-    hipLaunchKernelGGL(locnet_fwd_k, dim3(ngroups * n_per_group), dim3(NT), lds, cg::S(stream), a);
-    CG_LAUNCH_CHECK();
-    return 0;
+    const int nb = ngroups * n_per_group;
+    if (v2::has(S, Cin)) return v2::fwd(cg::S(stream), a, nb);
+    return launch<locnet_fwd_k>(cg::S(stream), nb, NT, fwd_lds_floats(S, Cin) * 4, a);
 }
 
 int cg_locnet_backward(void* stream, int ngroups, int n_per_group, const float* const* weights, int S, int Cin, int P, int use_rot,
                        int use_scale, int use_trans, float slope, int Hg, int Wg, const float* h1, const float* m2, const float* h3,
                        const float* params, const float* ggrid, float* ga1, float* ga2, float* g3, float* g4, float* gx) {
     CG_REQUIRE(weights && h1 && m2 && h3 && params && ggrid && ga1 && ga2 && g3 && g4 && gx, "cg_locnet_backward: null pointer");
-    CG_REQUIRE(ngroups >= 1 && ngroups <= 4 && n_per_group > 0, "cg_locnet_backward: %d groups of %d samples", ngroups, n_per_group);
-    CG_REQUIRE(cg_locnet_supported(S, Cin, P), "cg_locnet_backward: S %d Cin %d P %d not supported", S, Cin, P);
-    CG_REQUIRE(P == (use_rot ? 1 : 0) + (use_scale ? 1 : 0) + (use_trans ? 2 : 0), "cg_locnet_backward: P does not match the transform");
-    // the kernels decide LeakyReLU's side on the stored activations h1, m2, h3; only a positive slope keeps the sign of the layer's input
-    CG_REQUIRE(slope > 0.f, "cg_locnet_backward: slope %g: the backward takes slope > 0 (use the modules)", (double)slope);
     LocBwd a;
-    for (int g = 0; g < ngroups; ++g) {
-        const float* const* w = weights + 12 * g;
-        for (int k = 0; k < 12; ++k) CG_REQUIRE(w[k], "cg_locnet_backward: null weight pointer");
-        a.g[g] = LocW{w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7], w[8], w[9], w[10], w[11]};
-    }
-    a.G = ngroups; a.N = n_per_group; a.S = S; a.Cin = Cin; a.P = P; a.Hg = Hg; a.Wg = Wg;
-    a.ur = use_rot ? 1 : 0; a.us = use_scale ? 1 : 0; a.ut = use_trans ? 1 : 0; a.slope = slope;
+    if (const int rc = loc_geo("cg_locnet_backward", true, a, ngroups, n_per_group, weights, S, Cin, P, use_rot, use_scale, use_trans, slope, Hg, Wg)) return rc;
     a.h1buf = h1; a.m2buf = m2; a.h3buf = h3; a.params = params; a.ggrid = ggrid;
     a.ga1 = ga1; a.ga2 = ga2; a.g3 = g3; a.g4 = g4; a.gx = gx;
-    if (v2::enabled() && v2::has(S, Cin)) {
-        const int nb = ngroups * n_per_group;
-        const int rc = v2::bwd(cg::S(stream), a, nb);
-        if (rc) return rc;
-        CG_LAUNCH_CHECK();
-        return 0;
-    }
-    const size_t lds = bwd_lds_floats(S, Cin) * 4;
-    static size_t granted = 64 * 1024;
-    if (lds > granted) { CG_HIP(hipFuncSetAttribute((const void*)locnet_bwd_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); granted = lds; }
-    hipLaunchKernelGGL(locnet_bwd_k, dim3(ngroups * n_per_group), dim3(NT), lds, cg::S(stream), a);
-    CG_LAUNCH_CHECK();
-    return 0;
+    const int nb = ngroups * n_per_group;
+    if (v2::has(S, Cin)) return v2::bwd(cg::S(stream), a, nb);
+    return launch<locnet_bwd_k>(cg::S(stream), nb, NT, bwd_lds_floats(S, Cin) * 4, a);
 }
 
 }  // extern "C"

@@ -6,48 +6,17 @@ namespace {
 using cg::block_sum_256;
 using cg::Vec;
 
-// T = R(theta) * S(s) * Tr(tx,ty); rows: [c*s, -sn*s, c*s*tx - sn*s*ty], [sn*s, c*s, sn*s*tx + c*s*ty]
+// The affine arithmetic itself (T, its gradient, the grid coordinate, the grid-gradient terms) is csrc/common.h's.
 __global__ void affine_matrix_fwd_k(const float* params, float* T, int N, int ur, int us, int ut) {
     const int P = ur + us + 2 * ut;
-    CG_GRID_STRIDE(n, N) {
-        const float* p = params + (long)n * P;
-        int k = 0;
-        float th = 0.f, sc = 1.f, tx = 0.f, ty = 0.f;
-        if (ur) th = p[k++];
-        if (us) sc = p[k++];
-        if (ut) { tx = p[k]; ty = p[k + 1]; }
-        const float c = cosf(th), s = sinf(th);
-        float* t = T + (long)n * 6;
-        t[0] = c * sc;  t[1] = -s * sc; t[2] = c * sc * tx - s * sc * ty;
-        t[3] = s * sc;  t[4] = c * sc;  t[5] = s * sc * tx + c * sc * ty;
-    }
+    CG_GRID_STRIDE(n, N) cg::affine_T(params + (long)n * P, ur, us, ut, T + (long)n * 6);
 }
 __global__ void affine_matrix_bwd_k(const float* params, const float* gT, float* gparams, int N, int ur, int us, int ut) {
     const int P = ur + us + 2 * ut;
     CG_GRID_STRIDE(n, N) {
-        const float* p = params + (long)n * P;
-        int k = 0;
-        float th = 0.f, sc = 1.f, tx = 0.f, ty = 0.f;
-        if (ur) th = p[k++];
-        if (us) sc = p[k++];
-        if (ut) { tx = p[k]; ty = p[k + 1]; }
-        const float c = cosf(th), s = sinf(th);
-        const float* g = gT + (long)n * 6;
-        float* gp = gparams + (long)n * P;
-        k = 0;
-        if (ur) {
-            // d/dtheta: c -> -s, s -> c
-            const float d0 = -s * sc, d1 = -c * sc, d2 = -s * sc * tx - c * sc * ty;
-            const float d3 = c * sc, d4 = -s * sc, d5 = c * sc * tx - s * sc * ty;
-            gp[k++] = g[0] * d0 + g[1] * d1 + g[2] * d2 + g[3] * d3 + g[4] * d4 + g[5] * d5;
-        }
-        if (us) {
-            gp[k++] = g[0] * c + g[1] * (-s) + g[2] * (c * tx - s * ty) + g[3] * s + g[4] * c + g[5] * (s * tx + c * ty);
-        }
-        if (ut) {
-            gp[k] = g[2] * (c * sc) + g[5] * (s * sc);
-            gp[k + 1] = g[2] * (-s * sc) + g[5] * (c * sc);
-        }
+        float T[6], cs[5];
+        cg::affine_T(params + (long)n * P, ur, us, ut, T, cs);
+        cg::affine_param_grad(cs[0], cs[1], cs[2], cs[3], cs[4], gT + (long)n * 6, ur, us, ut, gparams + (long)n * P);
     }
 }
 __global__ void affine_grid_fwd_k(const float* T, float* grid, int N, int H, int W) {
@@ -57,8 +26,7 @@ __global__ void affine_grid_fwd_k(const float* T, float* grid, int N, int H, int
         long r = i / W;
         const int ii = (int)(r % H);
         const long n = r / H;
-        const float y = H > 1 ? -1.f + 2.f * (float)ii / (float)(H - 1) : -1.f;
-        const float x = W > 1 ? -1.f + 2.f * (float)j / (float)(W - 1) : -1.f;
+        const float y = cg::grid_coord(ii, H), x = cg::grid_coord(j, W);
         const float* t = T + n * 6;
         grid[i * 2 + 0] = t[0] * y + t[1] * x + t[2];
         grid[i * 2 + 1] = t[3] * y + t[4] * x + t[5];
@@ -72,12 +40,7 @@ __global__ __launch_bounds__(256) void affine_grid_bwd_k(const float* ggrid, flo
     const int HW = H * W;
     for (int p = threadIdx.x; p < HW; p += blockDim.x) {
         const int ii = p / W, j = p - ii * W;
-        const float y = H > 1 ? -1.f + 2.f * (float)ii / (float)(H - 1) : -1.f;
-        const float x = W > 1 ? -1.f + 2.f * (float)j / (float)(W - 1) : -1.f;
-        const float g0 = ggrid[((long)n * HW + p) * 2 + 0];
-        const float g1 = ggrid[((long)n * HW + p) * 2 + 1];
-        acc[0] += g0 * y; acc[1] += g0 * x; acc[2] += g0;
-        acc[3] += g1 * y; acc[4] += g1 * x; acc[5] += g1;
+        cg::affine_grid_acc(acc, ggrid[((long)n * HW + p) * 2 + 0], ggrid[((long)n * HW + p) * 2 + 1], cg::grid_coord(ii, H), cg::grid_coord(j, W));
     }
     for (int k = 0; k < 6; ++k) {
         const double t = block_sum_256(acc[k], sh);

@@ -64,3 +64,4 @@ def case(name, G, S, Cin, P, ur, us, ut, shared):
 
 case("first transformer  ", 1, 16, 3, 1, 1, 0, 0, False)
 case("branch transformers", 3, 8, 64, 4, 1, 1, 1, True)
+case("first at 16 px, VALU", 1, 8, 3, 4, 1, 1, 1, False)        # a shape of the fallback family (the two above run the MFMA kernels)

@@ -24,6 +24,7 @@ import torch
 
 import test_gpu_membound_edges as E
 from helpers import dev, duplicate_in_windows, edge_normal, host, options, out_like
+from test_gpu_locnet_stages import mfma_shape
 from test_gpu_membound_edges import ptrs, scalar
 
 pytestmark = pytest.mark.gpu
@@ -300,26 +301,109 @@ def test_gemm_activation_epilogue(cg, golden, act, splits):
     check(golden, f"conv epilogue act {act} / splits {splits}", y, ya)
 
 
-def test_locnet_forward(cg, golden):
-    """cg_locnet_forward at the smallest localisation shape of tests/test_gpu_parity.py (16 x 16 input of 8 planes: S = 8, all four
-    transform parameters), one group of two samples; sample 1 is all zero and every second bias of the first convolution is zero."""
+def locnet_weights(cg, rs, S, Cin, P, zero_b3):
+    """The 12 device tensors of one localisation net (the canonical eight, then cg_pack_conv_weight's copies of both convolutions);
+    every second bias of the first convolution (zero_b3: and of the first linear layer) is zero."""
     L, st = cg.lib(), cg.tensor.stream()
-    G, N, S, Cin, P = 1, 2, 8, 8, 4
-    assert L.locnet_supported(S, Cin, P) == 1
-    rs = np.random.RandomState(S)
     K3 = 16 * (S // 2) ** 2
     T = lambda *shape, sc=1.0: (rs.randn(*shape) * sc).astype(f32)
     w1, b1, w2, b2 = T(16, Cin, 3, 3, sc=0.1), T(16, sc=0.1), T(16, 16, 3, 3, sc=0.1), T(16, sc=0.1)
     w3, b3, w4, b4 = T(64, K3, sc=0.05), T(64, sc=0.1), T(P, 64, sc=0.05), T(P, sc=0.1)
     b1[::2] = 0.0
-    x = T(N, 2 * S, 2 * S, Cin)
-    x[1] = 0.0
+    if zero_b3:
+        b3[::2] = 0.0
     ts = [dev(a) for a in (w1, b1, w2, b2, w3, b3, w4, b4)]
     ts += [out_like(9 * Cin * 16), out_like(9 * 16 * Cin), out_like(9 * 256), out_like(9 * 256)]
     L.pack_conv_weight(st, p(ts[0]), p(ts[8]), p(ts[9]), 16, Cin, 3, 3)
     L.pack_conv_weight(st, p(ts[2]), p(ts[10]), p(ts[11]), 16, 16, 3, 3)
+    return ts
+
+
+def locnet_forward_outs(cg, G, N, S, Cin, flags, hw, ts, x, x_shared):
+    L, st = cg.lib(), cg.tensor.stream()
+    P, GN, K3 = flags[0] + flags[1] + 2 * flags[2], G * N, 16 * (S // 2) ** 2
     xt = dev(x)
-    sizes = (N * S * S * Cin, N * S * S * 16, N * S * S * 16, N * K3, N * 64, N * P, N * 2 * S * 2 * S * 2)
-    pooled, h1, m2, h2, h3, prm, grid = outs = [out_like(k) for k in sizes]
-    L.locnet_forward(st, G, N, p(xt), 0, ptrs(ts), S, Cin, P, 1, 1, 1, -0.333, 2 * S, 2 * S, p(pooled), p(h1), p(m2), p(h2), p(h3), p(prm), p(grid))
-    check(golden, "locnet forward S 8 Cin 8 P 4", *outs)
+    sizes = (GN * S * S * Cin, GN * S * S * 16, GN * S * S * 16, GN * K3, GN * 64, GN * P, GN * hw[0] * hw[1] * 2)
+    outs = [out_like(k) for k in sizes]
+    L.locnet_forward(st, G, N, p(xt), x_shared, ptrs(ts), S, Cin, P, *flags, -0.333, *hw, *[p(o) for o in outs])
+    return outs
+
+
+def locnet_backward_outs(cg, G, N, S, Cin, flags, hw, ts, seed):
+    """cg_locnet_backward at slope 0.25 on independent arrays with zeros planted (the backward is a pure function of its arrays, as the
+    `indep` cases of tests/test_gpu_locnet_stages.py use it): ga1, ga2, g3, g4, gx."""
+    L, st = cg.lib(), cg.tensor.stream()
+    P, GN = flags[0] + flags[1] + 2 * flags[2], G * N
+    rng = np.random.default_rng(seed)
+    h1, m2, h3 = edge_normal(rng, (GN, S, S, 16)), edge_normal(rng, (GN, S, S, 16)), edge_normal(rng, (GN, 64))
+    prm = np.concatenate(([rng.uniform(-3.0, 3.0, (GN, 1))] if flags[0] else []) + ([rng.uniform(0.5, 1.5, (GN, 1))] if flags[1] else [])
+                         + ([rng.uniform(-0.5, 0.5, (GN, 2))] if flags[2] else []), 1).astype(f32)
+    ggrid = edge_normal(rng, (GN, *hw, 2))
+    assert all((a == 0).any() for a in (h1, m2, h3, ggrid))
+    ins = [dev(a) for a in (h1, m2, h3, prm, ggrid)]
+    outs = [out_like(k) for k in (GN * S * S * 16, GN * S * S * 16, GN * 64, GN * P, GN * 4 * S * S * Cin)]
+    L.locnet_backward(st, G, N, ptrs(ts), S, Cin, P, *flags, 0.25, *hw, *[p(t) for t in ins], *[p(o) for o in outs])
+    return outs
+
+
+def test_locnet_forward(cg, golden):
+    """cg_locnet_forward at the smallest localisation shape of tests/test_gpu_parity.py (16 x 16 input of 8 planes: S = 8, all four
+    transform parameters), one group of two samples; sample 1 is all zero and every second bias of the first convolution is zero."""
+    G, N, S, Cin, P = 1, 2, 8, 8, 4
+    assert cg.lib().locnet_supported(S, Cin, P) == 1 and not mfma_shape(S, Cin)
+    rs = np.random.RandomState(S)
+    ts = locnet_weights(cg, rs, S, Cin, P, zero_b3=False)
+    x = (rs.randn(N, 2 * S, 2 * S, Cin) * 1.0).astype(f32)
+    x[1] = 0.0
+    check(golden, "locnet forward S 8 Cin 8 P 4", *locnet_forward_outs(cg, G, N, S, Cin, (1, 1, 1), (2 * S, 2 * S), ts, x, 0))
+
+
+def test_locnet_backward_valu(cg, golden):
+    """cg_locnet_backward of the VALU kernels at the forward case's shape (S 8, Cin 8, P 4, one group of two samples), slope 0.25."""
+    G, N, S, Cin, P = 1, 2, 8, 8, 4
+    assert cg.lib().locnet_supported(S, Cin, P) == 1 and not mfma_shape(S, Cin)
+    ts = locnet_weights(cg, np.random.RandomState(S + 100), S, Cin, P, zero_b3=True)
+    check(golden, "locnet backward S 8 Cin 8 P 4", *locnet_backward_outs(cg, G, N, S, Cin, (1, 1, 1), (2 * S, 2 * S), ts, seed=S))
+
+
+@pytest.mark.parametrize("S,Cin,G,shared,hw", [
+    (4, 64, 1, 0, (8, 8)),         # one M tile, the K3 = 64 paths, conv 2 on wave 0
+    (8, 64, 1, 0, (16, 16)),       # KSPLIT partials over the pooled image, NSPLIT data gradient
+    (16, 3, 2, 1, (32, 32)),       # zero-padded K step and N tile, the scalar pooling branch; two groups on one input
+    (4, 64, 1, 0, (1, 7)),         # Hg == 1: the n == 1 side of the grid coordinate
+], ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_locnet_mfma(cg, golden, S, Cin, G, shared, hw):
+    """cg_locnet_forward (slope -0.333) and cg_locnet_backward (slope 0.25) of the MFMA kernels, one case per instantiated shape: two
+    samples per group, sample 1 all zero, every second bias of conv 1 and of linear 1 zero."""
+    N, P = 2, 4
+    assert cg.lib().locnet_supported(S, Cin, P) == 1 and mfma_shape(S, Cin)
+    rs = np.random.RandomState(1000 * S + Cin + hw[0])
+    ts = [t for _ in range(G) for t in locnet_weights(cg, rs, S, Cin, P, zero_b3=True)]
+    x = rs.randn(N if shared else G * N, 2 * S, 2 * S, Cin).astype(f32)
+    x[1::2] = 0.0
+    case = f"locnet MFMA S {S} Cin {Cin} G {G} shared {shared} grid {hw[0]}x{hw[1]}"
+    check(golden, f"{case} / forward", *locnet_forward_outs(cg, G, N, S, Cin, (1, 1, 1), hw, ts, x, shared))
+    check(golden, f"{case} / backward", *locnet_backward_outs(cg, G, N, S, Cin, (1, 1, 1), hw, ts, seed=S + Cin + hw[1]))
+
+
+@pytest.mark.parametrize("flags", [(1, 1, 1), (1, 0, 0)], ids=["TTT", "TFF"])
+def test_affine_entry_points(cg, golden, flags):
+    """The four cg_affine_* entry points called directly: five samples, row 1 of the parameters all zero, on grids (5, 12) and (1, 7)
+    (H == 1: the n == 1 side of the grid coordinate)."""
+    L, st = cg.lib(), cg.tensor.stream()
+    N, P = 5, flags[0] + flags[1] + 2 * flags[2]
+    rng = np.random.default_rng(70 + P)
+    prm = np.concatenate(([rng.uniform(-3.1, 3.1, (N, 1))] if flags[0] else []) + ([rng.uniform(0.3, 2.0, (N, 1))] if flags[1] else [])
+                         + ([rng.uniform(-1.0, 1.0, (N, 2))] if flags[2] else []), 1).astype(f32)
+    prm[1] = 0.0
+    pt, T = dev(prm), out_like(N * 6)
+    L.affine_matrix_forward(st, p(pt), p(T), N, *flags)
+    res = [T]
+    for hw in ((5, 12), (1, 7)):
+        grid, gT, gp = out_like(N * hw[0] * hw[1] * 2), out_like(N * 6), out_like(N * P)
+        gg = dev(edge_normal(rng, (N, *hw, 2)))
+        L.affine_grid_forward(st, p(T), p(grid), N, *hw)
+        L.affine_grid_backward(st, p(gg), p(gT), N, *hw)
+        L.affine_matrix_backward(st, p(pt), p(gT), p(gp), N, *flags)
+        res += [grid, gT, gp]
+    check(golden, f"affine entry points flags {flags}", *res)
