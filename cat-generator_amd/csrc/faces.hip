@@ -450,6 +450,71 @@ struct Side2 {
     int H, W;
 };
 
+// What the three entry points do alike around their own horizontal pass.  plan() brings the descriptors back, checks them and fills the
+// workspace's head; upload() checks the workspace's size, puts the head in place and, where crops take part, enqueues them; vpass()
+// enqueues the vertical pass.  The entry point says, in the order of the fields: per_face, the items of a face in tmp and dst; crops,
+// whether the padded crops take part; padded, whether every face has a pad of its own, pads [N] on the device - then the bands, the
+// ksizes and the tap tables belong to the padded sides, which pgeom holds - or all have pad_all.
+// workspace: band_start [N + 1] int32 | with crops, Crops' maps: cblk_start [N + 1], the two median launches' line_start [N + 1] and
+//            line_face [N] int32, crop_off [N] uint64 | tmp_off [N] uint64 | with padded, pgeom [N][8] int32, geom with the padded sides in
+//            place of the rectangle's | with crops, the padded crops | tmp bytes
+struct Job {
+    const char* who;
+    hipStream_t s;
+    const unsigned char* src; const uint64_t* src_off; const int32_t* geom; const float* inv; const int32_t* taps; const uint64_t* tap_off;
+    unsigned char* dst; int N, out; void* workspace; size_t workspace_bytes;
+    int per_face; bool crops, padded; const int32_t* pads; int pad_all;
+    Faces h;
+    Crops c;
+    Bands b;
+    size_t off_band = 0, off_tmpoff = 0, off_pgeom = 0, off_crops = 0, off_tmp = 0;
+    std::vector<unsigned char> head;
+    unsigned char* ws = nullptr;   // the workspace once the head is in place
+    int bpf = 0;                   // blocks per item of the vertical pass
+    const int32_t* di32(size_t off) const { return reinterpret_cast<const int32_t*>(ws + off); }
+    const uint64_t* du64(size_t off) const { return reinterpret_cast<const uint64_t*>(ws + off); }
+    int plan(size_t src_bytes, size_t ntaps) {
+        if (int rc = h.read(who, s, src, src_bytes, src_off, geom, inv, taps, ntaps, tap_off, dst, N, out, workspace, pads, padded)) return rc;
+        Layout lay;
+        off_band = lay.take((size_t)(N + 1) * 4);
+        if (crops) c.reserve(lay, N);
+        off_tmpoff = lay.take((size_t)N * 8);
+        if (padded) off_pgeom = lay.take((size_t)N * kGeom * 4);
+        off_crops = lay.bytes;
+        head.assign(off_crops, 0);
+        const int32_t* sides = h.geom.data();   // whose (H, W) go into the horizontal pass
+        if (padded) {
+            int32_t* pgeom = reinterpret_cast<int32_t*>(head.data() + off_pgeom);
+            for (int f = 0; f < N; ++f) {
+                std::copy_n(h.geom.data() + (size_t)f * kGeom, kGeom, pgeom + (size_t)f * kGeom);
+                pgeom[(size_t)f * kGeom + 4] += 2 * h.pads[f], pgeom[(size_t)f * kGeom + 5] += 2 * h.pads[f];
+            }
+            sides = pgeom;
+        }
+        b.plan(reinterpret_cast<int32_t*>(head.data() + off_band), reinterpret_cast<uint64_t*>(head.data() + off_tmpoff), N,
+               (uint64_t)per_face * out * 3, [&](int f) { return Side2{sides[(size_t)f * kGeom + 4], sides[(size_t)f * kGeom + 5]}; });
+        if (crops) c.plan(head.data(), h.geom.data(), N, [&](int f) { return padded ? h.pads[f] : pad_all; });
+        bpf = cdiv((long)out * out * 3, 256);
+        off_tmp = off_crops + c.bytes;
+        return 0;
+    }
+    bool fits_one_launch() const { return b.bands <= INT32_MAX && c.fit_one_launch() && (long)N * per_face * bpf <= INT32_MAX; }
+    int upload() {
+        const size_t need = off_tmp + b.rows * (size_t)per_face * out * 3;
+        CG_REQUIRE(workspace_bytes >= need, "%s: the workspace has %zu bytes, %zu are needed", who, workspace_bytes, need);
+        ws = static_cast<unsigned char*>(workspace);
+        CG_HIP(hipMemcpyAsync(ws, head.data(), head.size(), hipMemcpyHostToDevice, s));
+        CG_HIP(hipStreamSynchronize(s));   // `head` is pageable and ends with this call
+        return crops ? c.launch(s, src, src_off, geom, inv, ws, off_crops, N, pads, pad_all) : 0;
+    }
+    int vpass() const {
+        hipLaunchKernelGGL(faces_vpass_k, dim3((unsigned)((long)N * per_face * bpf)), dim3(256), 0, s, ws + off_tmp, du64(off_tmpoff),
+                           padded ? di32(off_pgeom) : geom, taps, tap_off, dst, out, bpf, per_face);
+        CG_LAUNCH_CHECK();
+        return 0;
+    }
+};
+
 }  // namespace
 }  // namespace cg
 
@@ -458,31 +523,14 @@ using namespace cg;
 int cg_faces_u8_extract(void* stream, const unsigned char* src, size_t src_bytes, const uint64_t* src_off, const int32_t* geom,
                         const float* inv, const int32_t* taps, size_t ntaps, const uint64_t* tap_off, unsigned char* dst, int N, int out,
                         void* workspace, size_t workspace_bytes) {
-    static const char who[] = "cg_faces_u8_extract";
-    hipStream_t s = S(stream);
-    Faces h;
-    if (int rc = h.read(who, s, src, src_bytes, src_off, geom, inv, taps, ntaps, tap_off, dst, N, out, workspace)) return rc;
-    // workspace: band_start [N + 1] int32 | tmp_off [N] uint64 | tmp bytes
-    Layout lay;
-    const size_t off_band = lay.take((size_t)(N + 1) * 4), off_tmpoff = lay.take((size_t)N * 8), off_tmp = lay.bytes;
-    std::vector<unsigned char> head(off_tmp, 0);
-    Bands b;
-    b.plan(reinterpret_cast<int32_t*>(head.data() + off_band), reinterpret_cast<uint64_t*>(head.data() + off_tmpoff), N, (uint64_t)out * 3,
-           [&](int f) { return Side2{h.geom[(size_t)f * kGeom + 4], h.geom[(size_t)f * kGeom + 5]}; });
-    CG_REQUIRE(b.bands <= INT32_MAX, "%s: %ld bands of rows do not fit one launch", who, b.bands);
-    const size_t need = off_tmp + b.rows * (size_t)out * 3;
-    CG_REQUIRE(workspace_bytes >= need, "%s: the workspace has %zu bytes, %zu are needed", who, workspace_bytes, need);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    CG_HIP(hipMemcpyAsync(ws, head.data(), head.size(), hipMemcpyHostToDevice, s));
-    CG_HIP(hipStreamSynchronize(s));   // `head` is pageable and ends with this call
-    hipLaunchKernelGGL(faces_warp_hpass_k, dim3((unsigned)b.bands), dim3(256), 0, s, src, src_off, geom, inv, taps, tap_off,
-                       reinterpret_cast<const int32_t*>(ws + off_band), reinterpret_cast<const uint64_t*>(ws + off_tmpoff), ws + off_tmp, N, out);
+    Job j{"cg_faces_u8_extract", S(stream), src, src_off, geom, inv, taps, tap_off, dst, N, out, workspace, workspace_bytes, 1, false, false, nullptr, 0};
+    if (int rc = j.plan(src_bytes, ntaps)) return rc;
+    CG_REQUIRE(j.fits_one_launch(), "%s: %ld bands of rows do not fit one launch", j.who, j.b.bands);
+    if (int rc = j.upload()) return rc;
+    hipLaunchKernelGGL(faces_warp_hpass_k, dim3((unsigned)j.b.bands), dim3(256), 0, j.s, src, src_off, geom, inv, taps, tap_off,
+                       j.di32(j.off_band), j.du64(j.off_tmpoff), j.ws + j.off_tmp, N, out);
     CG_LAUNCH_CHECK();
-    const int bpf = cdiv((long)out * out * 3, 256);
-    hipLaunchKernelGGL(faces_vpass_k, dim3((unsigned)(N * (long)bpf)), dim3(256), 0, s, ws + off_tmp,
-                       reinterpret_cast<const uint64_t*>(ws + off_tmpoff), geom, taps, tap_off, dst, out, bpf, 1);
-    CG_LAUNCH_CHECK();
-    return 0;
+    return j.vpass();
 }
 
 int cg_faces_u8_extract_variants(void* stream, const unsigned char* src, size_t src_bytes, const uint64_t* src_off, const int32_t* geom,
@@ -494,86 +542,30 @@ int cg_faces_u8_extract_variants(void* stream, const unsigned char* src, size_t 
     CG_REQUIRE(pad >= 0 && pad <= 64, "%s: pad = %d is outside 0..64", who, pad);
     CG_REQUIRE(A >= 1 && A <= 999, "%s: A = %d is outside 1..999", who, A);
     CG_REQUIRE(noise_scale >= 0.f && noise_scale <= 3.0e38f, "%s: noise_scale = %g is negative or not finite", who, (double)noise_scale);
-    hipStream_t s = S(stream);
-    Faces h;
-    if (int rc = h.read(who, s, src, src_bytes, src_off, geom, inv, taps, ntaps, tap_off, dst, N, out, workspace)) return rc;
+    Job j{who, S(stream), src, src_off, geom, inv, taps, tap_off, dst, N, out, workspace, workspace_bytes, A, true, false, nullptr, pad};
+    if (int rc = j.plan(src_bytes, ntaps)) return rc;
     for (int f = 0; f < N; ++f) {
-        const int Hp = h.geom[(size_t)f * kGeom + 4] + 2 * pad, Wp = h.geom[(size_t)f * kGeom + 5] + 2 * pad;
+        const int Hp = j.h.geom[(size_t)f * kGeom + 4] + 2 * pad, Wp = j.h.geom[(size_t)f * kGeom + 5] + 2 * pad;
         CG_REQUIRE(Hp <= 4096 + 2 * 64 && Wp <= 4096 + 2 * 64, "%s: face %d: a padded crop of %d x %d is beyond %d", who, f, Wp, Hp, 4096 + 2 * 64);
     }
-    // workspace: band_start [N + 1] int32 | Crops' maps: cblk_start [N + 1], the two median launches' line_start [N + 1] and
-    //            line_face [N] int32, crop_off [N] uint64 | tmp_off [N] uint64 | the padded crops | tmp bytes
-    Layout lay;
-    const size_t off_band = lay.take((size_t)(N + 1) * 4);
-    Crops c;
-    c.reserve(lay, N);
-    const size_t off_tmpoff = lay.take((size_t)N * 8), off_crops = lay.bytes;
-    std::vector<unsigned char> head(off_crops, 0);
-    Bands b;
-    b.plan(reinterpret_cast<int32_t*>(head.data() + off_band), reinterpret_cast<uint64_t*>(head.data() + off_tmpoff), N, (uint64_t)A * out * 3,
-           [&](int f) { return Side2{h.geom[(size_t)f * kGeom + 4], h.geom[(size_t)f * kGeom + 5]}; });
-    c.plan(head.data(), h.geom.data(), N, [&](int) { return pad; });
-    const int bpf = cdiv((long)out * out * 3, 256);
-    CG_REQUIRE(b.bands <= INT32_MAX && c.fit_one_launch() && (long)N * A * bpf <= INT32_MAX,
-               "%s: %d faces with %d variants (%ld bands of rows, %ld crop blocks) do not fit one launch", who, N, A, b.bands, c.cblks);
-    const size_t off_tmp = off_crops + c.bytes, need = off_tmp + b.rows * (size_t)A * out * 3;
-    CG_REQUIRE(workspace_bytes >= need, "%s: the workspace has %zu bytes, %zu are needed", who, workspace_bytes, need);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    CG_HIP(hipMemcpyAsync(ws, head.data(), head.size(), hipMemcpyHostToDevice, s));
-    CG_HIP(hipStreamSynchronize(s));   // `head` is pageable and ends with this call
-    auto di32 = [&](size_t off) { return reinterpret_cast<const int32_t*>(ws + off); };
-    auto du64 = [&](size_t off) { return reinterpret_cast<const uint64_t*>(ws + off); };
-    if (int rc = c.launch(s, src, src_off, geom, inv, ws, off_crops, N, nullptr, pad)) return rc;
-    hipLaunchKernelGGL(faces_variant_hpass_k, dim3((unsigned)b.bands, (unsigned)A), dim3(256), 0, s, ws + off_crops, du64(c.off_cropoff), geom,
-                       desc, bases, taps, tap_off, di32(off_band), du64(off_tmpoff), ws + off_tmp, N, A, pad, out, noise_scale, seed);
+    CG_REQUIRE(j.fits_one_launch(), "%s: %d faces with %d variants (%ld bands of rows, %ld crop blocks) do not fit one launch", who, N, A,
+               j.b.bands, j.c.cblks);
+    if (int rc = j.upload()) return rc;
+    hipLaunchKernelGGL(faces_variant_hpass_k, dim3((unsigned)j.b.bands, (unsigned)A), dim3(256), 0, j.s, j.ws + j.off_crops, j.du64(j.c.off_cropoff),
+                       geom, desc, bases, taps, tap_off, j.di32(j.off_band), j.du64(j.off_tmpoff), j.ws + j.off_tmp, N, A, pad, out, noise_scale, seed);
     CG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(faces_vpass_k, dim3((unsigned)((long)N * A * bpf)), dim3(256), 0, s, ws + off_tmp, du64(off_tmpoff), geom, taps, tap_off,
-                       dst, out, bpf, A);
-    CG_LAUNCH_CHECK();
-    return 0;
+    return j.vpass();
 }
 
 int cg_faces_u8_extract_padded(void* stream, const unsigned char* src, size_t src_bytes, const uint64_t* src_off, const int32_t* geom,
                                const float* inv, const int32_t* taps, size_t ntaps, const uint64_t* tap_off, const int32_t* pads,
                                unsigned char* dst, int N, int out, void* workspace, size_t workspace_bytes) {
-    static const char who[] = "cg_faces_u8_extract_padded";
-    hipStream_t s = S(stream);
-    Faces h;
-    if (int rc = h.read(who, s, src, src_bytes, src_off, geom, inv, taps, ntaps, tap_off, dst, N, out, workspace, pads, true)) return rc;
-    // workspace: band_start [N + 1] int32 | Crops' maps (as the variants') | tmp_off [N] uint64 | pgeom [N][8] int32, geom with the
-    //            padded sides in place of the rectangle's | the padded crops | tmp bytes
-    Layout lay;
-    const size_t off_band = lay.take((size_t)(N + 1) * 4);
-    Crops c;
-    c.reserve(lay, N);
-    const size_t off_tmpoff = lay.take((size_t)N * 8), off_pgeom = lay.take((size_t)N * kGeom * 4), off_crops = lay.bytes;
-    std::vector<unsigned char> head(off_crops, 0);
-    int32_t* pgeom = reinterpret_cast<int32_t*>(head.data() + off_pgeom);
-    for (int f = 0; f < N; ++f) {
-        std::copy_n(h.geom.data() + (size_t)f * kGeom, kGeom, pgeom + (size_t)f * kGeom);
-        pgeom[(size_t)f * kGeom + 4] += 2 * h.pads[f], pgeom[(size_t)f * kGeom + 5] += 2 * h.pads[f];
-    }
-    Bands b;
-    b.plan(reinterpret_cast<int32_t*>(head.data() + off_band), reinterpret_cast<uint64_t*>(head.data() + off_tmpoff), N, (uint64_t)out * 3,
-           [&](int f) { return Side2{pgeom[(size_t)f * kGeom + 4], pgeom[(size_t)f * kGeom + 5]}; });
-    c.plan(head.data(), h.geom.data(), N, [&](int f) { return h.pads[f]; });
-    const int bpf = cdiv((long)out * out * 3, 256);
-    CG_REQUIRE(b.bands <= INT32_MAX && c.fit_one_launch() && (long)N * bpf <= INT32_MAX,
-               "%s: %d faces (%ld bands of rows, %ld crop blocks) do not fit one launch", who, N, b.bands, c.cblks);
-    const size_t off_tmp = off_crops + c.bytes, need = off_tmp + b.rows * (size_t)out * 3;
-    CG_REQUIRE(workspace_bytes >= need, "%s: the workspace has %zu bytes, %zu are needed", who, workspace_bytes, need);
-    unsigned char* ws = static_cast<unsigned char*>(workspace);
-    CG_HIP(hipMemcpyAsync(ws, head.data(), head.size(), hipMemcpyHostToDevice, s));
-    CG_HIP(hipStreamSynchronize(s));   // `head` is pageable and ends with this call
-    auto di32 = [&](size_t off) { return reinterpret_cast<const int32_t*>(ws + off); };
-    auto du64 = [&](size_t off) { return reinterpret_cast<const uint64_t*>(ws + off); };
-    if (int rc = c.launch(s, src, src_off, geom, inv, ws, off_crops, N, pads, 0)) return rc;
-    hipLaunchKernelGGL(faces_crop_hpass_k, dim3((unsigned)b.bands), dim3(256), 0, s, ws + off_crops, du64(c.off_cropoff), di32(off_pgeom), taps,
-                       tap_off, di32(off_band), du64(off_tmpoff), ws + off_tmp, N, out);
+    Job j{"cg_faces_u8_extract_padded", S(stream), src, src_off, geom, inv, taps, tap_off, dst, N, out, workspace, workspace_bytes, 1, true, true, pads, 0};
+    if (int rc = j.plan(src_bytes, ntaps)) return rc;
+    CG_REQUIRE(j.fits_one_launch(), "%s: %d faces (%ld bands of rows, %ld crop blocks) do not fit one launch", j.who, N, j.b.bands, j.c.cblks);
+    if (int rc = j.upload()) return rc;
+    hipLaunchKernelGGL(faces_crop_hpass_k, dim3((unsigned)j.b.bands), dim3(256), 0, j.s, j.ws + j.off_crops, j.du64(j.c.off_cropoff),
+                       j.di32(j.off_pgeom), taps, tap_off, j.di32(j.off_band), j.du64(j.off_tmpoff), j.ws + j.off_tmp, N, out);
     CG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(faces_vpass_k, dim3((unsigned)((long)N * bpf)), dim3(256), 0, s, ws + off_tmp, du64(off_tmpoff), di32(off_pgeom), taps,
-                       tap_off, dst, out, bpf, 1);
-    CG_LAUNCH_CHECK();
-    return 0;
+    return j.vpass();
 }
-

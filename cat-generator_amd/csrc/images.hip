@@ -284,9 +284,14 @@ int cg_images_u8_to_f32(void* stream, const unsigned char* src, float* dst, long
     CG_EW_LAUNCH(images_u8_to_f32_k, npixels, src, dst, npixels, colorspace); return 0;
 }
 
+// the two scaling entry points' checks; `given`: whether what the form has beyond the sizes, its pointers and the set's size, is there
+static int scale_check(const char* who, bool given, int N, int Hs, int Ws, int Hd, int Wd, int colorspace) {
+    CG_REQUIRE(given && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && colorspace >= CS_RGB && colorspace <= CS_HSL, "%s: bad arguments", who);
+    CG_REQUIRE(Hs <= 6 * Hd && Ws <= 6 * Wd, "%s: down-scaling by more than 6 is not supported", who);
+    return 0;
+}
 int cg_images_u8_scale_to_f32(void* stream, const unsigned char* src, float* dst, int N, int Hs, int Ws, int Hd, int Wd, int colorspace) {
-    CG_REQUIRE(src && dst && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && colorspace >= CS_RGB && colorspace <= CS_HSL, "cg_images_u8_scale_to_f32: bad arguments");
-    CG_REQUIRE(Hs <= 6 * Hd && Ws <= 6 * Wd, "cg_images_u8_scale_to_f32: down-scaling by more than 6 is not supported");
+    if (int rc = scale_check("cg_images_u8_scale_to_f32", src && dst, N, Hs, Ws, Hd, Wd, colorspace)) return rc;
     const long total = (long)N * Hd * Wd;
     CG_EW_LAUNCH(images_u8_scale_k, total, src, dst, N, Hs, Ws, Hd, Wd, colorspace); return 0;
 }
@@ -348,9 +353,7 @@ int cg_images_u8_augment_to_f32(void* stream, const unsigned char* src, float* d
 
 int cg_images_u8_gather_scale_to_f32(void* stream, const unsigned char* set, long M, const int32_t* idx, float* dst, int N, int Hs, int Ws,
                                      int Hd, int Wd, int colorspace) {
-    CG_REQUIRE(set && idx && dst && M > 0 && N > 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && colorspace >= CS_RGB && colorspace <= CS_HSL,
-               "cg_images_u8_gather_scale_to_f32: bad arguments");
-    CG_REQUIRE(Hs <= 6 * Hd && Ws <= 6 * Wd, "cg_images_u8_gather_scale_to_f32: down-scaling by more than 6 is not supported");
+    if (int rc = scale_check("cg_images_u8_gather_scale_to_f32", set && idx && dst && M > 0, N, Hs, Ws, Hd, Wd, colorspace)) return rc;
     const long total = (long)N * Hd * Wd;
     CG_EW_LAUNCH(images_u8_gather_scale_k, total, set, M, idx, dst, N, Hs, Ws, Hd, Wd, colorspace); return 0;
 }

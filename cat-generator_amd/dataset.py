@@ -471,6 +471,55 @@ def loadRandomImages(count):
     return _Data(rgbToColorSpace(data, colorSpace))
 
 
+def _kernel_limit(Hs, Ws, aug):
+    """Why the device kernels cannot serve sources of Hs x Ws pixels (padded ones, with dataset.margin) - (the reason, what the host does
+    in their place, a note for those who cannot fall back) - or None: they shrink a window at most 6x (images_u8_scale_k's box loop), and
+    the augmentation kernel, which a margin goes through too, keeps one whole source image in the LDS."""
+    Hw, Ww = _window(Hs, Ws)
+    if Hw > 6 * height or Ww > 6 * width:
+        return f"{Ww}x{Hw} sources are more than 6x the {width}x{height} target", "scaling on the host", " (the kernels' limit)"
+    if (aug or margin) and Hs * Ws * 12 > AUG_LDS_BYTES:
+        return f"{Ws}x{Hs} sources do not fit the augmentation kernel's LDS", "augmenting on the host", ""
+    return None
+
+
+def _pools(count, k):
+    """What a loader's pools have in common: the colour space's code (include/catgan.h), its planes C, and k engine tensors
+    [count, C, height, width] in NHWC memory."""
+    from .tensor import Tensor
+    C = 1 if colorSpace == "y" else 3
+    return COLOR_SPACES[colorSpace], C, [Tensor.empty((count, C, height, width), "nhwc") for _ in range(k)]
+
+
+def _to_pool(L, st, src, pool, n, Hs, Ws, m, cs_code, gather=(), desc=None, draw=None):
+    """8-bit images on the device -> the first n images of the fp32 pool at `pool`, queued on stream st: the n Hs x Ws images at src or,
+    with gather = (M, idx), those of the M at src that the n int32 indices at idx name.  One of the six cg_images_u8_* entry points: with
+    a margin m the window form, whose descriptor is null unless augmenting; with a draw (augment_draw's, its descriptors [n][8] at desc)
+    alone the augment form; else the scale form."""
+    noise_std, nseed = (draw["noise_std"], draw["seed"]) if draw is not None else (0.0, 0)
+    form = "gather_" if gather else ""
+    if m:
+        getattr(L, f"images_u8_{form}augment_window_to_f32")(st, src, *gather, pool, n, Hs, Ws, m, height, width, cs_code,
+                                                             desc if draw is not None else None, noise_std, nseed, 0)
+    elif draw is not None:
+        getattr(L, f"images_u8_{form}augment_to_f32")(st, src, *gather, pool, n, Hs, Ws, height, width, cs_code, desc, noise_std, nseed, 0)
+    else:
+        getattr(L, f"images_u8_{form}scale_to_f32")(st, src, *gather, pool, n, Hs, Ws, height, width, cs_code)
+
+
+class _Chunks:
+    """Iterating a chunk loader: its next() gives (pool, index0, n), and None once the list is exhausted."""
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        item = self.next()
+        if item is None:
+            raise StopIteration
+        return item
+
+
 class AsyncLoader:
     """Double-buffered epoch pools in HBM.  next() returns the pool (an engine tensor [n,C,H,W], NHWC memory) whose upload
     was started one call earlier and immediately starts on the following one: decode (worker thread) -> pinned u8 buffer ->
@@ -498,24 +547,16 @@ class AsyncLoader:
         from .tensor import Tensor, lib
         self._ct, self._T, self.L = ctypes, Tensor, lib()
         self.count, self.depth = int(count), int(depth)
-        self.cs_code = COLOR_SPACES[colorSpace]
-        self.C = 1 if colorSpace == "y" else 3
+        self.cs_code, self.C, pools = _pools(self.count, self.depth)
         self.Hs, self.Ws = _decode(probe).shape[:2]      # the dataset is written at one size (generate_dataset.py: 64 x 64)
-        # The device kernel scales a batch of ONE source size, and at most 6x down (images_u8_scale_k's box loop).  The reference
-        # (dataset.lua:129-131) scales every image on its own: an image of another size - or all of them, if the source is more than
-        # 6x the target - takes the blocking loader's host path (image_scale, same arithmetic) and is patched into the pool.
-        # With a margin, Hs x Ws is the padded size: the 6x limit is the window's, the LDS limit below the padded image's.
-        self.margin = margin
-        Hw, Ww = _window(self.Hs, self.Ws)
-        self.host_all = Hw > 6 * height or Ww > 6 * width
-        if self.host_all:
-            import warnings
-            warnings.warn(f"{type(self).__name__}: {Ww}x{Hw} sources are more than 6x the {width}x{height} target: scaling on the host")
-        self.aug = aug
-        if (self.aug or self.margin) and not self.host_all and self.Hs * self.Ws * 12 > AUG_LDS_BYTES:      # the kernel keeps one source image in the LDS
-            import warnings
-            warnings.warn(f"{type(self).__name__}: {self.Ws}x{self.Hs} sources do not fit the augmentation kernel's LDS: augmenting on the host")
-            self.host_all = True
+        # The device kernel scales a batch of ONE source size, within _kernel_limit.  The reference (dataset.lua:129-131) scales every
+        # image on its own: an image of another size - or all of them, beyond that limit - takes the blocking loader's host path
+        # (image_scale, same arithmetic) and is patched into the pool.  With a margin, Hs x Ws is the padded size.
+        self.margin, self.aug = margin, aug
+        limit = _kernel_limit(self.Hs, self.Ws, aug)
+        self.host_all = limit is not None
+        if limit:
+            warnings.warn(f"{type(self).__name__}: {limit[0]}: {limit[1]}")
         # host_all: nothing is scaled on the device, so no 8-bit staging / device buffer of the (large) SOURCE size exists at all - the
         # worker writes the finished fp32 NHWC rows into a pinned buffer of the POOL's size and one asynchronous copy moves them
         # (the u8 path would pin count x Hs x Ws x 3 bytes per slot for images it never uploads).  Otherwise: the u8
@@ -526,12 +567,11 @@ class AsyncLoader:
         self.L.stream_create(ctypes.byref(self.copy_stream))
         self.slots = []
         f32p = ctypes.POINTER(ctypes.c_float)
-        for _ in range(self.depth):
+        for pool in pools:
             host, dev_u8, ev_ready, ev_free, side = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
             host_desc, dev_desc, desc = ctypes.c_void_p(), ctypes.c_void_p(), None
             self.L.host_alloc(ctypes.byref(host), self.nbytes)
             self.L.event_create(ctypes.byref(ev_ready)); self.L.event_create(ctypes.byref(ev_free))
-            pool = Tensor.empty((self.count, self.C, height, width), "nhwc")
             if self.host_all:
                 staging = np.ctypeslib.as_array(ctypes.cast(host, f32p), shape=(self.count, height, width, self.C))
                 patch = None
@@ -595,15 +635,7 @@ class AsyncLoader:
             L.memcpy_h2d(cs, slot["dev_u8"], slot["host"], n * self.Hs * self.Ws * 3)
             if self.aug:
                 L.memcpy_h2d(cs, slot["dev_desc"], slot["host_desc"], n * 32)
-            noise_std, nseed = (slot["draw"]["noise_std"], slot["draw"]["seed"]) if self.aug else (0.0, 0)
-            if self.margin:
-                L.images_u8_augment_window_to_f32(cs, slot["dev_u8"], slot["pool"].ptr, n, self.Hs, self.Ws, self.margin, height, width,
-                                                  self.cs_code, slot["dev_desc"] if self.aug else None, noise_std, nseed, 0)
-            elif self.aug:
-                L.images_u8_augment_to_f32(cs, slot["dev_u8"], slot["pool"].ptr, n, self.Hs, self.Ws, height, width, self.cs_code,
-                                           slot["dev_desc"], noise_std, nseed, 0)
-            else:
-                L.images_u8_scale_to_f32(cs, slot["dev_u8"], slot["pool"].ptr, n, self.Hs, self.Ws, height, width, self.cs_code)
+            _to_pool(L, cs, slot["dev_u8"], slot["pool"].ptr, n, self.Hs, self.Ws, self.margin, self.cs_code, desc=slot["dev_desc"], draw=slot["draw"])
             for i in slot["patches"]:     # images scaled on the host (another source size): over the rows the kernel produced from zeros
                 L.memcpy_h2d(cs, slot["pool"].ptr + i * self.row, slot["side"].value + i * self.row, self.row)
             slot["patches"] = []
@@ -648,7 +680,7 @@ class AsyncLoader:
         self.slots = []
 
 
-class SequentialLoader(AsyncLoader):
+class SequentialLoader(_Chunks, AsyncLoader):
     """AsyncLoader's pipeline (worker decode -> pinned 8-bit buffer -> copy stream -> cg_images_u8_scale_to_f32 -> event, two pools) over
     a GIVEN file list, in that order, `chunk` files at a time: what a pass over the whole training set needs (sample.py --neighbours,
     nn_utils.findClosestNeighboursOnDevice) without ever holding the set.  next() returns (pool, index0, n) - the engine tensor
@@ -678,15 +710,6 @@ class SequentialLoader(AsyncLoader):
             return None
         index0, n = slot["index0"], slot["n"]
         return AsyncLoader.next(self), index0, n
-
-    def __iter__(self):
-        return self
-
-    def __next__(self):
-        item = self.next()
-        if item is None:
-            raise StopIteration
-        return item
 
     def close(self):
         self._release()
@@ -802,12 +825,10 @@ def openPack(d):
 
 
 def _check_resident(who, Hs, Ws, aug):
-    """The kernels' limits for a set of Hs x Ws images (padded ones, with dataset.margin): 6x from the window, the LDS from the whole."""
-    Hw, Ww = _window(Hs, Ws)
-    if Hw > 6 * height or Ww > 6 * width:
-        raise ValueError(f"{who}: {Ww}x{Hw} sources are more than 6x the {width}x{height} target (the kernels' limit)")
-    if (aug or margin) and Hs * Ws * 12 > AUG_LDS_BYTES:
-        raise ValueError(f"{who}: {Ws}x{Hs} sources do not fit the augmentation kernel's LDS")
+    """A resident set has no host path: what _kernel_limit names is an error."""
+    limit = _kernel_limit(Hs, Ws, aug)
+    if limit:
+        raise ValueError(f"{who}: {limit[0]}{limit[2]}")
 
 
 class ResidentSet:
@@ -854,19 +875,16 @@ class ResidentSet:
             pass
 
 
-class _ResidentChunks:
+class _ResidentChunks(_Chunks):
     """cg_images_u8_scale_to_f32 (of a padded set, dataset.margin: cg_images_u8_augment_window_to_f32's identity form) on consecutive
     slices of a ResidentSet, on the caller's stream, alternating two pools: a pool stays valid until the next-but-one next()."""
 
     def __init__(self, rset, chunk):
-        from .tensor import Tensor
         if int(chunk) < 1:
             raise ValueError(f"ResidentSet.chunks: chunk = {chunk}")
         _check_resident("ResidentSet.chunks", rset.Hs, rset.Ws, False)
         self.set, self.files, self.count, self.margin = rset, rset.paths, min(int(chunk), rset.M), margin
-        self.C = 1 if colorSpace == "y" else 3
-        self.cs_code = COLOR_SPACES[colorSpace]
-        self.pools = [Tensor.empty((self.count, self.C, height, width), "nhwc") for _ in range(2)]
+        self.cs_code, self.C, self.pools = _pools(self.count, 2)
         self._pos, self.k = 0, 0
 
     def next(self):
@@ -876,23 +894,10 @@ class _ResidentChunks:
             return None
         index0, n = self._pos, min(self.count, s.M - self._pos)
         pool = self.pools[self.k]
-        if self.margin:
-            s.L.images_u8_augment_window_to_f32(stream(), s.ptr + index0 * s.per, pool.ptr, n, s.Hs, s.Ws, self.margin, height, width,
-                                                self.cs_code, None, 0.0, 0, 0)
-        else:
-            s.L.images_u8_scale_to_f32(stream(), s.ptr + index0 * s.per, pool.ptr, n, s.Hs, s.Ws, height, width, self.cs_code)
+        _to_pool(s.L, stream(), s.ptr + index0 * s.per, pool.ptr, n, s.Hs, s.Ws, self.margin, self.cs_code)
         self._pos += n
         self.k ^= 1
         return (pool if n == self.count else pool.rows(1, n)), index0, n
-
-    def __iter__(self):
-        return self
-
-    def __next__(self):
-        item = self.next()
-        if item is None:
-            raise StopIteration
-        return item
 
     def close(self):
         self.pools = []
@@ -912,7 +917,7 @@ class ResidentLoader:
 
     def __init__(self, count, resident_set):
         import ctypes
-        from .tensor import Tensor, lib
+        from .tensor import lib
         s = self.set = resident_set
         self.aug, self.margin = augmentation is not None, margin
         _check_resident(type(self).__name__, s.Hs, s.Ws, self.aug)
@@ -920,9 +925,7 @@ class ResidentLoader:
             raise ValueError(f"{type(self).__name__}: the resident set does not hold the files of {dirs}")
         self.L, self.count = lib(), int(count)
         n = min(self.count, s.M)
-        self.cs_code = COLOR_SPACES[colorSpace]
-        self.C = 1 if colorSpace == "y" else 3
-        self.pools = [Tensor.empty((n, self.C, height, width), "nhwc") for _ in range(2)]
+        self.cs_code, self.C, self.pools = _pools(n, 2)
         self.k, self.used = 0, False
         # indices [n] int32, then descriptors [n][8] float32: one page-locked block, one device block
         self.host, self.dev, self.staged = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
@@ -951,16 +954,8 @@ class ResidentLoader:
         self.used = True
         pool = self.pools[self.k]
         self.k ^= 1
-        dev_desc = self.dev.value + len(self.idx) * 4
-        if self.margin:
-            noise_std, nseed = (draw["noise_std"], draw["seed"]) if self.aug else (0.0, 0)
-            L.images_u8_gather_augment_window_to_f32(st, s.ptr, s.M, self.dev.value, pool.ptr, n, s.Hs, s.Ws, self.margin, height, width,
-                                                     self.cs_code, dev_desc if self.aug else None, noise_std, nseed, 0)
-        elif self.aug:
-            L.images_u8_gather_augment_to_f32(st, s.ptr, s.M, self.dev.value, pool.ptr, n, s.Hs, s.Ws, height, width, self.cs_code,
-                                              dev_desc, draw["noise_std"], draw["seed"], 0)
-        else:
-            L.images_u8_gather_scale_to_f32(st, s.ptr, s.M, self.dev.value, pool.ptr, n, s.Hs, s.Ws, height, width, self.cs_code)
+        _to_pool(L, st, s.ptr, pool.ptr, n, s.Hs, s.Ws, self.margin, self.cs_code, gather=(s.M, self.dev.value),
+                 desc=self.dev.value + len(self.idx) * 4, draw=draw)
         return pool if n == pool.shape[0] else pool.rows(1, n)
 
     def close(self):

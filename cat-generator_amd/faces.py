@@ -330,23 +330,42 @@ def workspace_bytes(N, out, rows):
     return 16 * N + 48 + 3 * out * rows
 
 
+class _DeviceBatch:
+    """One batch held on the device for the three entry points: the concatenated sources and the arrays of the descriptors `d`
+    (pack_descriptors' or pack_padded_descriptors'), uploaded once each, and one workspace of `wsb` bytes that every call of the batch
+    shares."""
+
+    def __init__(self, images, d, wsb):
+        import torch
+        from . import tensor
+        self.torch, self.dev, self.lib, self.N = torch, tensor.device(), tensor.lib(), len(images)
+        self.src = self.up(np.concatenate([np.ascontiguousarray(im, dtype=np.uint8).reshape(-1) for im in images]))
+        self.d = {k: self.up(v) for k, v in d.items() if k != "rows"}
+        self.ws = torch.empty(wsb, dtype=torch.uint8, device=self.dev)
+
+    def up(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(self.dev)   # bytes: torch has no uint64 arithmetic to need
+
+    def call(self, fn, d, shape, *own):
+        """fn(the stream, the nine leading arguments out of the uploaded arrays d, *own, dst, N, side, the workspace) -> dst, uint8
+        [N, *shape, 3] with side = shape[-1], on the host."""
+        from . import tensor
+        dst = self.torch.empty((self.N,) + shape + (3,), dtype=self.torch.uint8, device=self.dev)
+        fn(tensor.stream(), self.src.data_ptr(), self.src.numel(), d["src_off"].data_ptr(), d["geom"].data_ptr(), d["inv"].data_ptr(),
+           d["taps"].data_ptr(), d["taps"].numel() // 4, d["tap_off"].data_ptr(), *own, dst.data_ptr(), self.N, shape[-1], self.ws.data_ptr(),
+           self.ws.numel())
+        return dst.cpu().numpy()
+
+    def faces(self, out, own=None):
+        """cg_faces_u8_extract over the batch; `own`: uploaded geom, taps and tap_off of the faces where the batch's are another form's."""
+        return self.call(self.lib.faces_u8_extract, {**self.d, **(own or {})}, (out, out))
+
+
 def extract_faces_device(images, geoms, out=64):
     """cg_faces_u8_extract over one batch: `images` 8-bit RGB arrays, `geoms` their face_geometry results -> uint8 [N, out, out, 3] on
     the host.  One upload of the concatenated sources and of the descriptors, one call, one download."""
-    import torch
-    from . import tensor
     d = pack_descriptors([im.shape[:2] for im in images], geoms, out)
-    N = len(images)
-    dev = tensor.device()
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)   # bytes: torch has no uint64 arithmetic to need
-    src = up(np.concatenate([np.ascontiguousarray(im, dtype=np.uint8).reshape(-1) for im in images]))
-    src_off, geom, inv, taps, tap_off = (up(d[k]) for k in ("src_off", "geom", "inv", "taps", "tap_off"))
-    wsb = workspace_bytes(N, out, d["rows"])
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    dst = torch.empty((N, out, out, 3), dtype=torch.uint8, device=dev)
-    tensor.lib().faces_u8_extract(tensor.stream(), src.data_ptr(), src.numel(), src_off.data_ptr(), geom.data_ptr(), inv.data_ptr(),
-                                  taps.data_ptr(), d["taps"].size, tap_off.data_ptr(), dst.data_ptr(), N, out, ws.data_ptr(), wsb)
-    return dst.cpu().numpy()
+    return _DeviceBatch(images, d, workspace_bytes(len(images), out, d["rows"])).faces(out)
 
 
 # ---------------------------------------------------------------- the variants out of the padded crop
@@ -463,29 +482,14 @@ def variants_workspace_bytes(rects, pad, A, out):
 def extract_variants_device(images, geoms, pad, desc, bases, scale, seed, out=64, with_faces=False):
     """cg_faces_u8_extract_variants over one batch: desc float32 [N, A, 8], bases uint64 [N, A] -> uint8 [N, A, out, out, 3] on the
     host.  with_faces also runs cg_faces_u8_extract over the same upload and returns (faces [N, out, out, 3], variants)."""
-    import torch
-    from . import tensor
     d = pack_descriptors([im.shape[:2] for im in images], geoms, out)
     desc, bases = np.ascontiguousarray(desc, np.float32), np.ascontiguousarray(bases, np.uint64)
     N, A = bases.shape
     assert N == len(images) and desc.shape == (N, A, 8)
-    dev, lib, s = tensor.device(), tensor.lib(), tensor.stream()
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
-    src = up(np.concatenate([np.ascontiguousarray(im, dtype=np.uint8).reshape(-1) for im in images]))
-    src_off, geom, inv, taps, tap_off, ddesc, dbases = (up(a) for a in (d["src_off"], d["geom"], d["inv"], d["taps"], d["tap_off"], desc, bases))
-    wsb = max(variants_workspace_bytes([g["rect"] for g in geoms], pad, A, out), workspace_bytes(N, out, d["rows"]))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    faces = None
-    if with_faces:
-        fdst = torch.empty((N, out, out, 3), dtype=torch.uint8, device=dev)
-        lib.faces_u8_extract(s, src.data_ptr(), src.numel(), src_off.data_ptr(), geom.data_ptr(), inv.data_ptr(), taps.data_ptr(),
-                             d["taps"].size, tap_off.data_ptr(), fdst.data_ptr(), N, out, ws.data_ptr(), wsb)
-        faces = fdst.cpu().numpy()
-    dst = torch.empty((N, A, out, out, 3), dtype=torch.uint8, device=dev)
-    lib.faces_u8_extract_variants(s, src.data_ptr(), src.numel(), src_off.data_ptr(), geom.data_ptr(), inv.data_ptr(), taps.data_ptr(),
-                                  d["taps"].size, tap_off.data_ptr(), pad, A, ddesc.data_ptr(), dbases.data_ptr(), float(scale), int(seed),
-                                  dst.data_ptr(), N, out, ws.data_ptr(), wsb)
-    v = dst.cpu().numpy()
+    b = _DeviceBatch(images, d, max(variants_workspace_bytes([g["rect"] for g in geoms], pad, A, out), workspace_bytes(N, out, d["rows"])))
+    ddesc, dbases = b.up(desc), b.up(bases)
+    faces = b.faces(out) if with_faces else None
+    v = b.call(b.lib.faces_u8_extract_variants, b.d, (A, out, out), pad, A, ddesc.data_ptr(), dbases.data_ptr(), float(scale), int(seed))
     return (faces, v) if with_faces else v
 
 
@@ -515,31 +519,13 @@ def extract_padded_device(images, geoms, margin, out=64, with_faces=False):
     [N, out + 2 margin, out + 2 margin, 3] on the host - padded_face_np's bytes, face f's pad being margin_pad(Hr, margin, out).  One
     upload of the concatenated sources and of the descriptors.  with_faces also runs cg_faces_u8_extract over the same upload (its
     own geometry and tap tables beside the padded ones) and returns (faces [N, out, out, 3], padded)."""
-    import torch
-    from . import tensor
     shapes, rects, N, side = [im.shape[:2] for im in images], [g["rect"] for g in geoms], len(images), out + 2 * margin
     pads = [margin_pad(r[2], margin, out) for r in rects]
     d = pack_padded_descriptors(shapes, geoms, pads, side)
-    dev, lib, s = tensor.device(), tensor.lib(), tensor.stream()
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(dev)
-    src = up(np.concatenate([np.ascontiguousarray(im, dtype=np.uint8).reshape(-1) for im in images]))
-    src_off, geom, inv, taps, tap_off, dpads = (up(d[k]) for k in ("src_off", "geom", "inv", "taps", "tap_off", "pads"))
-    wsb = padded_workspace_bytes(rects, pads, side)
     fd = pack_descriptors(shapes, geoms, out) if with_faces else None
-    if with_faces:
-        wsb = max(wsb, workspace_bytes(N, out, fd["rows"]))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    faces = None
-    if with_faces:
-        fgeom, ftaps, ftap_off = (up(fd[k]) for k in ("geom", "taps", "tap_off"))
-        fdst = torch.empty((N, out, out, 3), dtype=torch.uint8, device=dev)
-        lib.faces_u8_extract(s, src.data_ptr(), src.numel(), src_off.data_ptr(), fgeom.data_ptr(), inv.data_ptr(), ftaps.data_ptr(),
-                             fd["taps"].size, ftap_off.data_ptr(), fdst.data_ptr(), N, out, ws.data_ptr(), wsb)
-        faces = fdst.cpu().numpy()
-    dst = torch.empty((N, side, side, 3), dtype=torch.uint8, device=dev)
-    lib.faces_u8_extract_padded(s, src.data_ptr(), src.numel(), src_off.data_ptr(), geom.data_ptr(), inv.data_ptr(), taps.data_ptr(),
-                                d["taps"].size, tap_off.data_ptr(), dpads.data_ptr(), dst.data_ptr(), N, side, ws.data_ptr(), wsb)
-    p = dst.cpu().numpy()
+    b = _DeviceBatch(images, d, max(padded_workspace_bytes(rects, pads, side), workspace_bytes(N, out, fd["rows"]) if with_faces else 0))
+    faces = b.faces(out, {k: b.up(fd[k]) for k in ("geom", "taps", "tap_off")}) if with_faces else None
+    p = b.call(b.lib.faces_u8_extract_padded, b.d, (side, side), b.d["pads"].data_ptr())
     return (faces, p) if with_faces else p
 
 

@@ -149,6 +149,19 @@ def _variants(face, index, n, noise_seed, host):
     return (v * np.float32(255.0) + np.float32(0.5)).astype(np.int32).astype(np.uint8)
 
 
+def _runs(cost, limit):
+    """The device calls of one flush as runs (lo, hi) over its items' byte costs: a run takes items until the next one would pass
+    `limit`, and one at least."""
+    lo = 0
+    while lo < len(cost):
+        hi, nbytes = lo + 1, cost[lo]
+        while hi < len(cost) and nbytes + cost[hi] <= limit:
+            nbytes += cost[hi]
+            hi += 1
+        yield lo, hi
+        lo = hi
+
+
 def _crop_variants(batch, index0, A, pad, S, noise_seed, host):
     """--variantsFrom crop for the faces of one flush, (fp, image, geometry) each, the first of them face `index0` of the set:
     (faces [n, S, S, 3] or None on the host, variants [n, A, S, S, 3]).  Every face draws as _variants draws; the counter base of
@@ -168,18 +181,9 @@ def _crop_variants(batch, index0, A, pad, S, noise_seed, host):
         return None, np.stack([F.variants_np(im, g["inv"], g["rect"], pad, desc[i], bases[i], scale, noise_seed, S)
                                for i, (_, im, g) in enumerate(batch)])
     cost = [im.nbytes + F.variant_bytes(g["rect"], pad, A, S) for _, im, g in batch]
-    faces, variants, lo = [], [], 0
-    while lo < n:
-        hi, nbytes = lo + 1, cost[lo]
-        while hi < n and nbytes + cost[hi] <= VARIANT_BYTES:
-            nbytes += cost[hi]
-            hi += 1
-        f, v = F.extract_variants_device([b[1] for b in batch[lo:hi]], [b[2] for b in batch[lo:hi]], pad, desc[lo:hi], bases[lo:hi], scale,
-                                         noise_seed, S, with_faces=True)
-        faces.append(f)
-        variants.append(v)
-        lo = hi
-    return np.concatenate(faces), np.concatenate(variants)
+    got = [F.extract_variants_device([b[1] for b in batch[lo:hi]], [b[2] for b in batch[lo:hi]], pad, desc[lo:hi], bases[lo:hi], scale,
+                                     noise_seed, S, with_faces=True) for lo, hi in _runs(cost, VARIANT_BYTES)]
+    return np.concatenate([f for f, _ in got]), np.concatenate([v for _, v in got])
 
 
 def _padded_faces(batch, margin, S, with_faces):
@@ -201,19 +205,13 @@ def _padded_faces(batch, margin, S, with_faces):
         padded[i] = F.padded_face_np(im, g["inv"], g["rect"], margin, S)
         if with_faces:
             faces[i] = F.extract_faces_device([im], [g], S)[0]
-    lo = 0
-    while lo < len(dev):
-        hi, nbytes = lo + 1, cost[lo]
-        while hi < len(dev) and nbytes + cost[hi] <= PADDED_BYTES:
-            nbytes += cost[hi]
-            hi += 1
+    for lo, hi in _runs(cost, PADDED_BYTES):
         ix = dev[lo:hi]
         got = F.extract_padded_device([batch[i][1] for i in ix], [batch[i][2] for i in ix], margin, S, with_faces=with_faces)
         if with_faces:
             faces[ix], padded[ix] = got
         else:
             padded[ix] = got
-        lo = hi
     return faces, padded
 
 

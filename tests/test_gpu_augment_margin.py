@@ -269,6 +269,24 @@ def test_sequential_loader_over_a_padded_directory_equals_load_image_file(cg, ds
     np.testing.assert_array_equal(got, want)
 
 
+def test_resident_chunks_over_a_padded_directory_equal_load_image_file(cg, ds, padded_dir):
+    """ResidentSet.chunks with a margin: the window form's identity draw on consecutive slices, 12 files in chunks of 5."""
+    _setup(ds, padded_dir, True)
+    ds.buildPack(padded_dir, threads=2)
+    rset = ds.ResidentSet(ds.openPack(padded_dir))
+    ch = rset.chunks(5)
+    assert ch.margin == 4 and ch.files == rset.paths
+    seen = []
+    for pool, index0, n in ch:
+        seen.append((index0, n))
+        for i in range(n):
+            np.testing.assert_array_equal(cg.nn.as_nhwc(pool).numpy()[i], ds.loadImageFile(rset.paths[index0 + i]), err_msg=rset.paths[index0 + i])
+    assert seen == [(0, 5), (5, 5), (10, 2)] and ch.next() is None
+    torch.cuda.synchronize()
+    ch.close()
+    rset.close()
+
+
 @pytest.mark.parametrize("aug", [False, True])
 def test_async_loader_host_paths_follow_the_margin(cg, ds, padded_dir, aug):
     """An image of another size is scaled on the host and patched into the pool; a window more than 6x the target sends all of them
