@@ -835,15 +835,19 @@ def adagrad(x, g, state, lr=1e-3):
 
 # --------------------------------------------------------------------- the hot path
 class Trainer:
-    """One iteration of adversarial.lua:51-275 with D_iterations=G_iterations=1, Adam, defaults of
-    train.lua:26-45 (D_L1=0, D_L2=1e-4, G_L1=G_L2=0, D_clamp=1, G_clamp=5)."""
+    """One iteration of adversarial.lua:51-275 with the defaults of train.lua:26-45 (D_L1=0, D_L2=1e-4, G_L1=G_L2=0, D_clamp=1,
+    G_clamp=5, Adam for both nets, one D and one G iteration).  X_optmethod in {"adam", "sgd", "adagrad"} with the learning rates of
+    train.lua:191-207: adagrad 1e-3 for D and 3e-3 for G, sgd X_sgd_lr with X_sgd_momentum, adam optim's own defaults."""
 
-    def __init__(self, G, D, D_L1=0.0, D_L2=1e-4, G_L1=0.0, G_L2=0.0, D_clamp=1.0, G_clamp=5.0):
+    def __init__(self, G, D, D_L1=0.0, D_L2=1e-4, G_L1=0.0, G_L2=0.0, D_clamp=1.0, G_clamp=5.0, D_optmethod="adam", G_optmethod="adam",
+                 D_sgd_lr=0.02, G_sgd_lr=0.02, D_sgd_momentum=0.0, G_sgd_momentum=0.0, D_iterations=1, G_iterations=1):
         self.G, self.D = G, D
         self.pG, self.gG = get_parameters(G)
         self.pD, self.gD = get_parameters(D)
         self.stG, self.stD = {}, {}
-        self.o = dict(D_L1=D_L1, D_L2=D_L2, G_L1=G_L1, G_L2=G_L2, D_clamp=D_clamp, G_clamp=G_clamp)
+        self.o = dict(D_L1=D_L1, D_L2=D_L2, G_L1=G_L1, G_L2=G_L2, D_clamp=D_clamp, G_clamp=G_clamp, D_optmethod=D_optmethod,
+                      G_optmethod=G_optmethod, D_sgd_lr=D_sgd_lr, G_sgd_lr=G_sgd_lr, D_sgd_momentum=D_sgd_momentum,
+                      G_sgd_momentum=G_sgd_momentum, D_iterations=D_iterations, G_iterations=G_iterations)
         self.grad_allreduce = None  # data-parallel hook: f(gflat) -> mean over ranks, in place
 
     def feval_D(self, inputs, targets):
@@ -883,19 +887,35 @@ class Trainer:
             np.clip(self.gG, -o["G_clamp"], o["G_clamp"], out=self.gG)
         return f, samples, out
 
+    def update(self, which):
+        """adversarial.lua:240-248 / 257-265: the net's own optimiser on the gradient feval left behind."""
+        o, p, g, st = self.o, getattr(self, "p" + which), getattr(self, "g" + which), getattr(self, "st" + which)
+        m = o[which + "_optmethod"]
+        if m == "adam":
+            adam(p, g, st)
+        elif m == "sgd":
+            sgd(p, g, st, lr=o[which + "_sgd_lr"], momentum=o[which + "_sgd_momentum"])
+        else:
+            assert m == "adagrad", m
+            adagrad(p, g, st, lr=1e-3 if which == "D" else 1e-3 * 3)
+
     def step(self, real, noise_d, noise_g):
-        """real [N/2,C,S,S] in [0,1]; noise_d [N/2,nd]; noise_g [N,nd].  Returns dict of observables."""
+        """real [N/2,C,S,S] in [0,1]; noise_d [N/2,nd]; noise_g [N,nd].  Returns dict of observables (of the last D and the last G
+        iteration).  Every D iteration generates its own fake half (:232) and every G iteration its own pass, here from the same
+        injected rows and noise."""
         half = real.shape[0]
         N = 2 * half
-        # (1) D update: rows 1..N/2 real (target 1), rows N/2+1..N = G(noise) (target 0)  (:221-238)
-        fake = self.G.forward(noise_d)  # train-mode BN on N/2, no gradient (nn_utils.lua:52)
-        inputs = np.concatenate([real, fake], axis=0).astype(f32)
-        targets = np.concatenate([np.ones(half, f32), np.zeros(half, f32)])
-        fD, outD = self.feval_D(inputs, targets)
-        gD = self.gD.copy()   # what optim.adam receives (penalty + clamp applied); feval_G's D:backward adds to gD later
-        adam(self.pD, self.gD, self.stD)
-        # (2) G update: fresh noise, targets all "real" (:253-266)
-        fG, samples, outG = self.feval_G(noise_g, np.ones(N, f32))
-        gG = self.gG.copy()
-        adam(self.pG, self.gG, self.stG)
+        for _ in range(self.o["D_iterations"]):
+            # (1) D update: rows 1..N/2 real (target 1), rows N/2+1..N = G(noise) (target 0)  (:221-238)
+            fake = self.G.forward(noise_d)  # train-mode BN on N/2, no gradient (nn_utils.lua:52)
+            inputs = np.concatenate([real, fake], axis=0).astype(f32)
+            targets = np.concatenate([np.ones(half, f32), np.zeros(half, f32)])
+            fD, outD = self.feval_D(inputs, targets)
+            gD = self.gD.copy()   # what the optimiser receives (penalty + clamp applied); feval_G's D:backward adds to gD later
+            self.update("D")
+        for _ in range(self.o["G_iterations"]):
+            # (2) G update: fresh noise, targets all "real" (:253-266)
+            fG, samples, outG = self.feval_G(noise_g, np.ones(N, f32))
+            gG = self.gG.copy()
+            self.update("G")
         return dict(fD=fD, fG=fG, outD=outD, outG=outG, fake=fake, samples=samples, gD=gD, gG=gG)
